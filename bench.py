@@ -21,6 +21,16 @@ evaluations per launch (vr option "count" = 1) / mean kernel duration, against
 the 157.3 TFLOP/s fp32 vector peak.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config grid512|grid128|grid4k|cloud|cloud_shadow]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K frames and prints the line with the
+headline figure (metric, value, ms_per_step, the timed window's own clocks).
+--dump-outputs DIR then writes the last timed frame, as its caller receives it
+(rank 0's assembled frame), to DIR/frame.npy in float32.  --full adds every
+other measurement and check, each in passes of its own after the window: the
+executed-step counts, the roofline (gated and sampled passes, the measured HBM
+peak), the frame check against a plain render, the all-channels-loaded
+comparison, the other BASELINE configs and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -252,6 +262,34 @@ def frame_check_of(got, ref):
     return f"MISMATCH: {int(bad.sum())} pixels differ in {rows.size} rows (first row {int(rows[0])})"
 
 
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: all files together, .npy headers included
+DUMP_HEADER_BYTES = 1024      # reserved per file for its .npy header (128 B for these shapes)
+DUMP_SEED = 20240501
+
+
+def dump_outputs(dirname, arrays):
+    """Write each array as dirname/<name>.npy in float32 (float64 stays
+    float64).  Together they hold at most DUMP_MAX_BYTES: a larger array is
+    cut to a fixed sample of its flattened elements -- indices drawn without
+    replacement by numpy's default_rng(DUMP_SEED), sorted -- the same for
+    every run with the same shapes.  Returns what the line says about it."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays)) - DUMP_HEADER_BYTES
+    info = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes > budget:
+            n = budget // a.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+            entry.update({"sampled": n, "sample_def": f"elements numpy.random.default_rng({DUMP_SEED}).choice("
+                                                      f"size, {n}, replace=False), sorted, of the flattened array"})
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        info[name] = entry
+    return info
+
+
 def other_config(name, steps, warmup, warm_ms=0.0):
     """Time one more BASELINE config on this GPU in the same process, after the
     headline window (verdict r03 #6): ms/frame, kernel ms (HIP events on its
@@ -385,7 +423,14 @@ def main() -> int:
                     help="before each config's --warmup frames, queue untimed frames for this many ms of continuous "
                          "load (declared in the line as clock_warm; 0 = off)")
     ap.add_argument("--config", default="grid512", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window, also measure and check everything beside the headline figure: "
+                         "executed-step counts, roofline passes and the measured HBM peak, the frame check, the "
+                         "all-channels-loaded comparison, the other configs, the CPU baselines (off: none of them run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame (rank 0's, as the timed path hands it to its caller) to "
+                         "DIR/frame.npy in float32, at most 64 MB (a larger frame: a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--cpu-budget-other", type=float, default=3.0, help="CPU baseline budget of each other config")
     ap.add_argument("--no-other-configs", action="store_true",
@@ -480,14 +525,16 @@ def main() -> int:
                                  inflight=2 if proc_inflight2 else args.inflight)
     stream = torch.cuda.current_stream()
 
-    # executed ray-steps per launch (this rank's bands), one untimed pass
+    # executed ray-steps per launch (this rank's bands), one untimed pass (--full)
     counter = torch.zeros(1, dtype=torch.int64, device="cuda")
-    sharder.render_local(step_counter=counter)
-    torch.cuda.synchronize()
-    local_steps = int(counter.item())
+    local_steps = 0
+    if args.full:
+        sharder.render_local(step_counter=counter)
+        torch.cuda.synchronize()
+        local_steps = int(counter.item())
     local_evals = local_steps
     local_cells = None
-    if proc is not None:
+    if args.full and proc is not None:
         r.set_option("count", 1)
         counter.zero_()
         sharder.render_local(step_counter=counter)
@@ -501,7 +548,7 @@ def main() -> int:
         r.set_option("count", 0)
     red_dev = "cuda" if args.backend == "nccl" and not native else "cpu"
     tot = torch.tensor([local_steps, local_evals, local_cells or 0], dtype=torch.int64, device=red_dev)
-    if world > 1:
+    if world > 1 and args.full:
         dist.all_reduce(tot)
     frame_steps, frame_evals, frame_cells = (int(v) for v in tot.tolist())
 
@@ -515,6 +562,8 @@ def main() -> int:
     frame_check = None
     window = None
     pipe = None
+    kern_ms = host_el = queued_el = None   # (a spinning camera's one-stream path measures them under --full)
+    dump_frame = None
     if native:
         # No silent fallback: a multi-GPU number must come from the path its
         # label names.  If the native RCCL frame loop cannot be made, every
@@ -575,7 +624,11 @@ def main() -> int:
         # (the copy now, the reference render after the passes below: a plain
         # render's other target geometry would make the loop's next frame
         # rebuild its region lists on the host)
-        got = pipe.frame(stream)
+        # (--dump-outputs writes the same copy: what the loop hands its caller)
+        got = pipe.frame(stream) if args.full or args.dump_outputs else None
+        if args.dump_outputs and rank == 0:
+            dump_frame = got
+    if native and args.full:
         # untimed, after the window: the same K frames gated -- queued behind
         # GATE_FRAMES frames of the loop, so the GPU never waits for the host
         # between them and runs at the window's clocks -- with HIP events after
@@ -606,7 +659,7 @@ def main() -> int:
             frame_check = frame_check_of(got, r.render(W, H, fmt))
         if world > 1:
             dist.barrier()
-    elif args.spin:
+    if not native and args.spin:
         r.render_sequence(W, H, fmt, sharder.local, sd[:args.warmup])
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -614,6 +667,9 @@ def main() -> int:
         queued_el = time.perf_counter() - t0   # the host waits once the GPU's queue is full
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_frame = sharder.local.cpu()
+    if not native and args.spin and args.full:
         # host time per frame (untimed for the rate): the same frames enqueued 8 at
         # a time on an idle GPU, so no enqueue waits for the GPU to drain its queue
         host_el = 0.0
@@ -647,7 +703,7 @@ def main() -> int:
                 torch.cuda.synchronize()
                 sampled.append(int(counter.item()))
         local_steps = frame_steps = int(round(float(np.mean(sampled))))
-    else:
+    if not native and not args.spin:
         warm_frames = clock_warm_ranks(lambda: sharder.run_frames(8), torch.cuda.synchronize, args.clock_warm_ms, world,
                                        red_dev)
         sharder.run_frames(args.warmup)
@@ -657,20 +713,23 @@ def main() -> int:
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
               if i % ev_every == 0 else None for i in range(args.steps)]
         t0 = time.perf_counter()
-        sharder.run_frames(args.steps, events=ev)
+        last = sharder.run_frames(args.steps, events=ev)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         el = time.perf_counter() - t0
         kern_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev if e is not None]))
-        got = sharder.frame()   # collective: a frame gathered as the window's were, untimed
-        if rank == 0:
-            frame_check = frame_check_of(got, r.render(W, H, fmt))
+        if args.dump_outputs and rank == 0:
+            dump_frame = last.cpu()
+        if args.full:
+            got = sharder.frame()   # collective: a frame gathered as the window's were, untimed
+            if rank == 0:
+                frame_check = frame_check_of(got, r.render(W, H, fmt))
     # A uniform channel (the recipe's constant G) is a constant tap with no
     # loads ("_u" kernels).  For comparison, the same K
     # frames with every channel loaded, timed after the main window (N = 1).
     all_loaded = None
-    if world == 1 and not args.spin and "_u" in r.kernel_variant:
+    if args.full and world == 1 and not args.spin and "_u" in r.kernel_variant:
         skipped_variant = r.kernel_variant
         r.set_option("uniform_skip", 0)
         if native:   # the same loop as the headline
@@ -721,17 +780,17 @@ def main() -> int:
     # the other BASELINE configs, timed in this process after the headline
     # window (N = 1 only; a multi-GPU run keeps to the headline)
     others, other_cpu = {}, {}
-    if world == 1 and not args.spin and args.config == "grid512" and not args.no_other_configs:
+    if args.full and world == 1 and not args.spin and args.config == "grid512" and not args.no_other_configs:
         for name in ("grid4k", "cloud", "cloud_shadow"):
             others[name], other_cpu[name] = other_config(name, args.steps, args.warmup, args.clock_warm_ms)
     # the measured HBM roofline of this box: one-pass 16-B-per-lane streams of
     # 2 GiB (past the 256 MiB Infinity Cache), read-only and copy, 4 / 8 / 16
     # loads in flight per lane; the larger rate is the denominator
     bw = {}
-    if rank == 0:
+    if args.full and rank == 0:
         for kind in ("read", "copy"):
             bw[kind] = r.measure_bandwidth(kind, 0, 2 << 30, 10)
-    tt = torch.tensor([el, kern_ms, busy_ms_frame or 0.0], dtype=torch.float64, device=red_dev)
+    tt = torch.tensor([el, kern_ms or 0.0, busy_ms_frame or 0.0], dtype=torch.float64, device=red_dev)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     el, kern_ms_max, busy_max = float(tt[0]), float(tt[1]), float(tt[2])
@@ -748,9 +807,17 @@ def main() -> int:
     # vr_shard_run_frames renders a procedural medium on one stream (its frames cannot overlap)
     rs = pipe.render_streams if pipe is not None else (args.render_streams or 1)
     streams_eff = 1 if proc is not None else rs
-    if rank == 0:
-        ms_per_step = el / args.steps * 1e3
-        value = W * H * S * args.steps / el / 1e6
+    ms_per_step = el / args.steps * 1e3
+    value = W * H * S * args.steps / el / 1e6
+    compositor = native and pipe is not None and pipe.compositor
+    lead = pipe.lead_rows if compositor else 0   # rank 0's lead rows beside its assembly
+    rows_part = native and pipe is not None and pipe.partition == "rows"
+    serp = " serpentine" if native and pipe is not None and getattr(pipe, "serpentine", False) else ""
+
+    def roofline_figures():
+        """--full, rank 0: the roofline object from the passes after the
+        window, the time per frame it divides by, and the PMC traffic and
+        L1-lookup figures of profiles/traffic.json where they fit this run."""
         variant = r.kernel_variant
         # two render streams (native loop, N > 1): a launch overlaps the next, so
         # its duration is not a frame's -- the roofline takes the wall time per frame
@@ -760,10 +827,6 @@ def main() -> int:
         # first-start-to-last-end span measures -- else the launches' mean
         roof_ms = ((gated_ms_frame or (window["gpu_window_ms"] / args.steps if window else ms_per_step))
                    if overlap else kern_ms)
-        compositor = native and pipe is not None and pipe.compositor
-        lead = pipe.lead_rows if compositor else 0   # rank 0's lead rows beside its assembly
-        rows_part = native and pipe is not None and pipe.partition == "rows"
-        serp = " serpentine" if native and pipe is not None and getattr(pipe, "serpentine", False) else ""
         if compositor:   # rank 0 renders nothing: the per-GPU figure is a renderer's average share
             nr = world - 1
             roofline = roofline_of(r, proc, shadow, variant, frame_steps // nr, frame_evals // nr,
@@ -833,6 +896,10 @@ def main() -> int:
                           "def": "PMC TCP_TOTAL_CACHE_ACCESSES_sum per launch (profiles/traffic.json) / the mean "
                                  "march-kernel duration; peak = 256 CUs x 1 lookup/cycle x 2.4 GHz "
                                  "(tools/tcp_calib.hip)"}
+        return roofline, roof_ms, traffic, ta
+
+    if rank == 0:
+        roofline, roof_ms, traffic, ta = roofline_figures() if args.full else (None, None, None, None)
         out = {
             "metric": "Mray/s (= W*H*steps/s) at 1080p x 128 steps" if (W, H, S) == (1920, 1080, 128)
                       else f"Mray/s (= W*H*steps/s) at {W}x{H} x {S} steps",
@@ -873,17 +940,18 @@ def main() -> int:
                                              if rs >= 2 else "")
                                           if native else "")),
                        "collective": collective_label,
-                       "executed_steps_per_frame": frame_steps},
-            "executed_steps_per_s": round(frame_steps * args.steps / el, 1),
-            "kernel_ms_mean": round(kern_ms, 5),
-            **({"host_ms_per_frame": round(host_el / args.steps * 1e3, 4)} if args.spin or native else {}),
+                       **({"executed_steps_per_frame": frame_steps} if args.full else {})},
+            "full": args.full,
+            **({"executed_steps_per_s": round(frame_steps * args.steps / el, 1)} if args.full else {}),
+            **({"kernel_ms_mean": round(kern_ms, 5)} if kern_ms is not None else {}),
+            **({"host_ms_per_frame": round(host_el / args.steps * 1e3, 4)} if host_el is not None else {}),
             **({"host_ms_per_frame_queued": round(queued_el / args.steps * 1e3, 4),
                 "host_ms_def": "host time of vr_render_sequence per frame, frames enqueued 8 at a time on an idle "
                                "GPU (host_ms_per_frame_queued: the timed 64-frame call, which waits whenever the "
-                               "GPU's queue is full)"} if args.spin and not native else {}),
+                               "GPU's queue is full)"} if args.spin and not native and host_el is not None else {}),
             **({"region_lists": {"gpu_builds": r.get_option("region_gpu_builds"),
                                  "interval": r.get_option("region_interval")}} if args.spin and proc is None else {}),
-            "frame_check": frame_check,
+            **({"frame_check": frame_check} if args.full else {}),
             **({"frame_check_def": "rank 0's last frame of the timed window ("
                                    + ("RCCL-gathered and assembled" if world > 1 else "the frame loop's")
                                    + ") against a plain one-GPU vr_render of the same camera, untimed: 'exact' = "
@@ -892,22 +960,26 @@ def main() -> int:
             **({"window": window} if window else {}),
             **({"all_channels_loaded": all_loaded} if all_loaded else {}),
             **({"frames_in_flight_2": inflight2} if inflight2 else {}),
-            "kernel_ms_mean_max_rank": round(kern_ms_max, 5),
-            "roofline": dict(roofline, traffic=traffic,
-                             **({"traffic_GBs": round(traffic / (roof_ms * 1e-3) / 1e9, 1),
-                                 "traffic_frac": round(traffic / (roof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                 "traffic_def": "PMC bytes per frame (profiles/traffic.json: FETCH_SIZE x 2 + "
-                                                "WRITE_SIZE, re-collected on this build in round 6) / the same "
-                                                "time per frame; FETCH_SIZE counts the L2's fabric requests, "
-                                                "Infinity-Cache hits included, and its x2 gfx950 correction is "
-                                                "calibrated for 16-B-per-lane streams, not the march's 8-B "
-                                                "gathers: an upper bound of the HBM bytes"}
-                                if traffic else {}),
-                             **({"ta_lookup": ta} if ta else {})),
+            **({"kernel_ms_mean_max_rank": round(kern_ms_max, 5)} if kern_ms is not None else {}),
         }
+        if args.full:
+            out["roofline"] = dict(
+                roofline, traffic=traffic,
+                **({"traffic_GBs": round(traffic / (roof_ms * 1e-3) / 1e9, 1),
+                    "traffic_frac": round(traffic / (roof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                    "traffic_def": "PMC bytes per frame (profiles/traffic.json: FETCH_SIZE x 2 + WRITE_SIZE, "
+                                   "re-collected on this build in round 6) / the same time per frame; FETCH_SIZE "
+                                   "counts the L2's fabric requests, Infinity-Cache hits included, and its x2 "
+                                   "gfx950 correction is calibrated for 16-B-per-lane streams, not the march's "
+                                   "8-B gathers: an upper bound of the HBM bytes"}
+                   if traffic else {}),
+                **({"ta_lookup": ta} if ta else {}))
+        if dump_frame is not None:
+            out["outputs"] = dict(dir=args.dump_outputs,
+                                  **dump_outputs(args.dump_outputs, {"frame": dump_frame.cpu().numpy()}))
         if others:
             out["other_configs"] = others
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(None if proc is not None else r.get_volume(), osd, gsd, march, W, H,
                                                args.cpu_budget, procedural=proc)
             for name, (vol_o, osd_o, gsd_o, march_o, W_o, H_o, proc_o) in other_cpu.items():

@@ -18,7 +18,7 @@ if [[ $STEPS == *tests* ]]; then
     echo "pytest rc=$rc"; tail -15 "$OUT/pytest_gpu.log"; stop_if_fatal $rc pytest
 fi
 if [[ $STEPS == *bench* ]]; then
-    timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1; rc=$?
+    timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1; rc=$?
     echo "bench rc=$rc"; tail -3 "$OUT/bench.log"; stop_if_fatal $rc bench
 fi
 if [[ $STEPS == *offscreen* ]]; then
@@ -29,7 +29,7 @@ fi
 if [[ $STEPS == *prof* ]]; then
     rm -rf "$OUT/prof"
     timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \
-        -- python3 bench.py --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/prof.log" 2>&1; rc=$?
+        -- python3 bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/prof.log" 2>&1; rc=$?
     echo "prof rc=$rc"; tail -2 "$OUT/prof.log"; stop_if_fatal $rc prof
 fi
 echo "gpu_check done"

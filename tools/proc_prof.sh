@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 for c in ${CONFIGS:-cloud cloud_shadow grid4k}; do
     rm -rf "$OUT/prof_$c"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$c" -o run --output-format csv \
-        -- python3 bench.py --config $c --steps ${BSTEPS:-10} --cpu-budget 8 > "$OUT/bench_$c.log" 2>&1 || { echo "bench $c failed"; tail -5 "$OUT/bench_$c.log"; exit 9; }
+        -- python3 bench.py --full --config $c --steps ${BSTEPS:-10} --cpu-budget 8 > "$OUT/bench_$c.log" 2>&1 || { echo "bench $c failed"; tail -5 "$OUT/bench_$c.log"; exit 9; }
     grep '^{' "$OUT/bench_$c.log" | tail -1
 done
 echo proc_prof done

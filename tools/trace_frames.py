@@ -1,8 +1,8 @@
-"""Per-frame figures of a `rocprofv3 --kernel-trace` run of bench.py, read from
+"""Per-frame figures of a `rocprofv3 --kernel-trace` run of bench.py --full, read from
 its kernel_trace.csv (verdict r05 #1: the line's roofline must recompute from
 the committed trace).
 
-For each config of the default line, the march launches are found by kernel
+For each config of the --full line, the march launches are found by kernel
 name in dispatch order: the untimed counting passes, `--warmup` frames, then
 the `--steps` timed frames.  Printed per config:
 
