@@ -193,6 +193,34 @@ const char* vr_build_id(void);
  *      data into its own device layout.  The host call is synchronous.     */
 vr_status vr_set_volume(void* ctx, const uint8_t* rgba8, int nx, int ny, int nz);
 vr_status vr_set_volume_device(void* ctx, const void* d_rgba8, int nx, int ny, int nz, void* stream);
+/* Partial update: the buffer-to-image copy region with a non-zero
+ * imageOffset, which the reference never needs (it uploads once, offset 0,
+ * full extent).  Overwrite the texel box [x0,x0+bx) x [y0,y0+by) x [z0,z0+bz)
+ * of the installed volume with `rgba8` (bx*by*bz RGBA8 texels, tightly
+ * packed, x fastest -- the order of vr_set_volume).  Afterwards the ctx
+ * renders, and vr_get_volume reads, bit for bit what a vr_set_volume of the
+ * whole patched volume would give.  The work follows the box (plus a halo of
+ * one texel position in the device layouts), not the volume.
+ *
+ * VR_ERR_INVALID: a null pointer, a non-positive extent or a box that leaves
+ * the volume; VR_ERR_NO_VOLUME before an install.  A refused call leaves the
+ * volume untouched.  Dimensions, layout preference and buffers do not change.
+ *
+ * vr_update_volume is synchronous, like vr_set_volume.  The device variant is
+ * asynchronous on `stream`: it allocates nothing and never waits on the host,
+ * so `update, render, update, render ...` queues on one stream like the rest
+ * of the frame loop.  Renders of the same ctx queued on OTHER streams are the
+ * caller's to order against the update (an event, as for any shared buffer);
+ * `d_rgba8` must stay valid until the update has run.
+ *
+ * Uniform channels (option "uniform_mask": every texel of a channel equal,
+ * sampled as a constant): an update that breaks one clears its bit before
+ * the next render; while a channel is uniform that next render waits on the
+ * host once for the check, exactly as after an install.  A channel an update
+ * makes uniform AGAIN stays "not uniform" until the next full install -- the
+ * output is exact either way, only the loads are not skipped.             */
+vr_status vr_update_volume(void* ctx, const uint8_t* rgba8, int x0, int y0, int z0, int bx, int by, int bz);
+vr_status vr_update_volume_device(void* ctx, const void* d_rgba8, int x0, int y0, int z0, int bx, int by, int bz, void* stream);
 /* read the volume back as RGBA8 (host); for tests and tools             */
 vr_status vr_get_volume(void* ctx, uint8_t* rgba8_out);
 vr_status vr_volume_dims(void* ctx, int* nx, int* ny, int* nz);

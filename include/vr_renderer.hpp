@@ -52,6 +52,17 @@ public:
     {
         Check(vr_set_volume(ctx_, rgba, nx, ny, nz), "vr_set_volume");
     }
+    // The copy region with a non-zero imageOffset: overwrite the texel box
+    // (bx, by, bz) at (x0, y0, z0) of the installed volume (vr_update_volume).
+    void UpdateVolume(const uint8_t* rgba, int x0, int y0, int z0, int bx, int by, int bz)
+    {
+        Check(vr_update_volume(ctx_, rgba, x0, y0, z0, bx, by, bz), "vr_update_volume");
+    }
+    // the same from device memory, asynchronous on `stream` (vr_update_volume_device)
+    void UpdateVolumeDevice(const void* d_rgba, int x0, int y0, int z0, int bx, int by, int bz, void* stream = nullptr)
+    {
+        Check(vr_update_volume_device(ctx_, d_rgba, x0, y0, z0, bx, by, bz, stream), "vr_update_volume_device");
+    }
     void GenerateVolume(const vr_volume_recipe& r, void* stream = nullptr)
     {
         Check(vr_generate_volume(ctx_, &r, stream), "vr_generate_volume");

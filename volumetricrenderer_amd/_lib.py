@@ -108,6 +108,8 @@ _SIGS = {
     "vr_build_id": (ctypes.c_char_p, []),
     "vr_set_volume": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vr_set_volume_device": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "vr_update_volume": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6),
+    "vr_update_volume_device": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [_vp]),
     "vr_get_volume": (ctypes.c_int, [_vp, _vp]),
     "vr_volume_dims": (ctypes.c_int, [_vp, c_int_p, c_int_p, c_int_p]),
     "vr_volume_extent_ok": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),

@@ -397,6 +397,83 @@ try {
     return caught_exception("vr_set_volume_device");
 }
 
+}  // extern "C"
+
+namespace vrapi {
+
+// The argument checks of vr_update_volume / vr_update_volume_device: a refused
+// call has touched nothing.
+static vr_status check_update(const char* fn, void* p, const void* data, int x0, int y0, int z0, int bx, int by, int bz)
+{
+    if (!p || !data) return fail(VR_ERR_INVALID, "%s: null argument", fn);
+    if (bx <= 0 || by <= 0 || bz <= 0) return fail(VR_ERR_INVALID, "%s: bad box extent %dx%dx%d", fn, bx, by, bz);
+    const Ctx* c = as_ctx(p);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "%s: no volume set", fn);
+    if (x0 < 0 || y0 < 0 || z0 < 0 || bx > c->nx - x0 || by > c->ny - y0 || bz > c->nz - z0)
+        return fail(VR_ERR_INVALID, "%s: box %dx%dx%d at (%d, %d, %d) leaves the %dx%dx%d volume", fn, bx, by, bz, x0,
+                    y0, z0, c->nx, c->ny, c->nz);
+    return VR_OK;
+}
+
+// Patch the planes and the held fast layout on `s`: launches only, no
+// allocation, no host wait.  The scatter folds the box's byte range into d_mm,
+// so a uniform channel (uniform_mask, which the _uX kernels sample as a
+// constant) can only be lost: while some channel is uniform, or the install's
+// scan is still unresolved, the read-back is re-armed and the next render /
+// vr_kernel_variant / vr_get_option resolves it as after an install.  With no
+// uniform channel left nothing can change: no read-back, no `gen` bump, and
+// the cached launches stay valid (same buffers, same geometry).
+static vr_status update_volume_device(Ctx* c, const uint8_t* d_box, int x0, int y0, int z0, int bx, int by, int bz,
+                                      hipStream_t s)
+{
+    HIP_TRY(launch_update_planar(d_box, c->nx, c->ny, c->nz, x0, y0, z0, bx, by, bz, c->d_planar, c->d_mm, s));
+    if (c->fast_layout)
+        HIP_TRY(launch_build_layout_box(c->fast_layout, c->d_planar, c->nx, c->ny, c->nz, c->d_fast, x0, y0, z0, bx,
+                                        by, bz, s));
+    if (c->mm_pending || c->uniform_mask != 0) {
+        HIP_TRY(hipMemcpyAsync(c->h_mm, c->d_mm, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(c->mm_ready, s));
+        c->mm_pending = true;
+    }
+    return VR_OK;
+}
+
+}  // namespace vrapi
+
+extern "C" {
+
+vr_status vr_update_volume(void* p, const uint8_t* rgba8, int x0, int y0, int z0, int bx, int by, int bz)
+try {
+    if (vr_status st = check_update("vr_update_volume", p, rgba8, x0, y0, z0, bx, by, bz)) return st;
+    Ctx* c = as_ctx(p);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)bx * by * bz * 4;
+    uint8_t* staging = nullptr;   // the box, not the volume
+    HIP_TRY(hipMalloc(&staging, bytes));
+    hipError_t e = hipMemcpy(staging, rgba8, bytes, hipMemcpyHostToDevice);
+    vr_status st = VR_OK;
+    if (e == hipSuccess) st = update_volume_device(c, staging, x0, y0, z0, bx, by, bz, nullptr);
+    if (e == hipSuccess && st == VR_OK) e = hipDeviceSynchronize();
+    (void)hipFree(staging);
+    if (st != VR_OK) return st;
+    if (e != hipSuccess) return fail(VR_ERR_HIP, "vr_update_volume: %s", hipGetErrorString(e));
+    return VR_OK;
+} catch (...) {
+    return caught_exception("vr_update_volume");
+}
+
+vr_status vr_update_volume_device(void* p, const void* d_rgba8, int x0, int y0, int z0, int bx, int by, int bz,
+                                  void* stream)
+try {
+    if (vr_status st = check_update("vr_update_volume_device", p, d_rgba8, x0, y0, z0, bx, by, bz)) return st;
+    Ctx* c = as_ctx(p);
+    HIP_TRY(hipSetDevice(c->device));
+    return update_volume_device(c, static_cast<const uint8_t*>(d_rgba8), x0, y0, z0, bx, by, bz,
+                                static_cast<hipStream_t>(stream));
+} catch (...) {
+    return caught_exception("vr_update_volume_device");
+}
+
 int vr_volume_extent_ok(int nx, int ny, int nz) { return dims_ok(nx, ny, nz) ? 1 : 0; }
 
 vr_status vr_volume_dims(void* p, int* nx, int* ny, int* nz)

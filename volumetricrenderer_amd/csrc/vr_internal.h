@@ -411,6 +411,16 @@ hipError_t launch_repack(const uint8_t* d_rgba, int nx, int ny, int nz, uint8_t*
 // Build a fast layout from the planar planes.
 hipError_t launch_build_layout(int layout, const uint8_t* d_planar, int nx, int ny, int nz, uint8_t* d_out,
                                hipStream_t s);
+// vr_update_volume: scatter the tightly packed RGBA8 box d_box (bx x by x bz texels at texel
+// (x0, y0, z0), inside the volume) into the planar planes, and fold its per-channel byte
+// min / max into mm (launch_plane_minmax's layout) with atomicMin / atomicMax
+hipError_t launch_update_planar(const uint8_t* d_box, int nx, int ny, int nz, int x0, int y0, int z0, int bx, int by,
+                                int bz, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+// Rebuild the elements of a fast layout that store a texel of that box, from the (updated)
+// planar planes: work and bytes follow the box and its one-position halo.  The default
+// build's layouts (CORNERH, CORNER8, BRICK4832, COL48); any other is rebuilt whole.
+hipError_t launch_build_layout_box(int layout, const uint8_t* d_planar, int nx, int ny, int nz, uint8_t* d_out,
+                                   int x0, int y0, int z0, int bx, int by, int bz, hipStream_t s);
 size_t layout_plane_bytes(int layout, int nx, int ny, int nz);
 // bytes of all four planes of a fast layout (COL48Z's planes differ in size)
 size_t layout_total_bytes(int layout, int nx, int ny, int nz);

@@ -34,6 +34,62 @@ __global__ __launch_bounds__(kBlock) void k_repack_planar(const uchar4* __restri
     }
 }
 
+// vr_update_volume: scatter a tightly packed RGBA8 box (bx x by x bz texels at
+// texel (x0, y0, z0), x fastest) into the four planes.  One thread per texel,
+// consecutive lanes on consecutive x of a box row: a 4-B load, then one byte
+// store per plane -- the plane rows start at any byte (x0 and nx are
+// arbitrary), so nothing wider is assumed.  Each workgroup folds its texels'
+// per-channel byte min / max into mm (k_plane_minmax's [min x 4, max x 4]):
+// both only move outwards, so a channel can lose min == max but never gain it.
+__global__ __launch_bounds__(kBlock) void k_update_planar(const uchar4* __restrict__ src, int nx, int ny, int nz,
+                                                          int x0, int y0, int z0, int bx, int by, int bz,
+                                                          uint8_t* __restrict__ dst, unsigned* __restrict__ mm)
+{
+    const unsigned total = (unsigned)bx * (unsigned)by * (unsigned)bz;   // < 2^31 (inside the volume)
+    const long long plane = (long long)nx * ny * nz;
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
+        const unsigned t = i / (unsigned)bx;
+        const int x = (int)(i - t * (unsigned)bx), y = (int)(t % (unsigned)by), z = (int)(t / (unsigned)by);
+        const uchar4 v = src[i];
+        const long long d = ((long long)(z0 + z) * ny + (y0 + y)) * nx + (x0 + x);
+        dst[d] = v.x;
+        dst[d + plane] = v.y;
+        dst[d + 2 * plane] = v.z;
+        dst[d + 3 * plane] = v.w;
+        const unsigned c[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { lo[k] = min(lo[k], c[k]); hi[k] = max(hi[k], c[k]); }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        for (int off = 32; off > 0; off >>= 1) {
+            lo[k] = min(lo[k], (unsigned)__shfl_xor((int)lo[k], off));
+            hi[k] = max(hi[k], (unsigned)__shfl_xor((int)hi[k], off));
+        }
+    // waves -> workgroup through LDS, then at most one atomic per channel and
+    // bound: only where the box widens the range.  (mm only moves outwards, so a
+    // stale read of it can ask for a redundant atomic, never miss a needed one;
+    // a time-varying volume whose channels span 0..255 issues none.)
+    __shared__ unsigned red[kBlock / 64][8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { red[wave][k] = lo[k]; red[wave][4 + k] = hi[k]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const int k = threadIdx.x;
+        unsigned v = red[0][k];
+        for (int w = 1; w < kBlock / 64; ++w) v = k < 4 ? min(v, red[w][k]) : max(v, red[w][k]);
+        if (k < 4) {
+            if (v < mm[k]) atomicMin(&mm[k], v);
+        } else {
+            if (v > mm[k]) atomicMax(&mm[k], v);
+        }
+    }
+}
+
 // Fast layouts, built from the planar planes.  Every element stores
 // clamp-to-edge texels of the padded base position (a, b, c), where texel
 // index = padded index - 1 (vr_internal.h Layout).
@@ -50,24 +106,36 @@ struct PlaneSrc {
 // One thread per output element: a byte of an apron brick, or one 8-byte
 // footprint word (CORNER8).  Brick order and in-brick order match
 // axis_offset() in vr_internal.h, which the march kernel's LDS tables use.
+// Builds the bricks [o, o + n) per axis (CORNERH: positions; its "brick" is
+// one 16-B word): the full build is o = 0, n = (nbx, nby, nbz), a box update
+// (launch_build_layout_box) the bricks that store a texel of the box.
+struct BuildRange {
+    int o[3], n[3];
+};
 template <int LAYOUT>
 __global__ __launch_bounds__(kBlock) void k_build_layout(const uint8_t* __restrict__ planar, int nx, int ny,
-                                                         int nz, LayoutGeom g, long long plane_elems,
+                                                         int nz, LayoutGeom g, BuildRange r,
                                                          long long plane_bytes, uint8_t* __restrict__ out, int nch = 4)
 {
     const long long total_planar = (long long)nx * ny * nz;
-    for (long long i = blockIdx.x * (long long)kBlock + threadIdx.x; i < nch * plane_elems;
+    // elements per brick
+    const long long per = LAYOUT == LAYOUT_CORNER8 ? 64 : LAYOUT == LAYOUT_CORNERH ? 1
+                        : LAYOUT == LAYOUT_ZPAIR ? 128 : (long long)g.brick;
+    const long long range_elems = per * r.n[0] * r.n[1] * r.n[2];
+    for (long long i = blockIdx.x * (long long)kBlock + threadIdx.x; i < nch * range_elems;
          i += (long long)gridDim.x * kBlock) {
-        const int ch = (int)(i / plane_elems);
-        const long long e = i - ch * plane_elems;
+        const int ch = (int)(i / range_elems);
+        const long long l = i - ch * range_elems;
+        const long long lb = l / per;   // brick of the range, x fastest
+        const int in = (int)(l - lb * per);
+        const int bx = r.o[0] + (int)(lb % r.n[0]);
+        const long long t = lb / r.n[0];
+        const int by = r.o[1] + (int)(t % r.n[1]), bz = r.o[2] + (int)(t / r.n[1]);
+        const long long e = (((long long)bz * g.nby + by) * g.nbx + bx) * per + in;   // element of the plane
         const PlaneSrc src{planar + ch * total_planar, nx, ny, nz};
         uint8_t* dst = out + ch * plane_bytes;
         if constexpr (LAYOUT == LAYOUT_CORNER8) {
-            const long long brick = e >> 6;
-            const int pos = (int)(e & 63);
-            const int bx = (int)(brick % g.nbx);
-            const long long t = brick / g.nbx;
-            const int by = (int)(t % g.nby), bz = (int)(t / g.nby);
+            const int pos = in;
             const int a = 4 * bx + (pos & 3), b = 4 * by + ((pos >> 2) & 3), c = 4 * bz + (pos >> 4);
             unsigned long long q = 0;
             for (int k = 0; k < 8; ++k)
@@ -77,9 +145,7 @@ __global__ __launch_bounds__(kBlock) void k_build_layout(const uint8_t* __restri
             // position (a, b, c), x fastest; dword k = footprint row (y, z) =
             // (b + (k & 1), c + (k >> 1)): f16 a in the low half, f16 (b - a)
             // in the high half (both exact: |values| <= 255)
-            const int a = (int)(e % g.nbx);
-            const long long t = e / g.nbx;
-            const int b = (int)(t % g.nby), c = (int)(t / g.nby);
+            const int a = bx, b = by, c = bz;
             unsigned w[4];
             for (int k = 0; k < 4; ++k) {
                 const int y = b + (k & 1), z = c + (k >> 1);
@@ -91,21 +157,13 @@ __global__ __launch_bounds__(kBlock) void k_build_layout(const uint8_t* __restri
             reinterpret_cast<uint4*>(dst)[e] = make_uint4(w[0], w[1], w[2], w[3]);
         } else if constexpr (LAYOUT == LAYOUT_ZPAIR) {
             // byte = x + 4 * (z + 2 * y): 4-byte rows, z fastest
-            const long long brick = e >> 7;
-            const int byte = (int)(e & 127);
-            const int bx = (int)(brick % g.nbx);
-            const long long t = brick / g.nbx;
-            const int by = (int)(t % g.nby), bz = (int)(t / g.nby);
+            const int byte = in;
             dst[e] = src.at(3 * bx + (byte & 3), 15 * by + (byte >> 3), bz + ((byte >> 2) & 1));
         } else {
-            const long long brick = e / g.brick;
-            const int byte = (int)(e - brick * g.brick);
+            const int byte = in;
             unsigned int v = 0;
             if (byte < g.Rn[0] * g.Rn[1] * g.Rn[2]) {
                 const int u = byte % g.Rn[0], vv = (byte / g.Rn[0]) % g.Rn[1], w = byte / (g.Rn[0] * g.Rn[1]);
-                const int bx = (int)(brick % g.nbx);
-                const long long t = brick / g.nbx;
-                const int by = (int)(t % g.nby), bz = (int)(t / g.nby);
                 v = src.at(g.Ba[0] * bx + u, g.Ba[1] * by + vv, g.Ba[2] * bz + w);
             }
             dst[e] = (uint8_t)v;
@@ -127,16 +185,20 @@ constexpr int kBrickStageBytes = 16 * 1024;
 // builds segment blockIdx.y -- slices [zseg * seg, zseg * (seg + 1)) -- of a
 // run of columns; a column's segment is contiguous, the run's columns sit a
 // column (g.brick bytes) apart.
+//
+// The grid covers the bricks r.o[0] + [0, r.n[0]) in runs along x, r.o[1] +
+// [0, r.n[1]) along y and r.o[2] + [0, gridDim.y) along z (zseg > 0: segments):
+// everything for the full build, the bricks a box update touches otherwise.
 __global__ __launch_bounds__(kBlock) void k_build_bricks(const uint8_t* __restrict__ planar, int nx, int ny, int nz,
-                                                         LayoutGeom g, int run, long long plane_bytes, int zseg,
-                                                         uint8_t* __restrict__ out)
+                                                         LayoutGeom g, BuildRange r, int run, long long plane_bytes,
+                                                         int zseg, uint8_t* __restrict__ out)
 {
     __shared__ uint8_t st[kBrickStageBytes];
     const int ch = blockIdx.z;
     const uint8_t* __restrict__ p = planar + (long long)ch * nx * ny * nz;
-    const int runs_x = (g.nbx + run - 1) / run;
-    const int rx = (int)blockIdx.x % runs_x, by = (int)blockIdx.x / runs_x, bz = (int)blockIdx.y;
-    const int bx0 = rx * run, nb = min(run, g.nbx - bx0);
+    const int runs_x = (r.n[0] + run - 1) / run;
+    const int rx = (int)blockIdx.x % runs_x, by = r.o[1] + (int)blockIdx.x / runs_x, bz = r.o[2] + (int)blockIdx.y;
+    const int bx0 = r.o[0] + rx * run, nb = min(run, r.o[0] + r.n[0] - bx0);
     const int rn0 = g.Rn[0], rn1 = g.Rn[1], rn2 = zseg > 0 ? min(zseg, g.Rn[2] - zseg * bz) : g.Rn[2];
     // slice w of a COL48 column holds padded z position w (texel w - 1)
     const int x0 = g.Ba[0] * bx0 - 1, y0 = g.Ba[1] * by - 1, z0 = zseg > 0 ? zseg * bz - 1 : g.Ba[2] * bz - 1;
@@ -495,28 +557,30 @@ size_t layout_total_bytes(int layout, int nx, int ny, int nz)
     return 4 * layout_plane_bytes(layout, nx, ny, nz);
 }
 
-hipError_t launch_build_layout(int layout, const uint8_t* d_planar, int nx, int ny, int nz, uint8_t* d_out,
-                               hipStream_t s)
+namespace {
+// Build the bricks of range r (k_build_layout's units; COL48 / COL48Z: columns
+// in x and y, 32-slice segments in z) of a fast layout from the planar planes.
+constexpr int kColSeg = 32;   // COL48 z segment: 1 KiB of a column, BRICK4832's stage
+hipError_t launch_build_range(int layout, const uint8_t* d_planar, int nx, int ny, int nz, uint8_t* d_out,
+                              const BuildRange& r, hipStream_t s)
 {
     const LayoutGeom g = layout_geom(layout, nx, ny, nz);
-    const long long elems = layout_elems(layout, nx, ny, nz);
     const long long pb = (long long)layout_plane_bytes(layout, nx, ny, nz);
-    const dim3 gr(grid_for(4 * elems)), b(kBlock);
+    const dim3 b(kBlock);
     const long long rows = (long long)g.Rn[1] * g.Rn[2];
     if (layout == LAYOUT_COL48 || layout == LAYOUT_COL48Z) {
         const int nch = layout == LAYOUT_COL48Z ? 3 : 4;   // COL48Z: channel 3 is ZPAIR's, below
-        // columns in z segments of 32 slices (1 KiB of a column: BRICK4832's stage)
-        constexpr int kSeg = 32;
-        const long long srows = (long long)g.Rn[1] * kSeg;
-        const int run = (int)std::min<long long>(g.nbx, (kBrickStageBytes / srows - g.Rn[0] - 7) / g.Ba[0] + 1);
-        const int runs_x = (g.nbx + run - 1) / run;
-        const dim3 gb((unsigned)(runs_x * g.nby), (unsigned)((g.Rn[2] + kSeg - 1) / kSeg), nch);   // last segment partial
-        hipLaunchKernelGGL(k_build_bricks, gb, b, 0, s, d_planar, nx, ny, nz, g, run, pb, kSeg, d_out);
-        if (layout == LAYOUT_COL48Z) {
+        const long long srows = (long long)g.Rn[1] * kColSeg;
+        const int run = (int)std::min<long long>(r.n[0], (kBrickStageBytes / srows - g.Rn[0] - 7) / g.Ba[0] + 1);
+        const int runs_x = (r.n[0] + run - 1) / run;
+        const dim3 gb((unsigned)(runs_x * r.n[1]), (unsigned)r.n[2], nch);   // the column's last segment is partial
+        hipLaunchKernelGGL(k_build_bricks, gb, b, 0, s, d_planar, nx, ny, nz, g, r, run, pb, kColSeg, d_out);
+        if (layout == LAYOUT_COL48Z) {   // (full builds only: the ZPAIR plane is built whole)
             const LayoutGeom gz = layout_geom(LAYOUT_ZPAIR, nx, ny, nz);
             const long long ez = layout_elems(LAYOUT_ZPAIR, nx, ny, nz);
+            const BuildRange rz{{0, 0, 0}, {gz.nbx, gz.nby, gz.nbz}};
             hipLaunchKernelGGL(k_build_layout<LAYOUT_ZPAIR>, dim3(grid_for(ez)), b, 0, s,
-                               d_planar + 3 * (long long)nx * ny * nz, nx, ny, nz, gz, ez,
+                               d_planar + 3 * (long long)nx * ny * nz, nx, ny, nz, gz, rz,
                                (long long)layout_plane_bytes(LAYOUT_ZPAIR, nx, ny, nz), d_out + 3 * pb, 1);
         }
         return hipGetLastError();
@@ -525,30 +589,83 @@ hipError_t launch_build_layout(int layout, const uint8_t* d_planar, int nx, int 
         rows * (g.Ba[0] + g.Rn[0] + 8) <= kBrickStageBytes) {
         // bricks per workgroup: the longest run whose source box (+ up to 7
         // bytes of dword alignment per row) fits the stage
-        const int run = (int)std::min<long long>(g.nbx, (kBrickStageBytes / rows - g.Rn[0] - 7) / g.Ba[0] + 1);
-        const int runs_x = (g.nbx + run - 1) / run;
-        const dim3 gb((unsigned)(runs_x * g.nby), (unsigned)g.nbz, 4);
-        hipLaunchKernelGGL(k_build_bricks, gb, b, 0, s, d_planar, nx, ny, nz, g, run, pb, 0, d_out);
+        const int run = (int)std::min<long long>(r.n[0], (kBrickStageBytes / rows - g.Rn[0] - 7) / g.Ba[0] + 1);
+        const int runs_x = (r.n[0] + run - 1) / run;
+        const dim3 gb((unsigned)(runs_x * r.n[1]), (unsigned)r.n[2], 4);
+        hipLaunchKernelGGL(k_build_bricks, gb, b, 0, s, d_planar, nx, ny, nz, g, r, run, pb, 0, d_out);
         return hipGetLastError();
     }
+    const long long per = layout == LAYOUT_CORNER8 ? 64 : layout == LAYOUT_CORNERH ? 1
+                        : layout == LAYOUT_ZPAIR ? 128 : (long long)g.brick;
+    const dim3 gr(grid_for(4 * per * r.n[0] * r.n[1] * r.n[2]));
     switch (layout) {
-    case LAYOUT_BRICK4: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK4>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_BRICK5: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK5>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_BRICK8: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK8>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_BRICK16: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK16>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_BRICK448: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK448>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_BRICK488: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK488>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_BRICK4816: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK4816>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_BRICK4864: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK4864>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_BRICK4832: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK4832>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_COL48: hipLaunchKernelGGL(k_build_layout<LAYOUT_COL48>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_BRICK41616: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK41616>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_ZPAIR: hipLaunchKernelGGL(k_build_layout<LAYOUT_ZPAIR>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_CORNER8: hipLaunchKernelGGL(k_build_layout<LAYOUT_CORNER8>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
-    case LAYOUT_CORNERH: hipLaunchKernelGGL(k_build_layout<LAYOUT_CORNERH>, gr, b, 0, s, d_planar, nx, ny, nz, g, elems, pb, d_out); break;
+    case LAYOUT_BRICK4: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK4>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_BRICK5: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK5>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_BRICK8: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK8>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_BRICK16: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK16>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_BRICK448: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK448>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_BRICK488: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK488>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_BRICK4816: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK4816>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_BRICK4864: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK4864>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_BRICK4832: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK4832>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_COL48: hipLaunchKernelGGL(k_build_layout<LAYOUT_COL48>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_BRICK41616: hipLaunchKernelGGL(k_build_layout<LAYOUT_BRICK41616>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_ZPAIR: hipLaunchKernelGGL(k_build_layout<LAYOUT_ZPAIR>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_CORNER8: hipLaunchKernelGGL(k_build_layout<LAYOUT_CORNER8>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
+    case LAYOUT_CORNERH: hipLaunchKernelGGL(k_build_layout<LAYOUT_CORNERH>, gr, b, 0, s, d_planar, nx, ny, nz, g, r, pb, d_out); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+}  // namespace
+
+// The full build: the range that holds every brick.
+hipError_t launch_build_layout(int layout, const uint8_t* d_planar, int nx, int ny, int nz, uint8_t* d_out,
+                               hipStream_t s)
+{
+    const LayoutGeom g = layout_geom(layout, nx, ny, nz);
+    const bool col = layout == LAYOUT_COL48 || layout == LAYOUT_COL48Z;
+    const BuildRange r{{0, 0, 0}, {g.nbx, g.nby, col ? (g.Rn[2] + kColSeg - 1) / kColSeg : g.nbz}};
+    return launch_build_range(layout, d_planar, nx, ny, nz, d_out, r, s);
+}
+
+hipError_t launch_update_planar(const uint8_t* d_box, int nx, int ny, int nz, int x0, int y0, int z0, int bx, int by,
+                                int bz, uint8_t* d_planar, unsigned* mm, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_update_planar, dim3(grid_for((long long)bx * by * bz)), dim3(kBlock), 0, s,
+                       reinterpret_cast<const uchar4*>(d_box), nx, ny, nz, x0, y0, z0, bx, by, bz, d_planar, mm);
+    return hipGetLastError();
+}
+
+// A fast layout stores texel x (padded index x + 1) under the base positions
+// x and x + 1, and the clamp-to-edge copies of texels 0 and N - 1 under the
+// positions 0 and N: the box [x0, x0 + bx) changes the positions [x0, x0 + bx]
+// per axis -- the box and a halo of one position.  The bricks that hold them
+// are [lo / Ba, hi / Ba] per axis (layout_geom / axis_offset): the brick q
+// stores the padded texels Ba q .. Ba q + Ba, so a texel on a brick boundary
+// lies in both neighbours, and the last brick holds everything past N.
+hipError_t launch_build_layout_box(int layout, const uint8_t* d_planar, int nx, int ny, int nz, uint8_t* d_out,
+                                   int x0, int y0, int z0, int bx, int by, int bz, hipStream_t s)
+{
+    if (layout != LAYOUT_CORNERH && layout != LAYOUT_CORNER8 && layout != LAYOUT_BRICK4832 && layout != LAYOUT_COL48)
+        return launch_build_layout(layout, d_planar, nx, ny, nz, d_out, s);   // VR_EXPERIMENTS layouts: all of it
+    const LayoutGeom g = layout_geom(layout, nx, ny, nz);
+    const int lo[3] = {x0, y0, z0}, hi[3] = {x0 + bx, y0 + by, z0 + bz};
+    BuildRange r{};
+    for (int ax = 0; ax < 3; ++ax) {
+        // Ba: CORNER8's footprint words sit in 4^3 position bricks (the update rewrites
+        // whole ones), CORNERH's are addressed one by one (Ba = 1: the position box itself)
+        r.o[ax] = lo[ax] / g.Ba[ax];
+        r.n[ax] = hi[ax] / g.Ba[ax] - r.o[ax] + 1;
+    }
+    if (layout == LAYOUT_COL48) {
+        // one column through z: slice w holds padded z position w (texel w - 1), and
+        // the slices past nz + 1 (the even count) repeat the last texel
+        const int last = z0 + bz == nz ? g.Rn[2] - 1 : z0 + bz;
+        r.o[2] = z0 / kColSeg;
+        r.n[2] = last / kColSeg - r.o[2] + 1;
+    }
+    return launch_build_range(layout, d_planar, nx, ny, nz, d_out, r, s);
 }
 
 hipError_t launch_unpack(const uint8_t* d_planar, int nx, int ny, int nz, uint8_t* d_rgba, hipStream_t s)

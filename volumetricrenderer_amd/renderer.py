@@ -163,6 +163,30 @@ class Renderer:
         call("vr_set_volume_device", self._ctx, ctypes.c_void_p(t.data_ptr()), nx, ny, nz, h)
         (stream if stream is not None else torch.cuda.current_stream()).synchronize()
 
+    def update_volume(self, box, origin, stream=None) -> None:
+        """Overwrite the texel box shaped (bz, by, bx, 4) at origin = (x0, y0, z0)
+        of the installed volume (vr_update_volume): the renderer then holds the
+        patched volume, bit for bit, at a cost that follows the box.  A numpy
+        array goes through the synchronous host call.  A CUDA uint8 tensor is
+        queued on `stream` (default: the current stream); with a stream given
+        nothing waits, so update and render queue back to back on it, and the
+        caller keeps the tensor alive until the update has run."""
+        x0, y0, z0 = (int(v) for v in origin)
+        if isinstance(box, torch.Tensor) and box.is_cuda:
+            if box.dtype != torch.uint8 or box.dim() != 4 or box.shape[3] != 4 or not box.is_contiguous():
+                raise ValueError("device box must be a contiguous uint8 tensor (bz, by, bx, 4)")
+            bz, by, bx, _ = box.shape
+            call("vr_update_volume_device", self._ctx, ctypes.c_void_p(box.data_ptr()), x0, y0, z0, bx, by, bz,
+                 _stream_handle(stream))
+            if stream is None:
+                torch.cuda.current_stream().synchronize()
+            return
+        a = np.ascontiguousarray(box, dtype=np.uint8)
+        if a.ndim != 4 or a.shape[3] != 4:
+            raise ValueError("box must be shaped (bz, by, bx, 4)")
+        bz, by, bx, _ = a.shape
+        call("vr_update_volume", self._ctx, a.ctypes.data_as(ctypes.c_void_p), x0, y0, z0, bx, by, bz)
+
     def generate_volume(self, recipe: VolumeRecipe | None = None) -> None:
         """Build the TestMain.cpp:43-92 volume on the GPU."""
         r = recipe if recipe is not None else volume_recipe_defaults()
