@@ -911,7 +911,7 @@ try {
         if (sort_buf) {
             key = {(float)a.width, (float)a.height, (float)a.out_rows, (float)a.band_rows, (float)a.band_stride,
                    (float)a.band_first, (float)a.max_steps, a.step_size, (float)a.cam_mode,
-                   (float)(a.proc.shadow_steps > 0), (float)a.proc.enum_regions};
+                   (float)(a.proc.shadow_steps > 0), (float)a.proc.enum_regions, (float)a.band_flip};
             for (const float* v : {a.org, a.o, a.px, a.py, a.cam, a.box_min, a.box_max, a.box_range})
                 key.insert(key.end(), v, v + 3);
             key.insert(key.end(), a.r2, a.r2 + 4);

@@ -51,7 +51,7 @@ constexpr int kRegionRebuildInterval = 32;
 // order built for an older one, for R renders after the build (vr_render; the
 // march then also checks the pixels the old order left out, so every frame
 // stays exact).
-constexpr size_t kSortKeyGridPart = 11;   // leading sort-key entries a stale order must match
+constexpr size_t kSortKeyGridPart = 12;   // leading sort-key entries a stale order must match (band_flip is the last)
 constexpr int kMaxRegionStreams = 4;
 // largest deferred-shadow scratch (option "shadow_defer_mib"): the scratch is
 // sized from the frame (ensure_defer: ~0.35 GB at 1080p x 128, ~2.7 GB at
