@@ -278,6 +278,63 @@ vr_status vr_render(void* ctx, const vr_target* target, void* stream);
 vr_status vr_render_sequence(void* ctx, const vr_target* target, int frames, const vr_object_shader_data* osd,
                              const vr_global_shader_data* gsd, void* stream);
 
+/* ---- the scissor: replaces vkCmdSetScissor with a VkRect2D, a dynamic state
+ *      of the reference's pipeline (TestMain.cpp:192, 204-205, where it is
+ *      always the whole swapchain extent).  Pixels: x along a row, y the
+ *      frame row.                                                            */
+typedef struct { int32_t x, y, width, height; } vr_rect;
+/* Render the pixels [x, x+width) x [y, y+height) of a whole-frame target:
+ * each of them gets, bit for bit, what vr_render of the same target writes
+ * there; no other byte of `pixels` is touched.  `target` must be a plain
+ * whole-frame target (band_rows 0, band_flip 0, no VR_TARGET_* flag), in any
+ * format and with any valid row_pitch.  step_counter, when given, has the
+ * ray-steps of those pixels added (option "count" as for vr_render).
+ *
+ * An empty rectangle (width or height 0) is VR_OK and does nothing.
+ * VR_ERR_INVALID: a null pointer, a rectangle that is negative or leaves the
+ * frame, a band / row-range / in-place target; VR_ERR_NO_VOLUME and
+ * VR_ERR_NO_CAMERA as for vr_render.  A refused call writes nothing.
+ *
+ * Asynchronous on `stream`; allocates nothing and NEVER waits on the host.
+ * One wave marches one 8x8 tile of the rectangle and the grid is sized from
+ * the rectangle, so the cost follows it (down to the floor its longest ray
+ * sets).  The call uses none of the context's cached launches, region lists,
+ * cost-sort or deferred-shadow scratch and leaves them as they are: a
+ * vr_render before or after it behaves as without it, and a procedural
+ * rectangle needs none of vr_render's ordering across streams (its shadow
+ * rays are marched in place, its fBm hashes every corner).
+ * Uniform channels: the call marches every channel with loads (exact either
+ * way), so after a vr_update_volume it neither waits for the pending
+ * uniform-channel read-back nor resolves it -- the next vr_render does.
+ * Option "inject_throw" is honoured as by vr_render.                       */
+vr_status vr_render_rect(void* ctx, const vr_target* target, const vr_rect* rect, void* stream);
+
+/* Which pixels can an edit change?  *out = one rectangle inside the
+ * width x height frame that contains every pixel whose value, for ANY volume
+ * contents, can depend on a texel of the box [x0,x0+bx) x [y0,y0+by) x
+ * [z0,z0+bz) of an nx x ny x nz volume, rendered with this shader data and
+ * these march constants.  So: render the frame whole, vr_update_volume the
+ * box, vr_render_rect the footprint into the same buffer -- the buffer is
+ * then bit for bit the whole frame of the patched volume.  The rectangle may
+ * be empty (width = height = 0: no ray reads the box, or it projects off the
+ * frame) and it may be the whole frame: always when a corner of the box's
+ * image lies at or behind the eye, when the eye is inside the volume's box,
+ * when Projection*View or WorldToLocal is singular, and when CameraPosition
+ * is not the View eye (the rays then do not leave the projection centre).
+ * Pure host code in double precision: no context, no device.  All four taps,
+ * their scales, the MediaScroll offsets and mirrored repeat are followed
+ * (DESIGN.md sec. 5.2.2).  The procedural medium reads no volume.
+ * VR_ERR_INVALID: a null pointer, a non-positive extent, volume or frame
+ * size, a box that leaves the volume.                                      */
+vr_status vr_volume_box_footprint(const vr_object_shader_data* osd, const vr_global_shader_data* gsd,
+                                  const vr_march_params* march, int nx, int ny, int nz,
+                                  int width, int height,
+                                  int x0, int y0, int z0, int bx, int by, int bz, vr_rect* out);
+/* The same with the context's current shader data, march constants and
+ * volume dimensions; VR_ERR_NO_VOLUME / VR_ERR_NO_CAMERA before they are set. */
+vr_status vr_update_footprint(void* ctx, int width, int height,
+                              int x0, int y0, int z0, int bx, int by, int bz, vr_rect* out);
+
 /* ---- multi-GPU frame assembly.  The band sets of `nranks` ranks are
  *      gathered into one device buffer, d_gathered = [rank][packed rows].
  *      Each rank's set holds `rows_per_rank` rows.  This call scatters them

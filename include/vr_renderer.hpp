@@ -102,6 +102,29 @@ public:
         t.step_counter = d_step_counter;
         Check(vr_render(ctx_, &t, stream), "vr_render");
     }
+    // vkCmdSetScissor + the draw: render only the pixels `scissor` of the whole
+    // frame `frame` in d_pixels (vr_render_rect); the rest of it is untouched.
+    void RenderRect(const Rect2D& frame, const vr_rect& scissor, vr_format fmt, void* d_pixels, void* stream = nullptr,
+                    uint64_t* d_step_counter = nullptr, size_t row_pitch = 0)
+    {
+        vr_target t{};
+        t.width = frame.width;
+        t.height = frame.height;
+        t.format = fmt;
+        t.pixels = d_pixels;
+        t.row_pitch = row_pitch;
+        t.step_counter = d_step_counter;
+        Check(vr_render_rect(ctx_, &t, &scissor, stream), "vr_render_rect");
+    }
+    // The pixels of `frame` that an UpdateVolume of this texel box can change
+    // (vr_update_footprint): UpdateVolume, then RenderRect of it, gives the
+    // patched volume's whole frame.
+    vr_rect UpdateFootprint(const Rect2D& frame, int x0, int y0, int z0, int bx, int by, int bz) const
+    {
+        vr_rect r{};
+        Check(vr_update_footprint(ctx_, frame.width, frame.height, x0, y0, z0, bx, by, bz, &r), "vr_update_footprint");
+        return r;
+    }
     const char* KernelVariant() const { return vr_kernel_variant(ctx_); }
     void* Handle() const { return ctx_; }
 

@@ -99,6 +99,11 @@ class Target(ctypes.Structure):
                 ("band_flip", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class Rect(ctypes.Structure):
+    """vr_rect: a pixel rectangle of the frame (the scissor of vr_render_rect)."""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
 _vp = ctypes.c_void_p
 _SIGS = {
     "vr_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_vp)]),
@@ -131,6 +136,11 @@ _SIGS = {
     "vr_render": (ctypes.c_int, [_vp, ctypes.POINTER(Target), _vp]),
     "vr_render_sequence": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.c_int, ctypes.POINTER(ObjectShaderData),
                                           ctypes.POINTER(GlobalShaderData), _vp]),
+    "vr_render_rect": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.POINTER(Rect), _vp]),
+    "vr_volume_box_footprint": (ctypes.c_int, [ctypes.POINTER(ObjectShaderData), ctypes.POINTER(GlobalShaderData),
+                                               ctypes.POINTER(MarchParams)] + [ctypes.c_int] * 11
+                                + [ctypes.POINTER(Rect)]),
+    "vr_update_footprint": (ctypes.c_int, [_vp] + [ctypes.c_int] * 8 + [ctypes.POINTER(Rect)]),
     "vr_assemble_bands": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "vr_assemble_frame": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,

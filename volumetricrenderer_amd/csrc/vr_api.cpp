@@ -238,6 +238,85 @@ vr_status make_plan(Ctx* c, MarchArgs* a, Plan* p)
     return VR_OK;
 }
 
+// The parts of a launch's MarchArgs that vr_render and vr_render_rect share.
+// frame_args: the ray basis of a width x height frame and the march constants;
+// false when Projection*View is singular.
+bool frame_args(const Ctx* c, int width, int height, MarchArgs* ap)
+{
+    MarchArgs& a = *ap;
+    RayBasis b;
+    if (!make_ray_basis(c->obj, c->glob, width, height, &b)) return false;
+    std::memcpy(a.org, b.org, sizeof a.org); std::memcpy(a.o, b.o, sizeof a.o);
+    std::memcpy(a.px, b.px, sizeof a.px); std::memcpy(a.py, b.py, sizeof a.py);
+    std::memcpy(a.r2, b.r2, sizeof a.r2); std::memcpy(a.r3, b.r3, sizeof a.r3);
+    a.cam_mode = b.cam_mode;
+    std::memcpy(a.cam, b.cam, sizeof a.cam);
+    const vr_march_params& m = c->march;
+    a.step_size = (1.0f / (float)m.max_steps) * m.step_scale;   // frag.glsl:42
+    for (int ax = 0; ax < 3; ++ax) {
+        a.box_min[ax] = m.box_min[ax];
+        a.box_max[ax] = m.box_max[ax];
+        a.box_range[ax] = std::fabs(m.box_max[ax] - m.box_min[ax]);   // :51
+    }
+    a.density = m.density;
+    a.scale = m.scale;
+    a.max_steps = m.max_steps;
+    a.acc_limit = m.early_out > 0.0f
+                      ? (float)(-std::log((double)m.early_out) / ((double)m.density * (double)a.step_size))
+                      : INFINITY;
+    return true;
+}
+
+// The procedural medium's parameters and LDS table geometry (after
+// frame_args); the Perlin lattice table is the caller's (lat = nullptr here).
+void proc_args(const Ctx* c, MarchArgs* ap)
+{
+    MarchArgs& a = *ap;
+    const vr_march_params& m = c->march;
+    ProcParams& q = a.proc;
+    q.grid_scale = c->proc.grid_scale; q.octaves = c->proc.octaves; q.freq0 = c->proc.freq0;
+    q.lacunarity = c->proc.lacunarity; q.gain = c->proc.gain; q.seed_fbm = c->proc.seed_fbm;
+    q.worley_freq = c->proc.worley_freq; q.seed_worley = c->proc.seed_worley;
+    q.shadow_steps = c->proc.shadow_steps;
+    for (int ax = 0; ax < 3; ++ax) q.lstep[ax] = (a.step_size * c->proc.sun_dir[ax]) / a.box_range[ax];
+    q.od = a.step_size * m.density;
+    q.count_evals = c->count;
+    // deferred shadow rays need the sorted schedule and the fixed-geometry tables (vr_render checks);
+    // they march the waves in 64x64-region order, like config 2
+    q.enum_regions = c->proc_enum || (c->shadow_defer && q.shadow_steps > 0);
+    // Worley cell table (LDS): box points P in [0,1]^3 give cellular
+    // coordinates in [0, G] per axis, G = grid_scale * worley_freq; the
+    // 3x3x3 neighbourhood of rint() of those, with 2 cells of margin.
+    const double G = (double)q.grid_scale * (double)q.worley_freq;
+    const int lo = (int)std::floor(std::min(0.0, G)) - 2, hi = (int)std::ceil(std::max(0.0, G)) + 2;
+    const bool small = std::fabs(G) < 64.0;
+    int n = small ? hi - lo + 1 : 0;
+    q.wt_fixed = small && n <= 9;   // kernels' fixed geometry (noise::kWorleyN / kWorleyPz)
+    if (q.wt_fixed) n = 9;          // a superset of the cells needed
+    q.wt_lo = lo;
+    q.wt_pz = q.wt_fixed ? 83 : small ? worley_z_pitch(n) : 0;
+    q.wt_n = (small && (long long)n * q.wt_pz * 16 <= kMaxWorleyTableBytes) ? n : 0;   // + 8 KiB pairs
+    q.lat = nullptr;
+}
+
+// The volume buffers of the planned layout.
+void volume_args(const Ctx* c, const Plan& pl, MarchArgs* ap)
+{
+    MarchArgs& a = *ap;
+    if (pl.layout != LAYOUT_PLANAR) {
+        a.vol = c->d_fast;
+        a.plane_stride = (unsigned)c->fast_plane_bytes;
+        a.geom = layout_geom(pl.layout, c->nx, c->ny, c->nz);
+        if (pl.layout == LAYOUT_COL48Z) {
+            a.geom3 = layout_geom(LAYOUT_ZPAIR, c->nx, c->ny, c->nz);
+            a.plane3_bytes = (unsigned)layout_plane_bytes(LAYOUT_ZPAIR, c->nx, c->ny, c->nz);
+        }
+    } else {
+        a.vol = c->d_planar;
+        a.plane_stride = (unsigned)((size_t)c->nx * c->ny * c->nz);
+    }
+}
+
 const char* variant_name(const Plan& p)
 {
     static const char* names[kNumLayouts][2] = {
@@ -784,52 +863,11 @@ try {
             }
     }
     MarchArgs a{};
-    RayBasis b;
-    if (!make_ray_basis(c->obj, c->glob, t->width, t->height, &b))
-        return fail(VR_ERR_INVALID, "vr_render: Projection*View is singular");
-    std::memcpy(a.org, b.org, sizeof a.org); std::memcpy(a.o, b.o, sizeof a.o);
-    std::memcpy(a.px, b.px, sizeof a.px); std::memcpy(a.py, b.py, sizeof a.py);
-    std::memcpy(a.r2, b.r2, sizeof a.r2); std::memcpy(a.r3, b.r3, sizeof a.r3);
-    a.cam_mode = b.cam_mode;
-    std::memcpy(a.cam, b.cam, sizeof a.cam);
+    if (!frame_args(c, t->width, t->height, &a)) return fail(VR_ERR_INVALID, "vr_render: Projection*View is singular");
     const vr_march_params& m = c->march;
-    a.step_size = (1.0f / (float)m.max_steps) * m.step_scale;   // frag.glsl:42
-    for (int ax = 0; ax < 3; ++ax) {
-        a.box_min[ax] = m.box_min[ax];
-        a.box_max[ax] = m.box_max[ax];
-        a.box_range[ax] = std::fabs(m.box_max[ax] - m.box_min[ax]);   // :51
-    }
-    a.density = m.density;
-    a.scale = m.scale;
-    a.max_steps = m.max_steps;
-    a.acc_limit = m.early_out > 0.0f
-                      ? (float)(-std::log((double)m.early_out) / ((double)m.density * (double)a.step_size))
-                      : INFINITY;
     if (c->proc.enabled) {
         ProcParams& q = a.proc;
-        q.grid_scale = c->proc.grid_scale; q.octaves = c->proc.octaves; q.freq0 = c->proc.freq0;
-        q.lacunarity = c->proc.lacunarity; q.gain = c->proc.gain; q.seed_fbm = c->proc.seed_fbm;
-        q.worley_freq = c->proc.worley_freq; q.seed_worley = c->proc.seed_worley;
-        q.shadow_steps = c->proc.shadow_steps;
-        for (int ax = 0; ax < 3; ++ax) q.lstep[ax] = (a.step_size * c->proc.sun_dir[ax]) / a.box_range[ax];
-        q.od = a.step_size * m.density;
-        q.count_evals = c->count;
-        // deferred shadow rays need the sorted schedule and the fixed-geometry tables (checked below);
-        // they march the waves in 64x64-region order, like config 2
-        q.enum_regions = c->proc_enum || (c->shadow_defer && q.shadow_steps > 0);
-        // Worley cell table (LDS): box points P in [0,1]^3 give cellular
-        // coordinates in [0, G] per axis, G = grid_scale * worley_freq; the
-        // 3x3x3 neighbourhood of rint() of those, with 2 cells of margin.
-        const double G = (double)q.grid_scale * (double)q.worley_freq;
-        const int lo = (int)std::floor(std::min(0.0, G)) - 2, hi = (int)std::ceil(std::max(0.0, G)) + 2;
-        const bool small = std::fabs(G) < 64.0;
-        int n = small ? hi - lo + 1 : 0;
-        q.wt_fixed = small && n <= 9;   // kernels' fixed geometry (noise::kWorleyN / kWorleyPz)
-        if (q.wt_fixed) n = 9;          // a superset of the cells needed
-        q.wt_lo = lo;
-        q.wt_pz = q.wt_fixed ? 83 : small ? worley_z_pitch(n) : 0;
-        q.wt_n = (small && (long long)n * q.wt_pz * 16 <= kMaxWorleyTableBytes) ? n : 0;   // + 8 KiB pairs
-        q.lat = nullptr;
+        proc_args(c, &a);
         if (q.wt_fixed && q.wt_n > 0 && c->lattice && c->schedule != SCHED_STATIC && c->schedule != SCHED_RINGS) {
             const vr_status st = ensure_lattice(c, &q, static_cast<hipStream_t>(stream));
             if (st != VR_OK) return st;
@@ -844,18 +882,7 @@ try {
         a.umask = c->uniform_mask;
         for (int ch = 0; ch < 4; ++ch) a.uval[ch] = (float)c->uniform_val[ch] * (1.0f / 255.0f);   // blend()'s scale
     }
-    if (pl.layout != LAYOUT_PLANAR) {
-        a.vol = c->d_fast;
-        a.plane_stride = (unsigned)c->fast_plane_bytes;
-        a.geom = layout_geom(pl.layout, c->nx, c->ny, c->nz);
-        if (pl.layout == LAYOUT_COL48Z) {
-            a.geom3 = layout_geom(LAYOUT_ZPAIR, c->nx, c->ny, c->nz);
-            a.plane3_bytes = (unsigned)layout_plane_bytes(LAYOUT_ZPAIR, c->nx, c->ny, c->nz);
-        }
-    } else {
-        a.vol = c->d_planar;
-        a.plane_stride = (unsigned)((size_t)c->nx * c->ny * c->nz);
-    }
+    volume_args(c, pl, &a);
     a.width = t->width;
     a.height = t->height;
     if (row_range) {

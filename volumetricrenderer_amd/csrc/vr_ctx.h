@@ -2,7 +2,8 @@
 // translation units of the C ABI: vr_api.cpp (context, volume, render,
 // assembly), vr_options.cpp (vr_set_option / vr_get_option / the kernel
 // variant), vr_regions_host.cpp (region lists, row partition) and
-// vr_proc_host.cpp (procedural medium scratch and tables).  Internal: not
+// vr_proc_host.cpp (procedural medium scratch and tables); vr_rect.cpp (the
+// scissored render and the context's footprint call).  Internal: not
 // part of include/vr.h.
 #pragma once
 
@@ -278,6 +279,9 @@ void tap_constants(const Ctx* c, float S[4][3], float T[4][3]);
 bool clamp_is_exact(const Ctx* c, const float S[4][3], const float T[4][3]);
 int band_rows_packed(int height, int band_rows, int band_stride, int band_first, int band_flip = 0);
 vr_status make_plan(Ctx* c, MarchArgs* a, Plan* p);
+bool frame_args(const Ctx* c, int width, int height, MarchArgs* a);
+void proc_args(const Ctx* c, MarchArgs* a);
+void volume_args(const Ctx* c, const Plan& pl, MarchArgs* a);
 const char* variant_name(const Plan& p);
 
 // ---- vr_regions_host.cpp

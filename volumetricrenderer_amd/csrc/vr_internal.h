@@ -390,6 +390,15 @@ hipError_t launch_assemble_grey(const uint8_t* d_gathered, size_t rows_per_rank,
                                 bool serp = false);
 hipError_t launch_march_corner8(const MarchArgs& a, int layout, bool early, const Schedule& sc,
                                 hipStream_t s);   // CORNER8 / CORNERH, vr_march_c8.hip
+// vr_render_rect (vr_march_rect.hip): the frame pixels [x0, x1) x [y0, y1), one wave per 8x8 tile
+// anchored at (x0 & ~7, y0 & ~7); tiles_x = the tile columns that spans.  `a` describes the
+// whole frame (band_rows = height); the procedural launch needs a.proc.lat == nullptr.
+struct RectArgs {
+    int x0, y0, x1, y1, tiles_x;
+};
+RectArgs rect_args(int x, int y, int width, int height);
+hipError_t launch_march_rect(const MarchArgs& a, int layout, int wrap, bool early, const RectArgs& rc, hipStream_t s);
+hipError_t launch_march_proc_rect(const MarchArgs& a, bool early, const RectArgs& rc, hipStream_t s);
 hipError_t launch_march_slab(const MarchArgs& a, bool early, const Schedule& sc, hipStream_t s);   // vr_march_slab.hip
 constexpr int kSlabMaxChunks = 32;   // per channel and wave (64 B each): 8 KiB of LDS per wave
 // sort_buf (sort_layout) selects the cost-sorted schedule; null = 8x8

@@ -1,0 +1,141 @@
+// vr_march_rect.hip -- the scissored march of vr_render_rect (include/vr.h):
+// the pixels of one rectangle of the frame, at a cost that follows the
+// rectangle.
+//
+// One wave renders one 8x8 tile; the tiles are anchored at the rectangle's
+// origin rounded down to a multiple of 8, so a pixel sits in the lane it has
+// under vr_render's tilings.  The kernels are the shared device functions of
+// vr_march_kernels.h (fast_prologue, march_pixel, march_pixel_proc,
+// worley_table, add_steps, lane_x / lane_y) behind another tile map:
+// MarchArgs still describes the whole frame, so setup_ray and store_pixel
+// compute frame coordinates as they do for vr_render, and a pixel's
+// arithmetic is vr_render's.  A lane outside the rectangle is handed the
+// pixel x = a.width: setup_ray marks it not live, and it neither stores nor
+// counts.  The grid is sized from the rectangle, four waves per workgroup.
+//
+// Built with -fno-slp-vectorize like vr_march.hip and vr_march_c8.hip
+// (Makefile FLAGS_*), whose code generation these instantiations share.
+#include "vr_march_kernels.h"
+
+namespace vr {
+namespace {
+
+// The frame pixel of this lane, or (a.width, 0) outside the rectangle.
+// tiles_x = 8-px tile columns the rectangle spans from its anchor.
+template <int LAYOUT>
+__device__ __forceinline__ void rect_pixel(const MarchArgs& a, const RectArgs& rc, int* x, int* y)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = (int)blockIdx.x * (kThreads / 64) + (int)(threadIdx.x >> 6);
+    const int ty = t / rc.tiles_x, tx = t - ty * rc.tiles_x;
+    const int px = (rc.x0 & ~7) + tx * 8 + lane_x<LAYOUT>(lane);
+    const int py = (rc.y0 & ~7) + ty * 8 + lane_y<LAYOUT>(lane);
+    const bool in = px >= rc.x0 && px < rc.x1 && py >= rc.y0 && py < rc.y1;
+    *x = in ? px : a.width;
+    *y = in ? py : 0;
+}
+
+// No wave leaves before the prologue's barrier: the waves of a last, partly
+// used workgroup march pixels outside the rectangle (not live).
+template <int LAYOUT, int WRAP, bool EARLY>
+__global__ __launch_bounds__(kThreads) void march_rect(const MarchArgs a, const RectArgs rc)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned lds[];
+    const FastCtx f = fast_prologue<LAYOUT>(a, lds);
+    int x, y;
+    rect_pixel<LAYOUT>(a, rc, &x, &y);
+    const unsigned steps = march_pixel<LAYOUT, WRAP, EARLY>(a, f, x, y);
+    if (a.step_counter) add_steps(a, steps);
+}
+
+// Procedural medium: shadow rays marched in place (any shadow_steps), the fBm
+// hashing every corner (no lattice table), the Worley cells from LDS exactly
+// where march_proc takes them (TABLE 1) -- no context scratch is read or written.
+template <bool SHADOW, bool EARLY, int TABLE>
+__global__ __launch_bounds__(kThreads) void march_proc_rect(const MarchArgs a, const RectArgs rc)
+{
+    extern __shared__ float4 wt_lds[];
+    const float4* wt = worley_table<TABLE>(a.proc, wt_lds);
+    int x, y;
+    rect_pixel<0>(a, rc, &x, &y);
+    const unsigned long long steps = march_pixel_proc<SHADOW, EARLY, TABLE>(a, wt, x, y);
+    if (a.step_counter) add_steps(a, steps);
+}
+
+inline dim3 rect_grid(const RectArgs& rc)
+{
+    const long long waves = (long long)rc.tiles_x * (((rc.y1 + 7) >> 3) - (rc.y0 >> 3));
+    return dim3((unsigned)((waves + 3) / 4));
+}
+
+template <int L, int W>
+hipError_t launch_rect_lw(const MarchArgs& a, bool early, const RectArgs& rc, hipStream_t s)
+{
+    const size_t lds = L == LAYOUT_PLANAR || L == LAYOUT_CORNERH ? 0
+                     : (size_t)(a.nx + a.ny + a.nz + 3) * sizeof(unsigned) * (L == LAYOUT_COL48Z ? 2 : 1);
+    if (early) hipLaunchKernelGGL((march_rect<L, W, true>), rect_grid(rc), dim3(kThreads), lds, s, a, rc);
+    else hipLaunchKernelGGL((march_rect<L, W, false>), rect_grid(rc), dim3(kThreads), lds, s, a, rc);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+RectArgs rect_args(int x, int y, int width, int height)
+{
+    RectArgs rc{x, y, x + width, y + height, 0};
+    rc.tiles_x = ((rc.x1 + 7) >> 3) - (rc.x0 >> 3);
+    return rc;
+}
+
+hipError_t launch_march_rect(const MarchArgs& a, int layout, int wrap, bool early, const RectArgs& rc, hipStream_t s)
+{
+    if (rc.x1 <= rc.x0 || rc.y1 <= rc.y0) return hipSuccess;
+    switch (layout) {
+    case LAYOUT_BRICK4832: return launch_rect_lw<LAYOUT_BRICK4832, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_COL48: return launch_rect_lw<LAYOUT_COL48, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_CORNER8: return launch_rect_lw<LAYOUT_CORNER8, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_CORNERH: return launch_rect_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a, early, rc, s);
+#if VR_EXPERIMENTS
+    case LAYOUT_BRICK4: return launch_rect_lw<LAYOUT_BRICK4, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_BRICK448: return launch_rect_lw<LAYOUT_BRICK448, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_BRICK488: return launch_rect_lw<LAYOUT_BRICK488, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_BRICK4816: return launch_rect_lw<LAYOUT_BRICK4816, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_BRICK4864: return launch_rect_lw<LAYOUT_BRICK4864, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_BRICK41616: return launch_rect_lw<LAYOUT_BRICK41616, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_COL48Z: return launch_rect_lw<LAYOUT_COL48Z, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_ZPAIR: return launch_rect_lw<LAYOUT_ZPAIR, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_BRICK5: return launch_rect_lw<LAYOUT_BRICK5, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_BRICK8: return launch_rect_lw<LAYOUT_BRICK8, WRAP_CLAMP>(a, early, rc, s);
+    case LAYOUT_BRICK16: return launch_rect_lw<LAYOUT_BRICK16, WRAP_CLAMP>(a, early, rc, s);
+#endif
+    case LAYOUT_PLANAR:
+        if (wrap == WRAP_CLAMP) return launch_rect_lw<LAYOUT_PLANAR, WRAP_CLAMP>(a, early, rc, s);
+        return launch_rect_lw<LAYOUT_PLANAR, WRAP_MIRROR>(a, early, rc, s);
+    default: break;
+    }
+    return hipErrorInvalidValue;   // a layout this build does not hold: an error, never another kernel
+}
+
+hipError_t launch_march_proc_rect(const MarchArgs& a, bool early, const RectArgs& rc, hipStream_t s)
+{
+    if (rc.x1 <= rc.x0 || rc.y1 <= rc.y0) return hipSuccess;
+    const bool shadow = a.proc.shadow_steps > 0;
+    // the fixed geometry is also a valid runtime geometry (n = 9, pz = 83), as for march_proc
+    const size_t wt_bytes = a.proc.wt_n > 0 ? ((size_t)a.proc.wt_n * a.proc.wt_pz + 512) * sizeof(float4) : 0;
+    const int v = (shadow ? 4 : 0) | (early ? 2 : 0) | (wt_bytes ? 1 : 0);
+#define VR_PR(S, E, T) hipLaunchKernelGGL((march_proc_rect<S, E, T>), rect_grid(rc), dim3(kThreads), wt_bytes, s, a, rc)
+    switch (v) {
+    case 0: VR_PR(false, false, 0); break;
+    case 1: VR_PR(false, false, 1); break;
+    case 2: VR_PR(false, true, 0); break;
+    case 3: VR_PR(false, true, 1); break;
+    case 4: VR_PR(true, false, 0); break;
+    case 5: VR_PR(true, false, 1); break;
+    case 6: VR_PR(true, true, 0); break;
+    default: VR_PR(true, true, 1); break;
+    }
+#undef VR_PR
+    return hipGetLastError();
+}
+
+}  // namespace vr

@@ -16,6 +16,8 @@ Model/View/Projection/W2L producer          :func:`reference_shader_data`
 frag.glsl constants (:29-32, :42, :63-69)   :func:`march_defaults`, :meth:`Renderer.set_march`
 ``EnqueueRenderPass("BasePass")`` + draw    :meth:`Renderer.render`
 (TestMain.cpp:194-217)
+``vkCmdSetScissor`` with a ``VkRect2D``     :meth:`Renderer.render_rect`
+(TestMain.cpp:192, 204-205)
 ==========================================  =====================================
 
 torch is used only for device memory and streams.  All arithmetic runs in
@@ -31,8 +33,8 @@ import torch
 
 from . import _lib
 from ._lib import (BYTES_PER_PIXEL, CHANNELS, FLOAT_FORMATS, FMT_RGBA8_SRGB, FMT_RGBA8_UNORM, FMT_RGBA32F,  # noqa: F401
-                   GREY_OF, GlobalShaderData, MarchParams, ObjectShaderData, Procedural, Target, VolumeRecipe, VRError,
-                   call)
+                   GREY_OF, GlobalShaderData, MarchParams, ObjectShaderData, Procedural, Rect, Target, VolumeRecipe,
+                   VRError, call)
 
 _lib.load()  # fail at import if the HIP library is missing
 
@@ -108,6 +110,21 @@ def band_rows_packed(height: int, band_rows: int, band_stride: int = 1, band_fir
     if n < 0:
         raise ValueError(f"bad band set: rows {band_rows}, stride {band_stride}, flip {band_flip}")
     return n
+
+
+def volume_box_footprint(osd: ObjectShaderData, gsd: GlobalShaderData, march: MarchParams, dims, origin, extent,
+                         width: int, height: int) -> tuple[int, int, int, int]:
+    """vr_volume_box_footprint: the pixel rectangle (x, y, w, h) of the
+    width x height frame whose rays can read the texel box `extent` = (bx, by,
+    bz) at `origin` = (x0, y0, z0) of a volume of `dims` = (nx, ny, nz).  Host
+    code only: needs no renderer and no device.  (0, 0, 0, 0) = no pixel."""
+    r = Rect()
+    nx, ny, nz = (int(v) for v in dims)
+    x0, y0, z0 = (int(v) for v in origin)
+    bx, by, bz = (int(v) for v in extent)
+    call("vr_volume_box_footprint", ctypes.byref(osd), ctypes.byref(gsd), ctypes.byref(march), nx, ny, nz,
+         int(width), int(height), x0, y0, z0, bx, by, bz, ctypes.byref(r))
+    return r.x, r.y, r.width, r.height
 
 
 def shader_data_arrays(osd: ObjectShaderData, gsd: GlobalShaderData):
@@ -324,6 +341,38 @@ class Renderer:
                    band_flip=band_flip)
         call("vr_render", self._ctx, ctypes.byref(t), _stream_handle(stream))
         return out
+
+    def render_rect(self, out: torch.Tensor, rect, fmt: int = FMT_RGBA8_UNORM,
+                    step_counter: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """Render the pixels rect = (x, y, w, h) of the whole-frame target `out`
+        (vr_render_rect, the scissor): they get what :meth:`render` writes
+        there, bit for bit, and nothing else of `out` is touched.  The frame
+        size is `out`'s.  Asynchronous on `stream`; the cost follows the
+        rectangle."""
+        if not isinstance(out, torch.Tensor) or out.dim() < 2:
+            raise ValueError("render_rect needs a whole-frame target tensor (height, width[, 4])")
+        height, width = int(out.shape[0]), int(out.shape[1])
+        self._check_target(width, height, fmt, out, 0, 1, 0, step_counter)
+        x, y, w, h = (int(v) for v in rect)
+        t = Target(width=width, height=height, format=fmt, band_rows=0, band_stride=1, band_first=0,
+                   pixels=out.data_ptr(), row_pitch=out.stride(0) * out.element_size(),
+                   step_counter=step_counter.data_ptr() if step_counter is not None else None)
+        r = Rect(x, y, w, h)
+        call("vr_render_rect", self._ctx, ctypes.byref(t), ctypes.byref(r), _stream_handle(stream))
+        return out
+
+    def update_footprint(self, origin, extent, width: int, height: int) -> tuple[int, int, int, int]:
+        """vr_update_footprint: the rectangle (x, y, w, h) of the width x height
+        frame that an :meth:`update_volume` of the texel box `extent` = (bx, by,
+        bz) at `origin` = (x0, y0, z0) can change, for the current shader data
+        and march constants.  `update_volume(box)`, then `render_rect` of it
+        into a frame rendered before the update, gives the patched volume's
+        whole frame."""
+        x0, y0, z0 = (int(v) for v in origin)
+        bx, by, bz = (int(v) for v in extent)
+        r = Rect()
+        call("vr_update_footprint", self._ctx, int(width), int(height), x0, y0, z0, bx, by, bz, ctypes.byref(r))
+        return r.x, r.y, r.width, r.height
 
     def render_rows(self, width: int, height: int, fmt: int, first_row: int, rows: int,
                     out: torch.Tensor | None = None, in_place: bool = False, stream=None) -> torch.Tensor:
