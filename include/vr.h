@@ -309,6 +309,48 @@ typedef struct { int32_t x, y, width, height; } vr_rect;
  * Option "inject_throw" is honoured as by vr_render.                       */
 vr_status vr_render_rect(void* ctx, const vr_target* target, const vr_rect* rect, void* stream);
 
+/* The scissor for a set of rectangles: render the union of rects[0..count)
+ * into a whole-frame target in ONE kernel launch, whatever count is (none
+ * when the union is empty).  Apart from what follows the contract is
+ * vr_render_rect's: the same targets and formats, every pixel of the union
+ * gets bit for bit what vr_render writes there and no other byte of `pixels`
+ * is touched, asynchronous on `stream`, nothing allocated, no host wait, the
+ * context read and left as it is (cached launches, region lists, sort and
+ * deferred-shadow scratch, the pending uniform-channel read-back), every
+ * channel loaded, options "inject_throw" and "count" honoured.
+ *
+ * The rectangles may overlap, repeat, contain one another and be empty, in
+ * any order.  A pixel that several of them cover is marched and stored ONCE,
+ * so step_counter receives exactly the sum over the union's pixels -- K calls
+ * of vr_render_rect would count the overlaps K times -- and the launch pays
+ * the floor of its longest ray once, not K times.
+ *
+ * count == 0 is VR_OK and does nothing (rects may then be NULL).
+ * VR_ERR_INVALID: count < 0, count > VR_MAX_RECTS, rects NULL with count > 0,
+ * ANY rectangle of the list that is negative or leaves the frame, and
+ * everything vr_render_rect refuses.  A refused call writes nothing, not even
+ * the valid rectangles before the bad one.  More than VR_MAX_RECTS
+ * rectangles, or many tiny ones: vr_rects_coalesce first.                  */
+#define VR_MAX_RECTS 64
+vr_status vr_render_rects(void* ctx, const vr_target* target, const vr_rect* rects, int count, void* stream);
+
+/* Shorten a rectangle list: writes at most max_out (>= 1) rectangles to `out`
+ * (room for min(count, max_out)) and their number to *out_count.  Their union
+ * contains the union of the input, and each lies inside the bounding
+ * rectangle of the non-empty inputs.  Empty inputs are dropped, and so are
+ * inputs contained in another input (of identical ones the first is kept);
+ * what remains keeps its order.  While more than max_out remain, the pair
+ * whose bounding rectangle adds the least area beyond the two rectangles
+ * themselves is merged into that bounding rectangle, at the place of the
+ * pair's first (ties: the lowest pair of indices), and whatever the new
+ * rectangle contains is dropped.  Deterministic; areas and sums in 64 bits.
+ * Pure host code: no context, no device.
+ * VR_ERR_INVALID: count < 0, max_out < 1, a null pointer with count > 0, a
+ * negative coordinate or extent, x + width or y + height above INT32_MAX (no
+ * vr_rect could hold a bounding rectangle).  count == 0 is VR_OK; *out_count,
+ * when given, is then 0.                                                   */
+vr_status vr_rects_coalesce(const vr_rect* in, int count, int max_out, vr_rect* out, int* out_count);
+
 /* Which pixels can an edit change?  *out = one rectangle inside the
  * width x height frame that contains every pixel whose value, for ANY volume
  * contents, can depend on a texel of the box [x0,x0+bx) x [y0,y0+by) x

@@ -18,6 +18,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "vr.h"
 
@@ -40,6 +41,18 @@ inline void Check(vr_status s, const char* where)
 struct Rect2D {  // VkRect2D analogue: the rows/columns of the frame to draw
     int width = 0, height = 0;
 };
+
+// At most max_out rectangles whose union contains the union of `rects`
+// (vr_rects_coalesce): for a caller of Renderer::RenderRects with more than
+// VR_MAX_RECTS edits, or many tiny ones.  Host code only.
+inline std::vector<vr_rect> CoalesceRects(const std::vector<vr_rect>& rects, int max_out = VR_MAX_RECTS)
+{
+    std::vector<vr_rect> out(rects.size());
+    int n = 0;
+    Check(vr_rects_coalesce(rects.data(), (int)rects.size(), max_out, out.data(), &n), "vr_rects_coalesce");
+    out.resize((size_t)n);
+    return out;
+}
 
 class Renderer {
 public:
@@ -115,6 +128,27 @@ public:
         t.row_pitch = row_pitch;
         t.step_counter = d_step_counter;
         Check(vr_render_rect(ctx_, &t, &scissor, stream), "vr_render_rect");
+    }
+    // The scissor for a list: the union of scissors[0..count) in ONE launch, a
+    // pixel that several of them cover marched, stored and counted once
+    // (vr_render_rects; at most VR_MAX_RECTS -- CoalesceRects shortens a list).
+    // The K-edit loop: UpdateVolume K boxes, UpdateFootprint each, RenderRects.
+    void RenderRects(const Rect2D& frame, const vr_rect* scissors, int count, vr_format fmt, void* d_pixels,
+                     void* stream = nullptr, uint64_t* d_step_counter = nullptr, size_t row_pitch = 0)
+    {
+        vr_target t{};
+        t.width = frame.width;
+        t.height = frame.height;
+        t.format = fmt;
+        t.pixels = d_pixels;
+        t.row_pitch = row_pitch;
+        t.step_counter = d_step_counter;
+        Check(vr_render_rects(ctx_, &t, scissors, count, stream), "vr_render_rects");
+    }
+    void RenderRects(const Rect2D& frame, const std::vector<vr_rect>& scissors, vr_format fmt, void* d_pixels,
+                     void* stream = nullptr, uint64_t* d_step_counter = nullptr, size_t row_pitch = 0)
+    {
+        RenderRects(frame, scissors.data(), (int)scissors.size(), fmt, d_pixels, stream, d_step_counter, row_pitch);
     }
     // The pixels of `frame` that an UpdateVolume of this texel box can change
     // (vr_update_footprint): UpdateVolume, then RenderRect of it, gives the

@@ -7,8 +7,8 @@ interface (renderer) and the multi-GPU band sharding (distributed).
 """
 from ._lib import (FMT_R8_SRGB, FMT_R8_UNORM, FMT_R32F, FMT_RGBA8_SRGB, FMT_RGBA8_UNORM, FMT_RGBA32F,  # noqa: F401
                    GREY_OF, GlobalShaderData, MarchParams, ObjectShaderData, Target, VolumeRecipe, VRError)
-from ._lib import Procedural, Rect  # noqa: F401
-from .renderer import (Renderer, band_rows_packed, march_defaults, procedural_defaults,  # noqa: F401
+from ._lib import VR_MAX_RECTS, Procedural, Rect  # noqa: F401
+from .renderer import (Renderer, band_rows_packed, coalesce_rects, march_defaults, procedural_defaults,  # noqa: F401
                        reference_shader_data, scaled_recipe, shader_data_arrays, volume_box_footprint,
                        volume_recipe_defaults)
 
@@ -16,5 +16,5 @@ __all__ = [
     "Renderer", "VRError", "march_defaults", "procedural_defaults", "Procedural", "reference_shader_data", "volume_recipe_defaults",
     "scaled_recipe", "band_rows_packed", "shader_data_arrays", "FMT_RGBA32F", "FMT_RGBA8_UNORM",
     "FMT_RGBA8_SRGB", "FMT_R8_UNORM", "FMT_R8_SRGB", "FMT_R32F", "GREY_OF", "ObjectShaderData", "GlobalShaderData", "MarchParams", "VolumeRecipe", "Target",
-    "Rect", "volume_box_footprint",
+    "Rect", "volume_box_footprint", "coalesce_rects", "VR_MAX_RECTS",
 ]

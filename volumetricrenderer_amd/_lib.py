@@ -104,6 +104,8 @@ class Rect(ctypes.Structure):
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
 
+VR_MAX_RECTS = 64   # vr.h: the longest list vr_render_rects takes
+
 _vp = ctypes.c_void_p
 _SIGS = {
     "vr_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_vp)]),
@@ -137,6 +139,9 @@ _SIGS = {
     "vr_render_sequence": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.c_int, ctypes.POINTER(ObjectShaderData),
                                           ctypes.POINTER(GlobalShaderData), _vp]),
     "vr_render_rect": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.POINTER(Rect), _vp]),
+    "vr_render_rects": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.POINTER(Rect), ctypes.c_int, _vp]),
+    "vr_rects_coalesce": (ctypes.c_int, [ctypes.POINTER(Rect), ctypes.c_int, ctypes.c_int, ctypes.POINTER(Rect),
+                                         c_int_p]),
     "vr_volume_box_footprint": (ctypes.c_int, [ctypes.POINTER(ObjectShaderData), ctypes.POINTER(GlobalShaderData),
                                                ctypes.POINTER(MarchParams)] + [ctypes.c_int] * 11
                                 + [ctypes.POINTER(Rect)]),

@@ -399,6 +399,25 @@ struct RectArgs {
 RectArgs rect_args(int x, int y, int width, int height);
 hipError_t launch_march_rect(const MarchArgs& a, int layout, int wrap, bool early, const RectArgs& rc, hipStream_t s);
 hipError_t launch_march_proc_rect(const MarchArgs& a, bool early, const RectArgs& rc, hipStream_t s);
+// vr_render_rects (vr_march_rect.hip): a list of rectangles in one launch, by value in the
+// kernarg segment next to MarchArgs.  Rectangle k is the pixels [e[k][0], e[k][2]) x
+// [e[k][1], e[k][3]); its 8x8 tiles are anchored as RectArgs anchors them and numbered
+// tile_begin[k] .. tile_begin[k + 1) in row order (tile_begin: the exclusive prefix sum of
+// the tile counts, tile_begin[count] = all tiles).  A pixel belongs to the first rectangle
+// of the list that holds it.  Every rectangle is non-empty and inside the frame.
+constexpr int kMaxRects = 64;   // VR_MAX_RECTS (include/vr.h)
+struct RectList {
+    int count;
+    int pad[3];                        // e[] on a 16-B boundary: one scalar x4 load per rectangle
+    int e[kMaxRects][4];               // x0, y0, x1, y1
+    unsigned tile_begin[kMaxRects + 1];
+};
+static_assert(sizeof(MarchArgs) + sizeof(RectList) + 16 <= 4096,
+              "MarchArgs and RectList travel together in the 4-KiB kernarg segment");
+// Appends a non-empty rectangle inside the frame; false when the list is full.
+bool rect_list_add(RectList* rl, int x, int y, int width, int height);
+hipError_t launch_march_rects(const MarchArgs& a, int layout, int wrap, bool early, const RectList& rl, hipStream_t s);
+hipError_t launch_march_proc_rects(const MarchArgs& a, bool early, const RectList& rl, hipStream_t s);
 hipError_t launch_march_slab(const MarchArgs& a, bool early, const Schedule& sc, hipStream_t s);   // vr_march_slab.hip
 constexpr int kSlabMaxChunks = 32;   // per channel and wave (64 B each): 8 KiB of LDS per wave
 // sort_buf (sort_layout) selects the cost-sorted schedule; null = 8x8

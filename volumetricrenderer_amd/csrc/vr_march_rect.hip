@@ -13,6 +13,11 @@
 // pixel x = a.width: setup_ray marks it not live, and it neither stores nor
 // counts.  The grid is sized from the rectangle, four waves per workgroup.
 //
+// vr_render_rects marches a list of rectangles in one launch (march_rects,
+// march_proc_rects): the same tile anchoring per rectangle, the list by value
+// in the kernel arguments (RectList), a pixel owned by the first rectangle
+// that holds it.
+//
 // Built with -fno-slp-vectorize like vr_march.hip and vr_march_c8.hip
 // (Makefile FLAGS_*), whose code generation these instantiations share.
 #include "vr_march_kernels.h"
@@ -60,6 +65,83 @@ __global__ __launch_bounds__(kThreads) void march_proc_rect(const MarchArgs a, c
     rect_pixel<0>(a, rc, &x, &y);
     const unsigned long long steps = march_pixel_proc<SHADOW, EARLY, TABLE>(a, wt, x, y);
     if (a.step_counter) add_steps(a, steps);
+}
+
+// vr_render_rects: wave t of the launch renders tile t of the list.  Its
+// rectangle k (tile_begin[k] <= t < tile_begin[k + 1]) is wave-uniform and found
+// with scalar loads from the kernel arguments.  A lane is live only if its
+// pixel lies in rectangle k and in no rectangle j < k (ownership): a pixel that
+// several rectangles cover is marched, stored and counted by the first of them
+// alone.  Every other lane -- and every lane of a spare wave of the last
+// workgroup -- is handed x = a.width, the not-live pixel; such a wave still
+// reaches the prologue's barrier.
+template <int LAYOUT>
+__device__ __forceinline__ void rects_pixel(const MarchArgs& a, const RectList& rl, int* x, int* y)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned t = __builtin_amdgcn_readfirstlane(blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6));
+    const int count = rl.count;
+    *x = a.width;
+    *y = 0;
+    if (t >= rl.tile_begin[count]) return;   // wave-uniform: a spare wave of the last workgroup
+    int k = 0;
+    while (k + 1 < count && t >= rl.tile_begin[k + 1]) ++k;
+    const int x0 = rl.e[k][0], y0 = rl.e[k][1], x1 = rl.e[k][2], y1 = rl.e[k][3];
+    const int tiles_x = ((x1 + 7) >> 3) - (x0 >> 3);
+    const int tl = (int)(t - rl.tile_begin[k]);
+    const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
+    const int px = (x0 & ~7) + tx * 8 + lane_x<LAYOUT>(lane);
+    const int py = (y0 & ~7) + ty * 8 + lane_y<LAYOUT>(lane);
+    bool own = px >= x0 && px < x1 && py >= y0 && py < y1;
+    for (int j = 0; j < k; ++j)
+        own = own && !(px >= rl.e[j][0] && px < rl.e[j][2] && py >= rl.e[j][1] && py < rl.e[j][3]);
+    if (own) {
+        *x = px;
+        *y = py;
+    }
+}
+
+template <int LAYOUT, int WRAP, bool EARLY>
+__global__ __launch_bounds__(kThreads) void march_rects(const MarchArgs a, const RectList rl)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned lds[];
+    const FastCtx f = fast_prologue<LAYOUT>(a, lds);
+    int x, y;
+    rects_pixel<LAYOUT>(a, rl, &x, &y);
+    const unsigned steps = march_pixel<LAYOUT, WRAP, EARLY>(a, f, x, y);
+    if (a.step_counter) add_steps(a, steps);
+}
+
+template <bool SHADOW, bool EARLY, int TABLE>
+__global__ __launch_bounds__(kThreads) void march_proc_rects(const MarchArgs a, const RectList rl)
+{
+    extern __shared__ float4 wt_lds[];
+    const float4* wt = worley_table<TABLE>(a.proc, wt_lds);
+    int x, y;
+    rects_pixel<0>(a, rl, &x, &y);
+    const unsigned long long steps = march_pixel_proc<SHADOW, EARLY, TABLE>(a, wt, x, y);
+    if (a.step_counter) add_steps(a, steps);
+}
+
+inline dim3 rects_grid(const RectList& rl)
+{
+    return dim3((rl.tile_begin[rl.count] + 3u) / 4u);
+}
+
+// the grid's 2^31 limit, four waves per workgroup
+inline bool rects_launchable(const RectList& rl)
+{
+    return rl.count >= 0 && rl.count <= kMaxRects && rl.tile_begin[rl.count] <= 0x7fffffffu;
+}
+
+template <int L, int W>
+hipError_t launch_rects_lw(const MarchArgs& a, bool early, const RectList& rl, hipStream_t s)
+{
+    const size_t lds = L == LAYOUT_PLANAR || L == LAYOUT_CORNERH ? 0
+                     : (size_t)(a.nx + a.ny + a.nz + 3) * sizeof(unsigned) * (L == LAYOUT_COL48Z ? 2 : 1);
+    if (early) hipLaunchKernelGGL((march_rects<L, W, true>), rects_grid(rl), dim3(kThreads), lds, s, a, rl);
+    else hipLaunchKernelGGL((march_rects<L, W, false>), rects_grid(rl), dim3(kThreads), lds, s, a, rl);
+    return hipGetLastError();
 }
 
 inline dim3 rect_grid(const RectArgs& rc)
@@ -124,6 +206,70 @@ hipError_t launch_march_proc_rect(const MarchArgs& a, bool early, const RectArgs
     const size_t wt_bytes = a.proc.wt_n > 0 ? ((size_t)a.proc.wt_n * a.proc.wt_pz + 512) * sizeof(float4) : 0;
     const int v = (shadow ? 4 : 0) | (early ? 2 : 0) | (wt_bytes ? 1 : 0);
 #define VR_PR(S, E, T) hipLaunchKernelGGL((march_proc_rect<S, E, T>), rect_grid(rc), dim3(kThreads), wt_bytes, s, a, rc)
+    switch (v) {
+    case 0: VR_PR(false, false, 0); break;
+    case 1: VR_PR(false, false, 1); break;
+    case 2: VR_PR(false, true, 0); break;
+    case 3: VR_PR(false, true, 1); break;
+    case 4: VR_PR(true, false, 0); break;
+    case 5: VR_PR(true, false, 1); break;
+    case 6: VR_PR(true, true, 0); break;
+    default: VR_PR(true, true, 1); break;
+    }
+#undef VR_PR
+    return hipGetLastError();
+}
+
+bool rect_list_add(RectList* rl, int x, int y, int width, int height)
+{
+    if (rl->count >= kMaxRects) return false;
+    const int k = rl->count++;
+    const RectArgs rc = rect_args(x, y, width, height);
+    rl->e[k][0] = rc.x0; rl->e[k][1] = rc.y0; rl->e[k][2] = rc.x1; rl->e[k][3] = rc.y1;
+    const unsigned long long tiles = (unsigned long long)rc.tiles_x * (unsigned)(((rc.y1 + 7) >> 3) - (rc.y0 >> 3));
+    const unsigned long long end = rl->tile_begin[k] + tiles;
+    rl->tile_begin[k + 1] = end > 0xffffffffull ? 0xffffffffu : (unsigned)end;   // refused by the launch
+    return true;
+}
+
+hipError_t launch_march_rects(const MarchArgs& a, int layout, int wrap, bool early, const RectList& rl, hipStream_t s)
+{
+    if (!rects_launchable(rl)) return hipErrorInvalidValue;
+    if (rl.count == 0) return hipSuccess;
+    switch (layout) {
+    case LAYOUT_BRICK4832: return launch_rects_lw<LAYOUT_BRICK4832, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_COL48: return launch_rects_lw<LAYOUT_COL48, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_CORNER8: return launch_rects_lw<LAYOUT_CORNER8, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_CORNERH: return launch_rects_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a, early, rl, s);
+#if VR_EXPERIMENTS
+    case LAYOUT_BRICK4: return launch_rects_lw<LAYOUT_BRICK4, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_BRICK448: return launch_rects_lw<LAYOUT_BRICK448, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_BRICK488: return launch_rects_lw<LAYOUT_BRICK488, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_BRICK4816: return launch_rects_lw<LAYOUT_BRICK4816, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_BRICK4864: return launch_rects_lw<LAYOUT_BRICK4864, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_BRICK41616: return launch_rects_lw<LAYOUT_BRICK41616, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_COL48Z: return launch_rects_lw<LAYOUT_COL48Z, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_ZPAIR: return launch_rects_lw<LAYOUT_ZPAIR, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_BRICK5: return launch_rects_lw<LAYOUT_BRICK5, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_BRICK8: return launch_rects_lw<LAYOUT_BRICK8, WRAP_CLAMP>(a, early, rl, s);
+    case LAYOUT_BRICK16: return launch_rects_lw<LAYOUT_BRICK16, WRAP_CLAMP>(a, early, rl, s);
+#endif
+    case LAYOUT_PLANAR:
+        if (wrap == WRAP_CLAMP) return launch_rects_lw<LAYOUT_PLANAR, WRAP_CLAMP>(a, early, rl, s);
+        return launch_rects_lw<LAYOUT_PLANAR, WRAP_MIRROR>(a, early, rl, s);
+    default: break;
+    }
+    return hipErrorInvalidValue;   // a layout this build does not hold: an error, never another kernel
+}
+
+hipError_t launch_march_proc_rects(const MarchArgs& a, bool early, const RectList& rl, hipStream_t s)
+{
+    if (!rects_launchable(rl)) return hipErrorInvalidValue;
+    if (rl.count == 0) return hipSuccess;
+    const bool shadow = a.proc.shadow_steps > 0;
+    const size_t wt_bytes = a.proc.wt_n > 0 ? ((size_t)a.proc.wt_n * a.proc.wt_pz + 512) * sizeof(float4) : 0;
+    const int v = (shadow ? 4 : 0) | (early ? 2 : 0) | (wt_bytes ? 1 : 0);
+#define VR_PR(S, E, T) hipLaunchKernelGGL((march_proc_rects<S, E, T>), rects_grid(rl), dim3(kThreads), wt_bytes, s, a, rl)
     switch (v) {
     case 0: VR_PR(false, false, 0); break;
     case 1: VR_PR(false, false, 1); break;

@@ -1,10 +1,10 @@
-// vr_rect.cpp -- vr_render_rect, the scissored render, and vr_update_footprint
-// (include/vr.h).
+// vr_rect.cpp -- vr_render_rect and vr_render_rects, the scissored renders, and
+// vr_update_footprint (include/vr.h).
 //
-// vr_render_rect builds the whole frame's MarchArgs with the helpers it shares
-// with vr_render (frame_args, proc_args, make_plan, volume_args) and launches
-// the rectangle kernels of vr_march_rect.hip.  It reads the context and
-// changes nothing in it: no cached launch, region list, sort or deferred-shadow
+// Both renders build the whole frame's MarchArgs with the helpers it shares
+// with vr_render (frame_args, proc_args, make_plan, volume_args) and launch
+// the rectangle kernels of vr_march_rect.hip.  They read the context and
+// change nothing in it: no cached launch, region list, sort or deferred-shadow
 // scratch, no `gen` bump, and the pending uniform-channel read-back
 // (mm_pending) stays pending for the next vr_render -- the rectangle kernels
 // load every channel (umask 0), which is exact whatever the read-back will say.
@@ -12,60 +12,96 @@
 
 using namespace vrapi;
 
+namespace {
+
+// What vr_render_rect and vr_render_rects check before they look at a
+// rectangle: the context, the volume, the camera and a plain whole-frame target.
+// *pitch = the target's row pitch in bytes.
+vr_status check_frame_target(const char* fn, void* p, const vr_target* t, size_t* pitch)
+{
+    Ctx* c = as_ctx(p);
+    if (!c->d_planar && !c->proc.enabled)
+        return fail(VR_ERR_NO_VOLUME, "%s: no volume (vr_set_volume / vr_generate_volume)", fn);
+    if (!c->has_camera) return fail(VR_ERR_NO_CAMERA, "%s: no shader data (vr_set_shader_data)", fn);
+    if (t->width <= 0 || t->height <= 0) return fail(VR_ERR_INVALID, "%s: bad size %dx%d", fn, t->width, t->height);
+    if (t->format < 0 || t->format > 5)
+        return fail(VR_ERR_INVALID, "%s: bad format %d (a whole-frame target: no VR_TARGET_* flag)", fn, t->format);
+    if (t->band_rows != 0 || t->band_flip != 0)
+        return fail(VR_ERR_INVALID, "%s: a whole-frame target is needed (band_rows %d, band_flip %d)", fn,
+                    t->band_rows, t->band_flip);
+    if (t->reserved != 0) return fail(VR_ERR_INVALID, "%s: vr_target.reserved must be 0", fn);
+    if (!t->pixels) return fail(VR_ERR_INVALID, "%s: pixels is null", fn);
+    const int bpp = format_bytes(t->format);
+    *pitch = t->row_pitch ? t->row_pitch : (size_t)t->width * bpp;
+    if (*pitch < (size_t)t->width * bpp || *pitch % bpp != 0 || ((uintptr_t)t->pixels % bpp) != 0)
+        return fail(VR_ERR_INVALID, "%s: pitch/alignment (pitch %zu, bpp %d)", fn, *pitch, bpp);
+    return VR_OK;
+}
+
+bool rect_in_frame(const vr_target* t, const vr_rect* r)
+{
+    return r->x >= 0 && r->y >= 0 && r->width >= 0 && r->height >= 0 && r->width <= t->width - r->x &&
+           r->height <= t->height - r->y;
+}
+
+// Option inject_throw, honoured as by vr_render: consumed, then thrown.
+void honour_inject_throw(Ctx* c)
+{
+    if (!c->inject_throw) return;
+    const int k = c->inject_throw;
+    c->inject_throw = 0;
+    if (k == 2) throw std::bad_alloc();
+    throw std::runtime_error("injected by vr option inject_throw");
+}
+
+// The whole frame's MarchArgs, as vr_render describes it with band_rows = 0,
+// every channel loaded (umask 0); *pl = the layout, wrap and early-out variant.
+vr_status frame_march_args(const char* fn, Ctx* c, const vr_target* t, size_t pitch, MarchArgs* a, Plan* pl)
+{
+    if (!frame_args(c, t->width, t->height, a)) return fail(VR_ERR_INVALID, "%s: Projection*View is singular", fn);
+    *pl = Plan{LAYOUT_PLANAR, WRAP_CLAMP, c->march.early_out > 0.0f};
+    if (c->proc.enabled) proc_args(c, a);   // no lattice table: the fBm hashes every corner
+    else make_plan(c, a, pl);
+    a->nx = c->nx; a->ny = c->ny; a->nz = c->nz;
+    volume_args(c, *pl, a);
+    a->width = t->width;
+    a->height = t->height;
+    a->band_rows = t->height; a->band_stride = 1; a->band_first = 0;
+    a->out_rows = t->height;
+    a->tiles_x = (t->width + 15) / 16;
+    a->tiles_y = (t->height + 15) / 16;
+    a->num_blocks = 8 * ((a->tiles_y + 7) / 8) * a->tiles_x;
+    a->out = t->pixels;
+    a->pitch = (long long)pitch;
+    a->format = t->format;
+    a->step_counter = reinterpret_cast<unsigned long long*>(t->step_counter);
+    return VR_OK;
+}
+
+bool holds(const vr_rect& a, const vr_rect& b)   // a contains b, both non-empty
+{
+    return a.x <= b.x && a.y <= b.y && b.x + b.width <= a.x + a.width && b.y + b.height <= a.y + a.height;
+}
+
+}  // namespace
+
 extern "C" {
 
 vr_status vr_render_rect(void* p, const vr_target* t, const vr_rect* r, void* stream)
 try {
     if (!p || !t || !r) return fail(VR_ERR_INVALID, "vr_render_rect: null argument");
     Ctx* c = as_ctx(p);
-    if (!c->d_planar && !c->proc.enabled)
-        return fail(VR_ERR_NO_VOLUME, "vr_render_rect: no volume (vr_set_volume / vr_generate_volume)");
-    if (!c->has_camera) return fail(VR_ERR_NO_CAMERA, "vr_render_rect: no shader data (vr_set_shader_data)");
-    if (t->width <= 0 || t->height <= 0)
-        return fail(VR_ERR_INVALID, "vr_render_rect: bad size %dx%d", t->width, t->height);
-    if (t->format < 0 || t->format > 5)
-        return fail(VR_ERR_INVALID, "vr_render_rect: bad format %d (a whole-frame target: no VR_TARGET_* flag)", t->format);
-    if (t->band_rows != 0 || t->band_flip != 0)
-        return fail(VR_ERR_INVALID, "vr_render_rect: a whole-frame target is needed (band_rows %d, band_flip %d)",
-                    t->band_rows, t->band_flip);
-    if (t->reserved != 0) return fail(VR_ERR_INVALID, "vr_render_rect: vr_target.reserved must be 0");
-    if (!t->pixels) return fail(VR_ERR_INVALID, "vr_render_rect: pixels is null");
-    const int bpp = format_bytes(t->format);
-    const size_t pitch = t->row_pitch ? t->row_pitch : (size_t)t->width * bpp;
-    if (pitch < (size_t)t->width * bpp || pitch % bpp != 0 || ((uintptr_t)t->pixels % bpp) != 0)
-        return fail(VR_ERR_INVALID, "vr_render_rect: pitch/alignment (pitch %zu, bpp %d)", pitch, bpp);
-    if (r->x < 0 || r->y < 0 || r->width < 0 || r->height < 0 || r->width > t->width - r->x ||
-        r->height > t->height - r->y)
+    size_t pitch = 0;
+    if (const vr_status st = check_frame_target("vr_render_rect", p, t, &pitch)) return st;
+    if (!rect_in_frame(t, r))
         return fail(VR_ERR_INVALID, "vr_render_rect: rectangle %dx%d at (%d, %d) leaves the %dx%d frame", r->width,
                     r->height, r->x, r->y, t->width, t->height);
-    if (c->inject_throw) {
-        const int k = c->inject_throw;
-        c->inject_throw = 0;
-        if (k == 2) throw std::bad_alloc();
-        throw std::runtime_error("injected by vr option inject_throw");
-    }
+    honour_inject_throw(c);
     if (r->width == 0 || r->height == 0) return VR_OK;
 
     MarchArgs a{};
-    if (!frame_args(c, t->width, t->height, &a))
-        return fail(VR_ERR_INVALID, "vr_render_rect: Projection*View is singular");
-    Plan pl{LAYOUT_PLANAR, WRAP_CLAMP, c->march.early_out > 0.0f};
-    if (c->proc.enabled) proc_args(c, &a);   // no lattice table: the fBm hashes every corner
-    else make_plan(c, &a, &pl);
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    volume_args(c, pl, &a);
-    // the whole frame, as vr_render describes it with band_rows = 0
-    a.width = t->width;
-    a.height = t->height;
-    a.band_rows = t->height; a.band_stride = 1; a.band_first = 0;
-    a.out_rows = t->height;
-    a.tiles_x = (t->width + 15) / 16;
-    a.tiles_y = (t->height + 15) / 16;
-    a.num_blocks = 8 * ((a.tiles_y + 7) / 8) * a.tiles_x;
-    a.out = t->pixels;
-    a.pitch = (long long)pitch;
-    a.format = t->format;
-    a.step_counter = reinterpret_cast<unsigned long long*>(t->step_counter);
+    Plan pl{};
+    if (const vr_status st = frame_march_args("vr_render_rect", c, t, pitch, &a, &pl)) return st;
     const RectArgs rc = rect_args(r->x, r->y, r->width, r->height);
     const hipStream_t hs = static_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
@@ -74,6 +110,50 @@ try {
     return VR_OK;
 } catch (...) {
     return caught_exception("vr_render_rect");
+}
+
+vr_status vr_render_rects(void* p, const vr_target* t, const vr_rect* rects, int count, void* stream)
+try {
+    if (!p || !t) return fail(VR_ERR_INVALID, "vr_render_rects: null argument");
+    if (count < 0 || count > VR_MAX_RECTS)
+        return fail(VR_ERR_INVALID, "vr_render_rects: count %d (0 .. %d; vr_rects_coalesce shortens a list)", count,
+                    VR_MAX_RECTS);
+    if (count > 0 && !rects) return fail(VR_ERR_INVALID, "vr_render_rects: rects is null with count %d", count);
+    Ctx* c = as_ctx(p);
+    size_t pitch = 0;
+    if (const vr_status st = check_frame_target("vr_render_rects", p, t, &pitch)) return st;
+    for (int i = 0; i < count; ++i)
+        if (!rect_in_frame(t, &rects[i]))
+            return fail(VR_ERR_INVALID, "vr_render_rects: rectangle %d, %dx%d at (%d, %d), leaves the %dx%d frame", i,
+                        rects[i].width, rects[i].height, rects[i].x, rects[i].y, t->width, t->height);
+    honour_inject_throw(c);
+    // The kernel's list: no empty rectangle, and none that another one of the list holds (of
+    // identical ones the first stays) -- the union, and with it what is written and counted,
+    // is the same, and no wave is launched for a tile that owns no pixel.
+    RectList rl{};
+    for (int i = 0; i < count; ++i) {
+        const vr_rect& r = rects[i];
+        if (r.width == 0 || r.height == 0) continue;
+        bool held = false;
+        for (int j = 0; j < count && !held; ++j) {
+            const vr_rect& q = rects[j];
+            if (j == i || q.width == 0 || q.height == 0 || !holds(q, r)) continue;
+            held = !holds(r, q) || j < i;
+        }
+        if (!held) rect_list_add(&rl, r.x, r.y, r.width, r.height);
+    }
+    if (rl.count == 0) return VR_OK;
+
+    MarchArgs a{};
+    Plan pl{};
+    if (const vr_status st = frame_march_args("vr_render_rects", c, t, pitch, &a, &pl)) return st;
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->proc.enabled) HIP_TRY(launch_march_proc_rects(a, pl.early, rl, hs));
+    else HIP_TRY(launch_march_rects(a, pl.layout, pl.wrap, pl.early, rl, hs));
+    return VR_OK;
+} catch (...) {
+    return caught_exception("vr_render_rects");
 }
 
 vr_status vr_update_footprint(void* p, int width, int height, int x0, int y0, int z0, int bx, int by, int bz,

@@ -17,7 +17,7 @@ frag.glsl constants (:29-32, :42, :63-69)   :func:`march_defaults`, :meth:`Rende
 ``EnqueueRenderPass("BasePass")`` + draw    :meth:`Renderer.render`
 (TestMain.cpp:194-217)
 ``vkCmdSetScissor`` with a ``VkRect2D``     :meth:`Renderer.render_rect`
-(TestMain.cpp:192, 204-205)
+(TestMain.cpp:192, 204-205)                 :meth:`Renderer.render_rects` (a list)
 ==========================================  =====================================
 
 torch is used only for device memory and streams.  All arithmetic runs in
@@ -34,7 +34,7 @@ import torch
 from . import _lib
 from ._lib import (BYTES_PER_PIXEL, CHANNELS, FLOAT_FORMATS, FMT_RGBA8_SRGB, FMT_RGBA8_UNORM, FMT_RGBA32F,  # noqa: F401
                    GREY_OF, GlobalShaderData, MarchParams, ObjectShaderData, Procedural, Rect, Target, VolumeRecipe,
-                   VRError, call)
+                   VR_MAX_RECTS, VRError, call)
 
 _lib.load()  # fail at import if the HIP library is missing
 
@@ -125,6 +125,31 @@ def volume_box_footprint(osd: ObjectShaderData, gsd: GlobalShaderData, march: Ma
     call("vr_volume_box_footprint", ctypes.byref(osd), ctypes.byref(gsd), ctypes.byref(march), nx, ny, nz,
          int(width), int(height), x0, y0, z0, bx, by, bz, ctypes.byref(r))
     return r.x, r.y, r.width, r.height
+
+
+def _rect_array(rects):
+    """A ctypes array of vr_rect from (x, y, w, h) tuples or Rects."""
+    rects = list(rects)
+    arr = (Rect * len(rects))()
+    for i, r in enumerate(rects):
+        if isinstance(r, Rect):
+            arr[i] = Rect(r.x, r.y, r.width, r.height)
+        else:
+            x, y, w, h = (int(v) for v in r)
+            arr[i] = Rect(x, y, w, h)
+    return arr
+
+
+def coalesce_rects(rects, max_out: int = VR_MAX_RECTS) -> list[tuple[int, int, int, int]]:
+    """vr_rects_coalesce: at most `max_out` rectangles (x, y, w, h) whose union
+    contains the union of `rects`.  Empty and contained rectangles are dropped;
+    then the pair whose bounding rectangle adds the least area is merged until
+    the list fits.  Host code only: needs no renderer and no device."""
+    arr = _rect_array(rects)
+    out = (Rect * max(1, min(len(arr), max(int(max_out), 0))))()
+    n = ctypes.c_int(0)
+    call("vr_rects_coalesce", arr, len(arr), int(max_out), out, ctypes.byref(n))
+    return [(out[i].x, out[i].y, out[i].width, out[i].height) for i in range(n.value)]
 
 
 def shader_data_arrays(osd: ObjectShaderData, gsd: GlobalShaderData):
@@ -360,6 +385,32 @@ class Renderer:
         r = Rect(x, y, w, h)
         call("vr_render_rect", self._ctx, ctypes.byref(t), ctypes.byref(r), _stream_handle(stream))
         return out
+
+    def render_rects(self, out: torch.Tensor, rects, fmt: int = FMT_RGBA8_UNORM,
+                     step_counter: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """Render the union of `rects` -- a sequence of (x, y, w, h) tuples or
+        :class:`Rect` -- into the whole-frame target `out` in one launch
+        (vr_render_rects).  The rectangles may overlap, repeat, contain one
+        another and be empty; a pixel several of them cover is marched, stored
+        and counted once.  At most VR_MAX_RECTS of them: :func:`coalesce_rects`
+        shortens a longer list.  Otherwise as :meth:`render_rect`."""
+        if not isinstance(out, torch.Tensor) or out.dim() < 2:
+            raise ValueError("render_rects needs a whole-frame target tensor (height, width[, 4])")
+        height, width = int(out.shape[0]), int(out.shape[1])
+        self._check_target(width, height, fmt, out, 0, 1, 0, step_counter)
+        arr = _rect_array(rects)
+        t = Target(width=width, height=height, format=fmt, band_rows=0, band_stride=1, band_first=0,
+                   pixels=out.data_ptr(), row_pitch=out.stride(0) * out.element_size(),
+                   step_counter=step_counter.data_ptr() if step_counter is not None else None)
+        call("vr_render_rects", self._ctx, ctypes.byref(t), arr, len(arr), _stream_handle(stream))
+        return out
+
+    def update_footprints(self, boxes, width: int, height: int) -> list[tuple[int, int, int, int]]:
+        """:meth:`update_footprint` of every (origin, extent) pair of `boxes`:
+        one rectangle per box, in order.  `update_volume` each box, then one
+        `render_rects` of these into a frame rendered before the updates,
+        gives the patched volume's whole frame."""
+        return [self.update_footprint(origin, extent, width, height) for origin, extent in boxes]
 
     def update_footprint(self, origin, extent, width: int, height: int) -> tuple[int, int, int, int]:
         """vr_update_footprint: the rectangle (x, y, w, h) of the width x height
