@@ -277,6 +277,23 @@ vr_status vr_render(void* ctx, const vr_target* target, void* stream);
  * wait.  The ctx keeps the last frame's shader data.                       */
 vr_status vr_render_sequence(void* ctx, const vr_target* target, int frames, const vr_object_shader_data* osd,
                              const vr_global_shader_data* gsd, void* stream);
+/* Two queued frames in one launch: frame 0 into `t0` with shader data (osd[0],
+ * gsd[0]), frame 1 into `t1` with (osd[1], gsd[1]); osd and gsd both NULL =
+ * both frames with the ctx's current shader data.  The bytes in both targets
+ * and the sum added to step_counter are those of
+ *   vr_set_shader_data(0); vr_render(t0); vr_set_shader_data(1); vr_render(t1)
+ * and the ctx ends holding shader data 1.  The targets must agree in every
+ * field but `pixels` (VR_ERR_INVALID otherwise, nothing written).  A grid
+ * medium on the default regions schedule (one lane per ray; the COL48,
+ * BRICK4832 and CORNERH layouts) marches both frames in one kernel over one
+ * set of region lists -- frame 0's -- so the two frames read each brick of the
+ * volume at the same moment.  Anything else (a
+ * procedural medium, split rays, option slab, another schedule or layout,
+ * frames whose MediaScroll offsets select different kernels) is issued as the
+ * two ordinary renders.  Asynchronous on `stream`; steady state neither
+ * allocates nor waits on the host.                                          */
+vr_status vr_render_pair(void* ctx, const vr_target* t0, const vr_target* t1, const vr_object_shader_data osd[2],
+                         const vr_global_shader_data gsd[2], void* stream);
 
 /* ---- the scissor: replaces vkCmdSetScissor with a VkRect2D, a dynamic state
  *      of the reference's pipeline (TestMain.cpp:192, 204-205, where it is

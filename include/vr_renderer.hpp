@@ -115,6 +115,28 @@ public:
         t.step_counter = d_step_counter;
         Check(vr_render(ctx_, &t, stream), "vr_render");
     }
+    // Two queued frames in one launch (vr_render_pair): frame i into d_pixels[i]
+    // with (osd[i], gsd[i]); osd = gsd = nullptr renders both with the current
+    // shader data.  The same bytes as two EnqueueRenderPass calls.
+    void EnqueueRenderPassPair(const Rect2D& rect, vr_format fmt, void* const d_pixels[2],
+                               const vr_object_shader_data* osd = nullptr, const vr_global_shader_data* gsd = nullptr,
+                               void* stream = nullptr, uint64_t* d_step_counter = nullptr, int band_rows = 0,
+                               int band_stride = 1, int band_first = 0, int band_flip = 0)
+    {
+        vr_target t[2] = {};
+        for (int i = 0; i < 2; ++i) {
+            t[i].width = rect.width;
+            t[i].height = rect.height;
+            t[i].format = fmt;
+            t[i].band_rows = band_rows;
+            t[i].band_stride = band_stride;
+            t[i].band_first = band_first;
+            t[i].band_flip = band_flip;
+            t[i].pixels = d_pixels[i];
+            t[i].step_counter = d_step_counter;
+        }
+        Check(vr_render_pair(ctx_, &t[0], &t[1], osd, gsd, stream), "vr_render_pair");
+    }
     // vkCmdSetScissor + the draw: render only the pixels `scissor` of the whole
     // frame `frame` in d_pixels (vr_render_rect); the rest of it is untouched.
     void RenderRect(const Rect2D& frame, const vr_rect& scissor, vr_format fmt, void* d_pixels, void* stream = nullptr,

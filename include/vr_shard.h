@@ -131,7 +131,24 @@ vr_status vr_shard_rows(vr_shard* sh, int* my_rows, int* rows_per_rank);
  * instead of waiting forever.  Every later collective on the shard fails at
  * once (vr_shard_aborted = 1); vr_shard_destroy still frees it. */
 vr_status vr_shard_set_timeout(vr_shard* sh, double seconds);
-/* Render streams of vr_shard_run, 1 to 4: n >= 2 = frame i renders on stream
+/* Pairing (the ctx's option "frame_pairing", vr_set_option; read at every
+ * run): a one-rank pipeline (a one-rank communicator, or a solo rehearsal)
+ * that renders a grid medium on 2 or more render streams takes the frames of
+ * vr_shard_run / vr_shard_run_frames two at a time, each pair in ONE launch
+ * (vr.h vr_render_pair), so both frames read the volume at the same moment;
+ * an odd last frame renders alone.  1 = successive pairs on one render
+ * stream; 2 = pairs alternating over two render streams (four buffer sets);
+ * 0 = one launch per frame.  Frame i still renders with (osd[i], gsd[i]), and
+ * without cameras every frame is rendered, none copied.  vr_shard_frame,
+ * vr_shard_copy_frame and the join on the caller's stream keep their meaning.
+ * A sampled pair is bracketed by ONE event pair: with pairing, the kernel_ms
+ * of vr_shard_run is the mean duration of a PAIR (two frames), and
+ * vr_shard_sampled_busy the union of the pairs' intervals.  Multi-rank
+ * pipelines, the in-process loopback of several ranks and procedural media
+ * ignore the option: one launch per frame.  A run after the option changed
+ * first waits (host) for the frames in flight.
+ *
+ * Render streams of vr_shard_run, 1 to 4: n >= 2 = frame i renders on stream
  * i mod n of the shard with buffer set i mod n, so n consecutive frames are in
  * flight and their renders overlap (with the exchange on the render streams;
  * on the communication stream at most 2); the default is 2;

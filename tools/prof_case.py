@@ -30,6 +30,7 @@ def main():
     ap.add_argument("--proc-enum", type=int, default=-1, help="procedural sort: 1 region enumeration with shadows")
     ap.add_argument("--slab-cap", type=int, default=-1)
     ap.add_argument("--opt", action="append", default=[], help="vr option NAME=VALUE")
+    ap.add_argument("--pair", action="store_true", help="frames two at a time, each pair one launch (vr_render_pair)")
     a = ap.parse_args()
     with vr.Renderer(0) as r:
         if a.proc:
@@ -59,10 +60,14 @@ def main():
         r.set_shader_data(osd, gsd)
         r.set_march(vr.march_defaults(max_steps=a.steps))
         out = r.alloc_target(a.width, a.height, vr.FMT_RGBA8_UNORM)
-        for _ in range(a.frames):
-            r.render(a.width, a.height, vr.FMT_RGBA8_UNORM, out=out)
+        out1 = r.alloc_target(a.width, a.height, vr.FMT_RGBA8_UNORM) if a.pair else None
+        for _ in range(a.frames // 2 if a.pair else a.frames):
+            if a.pair:
+                r.render_pair(a.width, a.height, vr.FMT_RGBA8_UNORM, out, out1)
+            else:
+                r.render(a.width, a.height, vr.FMT_RGBA8_UNORM, out=out)
         torch.cuda.synchronize()
-        print("variant", r.kernel_variant, "schedule", r.get_option("schedule"))
+        print("variant", r.kernel_variant, "schedule", r.get_option("schedule"), "pair_launches", r.get_option("pair_launches"))
 
 
 if __name__ == "__main__":

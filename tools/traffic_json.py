@@ -6,6 +6,12 @@ HBM bytes per march-kernel launch = FETCH_SIZE*1024*2 + WRITE_SIZE*1024
 has a TCP_TOTAL_CACHE_ACCESSES_sum / TA_TA_BUSY_sum / GRBM_GUI_ACTIVE pass, the
 L1 lookups per launch and the TA busy fraction go in too: the TA-lookup
 roofline of the bench line (bench.py).
+
+A fourth argument F (default 1) = frames per march launch: 2 for a run of
+tools/prof_case.py --pair, whose launches each march two frames
+(vr_render_pair, the native frame loop's default).  Bytes and lookups are then
+written PER FRAME (the launch's / F), which is what bench.py divides by its
+time per frame.
 """
 import json
 import os
@@ -15,20 +21,25 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from pmc_summary import load  # noqa: E402
 
 tag, config, out = sys.argv[1], sys.argv[2], sys.argv[3]
+frames = int(sys.argv[4]) if len(sys.argv) > 4 else 1
 c = load(tag)
 kernel = None
 for line in open(f"gpurun_out/pmc_{tag}/p1.log"):
     if line.startswith("variant "):
         kernel = line.split()[1]
-fetch = c["FETCH_SIZE"] * 1024 * 2
-write = c["WRITE_SIZE"] * 1024
+fetch = c["FETCH_SIZE"] * 1024 * 2 / frames
+write = c["WRITE_SIZE"] * 1024 / frames
 res = {"config": config, "kernel": kernel, "hbm_bytes_per_launch": round(fetch + write),
        "fetch_bytes": round(fetch), "write_bytes": round(write),
        "raw": {k: c[k] for k in ("FETCH_SIZE", "WRITE_SIZE") if k in c},
        "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over tools/prof_case.py "
                  "(20 launches, mean per march launch); FETCH_SIZE x2 per the gfx950 correction"}
+if frames > 1:
+    res["frames_per_launch"] = frames
+    res["method"] += (f"; prof_case.py --pair: every launch marches {frames} frames (vr_render_pair), bytes and lookups "
+                      f"are the launch's / {frames} = per frame, raw counters per launch")
 if "TCP_TOTAL_CACHE_ACCESSES_sum" in c:
-    res["l1_lookups_per_launch"] = round(c["TCP_TOTAL_CACHE_ACCESSES_sum"])
+    res["l1_lookups_per_launch"] = round(c["TCP_TOTAL_CACHE_ACCESSES_sum"] / frames)
     res["raw"]["TCP_TOTAL_CACHE_ACCESSES_sum"] = c["TCP_TOTAL_CACHE_ACCESSES_sum"]
     res["method"] += "; a third pass TCP_TOTAL_CACHE_ACCESSES_sum TA_TA_BUSY_sum GRBM_GUI_ACTIVE SQ_INSTS_VMEM_RD"
 if "TA_TA_BUSY_sum" in c and c.get("GRBM_GUI_ACTIVE"):

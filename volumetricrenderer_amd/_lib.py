@@ -138,6 +138,8 @@ _SIGS = {
     "vr_render": (ctypes.c_int, [_vp, ctypes.POINTER(Target), _vp]),
     "vr_render_sequence": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.c_int, ctypes.POINTER(ObjectShaderData),
                                           ctypes.POINTER(GlobalShaderData), _vp]),
+    "vr_render_pair": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.POINTER(Target), ctypes.POINTER(ObjectShaderData),
+                                      ctypes.POINTER(GlobalShaderData), _vp]),
     "vr_render_rect": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.POINTER(Rect), _vp]),
     "vr_render_rects": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.POINTER(Rect), ctypes.c_int, _vp]),
     "vr_rects_coalesce": (ctypes.c_int, [ctypes.POINTER(Rect), ctypes.c_int, ctypes.c_int, ctypes.POINTER(Rect),

@@ -850,12 +850,17 @@ try {
     }
     // an unchanged grid frame on this stream and target: launch the cached arguments
     const hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (!c->proc.enabled && c->launch_cache && !c->mm_pending && !c->rg_pending) {
+    if (!c->proc.enabled && c->launch_cache && !c->mm_pending && !c->rg_pending && !(c->cap && c->cap->mode == 2)) {
         for (const Ctx::Cached& e : c->lc)
             if (e.valid && e.gen == c->gen && e.stream == hs && std::memcmp(&e.t, t, sizeof *t) == 0) {
                 HIP_TRY(hipSetDevice(c->device));
                 ++c->renders_since_build;
                 ++c->lc_hits;
+                if (c->cap) {   // vr_render_pair launches it
+                    *c->cap = Ctx::PairCapture{1, true, e.a, e.pl, e.sc, e.kind, e.slot};
+                    c->region_slot = e.slot;
+                    return VR_OK;
+                }
                 HIP_TRY(launch_march(e.a, e.pl.layout, e.pl.wrap, e.pl.early, e.sc, hs));
                 if (e.kind != SCHED_REGIONS) return VR_OK;
                 c->region_slot = e.slot;
@@ -1038,6 +1043,10 @@ try {
     sc.slab = pl.layout == LAYOUT_COL48 && c->slab;
     a.slab_cap = c->slab_cap;
     if (kind == SCHED_RINGS || kind == SCHED_REGIONS) box_centre_pixel(c, a, &sc.center_x, &sc.center_y);
+    if (c->cap && c->cap->mode == 2) {   // a pair's second frame: arguments and plan only
+        *c->cap = Ctx::PairCapture{2, true, a, pl, sc, kind, -1};
+        return VR_OK;
+    }
     if (kind == SCHED_REGIONS) {
         const bool splittable = is_b4_family(pl.layout) || pl.layout == LAYOUT_ZPAIR || pl.layout == LAYOUT_CORNER8 ||
                                 pl.layout == LAYOUT_CORNERH || pl.layout == LAYOUT_COL48Z;
@@ -1070,6 +1079,10 @@ try {
                     sc.map.nwx = std::max(1, std::min(sc.map.nwx, rb.most_marched * K));
             }
         }
+    }
+    if (c->cap) {   // vr_render_pair launches it (alone through finish_render, or paired)
+        *c->cap = Ctx::PairCapture{1, true, a, pl, sc, kind, c->region_slot};
+        return VR_OK;
     }
     HIP_TRY(launch_march(a, pl.layout, pl.wrap, pl.early, sc, hs));
     if (c->launch_cache) {   // remember it
@@ -1104,6 +1117,145 @@ try {
     return VR_OK;
 } catch (...) {
     return caught_exception("vr_render_sequence");
+}
+
+}   // extern "C"
+
+namespace {
+
+// A frame vr_render planned but did not launch (Ctx::PairCapture, mode 1): launch it alone,
+// with vr_render's own bookkeeping.
+vr_status finish_render(Ctx* c, const Ctx::PairCapture& f, const vr_target* t, hipStream_t hs, unsigned long long gen)
+{
+    HIP_TRY(launch_march(f.a, f.pl.layout, f.pl.wrap, f.pl.early, f.sc, hs));
+    bool cached = false;   // the plan may have come from the launch cache: no second entry for it
+    for (const Ctx::Cached& e : c->lc)
+        cached = cached || (e.valid && e.gen == gen && e.stream == hs && std::memcmp(&e.t, t, sizeof *t) == 0);
+    if (c->launch_cache && !cached) {
+        Ctx::Cached& e = c->lc[c->lc_next];
+        c->lc_next = (c->lc_next + 1) % (int)(sizeof c->lc / sizeof c->lc[0]);
+        e.valid = true;
+        e.gen = gen;   // the context's when the frame was planned
+        e.t = *t;
+        e.stream = hs;
+        e.a = f.a;
+        e.pl = f.pl;
+        e.sc = f.sc;
+        e.kind = f.kind;
+        e.slot = f.slot;
+    }
+    if (f.kind == SCHED_REGIONS) return note_region_render(c, hs);
+    return VR_OK;
+}
+
+// The second frame's arguments may differ from the first's only in what the paired kernel
+// reads per frame: the camera (ray basis, r2 / r3, cam, tap_T), the target buffer, the
+// empty-tile fill and the step counter.
+bool pair_compatible(const Ctx::PairCapture& f0, const Ctx::PairCapture& f1)
+{
+    if (f0.pl.layout != f1.pl.layout || f0.pl.wrap != f1.pl.wrap || f0.pl.early != f1.pl.early) return false;
+    const MarchArgs &a = f0.a, &b = f1.a;
+    // the shared part, field by field (the structs' padding is not compared)
+#define VR_SAME(F) (std::memcmp(&a.F, &b.F, sizeof a.F) == 0)
+    return VR_SAME(box_min) && VR_SAME(box_max) && VR_SAME(box_range) && VR_SAME(step_size) && VR_SAME(density) &&
+           VR_SAME(scale) && VR_SAME(acc_limit) && VR_SAME(max_steps) && VR_SAME(tap_S) && VR_SAME(zero_offsets) &&
+           VR_SAME(umask) && VR_SAME(uval) && VR_SAME(nx) && VR_SAME(ny) && VR_SAME(nz) && VR_SAME(vol) &&
+           VR_SAME(plane_stride) && VR_SAME(geom.B) && VR_SAME(geom.R) && VR_SAME(geom.Ba) && VR_SAME(geom.Rn) &&
+           VR_SAME(geom.brick) && VR_SAME(geom.nbx) && VR_SAME(geom.nby) && VR_SAME(geom.nbz) && VR_SAME(width) &&
+           VR_SAME(height) && VR_SAME(band_rows) && VR_SAME(band_stride) && VR_SAME(band_first) && VR_SAME(out_rows) &&
+           VR_SAME(band_flip) && VR_SAME(pitch) && VR_SAME(format) && VR_SAME(bands_in_place) && VR_SAME(slab_cap);
+#undef VR_SAME
+}
+
+// The region lists' empty tiles (built for frame 0's camera) are frame 1's too: the part
+// of build_regions' key that the camera sets is the same
+bool same_region_camera(const Ctx::PairCapture& f0, const Ctx::PairCapture& f1)
+{
+    const MarchArgs &a = f0.a, &b = f1.a;
+    return f0.sc.center_x == f1.sc.center_x && f0.sc.center_y == f1.sc.center_y &&
+           std::memcmp(a.org, b.org, sizeof a.org) == 0 && std::memcmp(a.o, b.o, sizeof a.o) == 0 &&
+           std::memcmp(a.px, b.px, sizeof a.px) == 0 && std::memcmp(a.py, b.py, sizeof a.py) == 0 &&
+           std::memcmp(a.r3, b.r3, sizeof a.r3) == 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+vr_status vr_render_pair(void* p, const vr_target* t0, const vr_target* t1, const vr_object_shader_data* osd,
+                         const vr_global_shader_data* gsd, void* stream)
+try {
+    if (!p || !t0 || !t1 || (!osd) != (!gsd)) return fail(VR_ERR_INVALID, "vr_render_pair: bad argument");
+    // field by field: the structs' padding is the caller's
+    if (t0->width != t1->width || t0->height != t1->height || t0->format != t1->format || t0->band_rows != t1->band_rows ||
+        t0->band_stride != t1->band_stride || t0->band_first != t1->band_first || t0->row_pitch != t1->row_pitch ||
+        t0->step_counter != t1->step_counter || t0->band_flip != t1->band_flip || t0->reserved != t1->reserved)
+        return fail(VR_ERR_INVALID, "vr_render_pair: the two targets must agree in everything but pixels");
+    {
+        const int f = t0->format & ~(VR_TARGET_BANDS_IN_PLACE | VR_TARGET_ROW_RANGE);
+        if (!t1->pixels || (f >= 0 && f <= 5 && (uintptr_t)t1->pixels % format_bytes(f) != 0))
+            return fail(VR_ERR_INVALID, "vr_render_pair: the second target's pixels are null or misaligned");
+    }
+    Ctx* c = as_ctx(p);
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (osd) {
+        const vr_status st = vr_set_shader_data(p, &osd[0], &gsd[0]);
+        if (st != VR_OK) return st;
+    }
+    // frame 0: vr_render's whole path (checks, plan, region lists) up to the launch
+    Ctx::PairCapture f0{};
+    f0.mode = 1;
+    c->cap = &f0;
+    vr_status st = vr_render(p, t0, stream);
+    c->cap = nullptr;
+    if (st != VR_OK) return st;
+    const unsigned long long gen0 = c->gen;
+    const bool pairable = f0.got && f0.kind == SCHED_REGIONS && f0.sc.split <= 1 && !f0.sc.slab && f0.sc.wg_waves == 4 &&
+                          pair_layout(f0.pl.layout) && f0.pl.wrap == WRAP_CLAMP;
+    Ctx::PairCapture f1{};
+    bool paired = false;
+    if (pairable) {
+        if (osd) st = vr_set_shader_data(p, &osd[1], &gsd[1]);
+        if (st == VR_OK) {
+            f1.mode = 2;
+            c->cap = &f1;
+            st = vr_render(p, t1, stream);
+            c->cap = nullptr;
+        }
+        if (st != VR_OK) {   // frame 0 is planned and counted: it still renders
+            (void)finish_render(c, f0, t0, hs, gen0);
+            return st;
+        }
+        paired = f1.got && f1.kind == f0.kind && pair_compatible(f0, f1);
+    }
+    if (!paired) {
+        // no paired kernel for this plan (a procedural medium, split rays, the slab, an
+        // experiment schedule, a layout without an instance, frames whose plans differ):
+        // the two ordinary renders
+        if (f0.got) {
+            st = finish_render(c, f0, t0, hs, gen0);
+            if (st != VR_OK) return st;
+        }
+        if (osd && !pairable) {
+            st = vr_set_shader_data(p, &osd[1], &gsd[1]);
+            if (st != VR_OK) return st;
+        }
+        return vr_render(p, t1, stream);
+    }
+    // frame 1 fills the lists' empty tiles only where they are its own (vr_render's
+    // region_exact rule); a frame that marches every entry keeps the unreduced wave count
+    const Ctx::RegionBuf& rb = c->region[c->region_cur];
+    f1.a.empty_fill = f0.a.empty_fill && same_region_camera(f0, f1) ? 1 : 0;
+    Schedule sc = f0.sc;
+    if (f0.a.empty_fill && !f1.a.empty_fill) sc.map.nwx = std::max(1, rb.map.nwx);
+    HIP_TRY(launch_march_pair(f0.a, f1.a, f0.pl.layout, f0.pl.early, sc, c->pair_deal, hs));
+    ++c->pair_launches;
+    ++c->renders_since_build;   // the second render with these lists (build_regions counted the first)
+    c->region_slot = f0.slot;
+    return note_region_render(c, hs);
+} catch (...) {
+    if (p) as_ctx(p)->cap = nullptr;
+    return caught_exception("vr_render_pair");
 }
 
 vr_status vr_assemble_frame(void* p, const void* d_gathered, int gathered_format, size_t rows_per_rank, int nranks,

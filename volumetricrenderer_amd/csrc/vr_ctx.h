@@ -259,6 +259,25 @@ struct Ctx {
     } lc[4];
     int lc_next = 0;
     long long lc_hits = 0;         // read-only option "launch_cache_hits"
+    // vr_render_pair: while `cap` is set, vr_render plans a grid frame without launching it.
+    // mode 1 = the whole path (region lists included), the launch left to the caller;
+    // mode 2 = the frame's arguments and plan only (the pair's second frame: the lists are
+    // the first frame's).  got stays false where vr_render ran the frame itself (a
+    // procedural medium).
+    struct PairCapture {
+        int mode = 0;
+        bool got = false;
+        MarchArgs a{};
+        Plan pl{};
+        Schedule sc{};
+        int kind = 0;
+        int slot = -1;
+    };
+    PairCapture* cap = nullptr;
+    int pair_deal = 0;             // option "pair_deal": 0 = the frame in the wave's parity, 1 = in the workgroup's
+    int frame_pairing = 2;         // option "frame_pairing": vr_shard_run_frames takes a one-rank grid pipeline's frames
+                                   // two at a time (0 off, 1 pairs on one render stream, 2 alternating over two)
+    long long pair_launches = 0;   // read-only option "pair_launches": paired launches so far
     uint2* d_lat = nullptr;
     size_t lat_cap = 0;            // bytes allocated
     long long lat_key[3] = {0, 0, -1};

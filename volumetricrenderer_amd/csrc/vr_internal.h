@@ -378,6 +378,15 @@ constexpr unsigned kDeferInPlace = 0xffffffffu;
 
 // launchers (vr_march.hip / vr_volume.hip); return hipError_t
 hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, const Schedule& sc, hipStream_t s);
+// Two frames in one regions launch (march_regions_pair, vr_render_pair): the layouts with a
+// paired kernel, and the launch -- a0 and a1 differ only in their per-frame arguments, sc
+// is a regions schedule with one lane per ray (no split, no slab, 4-wave workgroups);
+// deal 0 = the frame in the wave's parity, 1 = in the workgroup's (vr_march_kernels.h)
+bool pair_layout(int layout);
+hipError_t launch_march_pair(const MarchArgs& a0, const MarchArgs& a1, int layout, bool early, const Schedule& sc, int deal,
+                             hipStream_t s);
+hipError_t launch_march_pair_cornerh(const MarchArgs& a0, const MarchArgs& a1, bool early, const Schedule& sc, int deal,
+                                     hipStream_t s);   // vr_march_c8.hip
 // per-plane byte min (mm[0..3]) and max (mm[4..7]) of the planar volume; mm
 // must hold 0xffffffff x 4 then 0 x 4 (atomicMin / atomicMax)
 hipError_t launch_plane_minmax(const uint8_t* d_planar, long long total, unsigned* mm, hipStream_t s);

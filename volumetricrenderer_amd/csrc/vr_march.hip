@@ -176,6 +176,23 @@ hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, co
     return launch_lw<LAYOUT_PLANAR, WRAP_MIRROR>(a, early, sc, s);
 }
 
+bool pair_layout(int layout)
+{
+    return layout == LAYOUT_COL48 || layout == LAYOUT_BRICK4832 || layout == LAYOUT_CORNERH;
+}
+
+hipError_t launch_march_pair(const MarchArgs& a0, const MarchArgs& a1, int layout, bool early, const Schedule& sc, int deal,
+                             hipStream_t s)
+{
+    if (a0.width <= 0 || a0.out_rows <= 0) return hipSuccess;
+    switch (layout) {
+    case LAYOUT_COL48: return launch_pair_lw<LAYOUT_COL48, WRAP_CLAMP>(a0, a1, early, sc, deal, s);
+    case LAYOUT_BRICK4832: return launch_pair_lw<LAYOUT_BRICK4832, WRAP_CLAMP>(a0, a1, early, sc, deal, s);
+    case LAYOUT_CORNERH: return launch_march_pair_cornerh(a0, a1, early, sc, deal, s);   // vr_march_c8.hip
+    default: return hipErrorInvalidValue;   // no paired kernel: the caller renders the frames one by one
+    }
+}
+
 }  // namespace vr
 
 #ifdef VR_TIMELINE

@@ -15,6 +15,12 @@ hipError_t launch_march_corner8(const MarchArgs& a, int layout, bool early, cons
     return launch_lw<LAYOUT_CORNER8, WRAP_CLAMP>(a, early, sc, s);
 }
 
+hipError_t launch_march_pair_cornerh(const MarchArgs& a0, const MarchArgs& a1, bool early, const Schedule& sc, int deal,
+                                     hipStream_t s)
+{
+    return launch_pair_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a0, a1, early, sc, deal, s);
+}
+
 }  // namespace vr
 
 #ifdef VR_TIMELINE

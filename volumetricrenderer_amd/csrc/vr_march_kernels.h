@@ -1188,6 +1188,73 @@ __global__ __launch_bounds__(kThreads) VR_UM_ATTR void march_regions_u(const Mar
     regions_body<LAYOUT, WRAP, EARLY, ZO, kThreads / 64, UM>(a, tiles, hdr, nwx, lds);
 }
 
+// ---- two frames in one launch (vr_render_pair) ----
+// The regions schedule over one list and one header for two frames: a wave
+// takes (list entry, frame f) and marches the entry with frame f's arguments,
+// so both frames read an entry's bricks at the same moment on the same XCD.
+// a0 and a1 differ only in the camera (ray basis, r2 / r3, cam, tap_T), the
+// target buffer, empty_fill and step_counter (vr_api.cpp pair_compatible);
+// the lists are frame 0's.  f is wave-uniform and picks one of two inlined
+// copies of the march, each reading its own kernarg block as march_regions does.
+//   deal 0: f = the wave's parity in its workgroup -- a workgroup is 2
+//           consecutive entries x 2 frames, both readers on one CU (L1 and L2)
+//   deal 1: f = the workgroup's parity on its XCD -- a workgroup keeps 4
+//           consecutive entries (the 2x2 supertile) of one frame; L2 only
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
+__device__ __forceinline__ void pair_frame(const MarchArgs& a, FastCtx f, const unsigned* __restrict__ tiles, int begin,
+                                           int count, int w, int nwx)
+{
+    if constexpr (LAYOUT == LAYOUT_CORNERH)   // the one per-frame part of the prologue
+        for (int c = 0; c < 4; ++c) f.oz[c] = noise::in_vgpr(a.tap_T[c][2]);
+    const int lane = threadIdx.x & 63;
+    unsigned long long steps = 0;
+    for (int k = w; w < nwx && k < count; k += nwx) {
+        const unsigned t = tiles[begin + k];
+        const int tx = (int)(t & 0xffffu), ty = (int)(t >> 16);
+        steps += march_pixel<LAYOUT, WRAP, EARLY, ZO, UM>(a, f, tx * 8 + lane_x<LAYOUT>(lane),
+                                                          ty * 8 + lane_y<LAYOUT>(lane));
+    }
+    if (a.step_counter) add_steps(a, steps);
+}
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
+__device__ __forceinline__ void regions_pair_body(const MarchArgs& a0, const MarchArgs& a1, const unsigned* __restrict__ tiles,
+                                                  const int* __restrict__ hdr, int nwx, int deal, unsigned* lds)
+{
+    const int xcd = blockIdx.x & 7, g = (int)(blockIdx.x >> 3);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int fr = deal ? (g & 1) : (wave & 1);
+    const int first = deal ? (g >> 1) * 4 : g * 2;   // the workgroup's first entry wave
+    const int w = first + (deal ? wave : (wave >> 1));
+    const int begin = hdr[xcd], all = hdr[xcd + 1] - begin;
+    const int marched = min(hdr[kRegionWork + xcd], all);
+    const int count0 = a0.empty_fill ? marched : all, count1 = a1.empty_fill ? marched : all;
+    if (fr) {
+        if (a1.empty_fill) fill_empty_tiles(a1, tiles, begin, count1, all, w, nwx);
+    } else {
+        if (a0.empty_fill) fill_empty_tiles(a0, tiles, begin, count0, all, w, nwx);
+    }
+    if (first >= max(count0, count1)) return;   // whole workgroup (either deal), before the barrier
+    const FastCtx f = fast_prologue<LAYOUT>(a0, lds);   // volume and layout geometry: the frames' common part
+    if (fr) pair_frame<LAYOUT, WRAP, EARLY, ZO, UM>(a1, f, tiles, begin, count1, w, nwx);
+    else pair_frame<LAYOUT, WRAP, EARLY, ZO, UM>(a0, f, tiles, begin, count0, w, nwx);
+}
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO>
+__global__ __launch_bounds__(kThreads) void march_regions_pair(const MarchArgs a0, const MarchArgs a1,
+                                                              const unsigned* __restrict__ tiles,
+                                                              const int* __restrict__ hdr, int nwx, int deal)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned lds[];
+    regions_pair_body<LAYOUT, WRAP, EARLY, ZO, 0>(a0, a1, tiles, hdr, nwx, deal, lds);
+}
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
+__global__ __launch_bounds__(kThreads) VR_UM_ATTR void march_regions_pair_u(const MarchArgs a0, const MarchArgs a1,
+                                                                           const unsigned* __restrict__ tiles,
+                                                                           const int* __restrict__ hdr, int nwx, int deal)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned lds[];
+    regions_pair_body<LAYOUT, WRAP, EARLY, ZO, UM>(a0, a1, tiles, hdr, nwx, deal, lds);
+}
+
 
 // ---- step-split rays (regions schedule) ----
 // A wave whose rays march alone on their SIMD waits ~110 dependent memory
@@ -2090,6 +2157,40 @@ hipError_t launch_lw(const MarchArgs& a, bool early, const Schedule& sc, hipStre
         hipLaunchKernelGGL((march_grid<L, W, true>), grid, block, lds, s, a);
     else
         hipLaunchKernelGGL((march_grid<L, W, false>), grid, block, lds, s, a);
+    return hipGetLastError();
+}
+
+// The paired launch (march_regions_pair): the kernels of launch_lw's one-lane regions
+// dispatch above -- one uniform channel (_u) or the general kernel -- for two frames.
+// The caller has checked that the frames share the plan and everything but the per-frame
+// arguments (vr_api.cpp), that sc is a regions schedule without split, slab or wide
+// workgroups, and that L is one of the three layouts instantiated here.
+template <int L, int W>
+hipError_t launch_pair_lw(const MarchArgs& a0, const MarchArgs& a1, bool early, const Schedule& sc, int deal, hipStream_t s)
+{
+    static_assert(2 * sizeof(MarchArgs) + 64 <= 4096, "two MarchArgs travel in the 4-KiB kernarg segment");
+    const size_t lds = L == LAYOUT_CORNERH ? 0 : (size_t)(a0.nx + a0.ny + a0.nz + 3) * sizeof(unsigned);
+    const dim3 block(kThreads);
+    const int nwx = sc.map.nwx;
+    const dim3 grid((unsigned)(deal ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
+    const int um = a0.umask;
+    if (!early && a0.zero_offsets && (um == 1 || um == 2 || um == 4 || um == 8)) {
+#define VR_UMP(U) hipLaunchKernelGGL((march_regions_pair_u<L, W, false, true, U>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal)
+        if (um == 1) VR_UMP(1);
+        else if (um == 2) VR_UMP(2);
+        else if (um == 4) VR_UMP(4);
+        else VR_UMP(8);
+#undef VR_UMP
+        return hipGetLastError();
+    }
+    if (early && a0.zero_offsets)
+        hipLaunchKernelGGL((march_regions_pair<L, W, true, true>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
+    else if (early)
+        hipLaunchKernelGGL((march_regions_pair<L, W, true, false>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
+    else if (a0.zero_offsets)
+        hipLaunchKernelGGL((march_regions_pair<L, W, false, true>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
+    else
+        hipLaunchKernelGGL((march_regions_pair<L, W, false, false>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
     return hipGetLastError();
 }
 

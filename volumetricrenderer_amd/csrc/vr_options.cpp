@@ -64,6 +64,16 @@ try {
         ++c->gen;
         return VR_OK;
     }
+    if (n == "frame_pairing") {   // the native frame loop's pairs (vr_shard.h): 0 off, 1 one stream, 2 two streams
+        if (value < 0 || value > 2) return fail(VR_ERR_INVALID, "vr_set_option: frame_pairing is 0, 1 or 2");
+        c->frame_pairing = value;
+        return VR_OK;
+    }
+    if (n == "pair_deal") {   // vr_render_pair: the frame in the wave's parity (0) or the workgroup's (1)
+        if (value < 0 || value > 1) return fail(VR_ERR_INVALID, "vr_set_option: pair_deal is 0 or 1");
+        c->pair_deal = value;
+        return VR_OK;
+    }
     if (n == "inject_throw") {   // test hook: the next vr_render throws in its host path
         if (value < 0 || value > 2)
             return fail(VR_ERR_INVALID, "vr_set_option: inject_throw is 0, 1 (std::runtime_error) or 2 (std::bad_alloc)");
@@ -249,6 +259,9 @@ try {
     if (n == "row_setup") return c->row_setup;
     if (n == "row_pow") return c->row_pow;
     if (n == "row_first_pct") return c->row_first_pct;
+    if (n == "frame_pairing") return c->frame_pairing;
+    if (n == "pair_deal") return c->pair_deal;
+    if (n == "pair_launches") return (int)std::min<long long>(c->pair_launches, 0x7fffffff);
     if (n == "launch_cache_hits") return (int)std::min<long long>(c->lc_hits, 0x7fffffff);
     if (n == "experiments") return VR_EXPERIMENTS;   // read-only: the measured-slower variants are built
     if (n == "region_interval") return c->region_interval;

@@ -201,6 +201,11 @@ struct vr_shard {
                                       // vr_shard_share_volume's agreement vector
     bool pending[kMaxFramesInFlight] = {};        // done[p] recorded and not yet waited on
     int last = -1;                    // parity of the last frame
+    // frames two at a time through vr_render_pair (the ctx's option "frame_pairing", read
+    // at every run): 1 = successive pairs on render stream 0 with buffer sets 0 / 1; 2 =
+    // pairs alternating over render streams 0 and 1, stream q with buffer sets 2q / 2q + 1
+    int pairing = -1;                 // the last run's (-1: none yet)
+    int pairs_run = 0;                // pairs queued so far (the alternation carries over between runs)
     bool loopback = false;            // one process emulates all ranks (no RCCL)
     bool solo = false;                // loopback rehearsal of one rank: its own band set only, no exchange
     std::vector<hipEvent_t> timing;   // sampled render brackets (pairs)
@@ -555,6 +560,36 @@ vr_status one_frame_on_render(vr_shard* sh, int p, hipStream_t rs, hipEvent_t t0
     return VR_OK;
 }
 
+// Frames (buffer sets p0, p1) through one vr_render_pair on rs -- one rank, no exchange:
+// frame j with (osd[j], gsd[j]), or both with the current shader data.  Rank 0 of a solo
+// rehearsal still assembles each frame.  A sampled pair is bracketed by one event pair.
+vr_status pair_on_render(vr_shard* sh, int p0, int p1, hipStream_t rs, const vr_object_shader_data* osd,
+                         const vr_global_shader_data* gsd, hipEvent_t t0, hipEvent_t t1)
+{
+    const bool r0 = sh->rank == 0;
+    vr_target t = target_of(sh, sh->rank);
+    if (r0) {
+        t.format = sh->format | VR_TARGET_BANDS_IN_PLACE | range_flag(sh, sh->rank);
+        t.row_pitch = sh->pitch;
+    } else {
+        t.format = sh->gformat | range_flag(sh, sh->rank);
+        t.row_pitch = sh->gpitch;
+    }
+    vr_target ta = t, tb = t;
+    ta.pixels = r0 ? sh->frame[p0] : sh->local[p0];
+    tb.pixels = r0 ? sh->frame[p1] : sh->local[p1];
+    if (t0) HIP_TRY(hipEventRecord(t0, rs));
+    if (sh->my_rows > 0) VR_TRY(vr_render_pair(sh->ctx, &ta, &tb, osd, gsd, rs));
+    else if (osd) VR_TRY(vr_set_shader_data(sh->ctx, &osd[1], &gsd[1]));
+    if (t1) HIP_TRY(hipEventRecord(t1, rs));
+    if (r0 && sh->nranks > 1) {
+        SH_TRY(assemble(sh, p0, rs));
+        SH_TRY(assemble(sh, p1, rs));
+    }
+    sh->last = p1;
+    return VR_OK;
+}
+
 // Rank 0 as a compositor by default (vr_shard_set_compositor) from this many
 // ranks on.  Config 5 (1080p) at N = 8: rank 0 rendering its own 1/8 beside
 // the assembly of the other 7/8 takes 0.0208 ms per frame against 0.0165 on
@@ -802,7 +837,55 @@ try {
         for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->fence, 0));
     }
     const bool on_render = sh->on_render && two;
-    if (on_render && frames > 0) {
+    // one rank rendering a grid on 2+ render streams: frames two at a time, each pair one
+    // launch (vr_render_pair); multi-rank pipelines and loopback keep one launch per frame
+    const bool one_rank = sh->nranks == 1 || (sh->loopback && sh->solo);
+    const int pairing = vr_get_option(sh->ctx, "frame_pairing");
+    const bool pairs = pairing > 0 && two && one_rank && !others_here(sh) && vr_get_option(sh->ctx, "procedural") == 0;
+    if (one_rank && frames > 0) {
+        if (sh->pairing >= 0 && pairing != sh->pairing && sh->last >= 0) {
+            // frames of the old arrangement may still be in flight (vr_shard_set_render_streams)
+            for (int p = 0; p < kMaxFramesInFlight; ++p)
+                if (sh->pending[p]) SH_TRY(wait_event(sh, sh->done[p], "vr_shard_run: frame_pairing changed"));
+        }
+        sh->pairing = pairing;
+    }
+    if (pairs && frames > 0) {
+        for (int q = 0; q < kMaxFramesInFlight; ++q)   // (as below: buffer sets last used by comm-stream frames)
+            if (sh->pending[q]) {
+                for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->done[q], 0));
+                sh->pending[q] = false;
+            }
+        const bool alt = pairing == 2;
+        for (int i = 0; i < frames;) {
+            const bool pair = i + 1 < frames;
+            const bool samp = kernel_ms && (i % sample_every == 0 || (pair && (i + 1) % sample_every == 0));
+            hipEvent_t t0 = samp ? sh->timing[2 * next] : nullptr, t1 = samp ? sh->timing[2 * next + 1] : nullptr;
+            if (samp) ++next;
+            const int q = alt ? (sh->pairs_run & 1) : 0;
+            hipStream_t rs = sh->render_stream[q];
+            // one stream: the buffer sets alternate 0 / 1 in its order; two: stream q owns sets 2q, 2q + 1
+            const int p0 = alt ? 2 * q : (sh->last < 0 ? 0 : (sh->last + 1) % 2);
+            if (pair) {
+                SH_TRY(pair_on_render(sh, p0, alt ? p0 + 1 : p0 ^ 1, rs, osd ? &osd[i] : nullptr, gsd ? &gsd[i] : nullptr,
+                                      t0, t1));
+                i += 2;
+            } else {   // an odd last frame renders alone, in the pairs' order
+                if (osd) VR_TRY(vr_set_shader_data(sh->ctx, &osd[i], &gsd[i]));
+                SH_TRY(one_frame_on_render(sh, p0, rs, t0, t1));
+                i += 1;
+            }
+            ++sh->pairs_run;
+        }
+        for (int q = 0; q < 2; ++q) {   // join: the caller's stream after both streams' last frames
+            HIP_TRY(hipEventRecord(sh->tail[q], sh->render_stream[q]));
+            HIP_TRY(hipStreamWaitEvent(s, sh->tail[q], 0));
+        }
+        for (int b = 0; b < (alt ? 4 : 2); ++b) {   // a later unpaired frame of set b waits for these
+            HIP_TRY(hipEventRecord(sh->done[b], sh->render_stream[alt ? b >> 1 : 0]));
+            sh->pending[b] = true;
+        }
+    } else if (on_render && frames > 0) {
         // the communicators of streams 1..P-1, once each, split from the
         // first (collective: every rank runs its first such frames together,
         // in the same order; a one-rank communicator splits too, so its test
@@ -923,7 +1006,7 @@ try {
             if (st != VR_OK) return st;
         }
     }
-    if (sh->last >= 0 && frames > 0 && !on_render) {   // the caller's stream sees the frame
+    if (sh->last >= 0 && frames > 0 && !on_render && !pairs) {   // the caller's stream sees the frame
         if (sh->rank == 0 && !others_here(sh)) {
             // rank 0 recorded no event per frame: join the exchange / assembly
             // stream and the render streams now (the render streams' frames

@@ -509,6 +509,18 @@ class RcclBandPipeline:
     def render_streams(self, n: int) -> None:
         _lib.shard_call("vr_shard_set_render_streams", self._h, int(n))
 
+    @property
+    def pairing(self) -> int:
+        """Frames two at a time in one launch (the renderer's option
+        "frame_pairing", vr_shard.h): 0 = off, 1 = pairs on one render stream,
+        2 = pairs alternating over two.  Only a one-rank pipeline of a grid
+        medium pairs; run_frames' kernel time is then a pair's."""
+        return self.r.get_option("frame_pairing")
+
+    @pairing.setter
+    def pairing(self, mode: int) -> None:
+        self.r.set_option("frame_pairing", int(mode))
+
     def set_timeout(self, seconds: float) -> None:
         """Deadline (s) of every later host wait on a collective."""
         _lib.shard_call("vr_shard_set_timeout", self._h, float(seconds))

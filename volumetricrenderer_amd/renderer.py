@@ -367,6 +367,30 @@ class Renderer:
         call("vr_render", self._ctx, ctypes.byref(t), _stream_handle(stream))
         return out
 
+    def render_pair(self, width: int, height: int, fmt: int, out0: torch.Tensor, out1: torch.Tensor, cameras=None,
+                    band_rows: int = 0, band_stride: int = 1, band_first: int = 0, stream=None,
+                    step_counter: torch.Tensor | None = None, band_flip: int = 0, row_pitch: int | None = None):
+        """Two queued frames in one launch (vr_render_pair): frame i into `outi`
+        with cameras[i] = (ObjectShaderData, GlobalShaderData); cameras None =
+        both with the current shader data.  The same bytes as set_shader_data +
+        render per frame; the renderer ends holding cameras[1]."""
+        for out in (out0, out1):
+            self._check_target(width, height, fmt, out, band_rows, band_stride, band_first, step_counter, band_flip)
+        ts = [Target(width=width, height=height, format=fmt, band_rows=band_rows, band_stride=band_stride,
+                     band_first=band_first, pixels=out.data_ptr(),
+                     row_pitch=out.stride(0) * out.element_size() if row_pitch is None else row_pitch,
+                     step_counter=step_counter.data_ptr() if step_counter is not None else None, band_flip=band_flip)
+              for out in (out0, out1)]
+        osd = gsd = None
+        if cameras is not None:
+            cams = list(cameras)
+            if len(cams) != 2:
+                raise ValueError(f"render_pair: two cameras, got {len(cams)}")
+            osd = (ObjectShaderData * 2)(cams[0][0], cams[1][0])
+            gsd = (GlobalShaderData * 2)(cams[0][1], cams[1][1])
+        call("vr_render_pair", self._ctx, ctypes.byref(ts[0]), ctypes.byref(ts[1]), osd, gsd, _stream_handle(stream))
+        return out0, out1
+
     def render_rect(self, out: torch.Tensor, rect, fmt: int = FMT_RGBA8_UNORM,
                     step_counter: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         """Render the pixels rect = (x, y, w, h) of the whole-frame target `out`
