@@ -256,3 +256,103 @@ def test_pair_targets_must_agree(r, vols):
     torch.cuda.synchronize()
     for o in (o0, o1):
         assert bool((o.view(torch.uint8) == 0xA5).all())
+
+
+# ---- the paths between a vr_target and the pair's launch: launch cache, a failing second frame, inject_throw ----
+
+def test_pair_frame0_from_launch_cache(r, vols):
+    """Frame 0 is the cached launch of a plain render on the same stream, target and counter."""
+    setup(r, AUTO, vols["v64"])
+    fmt = FMT_RGBA8_UNORM
+    r.set_shader_data(*cam(20.0, -35.0))
+    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+    o0, o1 = target(r, fmt), target(r, fmt)
+
+    def plain_o0():
+        cnt.zero_()
+        o0.view(torch.uint8).fill_(0xA5)
+        r.render(W, H, fmt, out=o0, step_counter=cnt)
+        torch.cuda.synchronize()
+        return o0.cpu().numpy(), int(cnt.item())
+
+    plain_o0()   # (a region-list build of this render has completed before the next one is planned and cached)
+    want, steps = plain_o0()
+    hits, pairs = r.get_option("launch_cache_hits"), r.get_option("pair_launches")
+    cnt.zero_()
+    o0.view(torch.uint8).fill_(0xA5)
+    r.render_pair(W, H, fmt, o0, o1, cameras=None, step_counter=cnt)
+    torch.cuda.synchronize()
+    assert r.get_option("launch_cache_hits") - hits == 1
+    assert r.get_option("pair_launches") - pairs == 1
+    assert np.array_equal(o0.cpu().numpy(), want) and np.array_equal(o1.cpu().numpy(), want)
+    assert int(cnt.item()) == 2 * steps
+    again, steps_again = plain_o0()
+    assert r.get_option("launch_cache_hits") - hits == 2
+    assert np.array_equal(again, want) and steps_again == steps
+
+
+def test_pair_second_frame_fails_first_renders(r, vols):
+    """A singular second camera: VR_ERR_INVALID, frame 0 rendered, frame 1's target untouched."""
+    setup(r, AUTO, vols["v64"])
+    fmt = FMT_RGBA8_UNORM
+    a = cam(20.0, -35.0)
+    singular = cam(21.6, -35.0)
+    for k in range(16):
+        singular[0].projection[k] = 0.0
+    want, _ = plain(r, [a], fmt)
+    pairs = r.get_option("pair_launches")
+    o0, o1 = target(r, fmt), target(r, fmt)
+    with pytest.raises(VRError) as e:
+        r.render_pair(W, H, fmt, o0, o1, cameras=[a, singular])
+    assert e.value.status == VR_ERR_INVALID
+    torch.cuda.synchronize()
+    assert np.array_equal(o0.cpu().numpy(), want[0])
+    assert bool((o1.view(torch.uint8) == 0xA5).all())
+    assert r.get_option("pair_launches") == pairs
+    check(r, cameras("spin_1.6"))
+
+
+@pytest.mark.parametrize("kind,status", [(1, 2), (2, 5)], ids=["runtime_error", "bad_alloc"])
+def test_pair_inject_throw(r, vols, kind, status):
+    """The option fires in frame 0's host path: vr_render's status and message, consumed once."""
+    setup(r, AUTO, vols["v64"])
+    fmt = FMT_RGBA8_UNORM
+    cams = cameras("spin_1.6")
+    r.set_option("inject_throw", kind)
+    o0, o1 = target(r, fmt), target(r, fmt)
+    with pytest.raises(VRError) as e:
+        r.render_pair(W, H, fmt, o0, o1, cameras=cams)
+    assert e.value.status == status
+    assert "vr_render: " in str(e.value)
+    torch.cuda.synchronize()
+    for o in (o0, o1):   # nothing was launched
+        assert bool((o.view(torch.uint8) == 0xA5).all())
+    check(r, cams)   # the option is write-only: that it was consumed shows in the same call passing now
+
+
+def test_pair_unpaired_first_frame_cached_once(r, vols):
+    """split 2 (no paired kernel): the second call launches both frames from the cache, one entry each."""
+    setup(r, AUTO, vols["v64"])
+    fmt = FMT_RGBA8_UNORM
+    c = cam(20.0, -35.0)
+    try:
+        r.set_option("split", 2)
+        want, steps = plain(r, [c, c], fmt)
+        cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+        o0, o1 = target(r, fmt), target(r, fmt)
+        deltas = []
+        for _ in range(2):
+            cnt.zero_()
+            o0.view(torch.uint8).fill_(0xA5)
+            o1.view(torch.uint8).fill_(0xA5)
+            hits, pairs = r.get_option("launch_cache_hits"), r.get_option("pair_launches")
+            r.render_pair(W, H, fmt, o0, o1, cameras=None, step_counter=cnt)
+            torch.cuda.synchronize()
+            deltas.append(r.get_option("launch_cache_hits") - hits)
+            assert r.get_option("pair_launches") == pairs
+            assert np.array_equal(o0.cpu().numpy(), want[0]) and np.array_equal(o1.cpu().numpy(), want[1])
+            assert int(cnt.item()) == steps
+        print("launch_cache_hits per call:", deltas)
+        assert deltas[1] == 2   # (the first call's depends on which addresses the allocator hands out again)
+    finally:
+        r.set_option("split", 1)

@@ -2,15 +2,17 @@
 //
 // Owns the device copy of the volume (replaces vkc::Texture3D,
 // VulkanTexture.cpp:111-156) and the per-frame uniforms (replaces
-// UniformBuffer<T>, VulkanUniformBuffer.h:37-61).  It turns them into one
-// MarchArgs block per vr_render and launches the HIP march kernel.  That last
-// step replaces the EnqueueRenderPass + vkCmdDrawIndexed path of
-// TestMain.cpp:194-217.  No exception crosses the ABI; errors go through
-// vr_last_error().
+// UniformBuffer<T>, VulkanUniformBuffer.h:37-61), and the helpers that turn
+// them into the parts of a launch's MarchArgs (plan, ray basis, volume
+// buffers).  The render entry points that launch the HIP march kernel -- they
+// replace the EnqueueRenderPass + vkCmdDrawIndexed path of
+// TestMain.cpp:194-217 -- are in vr_render.cpp.  No exception crosses the ABI;
+// errors go through vr_last_error().
 //
 // The context type and the shared helpers are in vr_ctx.h; the options, the
 // region lists / row partition and the procedural scratch live in
-// vr_options.cpp, vr_regions_host.cpp and vr_proc_host.cpp.
+// vr_options.cpp, vr_regions_host.cpp and vr_proc_host.cpp; the scissored
+// renders in vr_rect.cpp.
 #include "vr_ctx.h"
 
 namespace vrapi {
@@ -238,7 +240,8 @@ vr_status make_plan(Ctx* c, MarchArgs* a, Plan* p)
     return VR_OK;
 }
 
-// The parts of a launch's MarchArgs that vr_render and vr_render_rect share.
+// The parts of a launch's MarchArgs that vr_render (vr_render.cpp) and the
+// scissored renders (vr_rect.cpp) share; the target's part is target_geometry.
 // frame_args: the ray basis of a width x height frame and the march constants;
 // false when Projection*View is singular.
 bool frame_args(const Ctx* c, int width, int height, MarchArgs* ap)
@@ -815,449 +818,6 @@ try {
 }
 
 
-vr_status vr_render(void* p, const vr_target* t, void* stream)
-try {
-    if (!p || !t) return fail(VR_ERR_INVALID, "vr_render: null argument");
-    Ctx* c = as_ctx(p);
-    if (!c->d_planar && !c->proc.enabled)
-        return fail(VR_ERR_NO_VOLUME, "vr_render: no volume (vr_set_volume / vr_generate_volume)");
-    if (!c->has_camera) return fail(VR_ERR_NO_CAMERA, "vr_render: no shader data (vr_set_shader_data)");
-    if (t->width <= 0 || t->height <= 0) return fail(VR_ERR_INVALID, "vr_render: bad size %dx%d", t->width, t->height);
-    const int tfmt = t->format & ~(VR_TARGET_BANDS_IN_PLACE | VR_TARGET_ROW_RANGE);
-    const bool in_place = (t->format & VR_TARGET_BANDS_IN_PLACE) != 0;
-    const bool row_range = (t->format & VR_TARGET_ROW_RANGE) != 0;
-    if (tfmt < 0 || tfmt > 5) return fail(VR_ERR_INVALID, "vr_render: bad format %d", t->format);
-    if (!t->pixels) return fail(VR_ERR_INVALID, "vr_render: pixels is null");
-    const int bpp = format_bytes(tfmt);
-    const size_t pitch = t->row_pitch ? t->row_pitch : (size_t)t->width * bpp;
-    if (pitch < (size_t)t->width * bpp || pitch % bpp != 0 || ((uintptr_t)t->pixels % bpp) != 0)
-        return fail(VR_ERR_INVALID, "vr_render: pitch/alignment (pitch %zu, bpp %d)", pitch, bpp);
-    if (t->band_rows < 0 || (t->band_rows > 0 && (t->band_stride <= 0 || t->band_first < 0)))
-        return fail(VR_ERR_INVALID, "vr_render: bad band selection");
-    if (row_range && (t->band_rows <= 0 || t->band_stride != 1 || t->band_first % 8 != 0))
-        return fail(VR_ERR_INVALID, "vr_render: bad row range (rows %d, stride %d, first row %d: need rows > 0, "
-                    "stride 1, first a multiple of 8)", t->band_rows, t->band_stride, t->band_first);
-    if (t->band_flip != 0 && (row_range || t->band_rows <= 0 || t->band_stride < 2 || std::abs(t->band_flip) >= t->band_stride))
-        return fail(VR_ERR_INVALID, "vr_render: band_flip %d needs a band set with |flip| < stride (%d)", t->band_flip,
-                    t->band_stride);
-    if (t->reserved != 0) return fail(VR_ERR_INVALID, "vr_render: vr_target.reserved must be 0");
-
-    if (c->inject_throw) {
-        const int k = c->inject_throw;
-        c->inject_throw = 0;
-        if (k == 2) throw std::bad_alloc();
-        throw std::runtime_error("injected by vr option inject_throw");
-    }
-    // an unchanged grid frame on this stream and target: launch the cached arguments
-    const hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (!c->proc.enabled && c->launch_cache && !c->mm_pending && !c->rg_pending && !(c->cap && c->cap->mode == 2)) {
-        for (const Ctx::Cached& e : c->lc)
-            if (e.valid && e.gen == c->gen && e.stream == hs && std::memcmp(&e.t, t, sizeof *t) == 0) {
-                HIP_TRY(hipSetDevice(c->device));
-                ++c->renders_since_build;
-                ++c->lc_hits;
-                if (c->cap) {   // vr_render_pair launches it
-                    *c->cap = Ctx::PairCapture{1, true, e.a, e.pl, e.sc, e.kind, e.slot};
-                    c->region_slot = e.slot;
-                    return VR_OK;
-                }
-                HIP_TRY(launch_march(e.a, e.pl.layout, e.pl.wrap, e.pl.early, e.sc, hs));
-                if (e.kind != SCHED_REGIONS) return VR_OK;
-                c->region_slot = e.slot;
-                return note_region_render(c, hs);
-            }
-    }
-    MarchArgs a{};
-    if (!frame_args(c, t->width, t->height, &a)) return fail(VR_ERR_INVALID, "vr_render: Projection*View is singular");
-    const vr_march_params& m = c->march;
-    if (c->proc.enabled) {
-        ProcParams& q = a.proc;
-        proc_args(c, &a);
-        if (q.wt_fixed && q.wt_n > 0 && c->lattice && c->schedule != SCHED_STATIC && c->schedule != SCHED_RINGS) {
-            const vr_status st = ensure_lattice(c, &q, static_cast<hipStream_t>(stream));
-            if (st != VR_OK) return st;
-        }
-    }
-    Plan pl{LAYOUT_PLANAR, WRAP_CLAMP, false};
-    if (!c->proc.enabled) make_plan(c, &a, &pl);
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    if (!c->proc.enabled && c->uniform_skip) {
-        const vr_status us = resolve_uniform(c);
-        if (us != VR_OK) return us;
-        a.umask = c->uniform_mask;
-        for (int ch = 0; ch < 4; ++ch) a.uval[ch] = (float)c->uniform_val[ch] * (1.0f / 255.0f);   // blend()'s scale
-    }
-    volume_args(c, pl, &a);
-    a.width = t->width;
-    a.height = t->height;
-    if (row_range) {
-        // rows [first, first + n) = the 8-row bands from first / 8 on, cut at n
-        // rows: the kernels' band-row mapping as it is
-        a.band_rows = 8; a.band_stride = 1; a.band_first = t->band_first / 8;
-    } else if (t->band_rows > 0) {
-        a.band_rows = t->band_rows; a.band_stride = t->band_stride; a.band_first = t->band_first;
-        a.band_flip = t->band_flip;
-    } else {
-        a.band_rows = t->height; a.band_stride = 1; a.band_first = 0;
-    }
-    a.out_rows = band_rows_packed(t->height, a.band_rows, a.band_stride, a.band_first, a.band_flip);
-    if (row_range) a.out_rows = std::min(a.out_rows, t->band_rows);
-    a.tiles_x = (t->width + 15) / 16;
-    a.tiles_y = (a.out_rows + 15) / 16;
-    a.num_blocks = 8 * ((a.tiles_y + 7) / 8) * a.tiles_x;
-    a.out = t->pixels;
-    a.pitch = (long long)pitch;
-    a.format = tfmt;
-    a.bands_in_place = in_place && (t->band_rows > 0 || row_range) ? 1 : 0;
-    a.empty_fill = 0;   // set with the schedule (regions, default kernels)
-    a.step_counter = reinterpret_cast<unsigned long long*>(t->step_counter);
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->proc.enabled) {
-        // schedule 0 = one 8x8 tile per wave in row order, 4 = in rings;
-        // otherwise (auto) the cost-sorted schedule
-        void* sort_buf = nullptr;
-        Schedule sc{c->schedule == SCHED_RINGS ? SCHED_RINGS : SCHED_STATIC, 0, 0, 1, 1, nullptr, nullptr, {}, 1, 0, 4, nullptr};
-        if (sc.kind == SCHED_RINGS) box_centre_pixel(c, a, &sc.center_x, &sc.center_y);
-        // the sort passes enumerate whole 64x64 regions (vr_march_kernels.h sort_pixel)
-        if (c->schedule != SCHED_STATIC && c->schedule != SCHED_RINGS && a.width < 65536 && a.out_rows < 65536 &&
-            (long long)((a.width + 63) / 64) * ((a.out_rows + 63) / 64) * 4096 < (1ll << 31)) {
-            const size_t need = sort_layout(a.width, a.out_rows).bytes;
-            if (need > c->sort_bytes) {
-                // the old buffer may still be read by queued work on another stream
-                HIP_TRY(hipDeviceSynchronize());
-                if (c->d_sort) (void)hipFree(c->d_sort);
-                c->d_sort = nullptr;
-                c->sort_bytes = 0;
-                c->sort_key.clear();
-                if (hipMalloc(&c->d_sort, need) != hipSuccess) return fail(VR_ERR_OOM, "vr_render: sort buffer");
-                HIP_TRY(hipMemset(c->d_sort, 0, need));   // the histogram starts at zero (proc_scan re-zeroes it)
-                c->sort_bytes = need;
-            }
-            sort_buf = c->d_sort;
-        }
-        // The sorted order depends only on each pixel's step count n (a3),
-        // i.e. on the frame geometry below, not on the medium: a frame with
-        // the same geometry reuses it (like the region lists of the grid path)
-        int reuse = SORT_BUILD;
-        std::vector<float> key;
-        if (sort_buf) {
-            key = {(float)a.width, (float)a.height, (float)a.out_rows, (float)a.band_rows, (float)a.band_stride,
-                   (float)a.band_first, (float)a.max_steps, a.step_size, (float)a.cam_mode,
-                   (float)(a.proc.shadow_steps > 0), (float)a.proc.enum_regions, (float)a.band_flip};
-            for (const float* v : {a.org, a.o, a.px, a.py, a.cam, a.box_min, a.box_max, a.box_range})
-                key.insert(key.end(), v, v + 3);
-            key.insert(key.end(), a.r2, a.r2 + 4);
-            key.insert(key.end(), a.r3, a.r3 + 4);
-            const bool same_size = key.size() == c->sort_key.size();
-            if (same_size && std::memcmp(key.data(), c->sort_key.data(), key.size() * sizeof(float)) == 0)
-                reuse = SORT_REUSE;
-            else if (same_size && c->renders_since_sort < c->sort_reuse &&
-                     std::memcmp(key.data(), c->sort_key.data(), kSortKeyGridPart * sizeof(float)) == 0)
-                reuse = SORT_STALE;
-        }
-        ShadowDefer defer{};
-        bool use_defer = sort_buf && c->shadow_defer && a.proc.shadow_steps > 0 && a.proc.wt_fixed &&
-                         a.proc.wt_n > 0;
-        // a stale order's keys do not bound the new step counts: no deferred ranges
-        if (reuse == SORT_STALE) use_defer = false;
-        bool defer_shared = false;
-        if (use_defer) {
-            const vr_status st = ensure_defer(c, a, sort_buf, static_cast<hipStream_t>(stream), &defer, &use_defer,
-                                              &defer_shared);
-            if (st != VR_OK) return st;
-        }
-        std::vector<float> built = reuse == SORT_BUILD ? key : c->sort_key;
-        c->sort_key.clear();   // valid again only once this launch is queued
-        const bool report = use_defer && reuse == SORT_BUILD;   // proc_scan writes the frame's need
-        const hipStream_t ps = static_cast<hipStream_t>(stream);
-        constexpr size_t kMaxProcStreams = 8;
-        bool known = false;
-        for (const auto& u : c->proc_uses) known = known || u.s == ps;
-        // a ninth stream is treated as a writer: it waits for every render.
-        // A deferred frame that reuses the order writes only its stream's
-        // scratch set: a reader of the shared sort scratch (round 6)
-        const bool writes = reuse == SORT_BUILD || (use_defer && defer_shared) ||
-                            (!known && c->proc_uses.size() >= kMaxProcStreams);
-        if (writes) {
-            for (const auto& u : c->proc_uses)
-                if (u.s != ps) {
-                    const vr_status sw = stream_wait_pending(ps, u.ev);
-                    if (sw != VR_OK) return sw;
-                }
-        } else if (c->proc_wpending && c->proc_wstream != ps) {
-            const vr_status sw = stream_wait_pending(ps, c->proc_wev);
-            if (sw != VR_OK) return sw;
-        }
-        // a scratch this frame outgrew: free once every earlier frame that used
-        // it has run -- after the waits above if it writes (this stream then
-        // follows every earlier procedural render), else on its own stream,
-        // the only one that used its set
-        for (auto& q : c->defer_retired)
-            if (!q.ev) {
-                HIP_TRY(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
-                HIP_TRY(hipEventRecord(q.ev, static_cast<hipStream_t>(stream)));
-            }
-        HIP_TRY(launch_march_procedural(a, m.early_out > 0.0f, sort_buf, reuse, sc, static_cast<hipStream_t>(stream),
-                                        use_defer ? &defer : nullptr, report ? c->d_need : nullptr));
-        Ctx::ProcUse* mine = nullptr;
-        for (auto& u : c->proc_uses)
-            if (u.s == ps) mine = &u;
-        if (!mine) {
-            if (c->proc_uses.size() >= kMaxProcStreams) {   // (this render waited for all of them)
-                for (auto& u : c->proc_uses) (void)hipEventDestroy(u.ev);
-                c->proc_uses.clear();
-            }
-            Ctx::ProcUse u{ps, nullptr};
-            HIP_TRY(hipEventCreateWithFlags(&u.ev, hipEventDisableTiming));
-            c->proc_uses.push_back(u);
-            mine = &c->proc_uses.back();
-        }
-        HIP_TRY(hipEventRecord(mine->ev, ps));
-        if (writes) {
-            if (!c->proc_wev) HIP_TRY(hipEventCreateWithFlags(&c->proc_wev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(c->proc_wev, ps));
-            c->proc_wstream = ps;
-            c->proc_wpending = true;
-        }
-        if (report) {
-            HIP_TRY(hipEventRecord(c->need_ev, static_cast<hipStream_t>(stream)));
-            c->need_pending = true;
-            c->need_pixsteps = (double)a.width * (double)a.out_rows * (double)std::max(a.max_steps, 1);
-            c->need_wavesteps = (double)sort_layout(a.width, a.out_rows).waves * (double)std::max(a.max_steps, 1);
-        }
-        c->defer_last = use_defer ? 1 : 0;
-        c->sort_key = std::move(built);
-        c->renders_since_sort = reuse == SORT_STALE ? c->renders_since_sort + 1 : 0;
-        return VR_OK;
-    }
-    // auto schedule (measured): regions -- per-XCD angular
-    // wedges of the frame, each walked inside-out (longest rays first)
-    const int kind = c->schedule >= 0 ? c->schedule : SCHED_REGIONS;
-    // tiles per wave, auto: rings 2; regions 3 for COL48 (the streamed 512^3
-    // layout: 0.1216 -> 0.1176 ms with 8 wedges, profiles/r04/r04_tpw_c5.txt)
-    // and 2 for the others (config 4 level); strided 1
-    const int tpw = c->tiles_per_wave > 0 ? c->tiles_per_wave
-                    : kind == SCHED_REGIONS ? (pl.layout == LAYOUT_COL48 ? 3 : 2)
-                    : kind == SCHED_RINGS ? 2 : 1;
-    Schedule sc{kind, 0, 0, tpw, c->waves_per_simd, c->d_heads, nullptr, {}, 1, 0, c->wg_waves, nullptr};
-    sc.slab = pl.layout == LAYOUT_COL48 && c->slab;
-    a.slab_cap = c->slab_cap;
-    if (kind == SCHED_RINGS || kind == SCHED_REGIONS) box_centre_pixel(c, a, &sc.center_x, &sc.center_y);
-    if (c->cap && c->cap->mode == 2) {   // a pair's second frame: arguments and plan only
-        *c->cap = Ctx::PairCapture{2, true, a, pl, sc, kind, -1};
-        return VR_OK;
-    }
-    if (kind == SCHED_REGIONS) {
-        const bool splittable = is_b4_family(pl.layout) || pl.layout == LAYOUT_ZPAIR || pl.layout == LAYOUT_CORNER8 ||
-                                pl.layout == LAYOUT_CORNERH || pl.layout == LAYOUT_COL48Z;
-        const vr_status st = build_regions(c, a, tpw, sc.center_x, sc.center_y, static_cast<hipStream_t>(stream));
-        if (st != VR_OK) return st;
-        const Ctx::RegionBuf& rb = c->region[c->region_cur];
-        sc.tiles = rb.d + kRegionHeader;
-        sc.hdr = reinterpret_cast<const int*>(rb.d);
-        sc.map = rb.map;
-        // the default kernels march the lists' first hdr[kRegionWork + x] entries
-        // and fill the rest (tile_is_empty); the slab march marches all
-        const bool fill = c->empty_fill && c->region_exact && !sc.slab;
-        a.empty_fill = fill ? 1 : 0;
-        // Waves: as many as before (the list over tiles_per_wave), but no more
-        // than marched entries -- the waves that held only empty tiles go;
-        // each marched tile keeps a wave of its own where it had one
-        if (fill && rb.most_marched > 0) sc.map.nwx = std::max(1, std::min(sc.map.nwx, rb.most_marched));
-        if (splittable) {
-            // step-split rays: K lanes per ray when the frame
-            // share is too small to fill the GPU with one-lane-per-ray waves
-            int K = c->split;
-            if (sc.slab) K = K == 0 ? 1 : K;   // the slab march has one lane per ray; split > 1 uses the plain march
-            if (K == 0) K = auto_split(c, rb.nwork);
-            if (K > 1) {
-                const int ktpw = tpw;
-                const int most = rb.most;
-                sc.split = K;
-                sc.map.nwx = std::max(1, (most * K + ktpw - 1) / ktpw);
-                if (a.empty_fill && rb.most_marched > 0)   // (as above, in split units)
-                    sc.map.nwx = std::max(1, std::min(sc.map.nwx, rb.most_marched * K));
-            }
-        }
-    }
-    if (c->cap) {   // vr_render_pair launches it (alone through finish_render, or paired)
-        *c->cap = Ctx::PairCapture{1, true, a, pl, sc, kind, c->region_slot};
-        return VR_OK;
-    }
-    HIP_TRY(launch_march(a, pl.layout, pl.wrap, pl.early, sc, hs));
-    if (c->launch_cache) {   // remember it
-        Ctx::Cached& e = c->lc[c->lc_next];
-        c->lc_next = (c->lc_next + 1) % (int)(sizeof c->lc / sizeof c->lc[0]);
-        e.valid = true;
-        e.gen = c->gen;
-        e.t = *t;
-        e.stream = hs;
-        e.a = a;
-        e.pl = pl;
-        e.sc = sc;
-        e.kind = kind;
-        e.slot = c->region_slot;
-    }
-    if (kind == SCHED_REGIONS) return note_region_render(c, hs);
-    return VR_OK;
-} catch (...) {
-    return caught_exception("vr_render");
-}
-
-vr_status vr_render_sequence(void* p, const vr_target* t, int frames, const vr_object_shader_data* osd,
-                             const vr_global_shader_data* gsd, void* stream)
-try {
-    if (!p || !t || frames < 0 || (frames > 0 && (!osd || !gsd)))
-        return fail(VR_ERR_INVALID, "vr_render_sequence: bad argument");
-    for (int i = 0; i < frames; ++i) {
-        vr_status st = vr_set_shader_data(p, &osd[i], &gsd[i]);
-        if (st == VR_OK) st = vr_render(p, t, stream);
-        if (st != VR_OK) return st;
-    }
-    return VR_OK;
-} catch (...) {
-    return caught_exception("vr_render_sequence");
-}
-
-}   // extern "C"
-
-namespace {
-
-// A frame vr_render planned but did not launch (Ctx::PairCapture, mode 1): launch it alone,
-// with vr_render's own bookkeeping.
-vr_status finish_render(Ctx* c, const Ctx::PairCapture& f, const vr_target* t, hipStream_t hs, unsigned long long gen)
-{
-    HIP_TRY(launch_march(f.a, f.pl.layout, f.pl.wrap, f.pl.early, f.sc, hs));
-    bool cached = false;   // the plan may have come from the launch cache: no second entry for it
-    for (const Ctx::Cached& e : c->lc)
-        cached = cached || (e.valid && e.gen == gen && e.stream == hs && std::memcmp(&e.t, t, sizeof *t) == 0);
-    if (c->launch_cache && !cached) {
-        Ctx::Cached& e = c->lc[c->lc_next];
-        c->lc_next = (c->lc_next + 1) % (int)(sizeof c->lc / sizeof c->lc[0]);
-        e.valid = true;
-        e.gen = gen;   // the context's when the frame was planned
-        e.t = *t;
-        e.stream = hs;
-        e.a = f.a;
-        e.pl = f.pl;
-        e.sc = f.sc;
-        e.kind = f.kind;
-        e.slot = f.slot;
-    }
-    if (f.kind == SCHED_REGIONS) return note_region_render(c, hs);
-    return VR_OK;
-}
-
-// The second frame's arguments may differ from the first's only in what the paired kernel
-// reads per frame: the camera (ray basis, r2 / r3, cam, tap_T), the target buffer, the
-// empty-tile fill and the step counter.
-bool pair_compatible(const Ctx::PairCapture& f0, const Ctx::PairCapture& f1)
-{
-    if (f0.pl.layout != f1.pl.layout || f0.pl.wrap != f1.pl.wrap || f0.pl.early != f1.pl.early) return false;
-    const MarchArgs &a = f0.a, &b = f1.a;
-    // the shared part, field by field (the structs' padding is not compared)
-#define VR_SAME(F) (std::memcmp(&a.F, &b.F, sizeof a.F) == 0)
-    return VR_SAME(box_min) && VR_SAME(box_max) && VR_SAME(box_range) && VR_SAME(step_size) && VR_SAME(density) &&
-           VR_SAME(scale) && VR_SAME(acc_limit) && VR_SAME(max_steps) && VR_SAME(tap_S) && VR_SAME(zero_offsets) &&
-           VR_SAME(umask) && VR_SAME(uval) && VR_SAME(nx) && VR_SAME(ny) && VR_SAME(nz) && VR_SAME(vol) &&
-           VR_SAME(plane_stride) && VR_SAME(geom.B) && VR_SAME(geom.R) && VR_SAME(geom.Ba) && VR_SAME(geom.Rn) &&
-           VR_SAME(geom.brick) && VR_SAME(geom.nbx) && VR_SAME(geom.nby) && VR_SAME(geom.nbz) && VR_SAME(width) &&
-           VR_SAME(height) && VR_SAME(band_rows) && VR_SAME(band_stride) && VR_SAME(band_first) && VR_SAME(out_rows) &&
-           VR_SAME(band_flip) && VR_SAME(pitch) && VR_SAME(format) && VR_SAME(bands_in_place) && VR_SAME(slab_cap);
-#undef VR_SAME
-}
-
-// The region lists' empty tiles (built for frame 0's camera) are frame 1's too: the part
-// of build_regions' key that the camera sets is the same
-bool same_region_camera(const Ctx::PairCapture& f0, const Ctx::PairCapture& f1)
-{
-    const MarchArgs &a = f0.a, &b = f1.a;
-    return f0.sc.center_x == f1.sc.center_x && f0.sc.center_y == f1.sc.center_y &&
-           std::memcmp(a.org, b.org, sizeof a.org) == 0 && std::memcmp(a.o, b.o, sizeof a.o) == 0 &&
-           std::memcmp(a.px, b.px, sizeof a.px) == 0 && std::memcmp(a.py, b.py, sizeof a.py) == 0 &&
-           std::memcmp(a.r3, b.r3, sizeof a.r3) == 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-vr_status vr_render_pair(void* p, const vr_target* t0, const vr_target* t1, const vr_object_shader_data* osd,
-                         const vr_global_shader_data* gsd, void* stream)
-try {
-    if (!p || !t0 || !t1 || (!osd) != (!gsd)) return fail(VR_ERR_INVALID, "vr_render_pair: bad argument");
-    // field by field: the structs' padding is the caller's
-    if (t0->width != t1->width || t0->height != t1->height || t0->format != t1->format || t0->band_rows != t1->band_rows ||
-        t0->band_stride != t1->band_stride || t0->band_first != t1->band_first || t0->row_pitch != t1->row_pitch ||
-        t0->step_counter != t1->step_counter || t0->band_flip != t1->band_flip || t0->reserved != t1->reserved)
-        return fail(VR_ERR_INVALID, "vr_render_pair: the two targets must agree in everything but pixels");
-    {
-        const int f = t0->format & ~(VR_TARGET_BANDS_IN_PLACE | VR_TARGET_ROW_RANGE);
-        if (!t1->pixels || (f >= 0 && f <= 5 && (uintptr_t)t1->pixels % format_bytes(f) != 0))
-            return fail(VR_ERR_INVALID, "vr_render_pair: the second target's pixels are null or misaligned");
-    }
-    Ctx* c = as_ctx(p);
-    const hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (osd) {
-        const vr_status st = vr_set_shader_data(p, &osd[0], &gsd[0]);
-        if (st != VR_OK) return st;
-    }
-    // frame 0: vr_render's whole path (checks, plan, region lists) up to the launch
-    Ctx::PairCapture f0{};
-    f0.mode = 1;
-    c->cap = &f0;
-    vr_status st = vr_render(p, t0, stream);
-    c->cap = nullptr;
-    if (st != VR_OK) return st;
-    const unsigned long long gen0 = c->gen;
-    const bool pairable = f0.got && f0.kind == SCHED_REGIONS && f0.sc.split <= 1 && !f0.sc.slab && f0.sc.wg_waves == 4 &&
-                          pair_layout(f0.pl.layout) && f0.pl.wrap == WRAP_CLAMP;
-    Ctx::PairCapture f1{};
-    bool paired = false;
-    if (pairable) {
-        if (osd) st = vr_set_shader_data(p, &osd[1], &gsd[1]);
-        if (st == VR_OK) {
-            f1.mode = 2;
-            c->cap = &f1;
-            st = vr_render(p, t1, stream);
-            c->cap = nullptr;
-        }
-        if (st != VR_OK) {   // frame 0 is planned and counted: it still renders
-            (void)finish_render(c, f0, t0, hs, gen0);
-            return st;
-        }
-        paired = f1.got && f1.kind == f0.kind && pair_compatible(f0, f1);
-    }
-    if (!paired) {
-        // no paired kernel for this plan (a procedural medium, split rays, the slab, an
-        // experiment schedule, a layout without an instance, frames whose plans differ):
-        // the two ordinary renders
-        if (f0.got) {
-            st = finish_render(c, f0, t0, hs, gen0);
-            if (st != VR_OK) return st;
-        }
-        if (osd && !pairable) {
-            st = vr_set_shader_data(p, &osd[1], &gsd[1]);
-            if (st != VR_OK) return st;
-        }
-        return vr_render(p, t1, stream);
-    }
-    // frame 1 fills the lists' empty tiles only where they are its own (vr_render's
-    // region_exact rule); a frame that marches every entry keeps the unreduced wave count
-    const Ctx::RegionBuf& rb = c->region[c->region_cur];
-    f1.a.empty_fill = f0.a.empty_fill && same_region_camera(f0, f1) ? 1 : 0;
-    Schedule sc = f0.sc;
-    if (f0.a.empty_fill && !f1.a.empty_fill) sc.map.nwx = std::max(1, rb.map.nwx);
-    HIP_TRY(launch_march_pair(f0.a, f1.a, f0.pl.layout, f0.pl.early, sc, c->pair_deal, hs));
-    ++c->pair_launches;
-    ++c->renders_since_build;   // the second render with these lists (build_regions counted the first)
-    c->region_slot = f0.slot;
-    return note_region_render(c, hs);
-} catch (...) {
-    if (p) as_ctx(p)->cap = nullptr;
-    return caught_exception("vr_render_pair");
-}
-
 vr_status vr_assemble_frame(void* p, const void* d_gathered, int gathered_format, size_t rows_per_rank, int nranks,
                             int width, int height, int band_rows, int frame_format, void* d_frame, void* stream)
 try {
@@ -1283,20 +843,6 @@ try {
     if (gathered_format != frame_format && grey_of(frame_format) != gathered_format)
         return fail(VR_ERR_INVALID, "vr_assemble_frame: format %d does not expand into %d", gathered_format,
                     frame_format);
-    if (gathered_format == frame_format) {
-        const int bpp = format_bytes(frame_format);
-        if (nranks <= 0 || width <= 0 || height <= 0 || band_rows <= 0)
-            return fail(VR_ERR_INVALID, "vr_assemble_frame: bad geometry");
-        for (int r = first_rank; r < nranks; ++r)
-            if ((size_t)band_rows_packed(height, band_rows, nranks, r, serp ? nranks - 1 - 2 * r : 0) > rows_per_rank)
-                return fail(VR_ERR_INVALID, "vr_assemble_frame: rows_per_rank %zu too small for rank %d", rows_per_rank, r);
-        Ctx* c = as_ctx(p);
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(launch_assemble(static_cast<const uint8_t*>(d_gathered), rows_per_rank, nranks, width, height,
-                                band_rows, bpp, first_rank, static_cast<uint8_t*>(d_frame),
-                                static_cast<hipStream_t>(stream), serp));
-        return VR_OK;
-    }
     if (nranks <= 0 || width <= 0 || height <= 0 || band_rows <= 0)
         return fail(VR_ERR_INVALID, "vr_assemble_frame: bad geometry");
     for (int r = first_rank; r < nranks; ++r)
@@ -1304,6 +850,12 @@ try {
             return fail(VR_ERR_INVALID, "vr_assemble_frame: rows_per_rank %zu too small for rank %d", rows_per_rank, r);
     Ctx* c = as_ctx(p);
     HIP_TRY(hipSetDevice(c->device));
+    if (gathered_format == frame_format) {
+        HIP_TRY(launch_assemble(static_cast<const uint8_t*>(d_gathered), rows_per_rank, nranks, width, height,
+                                band_rows, format_bytes(frame_format), first_rank, static_cast<uint8_t*>(d_frame),
+                                static_cast<hipStream_t>(stream), serp));
+        return VR_OK;
+    }
     HIP_TRY(launch_assemble_grey(static_cast<const uint8_t*>(d_gathered), rows_per_rank, nranks, width, height,
                                  band_rows, frame_format == VR_FMT_RGBA32F, first_rank, static_cast<uint8_t*>(d_frame),
                                  static_cast<hipStream_t>(stream), serp));

@@ -1,6 +1,7 @@
 // vr_ctx.h -- the library context (Ctx) and the host helpers shared by the
-// translation units of the C ABI: vr_api.cpp (context, volume, render,
-// assembly), vr_options.cpp (vr_set_option / vr_get_option / the kernel
+// translation units of the C ABI: vr_api.cpp (context, volume, assembly),
+// vr_render.cpp (vr_render, vr_render_sequence, vr_render_pair: target checks,
+// launch cache, frame planning), vr_options.cpp (vr_set_option / vr_get_option / the kernel
 // variant), vr_regions_host.cpp (region lists, row partition) and
 // vr_proc_host.cpp (procedural medium scratch and tables); vr_rect.cpp (the
 // scissored render and the context's footprint call).  Internal: not
@@ -78,6 +79,16 @@ constexpr long long kSplitOneLaneOverlap = 2500;
 struct Plan {
     int layout, wrap;
     bool early;
+};
+
+// A planned grid frame: what launch_march takes.  grid_frame_args fills it,
+// attach_regions adds the region lists; the launch cache keeps it.
+struct GridFrame {
+    MarchArgs a{};
+    Plan pl{};
+    Schedule sc{};
+    int kind = 0;
+    int slot = -1;   // the stream's slot in the region lists (note_region_render)
 };
 
 struct Ctx {
@@ -251,29 +262,10 @@ struct Ctx {
         unsigned long long gen = 0;
         vr_target t{};
         hipStream_t stream = nullptr;
-        MarchArgs a{};
-        Plan pl{};
-        Schedule sc{};
-        int kind = 0;
-        int slot = -1;   // the stream's slot in the region lists (note_region_render)
+        GridFrame f;
     } lc[4];
     int lc_next = 0;
     long long lc_hits = 0;         // read-only option "launch_cache_hits"
-    // vr_render_pair: while `cap` is set, vr_render plans a grid frame without launching it.
-    // mode 1 = the whole path (region lists included), the launch left to the caller;
-    // mode 2 = the frame's arguments and plan only (the pair's second frame: the lists are
-    // the first frame's).  got stays false where vr_render ran the frame itself (a
-    // procedural medium).
-    struct PairCapture {
-        int mode = 0;
-        bool got = false;
-        MarchArgs a{};
-        Plan pl{};
-        Schedule sc{};
-        int kind = 0;
-        int slot = -1;
-    };
-    PairCapture* cap = nullptr;
     int pair_deal = 0;             // option "pair_deal": 0 = the frame in the wave's parity, 1 = in the workgroup's
     int frame_pairing = 2;         // option "frame_pairing": vr_shard_run_frames takes a one-rank grid pipeline's frames
                                    // two at a time (0 off, 1 pairs on one render stream, 2 alternating over two)
@@ -303,6 +295,23 @@ void proc_args(const Ctx* c, MarchArgs* a);
 void volume_args(const Ctx* c, const Plan& pl, MarchArgs* a);
 const char* variant_name(const Plan& p);
 
+// ---- vr_render.cpp: what the whole-frame renders share with the scissored ones (vr_rect.cpp)
+// A checked target: the format without its VR_TARGET_* flags, the row pitch in bytes, the flags.
+struct TargetInfo {
+    int format;
+    size_t pitch;
+    bool in_place, row_range;
+};
+vr_status check_frame_state(const char* fn, const Ctx* c, const vr_target* t);   // volume, camera, frame size
+vr_status check_pixels(const char* fn, const vr_target* t, int format, size_t* pitch);   // non-null, pitch, alignment
+vr_status check_target(const char* fn, const Ctx* c, const vr_target* t, TargetInfo* ti);   // vr_render's checks, in its order
+// band fields, out_rows, tiles, num_blocks, out, pitch, format, bands_in_place, step_counter of a zeroed MarchArgs
+void target_geometry(const vr_target* t, const TargetInfo& ti, MarchArgs* a);
+void honour_inject_throw(Ctx* c);   // option inject_throw: consumed, then thrown
+// The whole frame's MarchArgs up to the schedule: ray basis and march constants, the procedural parameters or the
+// grid plan, volume buffers, target geometry; every channel loaded (umask 0).  *pl = layout, wrap, early-out variant.
+vr_status frame_march_args(const char* fn, Ctx* c, const vr_target* t, const TargetInfo& ti, MarchArgs* a, Plan* pl);
+
 // ---- vr_regions_host.cpp
 inline int wedges_of(const Ctx* c)
 {
@@ -322,5 +331,7 @@ vr_status ensure_lattice(Ctx* c, ProcParams* q, hipStream_t s);
 vr_status release_defer(Ctx* c);
 vr_status ensure_defer(Ctx* c, const MarchArgs& a, void* sort_buf, hipStream_t s, ShadowDefer* d, bool* ok, bool* shared);
 constexpr size_t kMaxDeferSets = 4;
+// the sort / deferred-shadow scratch, the stream order and the launch of a procedural frame
+vr_status render_procedural(Ctx* c, const MarchArgs& a, bool early, hipStream_t hs);
 
 }  // namespace vrapi

@@ -1,6 +1,7 @@
 // vr_proc_host.cpp -- the host side of the procedural medium (BASELINE configs
 // 2/3): its parameters (vr_procedural_defaults, vr_set_procedural), the Worley
-// table pitch, the Perlin lattice table and the deferred-shadow scratch.
+// table pitch, the Perlin lattice table, the deferred-shadow scratch and the
+// scratch and stream bookkeeping of a procedural render (render_procedural).
 #include "vr_ctx.h"
 
 namespace vrapi {
@@ -202,7 +203,7 @@ vr_status ensure_defer(Ctx* c, const MarchArgs& a, void* sort_buf, hipStream_t s
             if (!ds.d || L.waves > ds.waves) return VR_OK;
         } else {
             if (ds.d) {
-                c->defer_retired.push_back({ds.d, nullptr});   // its event: vr_render, before the launch
+                c->defer_retired.push_back({ds.d, nullptr});   // its event: render_procedural, before the launch
                 if (c->defer_retired.size() > kMaxDeferRetired) {   // rare: a device sync frees them
                     HIP_TRY(hipDeviceSynchronize());
                     for (const auto& q : c->defer_retired) {
@@ -243,6 +244,129 @@ vr_status ensure_defer(Ctx* c, const MarchArgs& a, void* sort_buf, hipStream_t s
     d->worley_cache = c->shadow_cache;
     d->eval_blocks = c->shadow_blocks ? (unsigned)c->shadow_blocks
                                       : (unsigned)std::max<size_t>(kShadowEvalBlocks, (size_t)L.waves * 3 / 8);
+    return VR_OK;
+}
+
+// A procedural frame from its MarchArgs to the launch: the cost-sort scratch
+// and its reuse, the deferred-shadow scratch, the order of this stream against
+// the other procedural renders (Ctx::ProcUse), the retired scratch events and
+// the frame's reported need.  Called by vr_render.
+vr_status render_procedural(Ctx* c, const MarchArgs& a, bool early, hipStream_t hs)
+{
+    // schedule 0 = one 8x8 tile per wave in row order, 4 = in rings;
+    // otherwise (auto) the cost-sorted schedule
+    void* sort_buf = nullptr;
+    Schedule sc{c->schedule == SCHED_RINGS ? SCHED_RINGS : SCHED_STATIC, 0, 0, 1, 1, nullptr, nullptr, {}, 1, 0, 4, nullptr};
+    if (sc.kind == SCHED_RINGS) box_centre_pixel(c, a, &sc.center_x, &sc.center_y);
+    // the sort passes enumerate whole 64x64 regions (vr_march_kernels.h sort_pixel)
+    if (c->schedule != SCHED_STATIC && c->schedule != SCHED_RINGS && a.width < 65536 && a.out_rows < 65536 &&
+        (long long)((a.width + 63) / 64) * ((a.out_rows + 63) / 64) * 4096 < (1ll << 31)) {
+        const size_t need = sort_layout(a.width, a.out_rows).bytes;
+        if (need > c->sort_bytes) {
+            // the old buffer may still be read by queued work on another stream
+            HIP_TRY(hipDeviceSynchronize());
+            if (c->d_sort) (void)hipFree(c->d_sort);
+            c->d_sort = nullptr;
+            c->sort_bytes = 0;
+            c->sort_key.clear();
+            if (hipMalloc(&c->d_sort, need) != hipSuccess) return fail(VR_ERR_OOM, "vr_render: sort buffer");
+            HIP_TRY(hipMemset(c->d_sort, 0, need));   // the histogram starts at zero (proc_scan re-zeroes it)
+            c->sort_bytes = need;
+        }
+        sort_buf = c->d_sort;
+    }
+    // The sorted order depends only on each pixel's step count n (a3),
+    // i.e. on the frame geometry below, not on the medium: a frame with
+    // the same geometry reuses it (like the region lists of the grid path)
+    int reuse = SORT_BUILD;
+    std::vector<float> key;
+    if (sort_buf) {
+        key = {(float)a.width, (float)a.height, (float)a.out_rows, (float)a.band_rows, (float)a.band_stride,
+               (float)a.band_first, (float)a.max_steps, a.step_size, (float)a.cam_mode,
+               (float)(a.proc.shadow_steps > 0), (float)a.proc.enum_regions, (float)a.band_flip};
+        for (const float* v : {a.org, a.o, a.px, a.py, a.cam, a.box_min, a.box_max, a.box_range})
+            key.insert(key.end(), v, v + 3);
+        key.insert(key.end(), a.r2, a.r2 + 4);
+        key.insert(key.end(), a.r3, a.r3 + 4);
+        const bool same_size = key.size() == c->sort_key.size();
+        if (same_size && std::memcmp(key.data(), c->sort_key.data(), key.size() * sizeof(float)) == 0)
+            reuse = SORT_REUSE;
+        else if (same_size && c->renders_since_sort < c->sort_reuse &&
+                 std::memcmp(key.data(), c->sort_key.data(), kSortKeyGridPart * sizeof(float)) == 0)
+            reuse = SORT_STALE;
+    }
+    ShadowDefer defer{};
+    bool use_defer = sort_buf && c->shadow_defer && a.proc.shadow_steps > 0 && a.proc.wt_fixed &&
+                     a.proc.wt_n > 0;
+    // a stale order's keys do not bound the new step counts: no deferred ranges
+    if (reuse == SORT_STALE) use_defer = false;
+    bool defer_shared = false;
+    if (use_defer) {
+        const vr_status st = ensure_defer(c, a, sort_buf, hs, &defer, &use_defer,
+                                          &defer_shared);
+        if (st != VR_OK) return st;
+    }
+    std::vector<float> built = reuse == SORT_BUILD ? key : c->sort_key;
+    c->sort_key.clear();   // valid again only once this launch is queued
+    const bool report = use_defer && reuse == SORT_BUILD;   // proc_scan writes the frame's need
+    constexpr size_t kMaxProcStreams = 8;
+    bool known = false;
+    for (const auto& u : c->proc_uses) known = known || u.s == hs;
+    // a ninth stream is treated as a writer: it waits for every render.
+    // A deferred frame that reuses the order writes only its stream's
+    // scratch set: a reader of the shared sort scratch (round 6)
+    const bool writes = reuse == SORT_BUILD || (use_defer && defer_shared) ||
+                        (!known && c->proc_uses.size() >= kMaxProcStreams);
+    if (writes) {
+        for (const auto& u : c->proc_uses)
+            if (u.s != hs) {
+                const vr_status sw = stream_wait_pending(hs, u.ev);
+                if (sw != VR_OK) return sw;
+            }
+    } else if (c->proc_wpending && c->proc_wstream != hs) {
+        const vr_status sw = stream_wait_pending(hs, c->proc_wev);
+        if (sw != VR_OK) return sw;
+    }
+    // a scratch this frame outgrew: free once every earlier frame that used
+    // it has run -- after the waits above if it writes (this stream then
+    // follows every earlier procedural render), else on its own stream,
+    // the only one that used its set
+    for (auto& q : c->defer_retired)
+        if (!q.ev) {
+            HIP_TRY(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(q.ev, hs));
+        }
+    HIP_TRY(launch_march_procedural(a, early, sort_buf, reuse, sc, hs,
+                                    use_defer ? &defer : nullptr, report ? c->d_need : nullptr));
+    Ctx::ProcUse* mine = nullptr;
+    for (auto& u : c->proc_uses)
+        if (u.s == hs) mine = &u;
+    if (!mine) {
+        if (c->proc_uses.size() >= kMaxProcStreams) {   // (this render waited for all of them)
+            for (auto& u : c->proc_uses) (void)hipEventDestroy(u.ev);
+            c->proc_uses.clear();
+        }
+        Ctx::ProcUse u{hs, nullptr};
+        HIP_TRY(hipEventCreateWithFlags(&u.ev, hipEventDisableTiming));
+        c->proc_uses.push_back(u);
+        mine = &c->proc_uses.back();
+    }
+    HIP_TRY(hipEventRecord(mine->ev, hs));
+    if (writes) {
+        if (!c->proc_wev) HIP_TRY(hipEventCreateWithFlags(&c->proc_wev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->proc_wev, hs));
+        c->proc_wstream = hs;
+        c->proc_wpending = true;
+    }
+    if (report) {
+        HIP_TRY(hipEventRecord(c->need_ev, hs));
+        c->need_pending = true;
+        c->need_pixsteps = (double)a.width * (double)a.out_rows * (double)std::max(a.max_steps, 1);
+        c->need_wavesteps = (double)sort_layout(a.width, a.out_rows).waves * (double)std::max(a.max_steps, 1);
+    }
+    c->defer_last = use_defer ? 1 : 0;
+    c->sort_key = std::move(built);
+    c->renders_since_sort = reuse == SORT_STALE ? c->renders_since_sort + 1 : 0;
     return VR_OK;
 }
 }  // namespace vrapi
