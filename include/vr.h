@@ -294,6 +294,35 @@ vr_status vr_render_sequence(void* ctx, const vr_target* target, int frames, con
  * allocates nor waits on the host.                                          */
 vr_status vr_render_pair(void* ctx, const vr_target* t0, const vr_target* t1, const vr_object_shader_data osd[2],
                          const vr_global_shader_data gsd[2], void* stream);
+/* n = 1..4 queued frames: frame i into `targets[i]` with shader data (osd[i],
+ * gsd[i]); osd and gsd both NULL = every frame with the ctx's current shader
+ * data.  The bytes in every target and the sum added to step_counter are
+ * those of vr_set_shader_data(i); vr_render(targets[i]) for i = 0..n-1 in
+ * order, and the ctx ends holding shader data n-1.  The targets must agree in
+ * every field but `pixels` (VR_ERR_INVALID otherwise, nothing written).
+ * Four frames that vr_render_pair would pair (a grid medium, the regions
+ * schedule with one lane per ray, the COL48, BRICK4832 and CORNERH layouts,
+ * frames that select one kernel) are marched by ONE kernel over frame 0's
+ * region lists: a workgroup is one list entry x four frames, so the four
+ * readers of a brick share one L1.  n = 3 is a pair
+ * (vr_render_pair's path) and a plain render, n = 2 vr_render_pair's path,
+ * n = 1 vr_render's.  Fallbacks: whatever vr_render_pair issues as ordinary
+ * renders -- a procedural medium, split rays, option slab, another schedule
+ * or layout, the planar layout with mirrored repeat, frames whose MediaScroll
+ * offsets select different kernels -- is issued here as n ordinary renders, in
+ * order: four frames that do not all share one plan do not degrade to pairs,
+ * even where two of them would pair with each other.  Frame 0 is planned as vr_render plans it and its errors read as
+ * vr_render's; a frame k that fails to plan leaves frames 0..k-1 rendered and
+ * returns its error.  Asynchronous on `stream`; steady state neither
+ * allocates nor waits on the host.                                          */
+#define VR_MAX_GROUP 4
+vr_status vr_render_group(void* ctx, const vr_target* targets, int n, const vr_object_shader_data* osd,
+                          const vr_global_shader_data* gsd, void* stream);
+/* How vr_render_group (and the native frame loop, vr_shard.h) issues n = 1..4
+ * frames: the frames per launch, in order, into launches[0..] (the rest 0) --
+ * 4 -> {4}, 3 -> {2, 1}, 2 -> {2}, 1 -> {1}.  Returns the number of launches,
+ * 0 for any other n.  Host arithmetic only.                                 */
+int vr_group_split(int n, int launches[3]);
 
 /* ---- the scissor: replaces vkCmdSetScissor with a VkRect2D, a dynamic state
  *      of the reference's pipeline (TestMain.cpp:192, 204-205, where it is

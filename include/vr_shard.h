@@ -148,6 +148,22 @@ vr_status vr_shard_set_timeout(vr_shard* sh, double seconds);
  * ignore the option: one launch per frame.  A run after the option changed
  * first waits (host) for the frames in flight.
  *
+ * Frames per launch where pairing is on (the ctx's option "frame_group", read
+ * at every run): 2 = the pairs above; 4 (the default, measured: DESIGN.md
+ * sec. 5.1.8) = a one-rank communicator takes its frames FOUR at a time, each four in one launch
+ * (vr.h vr_render_group: a workgroup marches one list entry for four frames),
+ * and the remainder of a run as a pair and / or a single frame.  Under
+ * "frame_pairing" 1 the launches follow each other on one render stream with
+ * buffer sets 0..3; under 2 they alternate over two render streams, stream q
+ * with sets 4q..4q + 3 -- eight sets, the second four allocated by the first
+ * run of that mode.  Everything said of pairs holds: frame i renders with
+ * (osd[i], gsd[i]), a static camera renders every frame, vr_shard_frame is the
+ * last frame, a sampled launch is bracketed by one event pair (kernel_ms is
+ * then the mean duration of a launch of up to four frames), and a run after
+ * the option changed first waits (host) for the frames in flight.  A solo
+ * rehearsal keeps its pairs; multi-rank pipelines, loopback ranks and
+ * procedural media ignore the option.
+ *
  * Render streams of vr_shard_run, 1 to 4: n >= 2 = frame i renders on stream
  * i mod n of the shard with buffer set i mod n, so n consecutive frames are in
  * flight and their renders overlap (with the exchange on the render streams;

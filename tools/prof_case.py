@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--slab-cap", type=int, default=-1)
     ap.add_argument("--opt", action="append", default=[], help="vr option NAME=VALUE")
     ap.add_argument("--pair", action="store_true", help="frames two at a time, each pair one launch (vr_render_pair)")
+    ap.add_argument("--group", action="store_true", help="frames four at a time, each four one launch (vr_render_group)")
     a = ap.parse_args()
     with vr.Renderer(0) as r:
         if a.proc:
@@ -61,13 +62,17 @@ def main():
         r.set_march(vr.march_defaults(max_steps=a.steps))
         out = r.alloc_target(a.width, a.height, vr.FMT_RGBA8_UNORM)
         out1 = r.alloc_target(a.width, a.height, vr.FMT_RGBA8_UNORM) if a.pair else None
-        for _ in range(a.frames // 2 if a.pair else a.frames):
-            if a.pair:
+        outs = [out] + [r.alloc_target(a.width, a.height, vr.FMT_RGBA8_UNORM) for _ in range(3)] if a.group else None
+        for _ in range(a.frames // 4 if a.group else a.frames // 2 if a.pair else a.frames):
+            if a.group:
+                r.render_group(a.width, a.height, vr.FMT_RGBA8_UNORM, outs)
+            elif a.pair:
                 r.render_pair(a.width, a.height, vr.FMT_RGBA8_UNORM, out, out1)
             else:
                 r.render(a.width, a.height, vr.FMT_RGBA8_UNORM, out=out)
         torch.cuda.synchronize()
-        print("variant", r.kernel_variant, "schedule", r.get_option("schedule"), "pair_launches", r.get_option("pair_launches"))
+        print("variant", r.kernel_variant, "schedule", r.get_option("schedule"), "pair_launches", r.get_option("pair_launches"),
+              "group_launches", r.get_option("group_launches"))
 
 
 if __name__ == "__main__":

@@ -9,7 +9,7 @@ roofline of the bench line (bench.py).
 
 A fourth argument F (default 1) = frames per march launch: 2 for a run of
 tools/prof_case.py --pair, whose launches each march two frames
-(vr_render_pair, the native frame loop's default).  Bytes and lookups are then
+(vr_render_pair, the native frame loop's default), 4 for --group (vr_render_group).  Bytes and lookups are then
 written PER FRAME (the launch's / F), which is what bench.py divides by its
 time per frame.
 """
@@ -36,7 +36,8 @@ res = {"config": config, "kernel": kernel, "hbm_bytes_per_launch": round(fetch +
                  "(20 launches, mean per march launch); FETCH_SIZE x2 per the gfx950 correction"}
 if frames > 1:
     res["frames_per_launch"] = frames
-    res["method"] += (f"; prof_case.py --pair: every launch marches {frames} frames (vr_render_pair), bytes and lookups "
+    how = "--group" if frames == 4 else "--pair"
+    res["method"] += (f"; prof_case.py {how}: every launch marches {frames} frames, bytes and lookups "
                       f"are the launch's / {frames} = per frame, raw counters per launch")
 if "TCP_TOTAL_CACHE_ACCESSES_sum" in c:
     res["l1_lookups_per_launch"] = round(c["TCP_TOTAL_CACHE_ACCESSES_sum"] / frames)

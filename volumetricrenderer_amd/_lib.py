@@ -140,6 +140,9 @@ _SIGS = {
                                           ctypes.POINTER(GlobalShaderData), _vp]),
     "vr_render_pair": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.POINTER(Target), ctypes.POINTER(ObjectShaderData),
                                       ctypes.POINTER(GlobalShaderData), _vp]),
+    "vr_render_group": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.c_int, ctypes.POINTER(ObjectShaderData),
+                                       ctypes.POINTER(GlobalShaderData), _vp]),
+    "vr_group_split": (ctypes.c_int, [ctypes.c_int, c_int_p]),
     "vr_render_rect": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.POINTER(Rect), _vp]),
     "vr_render_rects": (ctypes.c_int, [_vp, ctypes.POINTER(Target), ctypes.POINTER(Rect), ctypes.c_int, _vp]),
     "vr_rects_coalesce": (ctypes.c_int, [ctypes.POINTER(Rect), ctypes.c_int, ctypes.c_int, ctypes.POINTER(Rect),
@@ -170,7 +173,7 @@ _SIGS = {
                                             ctypes.POINTER(ctypes.c_int)]),
 }
 # functions whose int return is a value, not a vr_status
-_VALUE_RETURNS = {"vr_abi_version", "vr_band_rows_packed", "vr_get_option", "vr_volume_extent_ok"}
+_VALUE_RETURNS = {"vr_abi_version", "vr_band_rows_packed", "vr_get_option", "vr_volume_extent_ok", "vr_group_split"}
 
 _lib = None
 

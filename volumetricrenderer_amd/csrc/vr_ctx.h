@@ -269,7 +269,11 @@ struct Ctx {
     int pair_deal = 0;             // option "pair_deal": 0 = the frame in the wave's parity, 1 = in the workgroup's
     int frame_pairing = 2;         // option "frame_pairing": vr_shard_run_frames takes a one-rank grid pipeline's frames
                                    // two at a time (0 off, 1 pairs on one render stream, 2 alternating over two)
-    long long pair_launches = 0;   // read-only option "pair_launches": paired launches so far
+    long long pair_launches = 0;   // read-only option "pair_launches": frame pairs that shared a launch so far -- one per
+                                   // paired launch, two per four-frame launch
+    int frame_group = 4;           // option "frame_group": frames per launch of that loop where frame_pairing is on, 2 or
+                                   // 4 (measured)
+    long long group_launches = 0;  // read-only option "group_launches": four-frame launches so far (vr_render_group)
     uint2* d_lat = nullptr;
     size_t lat_cap = 0;            // bytes allocated
     long long lat_key[3] = {0, 0, -1};

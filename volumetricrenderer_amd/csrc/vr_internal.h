@@ -217,6 +217,53 @@ struct MarchArgs {
     int slab_cap;                // LDS slab march (COL48): chunks per channel the slab holds
 };
 
+// The part of MarchArgs that differs between the frames of one grouped launch
+// (vr_render_group): the camera (ray basis, r2 / r3, cam, tap_T), the target
+// buffer, the empty-tile fill and the step counter -- what vr_render.cpp's
+// pair_compatible leaves out.  Everything else is the launch's common part.
+struct FrameArgs {
+    float org[3], o[3], px[3], py[3];
+    float r2[4], r3[4];
+    int cam_mode;
+    float cam[3];
+    float tap_T[4][3];
+    int empty_fill;
+    void* out;
+    unsigned long long* step_counter;
+};
+__host__ __device__ inline FrameArgs frame_part(const MarchArgs& a)
+{
+    FrameArgs f{};
+    for (int i = 0; i < 3; ++i) { f.org[i] = a.org[i]; f.o[i] = a.o[i]; f.px[i] = a.px[i]; f.py[i] = a.py[i]; f.cam[i] = a.cam[i]; }
+    for (int i = 0; i < 4; ++i) { f.r2[i] = a.r2[i]; f.r3[i] = a.r3[i]; }
+    for (int t = 0; t < 4; ++t)
+        for (int i = 0; i < 3; ++i) f.tap_T[t][i] = a.tap_T[t][i];
+    f.cam_mode = a.cam_mode;
+    f.empty_fill = a.empty_fill;
+    f.out = a.out;
+    f.step_counter = a.step_counter;
+    return f;
+}
+__host__ __device__ inline void set_frame(MarchArgs* a, const FrameArgs& f)
+{
+    for (int i = 0; i < 3; ++i) { a->org[i] = f.org[i]; a->o[i] = f.o[i]; a->px[i] = f.px[i]; a->py[i] = f.py[i]; a->cam[i] = f.cam[i]; }
+    for (int i = 0; i < 4; ++i) { a->r2[i] = f.r2[i]; a->r3[i] = f.r3[i]; }
+    for (int t = 0; t < 4; ++t)
+        for (int i = 0; i < 3; ++i) a->tap_T[t][i] = f.tap_T[t][i];
+    a->cam_mode = f.cam_mode;
+    a->empty_fill = f.empty_fill;
+    a->out = f.out;
+    a->step_counter = f.step_counter;
+}
+// A grouped launch's kernel argument: the common part (frame 0's MarchArgs) and the frames
+constexpr int kGroupFrames = 4;
+struct GroupArgs {
+    MarchArgs c;
+    FrameArgs fr[kGroupFrames];
+};
+static_assert(sizeof(GroupArgs) + 64 <= 4096,
+              "one MarchArgs, four FrameArgs and the lists' pointers travel in the 4-KiB kernarg segment");
+
 // The frame band of a band set's k-th band (vr_target): band_first + k *
 // band_stride, every odd one shifted by band_flip (the serpentine deal)
 __host__ __device__ inline int set_band(int k, int first, int stride, int flip)
@@ -387,6 +434,12 @@ hipError_t launch_march_pair(const MarchArgs& a0, const MarchArgs& a1, int layou
                              hipStream_t s);
 hipError_t launch_march_pair_cornerh(const MarchArgs& a0, const MarchArgs& a1, bool early, const Schedule& sc, int deal,
                                      hipStream_t s);   // vr_march_c8.hip
+// Four frames in one regions launch (march_regions_group, vr_render_group): a is frame 0's
+// arguments, fr[k] frame k's per-frame part; the layouts and sc as for the pair
+hipError_t launch_march_group(const MarchArgs& a, const FrameArgs fr[kGroupFrames], int layout, bool early,
+                              const Schedule& sc, hipStream_t s);
+hipError_t launch_march_group_cornerh(const MarchArgs& a, const FrameArgs fr[kGroupFrames], bool early, const Schedule& sc,
+                                      hipStream_t s);   // vr_march_c8.hip
 // per-plane byte min (mm[0..3]) and max (mm[4..7]) of the planar volume; mm
 // must hold 0xffffffff x 4 then 0 x 4 (atomicMin / atomicMax)
 hipError_t launch_plane_minmax(const uint8_t* d_planar, long long total, unsigned* mm, hipStream_t s);

@@ -193,6 +193,18 @@ hipError_t launch_march_pair(const MarchArgs& a0, const MarchArgs& a1, int layou
     }
 }
 
+hipError_t launch_march_group(const MarchArgs& a, const FrameArgs fr[kGroupFrames], int layout, bool early,
+                              const Schedule& sc, hipStream_t s)
+{
+    if (a.width <= 0 || a.out_rows <= 0) return hipSuccess;
+    switch (layout) {
+    case LAYOUT_COL48: return launch_group_lw<LAYOUT_COL48, WRAP_CLAMP>(a, fr, early, sc, s);
+    case LAYOUT_BRICK4832: return launch_group_lw<LAYOUT_BRICK4832, WRAP_CLAMP>(a, fr, early, sc, s);
+    case LAYOUT_CORNERH: return launch_march_group_cornerh(a, fr, early, sc, s);   // vr_march_c8.hip
+    default: return hipErrorInvalidValue;   // no grouped kernel: the caller renders the frames one by one
+    }
+}
+
 }  // namespace vr
 
 #ifdef VR_TIMELINE

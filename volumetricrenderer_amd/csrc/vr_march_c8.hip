@@ -21,6 +21,12 @@ hipError_t launch_march_pair_cornerh(const MarchArgs& a0, const MarchArgs& a1, b
     return launch_pair_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a0, a1, early, sc, deal, s);
 }
 
+hipError_t launch_march_group_cornerh(const MarchArgs& a, const FrameArgs fr[kGroupFrames], bool early, const Schedule& sc,
+                                      hipStream_t s)
+{
+    return launch_group_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a, fr, early, sc, s);
+}
+
 }  // namespace vr
 
 #ifdef VR_TIMELINE

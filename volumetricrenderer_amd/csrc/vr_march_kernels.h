@@ -1255,6 +1255,48 @@ __global__ __launch_bounds__(kThreads) VR_UM_ATTR void march_regions_pair_u(cons
     regions_pair_body<LAYOUT, WRAP, EARLY, ZO, UM>(a0, a1, tiles, hdr, nwx, deal, lds);
 }
 
+// ---- four frames in one launch (vr_render_group) ----
+// A workgroup is one list entry x four frames: wave f of it marches the entry with frame
+// f's arguments, so all four readers of the entry's bricks sit behind one L1.  The frames
+// travel as one MarchArgs (frame 0's: the launch's common part) and FrameArgs fr[4]
+// (vr_internal.h).  There is one copy of the march: wave f's MarchArgs is the common part
+// with fr[f] laid over it -- scalar loads at the wave-uniform index f -- and equals what a
+// plain render of frame f passes.  XCD x runs nwx workgroups; workgroup w takes the entries
+// w, w + nwx, ...
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
+__device__ __forceinline__ void regions_group_body(const GroupArgs& g, const unsigned* __restrict__ tiles,
+                                                   const int* __restrict__ hdr, int nwx, unsigned* lds)
+{
+    const int xcd = blockIdx.x & 7, w = (int)(blockIdx.x >> 3);
+    const int fr = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int begin = hdr[xcd], all = hdr[xcd + 1] - begin;
+    const int marched = min(hdr[kRegionWork + xcd], all);
+    MarchArgs a = g.c;
+    set_frame(&a, g.fr[fr]);
+    const int count = a.empty_fill ? marched : all;
+    if (a.empty_fill) fill_empty_tiles(a, tiles, begin, count, all, w, nwx);
+    // the largest of the four frames' marched counts
+    const bool every = g.fr[0].empty_fill && g.fr[1].empty_fill && g.fr[2].empty_fill && g.fr[3].empty_fill;
+    if (w >= (every ? marched : all)) return;   // whole workgroup, before the barrier
+    const FastCtx f = fast_prologue<LAYOUT>(g.c, lds);   // volume and layout geometry: the frames' common part
+    pair_frame<LAYOUT, WRAP, EARLY, ZO, UM>(a, f, tiles, begin, count, w, nwx);
+}
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO>
+__global__ __launch_bounds__(kThreads) void march_regions_group(const GroupArgs g, const unsigned* __restrict__ tiles,
+                                                               const int* __restrict__ hdr, int nwx)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned lds[];
+    regions_group_body<LAYOUT, WRAP, EARLY, ZO, 0>(g, tiles, hdr, nwx, lds);
+}
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
+__global__ __launch_bounds__(kThreads) VR_UM_ATTR void march_regions_group_u(const GroupArgs g,
+                                                                            const unsigned* __restrict__ tiles,
+                                                                            const int* __restrict__ hdr, int nwx)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned lds[];
+    regions_group_body<LAYOUT, WRAP, EARLY, ZO, UM>(g, tiles, hdr, nwx, lds);
+}
+
 
 // ---- step-split rays (regions schedule) ----
 // A wave whose rays march alone on their SIMD waits ~110 dependent memory
@@ -2191,6 +2233,40 @@ hipError_t launch_pair_lw(const MarchArgs& a0, const MarchArgs& a1, bool early, 
         hipLaunchKernelGGL((march_regions_pair<L, W, false, true>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
     else
         hipLaunchKernelGGL((march_regions_pair<L, W, false, false>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
+    return hipGetLastError();
+}
+
+// The grouped launch (march_regions_group): launch_pair_lw's dispatch for four frames, a
+// workgroup per list entry wave -- XCD x runs sc.map.nwx workgroups of four waves.
+template <int L, int W>
+hipError_t launch_group_lw(const MarchArgs& a, const FrameArgs fr[kGroupFrames], bool early, const Schedule& sc, hipStream_t s)
+{
+    GroupArgs g;
+    g.c = a;
+    for (int k = 0; k < kGroupFrames; ++k) g.fr[k] = fr[k];
+    const size_t lds = L == LAYOUT_CORNERH ? 0 : (size_t)(a.nx + a.ny + a.nz + 3) * sizeof(unsigned);
+    const dim3 block(kThreads);
+    static_assert(kThreads == 64 * kGroupFrames, "a workgroup is one entry x four frames");
+    const int nwx = sc.map.nwx;
+    const dim3 grid((unsigned)(8 * nwx));
+    const int um = a.umask;
+    if (!early && a.zero_offsets && (um == 1 || um == 2 || um == 4 || um == 8)) {
+#define VR_UMG(U) hipLaunchKernelGGL((march_regions_group_u<L, W, false, true, U>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx)
+        if (um == 1) VR_UMG(1);
+        else if (um == 2) VR_UMG(2);
+        else if (um == 4) VR_UMG(4);
+        else VR_UMG(8);
+#undef VR_UMG
+        return hipGetLastError();
+    }
+    if (early && a.zero_offsets)
+        hipLaunchKernelGGL((march_regions_group<L, W, true, true>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx);
+    else if (early)
+        hipLaunchKernelGGL((march_regions_group<L, W, true, false>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx);
+    else if (a.zero_offsets)
+        hipLaunchKernelGGL((march_regions_group<L, W, false, true>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx);
+    else
+        hipLaunchKernelGGL((march_regions_group<L, W, false, false>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx);
     return hipGetLastError();
 }
 

@@ -69,6 +69,11 @@ try {
         c->frame_pairing = value;
         return VR_OK;
     }
+    if (n == "frame_group") {   // the native frame loop's frames per launch where frame_pairing is on (vr_shard.h)
+        if (value != 2 && value != 4) return fail(VR_ERR_INVALID, "vr_set_option: frame_group is 2 or 4");
+        c->frame_group = value;
+        return VR_OK;
+    }
     if (n == "pair_deal") {   // vr_render_pair: the frame in the wave's parity (0) or the workgroup's (1)
         if (value < 0 || value > 1) return fail(VR_ERR_INVALID, "vr_set_option: pair_deal is 0 or 1");
         c->pair_deal = value;
@@ -261,6 +266,8 @@ try {
     if (n == "row_first_pct") return c->row_first_pct;
     if (n == "frame_pairing") return c->frame_pairing;
     if (n == "pair_deal") return c->pair_deal;
+    if (n == "frame_group") return c->frame_group;
+    if (n == "group_launches") return (int)std::min<long long>(c->group_launches, 0x7fffffff);
     if (n == "pair_launches") return (int)std::min<long long>(c->pair_launches, 0x7fffffff);
     if (n == "launch_cache_hits") return (int)std::min<long long>(c->lc_hits, 0x7fffffff);
     if (n == "experiments") return VR_EXPERIMENTS;   // read-only: the measured-slower variants are built

@@ -1,8 +1,8 @@
 // vr_render.cpp -- the whole-frame render entry points of the C ABI: vr_render,
-// vr_render_sequence and vr_render_pair (include/vr.h).
+// vr_render_sequence, vr_render_pair and vr_render_group (include/vr.h).
 //
 // A grid frame goes from a vr_target to a launch in named steps, which
-// vr_render and vr_render_pair both call:
+// vr_render, vr_render_pair and vr_render_group call:
 //   check_target -> honour_inject_throw -> cache_hit, or else
 //   grid_frame_args -> attach_regions (regions schedule) -> launch_frame,
 // where launch_frame remembers a planned frame in the launch cache.  A
@@ -405,6 +405,120 @@ try {
     return note_region_render(c, hs);
 } catch (...) {
     return caught_exception("vr_render_pair");
+}
+
+vr_status vr_render_group(void* p, const vr_target* t, int n, const vr_object_shader_data* osd,
+                          const vr_global_shader_data* gsd, void* stream)
+try {
+    if (!p || !t || n < 1 || n > VR_MAX_GROUP || (!osd) != (!gsd)) return fail(VR_ERR_INVALID, "vr_render_group: bad argument");
+    // frames i..n-1 as ordinary renders, in order, each with its own shader data
+    const auto plain_from = [&](int i) {
+        vr_status st = VR_OK;
+        for (; i < n && st == VR_OK; ++i) {
+            if (osd) st = vr_set_shader_data(p, &osd[i], &gsd[i]);
+            if (st == VR_OK) st = vr_render(p, &t[i], stream);
+        }
+        return st;
+    };
+    for (int k = 1; k < n; ++k) {
+        // field by field: the structs' padding is the caller's
+        const vr_target &a = t[0], &b = t[k];
+        if (a.width != b.width || a.height != b.height || a.format != b.format || a.band_rows != b.band_rows ||
+            a.band_stride != b.band_stride || a.band_first != b.band_first || a.row_pitch != b.row_pitch ||
+            a.step_counter != b.step_counter || a.band_flip != b.band_flip || a.reserved != b.reserved)
+            return fail(VR_ERR_INVALID, "vr_render_group: the targets must agree in everything but pixels");
+        const int f = a.format & ~(VR_TARGET_BANDS_IN_PLACE | VR_TARGET_ROW_RANGE);
+        if (!b.pixels || (f >= 0 && f <= 5 && (uintptr_t)b.pixels % format_bytes(f) != 0))
+            return fail(VR_ERR_INVALID, "vr_render_group: target %d's pixels are null or misaligned", k);
+    }
+    int launches[3];
+    const int nl = vr_group_split(n, launches);
+    if (launches[0] != VR_MAX_GROUP) {   // n < 4: a pair and / or a plain render, vr_render_pair's and vr_render's paths
+        int i = 0;
+        for (int l = 0; l < nl; ++l) {
+            const vr_status st = launches[l] == 2 ? vr_render_pair(p, &t[i], &t[i + 1], osd ? &osd[i] : nullptr,
+                                                                   gsd ? &gsd[i] : nullptr, stream)
+                                                  : plain_from(i);
+            if (st != VR_OK) return st;
+            i += launches[l];
+        }
+        return VR_OK;
+    }
+    Ctx* c = as_ctx(p);
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (c->proc.enabled) return plain_from(0);   // a procedural medium: the ordinary renders
+    if (osd) {
+        const vr_status st = vr_set_shader_data(p, &osd[0], &gsd[0]);
+        if (st != VR_OK) return st;
+    }
+    // frame 0: vr_render's whole path (checks, plan, region lists) up to the launch
+    TargetInfo ti;
+    GridFrame f[VR_MAX_GROUP];
+    vr_status st = plan_first_frame(c, &t[0], hs, &ti, &f[0]);
+    if (st != VR_OK) return st;
+    const unsigned long long gen0 = c->gen;
+    const auto frame0_alone = [&] {
+        return launch_frame(c, f[0], cached_frame(c, &t[0], hs, gen0) ? nullptr : &t[0], gen0, hs);
+    };
+    const bool groupable = f[0].kind == SCHED_REGIONS && f[0].sc.split <= 1 && !f[0].sc.slab && f[0].sc.wg_waves == 4 &&
+                           pair_layout(f[0].pl.layout) && f[0].pl.wrap == WRAP_CLAMP;
+    bool grouped = groupable;
+    for (int k = 1; k < n && groupable; ++k) {
+        // frame k: its arguments and plan only (the lists are frame 0's); t[k] passed t[0]'s checks
+        if (osd) st = vr_set_shader_data(p, &osd[k], &gsd[k]);
+        if (st == VR_OK) st = grid_frame_args(c, &t[k], ti, &f[k]);
+        if (st != VR_OK) {   // frames 0..k-1 still render (frame 0 is planned and counted)
+            const std::string msg = g_err;
+            vr_status rs = frame0_alone();
+            for (int j = 1; j < k && rs == VR_OK; ++j) {
+                if (osd) rs = vr_set_shader_data(p, &osd[j], &gsd[j]);
+                if (rs == VR_OK) rs = vr_render(p, &t[j], stream);
+            }
+            if (osd) (void)vr_set_shader_data(p, &osd[k], &gsd[k]);   // the ctx holds what the failed frame set
+            g_err = msg;
+            return st;
+        }
+        grouped = grouped && f[k].kind == f[0].kind && pair_compatible(f[0], f[k]);
+    }
+    if (!grouped) {
+        // no grouped kernel for this plan, or frames whose plans differ: the ordinary renders
+        st = frame0_alone();
+        return st == VR_OK ? plain_from(1) : st;
+    }
+    // frame k fills the lists' empty tiles only where they are its own (attach_regions'
+    // region_exact rule); a group one frame of which marches every entry keeps the
+    // unreduced wave count
+    const Ctx::RegionBuf& rb = c->region[c->region_cur];
+    FrameArgs fr[kGroupFrames];
+    bool every = f[0].a.empty_fill != 0;
+    for (int k = 0; k < n; ++k) {
+        if (k > 0) f[k].a.empty_fill = f[0].a.empty_fill && same_region_camera(f[0], f[k]) ? 1 : 0;
+        every = every && f[k].a.empty_fill;
+        fr[k] = frame_part(f[k].a);
+    }
+    Schedule sc = f[0].sc;
+    if (f[0].a.empty_fill && !every) sc.map.nwx = std::max(1, rb.map.nwx);
+    HIP_TRY(launch_march_group(f[0].a, fr, f[0].pl.layout, f[0].pl.early, sc, hs));
+    ++c->group_launches;
+    c->pair_launches += 2;   // (two pairs of frames shared this launch)
+    c->renders_since_build += n - 1;   // the later renders with these lists (build_regions counted the first)
+    c->region_slot = f[0].slot;
+    return note_region_render(c, hs);
+} catch (...) {
+    return caught_exception("vr_render_group");
+}
+
+int vr_group_split(int n, int launches[3])
+{
+    if (!launches || n < 1 || n > VR_MAX_GROUP) return 0;
+    int k = 0;
+    if (n == VR_MAX_GROUP) launches[k++] = VR_MAX_GROUP;
+    else {
+        if (n >= 2) launches[k++] = 2;
+        if (n & 1) launches[k++] = 1;
+    }
+    for (int i = k; i < 3; ++i) launches[i] = 0;
+    return k;
 }
 
 }   // extern "C"

@@ -200,12 +200,19 @@ struct vr_shard {
     int* token = nullptr;             // [0]: vr_shard_barrier's all-reduced int; [1..7]:
                                       // vr_shard_share_volume's agreement vector
     bool pending[kMaxFramesInFlight] = {};        // done[p] recorded and not yet waited on
-    int last = -1;                    // parity of the last frame
+    int last = -1;                    // buffer set of the last frame: 0..3, and 4..7 (frame_more, read through
+                                      // frame_set) after a run of four-frame launches on two streams -- every
+                                      // other path sets it below kMaxFramesInFlight before it indexes done[] / pending[]
     // frames two at a time through vr_render_pair (the ctx's option "frame_pairing", read
     // at every run): 1 = successive pairs on render stream 0 with buffer sets 0 / 1; 2 =
     // pairs alternating over render streams 0 and 1, stream q with buffer sets 2q / 2q + 1
     int pairing = -1;                 // the last run's (-1: none yet)
     int pairs_run = 0;                // pairs queued so far (the alternation carries over between runs)
+    // frames four at a time through vr_render_group (the ctx's option "frame_group" = 4, one
+    // rank): one stream = buffer sets 0..3; two streams = stream q owns sets 4q..4q + 3, the
+    // sets 4..7 being frame_more[], allocated by the first run of that mode
+    int group = -1;                   // the last run's frame_group (-1: none yet)
+    uint8_t* frame_more[kMaxFramesInFlight] = {};
     bool loopback = false;            // one process emulates all ranks (no RCCL)
     bool solo = false;                // loopback rehearsal of one rank: its own band set only, no exchange
     std::vector<hipEvent_t> timing;   // sampled render brackets (pairs)
@@ -335,6 +342,7 @@ void release(vr_shard* sh)
         if (sh->local[p]) (void)hipFree(sh->local[p]);
         if (sh->gathered[p]) (void)hipFree(sh->gathered[p]);
         if (sh->frame[p]) (void)hipFree(sh->frame[p]);
+        if (sh->frame_more[p]) (void)hipFree(sh->frame_more[p]);
         if (sh->rendered[p]) (void)hipEventDestroy(sh->rendered[p]);
         if (sh->done[p]) (void)hipEventDestroy(sh->done[p]);
         if (sh->tail[p]) (void)hipEventDestroy(sh->tail[p]);
@@ -590,6 +598,28 @@ vr_status pair_on_render(vr_shard* sh, int p0, int p1, hipStream_t rs, const vr_
     return VR_OK;
 }
 
+// m = 1..4 frames of a one-rank communicator (no exchange, no assembly) through one
+// vr_render_group on rs: frame j into buffer set base + j (sets 4..7: frame_more) with
+// (osd[j], gsd[j]), or all with the current shader data.  One event pair brackets the launch.
+uint8_t* frame_set(vr_shard* sh, int p) { return p < kMaxFramesInFlight ? sh->frame[p] : sh->frame_more[p - kMaxFramesInFlight]; }
+vr_status group_on_render(vr_shard* sh, int base, int m, hipStream_t rs, const vr_object_shader_data* osd,
+                          const vr_global_shader_data* gsd, hipEvent_t t0, hipEvent_t t1)
+{
+    vr_target t = target_of(sh, sh->rank);
+    t.format = sh->format | VR_TARGET_BANDS_IN_PLACE | range_flag(sh, sh->rank);
+    t.row_pitch = sh->pitch;
+    vr_target ts[VR_MAX_GROUP];
+    for (int j = 0; j < m; ++j) {
+        ts[j] = t;
+        ts[j].pixels = frame_set(sh, base + j);
+    }
+    if (t0) HIP_TRY(hipEventRecord(t0, rs));
+    VR_TRY(vr_render_group(sh->ctx, ts, m, osd, gsd, rs));
+    if (t1) HIP_TRY(hipEventRecord(t1, rs));
+    sh->last = base + m - 1;
+    return VR_OK;
+}
+
 // Rank 0 as a compositor by default (vr_shard_set_compositor) from this many
 // ranks on.  Config 5 (1080p) at N = 8: rank 0 rendering its own 1/8 beside
 // the assembly of the other 7/8 takes 0.0208 ms per frame against 0.0165 on
@@ -842,15 +872,60 @@ try {
     const bool one_rank = sh->nranks == 1 || (sh->loopback && sh->solo);
     const int pairing = vr_get_option(sh->ctx, "frame_pairing");
     const bool pairs = pairing > 0 && two && one_rank && !others_here(sh) && vr_get_option(sh->ctx, "procedural") == 0;
+    // frame_group 4: a one-rank communicator takes them four at a time (vr_render_group), the
+    // remainder as a pair and / or a single frame; a solo rehearsal keeps its pairs
+    const int group = pairs && sh->nranks == 1 && sh->my_rows > 0 ? vr_get_option(sh->ctx, "frame_group") : 2;
     if (one_rank && frames > 0) {
-        if (sh->pairing >= 0 && pairing != sh->pairing && sh->last >= 0) {
+        if (sh->last >= 0 && ((sh->pairing >= 0 && pairing != sh->pairing) || (sh->group >= 0 && group != sh->group))) {
             // frames of the old arrangement may still be in flight (vr_shard_set_render_streams)
             for (int p = 0; p < kMaxFramesInFlight; ++p)
                 if (sh->pending[p]) SH_TRY(wait_event(sh, sh->done[p], "vr_shard_run: frame_pairing changed"));
         }
         sh->pairing = pairing;
+        sh->group = group;
     }
-    if (pairs && frames > 0) {
+    if (pairs && group == 4 && pairing == 2 && frames > 0 && !sh->frame_more[0]) {   // the second stream's four sets
+        for (int p = 0; p < kMaxFramesInFlight; ++p) {
+            const hipError_t e = hipMalloc(&sh->frame_more[p], (size_t)sh->height * sh->pitch);
+            if (e != hipSuccess) {
+                sh->frame_more[p] = nullptr;
+                for (int k = 0; k < p; ++k) {
+                    (void)hipFree(sh->frame_more[k]);
+                    sh->frame_more[k] = nullptr;
+                }
+                return fail(e == hipErrorOutOfMemory ? VR_ERR_OOM : VR_ERR_HIP, "vr_shard_run: frame buffers: %s",
+                            hipGetErrorString(e));
+            }
+        }
+    }
+    if (pairs && group == 4 && frames > 0) {
+        for (int q = 0; q < kMaxFramesInFlight; ++q)   // (as below: buffer sets last used by other paths' frames)
+            if (sh->pending[q]) {
+                for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->done[q], 0));
+                sh->pending[q] = false;
+            }
+        const bool alt = pairing == 2;
+        for (int i = 0; i < frames;) {
+            const int m = std::min(frames - i, VR_MAX_GROUP);
+            bool samp = false;
+            for (int j = i; j < i + m && kernel_ms; ++j) samp = samp || j % sample_every == 0;
+            hipEvent_t t0 = samp ? sh->timing[2 * next] : nullptr, t1 = samp ? sh->timing[2 * next + 1] : nullptr;
+            if (samp) ++next;
+            const int q = alt ? (sh->pairs_run & 1) : 0;
+            SH_TRY(group_on_render(sh, alt ? kMaxFramesInFlight * q : 0, m, sh->render_stream[q], osd ? &osd[i] : nullptr,
+                                   gsd ? &gsd[i] : nullptr, t0, t1));
+            i += m;
+            ++sh->pairs_run;
+        }
+        for (int q = 0; q < 2; ++q) {   // join: the caller's stream after both streams' last frames
+            HIP_TRY(hipEventRecord(sh->tail[q], sh->render_stream[q]));
+            HIP_TRY(hipStreamWaitEvent(s, sh->tail[q], 0));
+        }
+        for (int b = 0; b < kMaxFramesInFlight; ++b) {   // a later frame of another arrangement waits for these
+            HIP_TRY(hipEventRecord(sh->done[b], sh->render_stream[alt ? b & 1 : 0]));
+            sh->pending[b] = true;
+        }
+    } else if (pairs && frames > 0) {
         for (int q = 0; q < kMaxFramesInFlight; ++q)   // (as below: buffer sets last used by comm-stream frames)
             if (sh->pending[q]) {
                 for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->done[q], 0));
@@ -1007,6 +1082,8 @@ try {
         }
     }
     if (sh->last >= 0 && frames > 0 && !on_render && !pairs) {   // the caller's stream sees the frame
+        if (sh->last >= kMaxFramesInFlight)   // (only a run of four-frame launches leaves such a set: not this path)
+            return fail(VR_ERR_INVALID, "vr_shard_run: internal: buffer set %d outside the per-frame events", sh->last);
         if (sh->rank == 0 && !others_here(sh)) {
             // rank 0 recorded no event per frame: join the exchange / assembly
             // stream and the render streams now (the render streams' frames
@@ -1278,7 +1355,7 @@ vr_status vr_shard_frame(vr_shard* sh, void** pixels, size_t* row_pitch, int* ro
 try {
     if (!sh || !pixels) return fail(VR_ERR_INVALID, "vr_shard_frame: null argument");
     if (sh->last < 0) return fail(VR_ERR_INVALID, "vr_shard_frame: no frame rendered yet");
-    *pixels = sh->rank == 0 ? sh->frame[sh->last] : sh->local[sh->last];
+    *pixels = sh->rank == 0 ? frame_set(sh, sh->last) : sh->local[sh->last];
     if (row_pitch) *row_pitch = sh->rank == 0 ? sh->pitch : sh->gpitch;
     if (rows) *rows = sh->rank == 0 ? sh->height : sh->my_rows;
     return VR_OK;

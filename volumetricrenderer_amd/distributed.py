@@ -521,6 +521,17 @@ class RcclBandPipeline:
     def pairing(self, mode: int) -> None:
         self.r.set_option("frame_pairing", int(mode))
 
+    @property
+    def frame_group(self) -> int:
+        """Frames per launch where pairing is on (the renderer's option "frame_group",
+        vr_shard.h): 2 = pairs, 4 = four at a time through vr_render_group, the
+        remainder as a pair and / or a single frame."""
+        return self.r.get_option("frame_group")
+
+    @frame_group.setter
+    def frame_group(self, frames: int) -> None:
+        self.r.set_option("frame_group", int(frames))
+
     def set_timeout(self, seconds: float) -> None:
         """Deadline (s) of every later host wait on a collective."""
         _lib.shard_call("vr_shard_set_timeout", self._h, float(seconds))

@@ -391,6 +391,35 @@ class Renderer:
         call("vr_render_pair", self._ctx, ctypes.byref(ts[0]), ctypes.byref(ts[1]), osd, gsd, _stream_handle(stream))
         return out0, out1
 
+    def render_group(self, width: int, height: int, fmt: int, outs, cameras=None, band_rows: int = 0,
+                     band_stride: int = 1, band_first: int = 0, stream=None, step_counter: torch.Tensor | None = None,
+                     band_flip: int = 0, row_pitch: int | None = None):
+        """len(outs) = 1..4 queued frames (vr_render_group): frame i into outs[i] with
+        cameras[i] = (ObjectShaderData, GlobalShaderData); cameras None = all with the
+        current shader data.  Four frames are one launch where a grouped kernel applies,
+        three a pair and a plain render.  The same bytes as set_shader_data + render per
+        frame; the renderer ends holding the last camera."""
+        outs = list(outs)
+        n = len(outs)
+        if not 1 <= n <= 4:
+            raise ValueError(f"render_group: 1 to 4 targets, got {n}")
+        for out in outs:
+            self._check_target(width, height, fmt, out, band_rows, band_stride, band_first, step_counter, band_flip)
+        ts = (Target * n)(*[Target(width=width, height=height, format=fmt, band_rows=band_rows, band_stride=band_stride,
+                                   band_first=band_first, pixels=out.data_ptr(),
+                                   row_pitch=out.stride(0) * out.element_size() if row_pitch is None else row_pitch,
+                                   step_counter=step_counter.data_ptr() if step_counter is not None else None,
+                                   band_flip=band_flip) for out in outs])
+        osd = gsd = None
+        if cameras is not None:
+            cams = list(cameras)
+            if len(cams) != n:
+                raise ValueError(f"render_group: {n} cameras, got {len(cams)}")
+            osd = (ObjectShaderData * n)(*[c[0] for c in cams])
+            gsd = (GlobalShaderData * n)(*[c[1] for c in cams])
+        call("vr_render_group", self._ctx, ts, n, osd, gsd, _stream_handle(stream))
+        return tuple(outs)
+
     def render_rect(self, out: torch.Tensor, rect, fmt: int = FMT_RGBA8_UNORM,
                     step_counter: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         """Render the pixels rect = (x, y, w, h) of the whole-frame target `out`
