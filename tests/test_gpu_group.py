@@ -58,36 +58,36 @@ def setup(rr, pref, vol, march=None):
     rr.set_march(march if march is not None else vr.march_defaults(max_steps=STEPS))
 
 
-def cam(phi=0.0, theta=0.0, t=0.0):
-    return vr.reference_shader_data(W / H, phi, theta, t)
+def cam(phi=0.0, theta=0.0, t=0.0, size=(W, H)):
+    return vr.reference_shader_data(size[0] / size[1], phi, theta, t)
 
 
-def target(rr, fmt, **band):
-    out = rr.alloc_target(W, H, fmt, **band)
+def target(rr, fmt, size=(W, H), **band):
+    out = rr.alloc_target(*size, fmt, **band)
     out.view(torch.uint8).fill_(0xA5)
     return out
 
 
-def plain(rr, cams, fmt, **band):
+def plain(rr, cams, fmt, size=(W, H), **band):
     """The ordinary renders: (frames, counted steps)."""
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
     outs = []
     for c in cams:
         rr.set_shader_data(*c)
-        outs.append(rr.render(W, H, fmt, out=target(rr, fmt, **band), step_counter=cnt, **band))
+        outs.append(rr.render(*size, fmt, out=target(rr, fmt, size, **band), step_counter=cnt, **band))
     torch.cuda.synchronize()
     return [o.cpu().numpy() for o in outs], int(cnt.item())
 
 
-def grouped(rr, cams, fmt, **band):
+def grouped(rr, cams, fmt, size=(W, H), **band):
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    outs = [target(rr, fmt, **band) for _ in cams]
-    rr.render_group(W, H, fmt, outs, cameras=cams, step_counter=cnt, **band)
+    outs = [target(rr, fmt, size, **band) for _ in cams]
+    rr.render_group(*size, fmt, outs, cameras=cams, step_counter=cnt, **band)
     torch.cuda.synchronize()
     return [o.cpu().numpy() for o in outs], int(cnt.item())
 
 
-def check(rr, cams, fmt=FMT_RGBA8_UNORM, groups=None, pairs=None, **band):
+def check(rr, cams, fmt=FMT_RGBA8_UNORM, groups=None, pairs=None, size=(W, H), **band):
     """The group of len(cams) frames against the plain renders; `groups` / `pairs`: the four-frame
     and two-frame launches expected (default: what vr_group_split names for len(cams))."""
     n = len(cams)
@@ -95,9 +95,9 @@ def check(rr, cams, fmt=FMT_RGBA8_UNORM, groups=None, pairs=None, **band):
         groups = 1 if n == 4 else 0
     if pairs is None:
         pairs = 1 if n in (2, 3) else 0
-    want, steps = plain(rr, cams, fmt, **band)
+    want, steps = plain(rr, cams, fmt, size, **band)
     g0, p0 = rr.get_option("group_launches"), rr.get_option("pair_launches")
-    got, gsteps = grouped(rr, cams, fmt, **band)
+    got, gsteps = grouped(rr, cams, fmt, size, **band)
     for i in range(n):
         assert np.array_equal(got[i].view(np.uint8), want[i].view(np.uint8)), f"frame {i}"
     assert gsteps == steps
@@ -113,8 +113,8 @@ CAMERA_ANGLES = {
 }
 
 
-def cameras(name, n=4):
-    return [cam(phi, -35.0) for phi in CAMERA_ANGLES[name][:n]]
+def cameras(name, n=4, size=(W, H)):
+    return [cam(phi, -35.0, size=size) for phi in CAMERA_ANGLES[name][:n]]
 
 
 @pytest.mark.parametrize("cams", list(CAMERA_ANGLES))
@@ -125,6 +125,23 @@ def test_group_equals_four_renders(r, vols, pref, name, vol, cams):
     r.set_shader_data(*cameras(cams)[0])
     assert name in r.kernel_variant and ("_u" in r.kernel_variant) == (vol == "uni")
     check(r, cameras(cams))
+
+
+SMALL = (24, 16)   # 3 x 2 wave tiles
+
+
+@pytest.mark.parametrize("fill", [0, 1])
+@pytest.mark.parametrize("pref,name", LAYOUTS, ids=LAYOUT_IDS)
+def test_group_frame_of_six_tiles(r, vols, pref, name, fill):
+    """24 x 16 pixels: several XCDs' lists are empty and there is one workgroup per XCD (nwx 1)."""
+    setup(r, pref, vols["v64"])
+    r.set_option("empty_fill", fill)
+    try:
+        for cams in ("equal", "apart_40"):
+            for frame in check(r, cameras(cams, size=SMALL), size=SMALL):
+                assert not (frame.view(np.uint32) == 0xA5A5A5A5).any(), cams   # a pixel nobody wrote
+    finally:
+        r.set_option("empty_fill", 1)
 
 
 @pytest.mark.parametrize("n", [3, 2, 1])

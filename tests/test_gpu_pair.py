@@ -54,39 +54,39 @@ def setup(rr, pref, vol, march=None):
     rr.set_march(march if march is not None else vr.march_defaults(max_steps=STEPS))
 
 
-def cam(phi=0.0, theta=0.0, t=0.0):
-    return vr.reference_shader_data(W / H, phi, theta, t)
+def cam(phi=0.0, theta=0.0, t=0.0, size=(W, H)):
+    return vr.reference_shader_data(size[0] / size[1], phi, theta, t)
 
 
-def target(rr, fmt, **band):
-    out = rr.alloc_target(W, H, fmt, **band)
+def target(rr, fmt, size=(W, H), **band):
+    out = rr.alloc_target(*size, fmt, **band)
     out.view(torch.uint8).fill_(0xA5)
     return out
 
 
-def plain(rr, cams, fmt, **band):
+def plain(rr, cams, fmt, size=(W, H), **band):
     """The two ordinary renders: (frames, counted steps)."""
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
     outs = []
     for c in cams:
         rr.set_shader_data(*c)
-        outs.append(rr.render(W, H, fmt, out=target(rr, fmt, **band), step_counter=cnt, **band))
+        outs.append(rr.render(*size, fmt, out=target(rr, fmt, size, **band), step_counter=cnt, **band))
     torch.cuda.synchronize()
     return [o.cpu().numpy() for o in outs], int(cnt.item())
 
 
-def paired(rr, cams, fmt, **band):
+def paired(rr, cams, fmt, size=(W, H), **band):
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    o0, o1 = target(rr, fmt, **band), target(rr, fmt, **band)
-    rr.render_pair(W, H, fmt, o0, o1, cameras=cams, step_counter=cnt, **band)
+    o0, o1 = target(rr, fmt, size, **band), target(rr, fmt, size, **band)
+    rr.render_pair(*size, fmt, o0, o1, cameras=cams, step_counter=cnt, **band)
     torch.cuda.synchronize()
     return [o0.cpu().numpy(), o1.cpu().numpy()], int(cnt.item())
 
 
-def check(rr, cams, fmt=FMT_RGBA8_UNORM, expect_pair=True, **band):
-    want, steps = plain(rr, cams, fmt, **band)
+def check(rr, cams, fmt=FMT_RGBA8_UNORM, expect_pair=True, size=(W, H), **band):
+    want, steps = plain(rr, cams, fmt, size, **band)
     n0 = rr.get_option("pair_launches")
-    got, psteps = paired(rr, cams, fmt, **band)
+    got, psteps = paired(rr, cams, fmt, size, **band)
     for i in range(2):
         assert np.array_equal(got[i].view(np.uint8), want[i].view(np.uint8)), f"frame {i}"
     assert psteps == steps
@@ -102,8 +102,8 @@ CAMERA_ANGLES = {
 VR_ERR_INVALID = 1
 
 
-def cameras(name):
-    return [cam(phi, -35.0) for phi in CAMERA_ANGLES[name]]
+def cameras(name, size=(W, H)):
+    return [cam(phi, -35.0, size=size) for phi in CAMERA_ANGLES[name]]
 
 
 @pytest.mark.parametrize("cams", list(CAMERA_ANGLES))
@@ -114,6 +114,27 @@ def test_pair_equals_two_renders(r, vols, pref, name, vol, cams):
     r.set_shader_data(*cameras(cams)[0])
     assert name in r.kernel_variant and ("_u" in r.kernel_variant) == (vol == "uni")
     check(r, cameras(cams))
+
+
+SMALL = (24, 16)   # 3 x 2 wave tiles
+
+
+@pytest.mark.parametrize("fill", [0, 1])
+@pytest.mark.parametrize("pref,name", LAYOUTS, ids=LAYOUT_IDS)
+def test_pair_frame_of_six_tiles(r, vols, pref, name, fill):
+    """24 x 16 pixels: several XCDs' lists are empty, there is one entry wave per XCD (nwx 1), and
+    the second entry wave of a pair's workgroup has no entries (w >= nwx), in either deal."""
+    setup(r, pref, vols["v64"])
+    r.set_option("empty_fill", fill)
+    try:
+        for deal in (0, 1):
+            r.set_option("pair_deal", deal)
+            for cams in ("equal", "apart_40"):
+                for frame in check(r, cameras(cams, SMALL), size=SMALL):
+                    assert not (frame.view(np.uint32) == 0xA5A5A5A5).any(), (deal, cams)   # a pixel nobody wrote
+    finally:
+        r.set_option("empty_fill", 1)
+        r.set_option("pair_deal", 0)
 
 
 @pytest.mark.parametrize("fmt", [FMT_RGBA8_UNORM, FMT_RGBA32F])

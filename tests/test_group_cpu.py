@@ -66,13 +66,14 @@ def test_bad_arguments_are_refused():
 
 
 def test_frame_args_layout(tmp_path):
-    """FrameArgs holds exactly the per-frame fields and four of them travel with one MarchArgs
-    and the lists' pointers inside the 4096-B kernarg segment (host compile of vr_internal.h)."""
+    """FrameArgs holds exactly the per-frame fields and four of them (a pair's launch: two) travel with
+    one MarchArgs and the lists' pointers inside the 4096-B kernarg segment (host compile of vr_internal.h)."""
     hipcc = "/opt/rocm/bin/hipcc"
     src = tmp_path / "t.cpp"
     fields = ["org", "o", "px", "py", "r2", "r3", "cam_mode", "cam", "tap_T", "empty_fill", "out", "step_counter"]
     src.write_text('#include <cstdio>\n#include <cstddef>\n#include "vr_internal.h"\nusing namespace vr;\nint main(){'
-                   'printf("%zu %zu %zu %d", sizeof(FrameArgs), sizeof(MarchArgs), sizeof(GroupArgs), kGroupFrames);'
+                   'printf("%zu %zu %zu %d %zu", sizeof(FrameArgs), sizeof(MarchArgs), sizeof(GroupArgs), kGroupFrames,'
+                   ' sizeof(FramesArgs<2>));'
                    + "".join('printf(" %%zu %%zu", offsetof(FrameArgs, %s), sizeof(FrameArgs::%s));' % (f, f) for f in fields)
                    + 'MarchArgs a{}; a.org[1] = 3.f; a.tap_T[2][1] = 7.f; a.cam_mode = 1; a.empty_fill = 1; a.max_steps = 5;'
                    'a.out = &a; MarchArgs b{}; b.max_steps = 9; set_frame(&b, frame_part(a));'
@@ -82,9 +83,11 @@ def test_frame_args_layout(tmp_path):
     subprocess.run([hipcc, "-std=c++17", "-x", "c++", "-I", CSRC, "-I", "/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
                     str(src), "-o", str(exe), "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"], check=True)
     got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    frame, march, group, k = got[:4]
+    frame, march, group, k, pair = got[:5]
+    print("FrameArgs", frame, "MarchArgs", march, "FramesArgs<4>", group, "FramesArgs<2>", pair)
     assert k == 4 and group == march + 4 * frame and group + 64 <= 4096
-    offs = got[4:-1]
+    assert pair == march + 2 * frame
+    offs = got[5:-1]
     end = 0
     for i in range(len(fields)):   # in declaration order, no field missing, nothing but alignment padding between
         off, size = offs[2 * i], offs[2 * i + 1]

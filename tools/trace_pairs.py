@@ -1,7 +1,8 @@
 """The timed window of a plain `rocprofv3 --kernel-trace` run of bench.py (config 5), read
 from its kernel_trace.csv: the last K frames' march launches -- one per frame
-(march_regions_u), one per pair (march_regions_pair_u, the native loop's paired frames) or
-one per four frames (march_regions_group_u, option frame_group 4).
+(march_regions_u) or one per NF frames (march_regions_frames_u<..., NF>: the native loop's pairs,
+NF 2, and groups of four, option frame_group 4).  Traces of earlier builds name those kernels
+march_regions_pair_u and march_regions_group_u.
 
     python tools/trace_pairs.py TRACE.csv [--steps 50]
 
@@ -11,6 +12,7 @@ span (first start to last end) and the busy time (union of the launches' interva
 import argparse
 import json
 import os
+import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +26,10 @@ rows = [r for r in load(a.trace) if "march_regions" in r[2]]
 
 
 def frames_of(name):
+    # march_regions_frames[_u]<layout, wrap, early, zero offsets, [mask,] NF>(vr::FramesArgs<NF>, ...)
+    m = re.search(r"march_regions_frames(?:_u)?<[^>]*?(\d+)>", name) or re.search(r"FramesArgs<(\d+)>", name)
+    if m:
+        return int(m.group(1))
     return 4 if "march_regions_group" in name else 2 if "march_regions_pair" in name else 1
 
 

@@ -217,10 +217,12 @@ struct MarchArgs {
     int slab_cap;                // LDS slab march (COL48): chunks per channel the slab holds
 };
 
-// The part of MarchArgs that differs between the frames of one grouped launch
-// (vr_render_group): the camera (ray basis, r2 / r3, cam, tap_T), the target
-// buffer, the empty-tile fill and the step counter -- what vr_render.cpp's
-// pair_compatible leaves out.  Everything else is the launch's common part.
+// The part of MarchArgs that differs between the frames of one multi-frame launch
+// (vr_render_pair, vr_render_group): the camera (ray basis, r2 / r3, cam, tap_T), the
+// target buffer, the empty-tile fill and the step counter -- what vr_render.cpp's
+// pair_compatible leaves out.  Everything else is the launch's common part.  A field
+// that a later change makes per-frame moves here (and into frame_part / set_frame and out
+// of pair_compatible): the two- and the four-frame kernels both read it from FramesArgs.
 struct FrameArgs {
     float org[3], o[3], px[3], py[3];
     float r2[4], r3[4];
@@ -255,14 +257,17 @@ __host__ __device__ inline void set_frame(MarchArgs* a, const FrameArgs& f)
     a->out = f.out;
     a->step_counter = f.step_counter;
 }
-// A grouped launch's kernel argument: the common part (frame 0's MarchArgs) and the frames
+// A multi-frame launch's kernel argument: the common part (frame 0's MarchArgs) and the
+// NF frames' own parts, NF = 2 (vr_render_pair) or 4 (vr_render_group)
 constexpr int kGroupFrames = 4;
-struct GroupArgs {
+template <int NF>
+struct FramesArgs {
     MarchArgs c;
-    FrameArgs fr[kGroupFrames];
+    FrameArgs fr[NF];
 };
-static_assert(sizeof(GroupArgs) + 64 <= 4096,
-              "one MarchArgs, four FrameArgs and the lists' pointers travel in the 4-KiB kernarg segment");
+using GroupArgs = FramesArgs<kGroupFrames>;
+static_assert(sizeof(FramesArgs<2>) + 64 <= 4096 && sizeof(GroupArgs) + 64 <= 4096,
+              "one MarchArgs, the FrameArgs and the lists' pointers travel in the 4-KiB kernarg segment");
 
 // The frame band of a band set's k-th band (vr_target): band_first + k *
 // band_stride, every odd one shifted by band_flip (the serpentine deal)
@@ -425,21 +430,16 @@ constexpr unsigned kDeferInPlace = 0xffffffffu;
 
 // launchers (vr_march.hip / vr_volume.hip); return hipError_t
 hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, const Schedule& sc, hipStream_t s);
-// Two frames in one regions launch (march_regions_pair, vr_render_pair): the layouts with a
-// paired kernel, and the launch -- a0 and a1 differ only in their per-frame arguments, sc
-// is a regions schedule with one lane per ray (no split, no slab, 4-wave workgroups);
-// deal 0 = the frame in the wave's parity, 1 = in the workgroup's (vr_march_kernels.h)
+// nf (2 or 4) frames in one regions launch (march_regions_frames; vr_render_pair,
+// vr_render_group): the layouts with such a kernel, and the launch -- a is frame 0's
+// arguments, fr[k] frame k's per-frame part (the frames differ in nothing else), sc is a
+// regions schedule with one lane per ray (no split, no slab, 4-wave workgroups); deal
+// (nf = 2 only) 0 = the frame in the wave's parity, 1 = in the workgroup's (vr_march_kernels.h)
 bool pair_layout(int layout);
-hipError_t launch_march_pair(const MarchArgs& a0, const MarchArgs& a1, int layout, bool early, const Schedule& sc, int deal,
-                             hipStream_t s);
-hipError_t launch_march_pair_cornerh(const MarchArgs& a0, const MarchArgs& a1, bool early, const Schedule& sc, int deal,
-                                     hipStream_t s);   // vr_march_c8.hip
-// Four frames in one regions launch (march_regions_group, vr_render_group): a is frame 0's
-// arguments, fr[k] frame k's per-frame part; the layouts and sc as for the pair
-hipError_t launch_march_group(const MarchArgs& a, const FrameArgs fr[kGroupFrames], int layout, bool early,
-                              const Schedule& sc, hipStream_t s);
-hipError_t launch_march_group_cornerh(const MarchArgs& a, const FrameArgs fr[kGroupFrames], bool early, const Schedule& sc,
-                                      hipStream_t s);   // vr_march_c8.hip
+hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
+                               int deal, hipStream_t s);
+hipError_t launch_march_frames_cornerh(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc,
+                                       int deal, hipStream_t s);   // vr_march_c8.hip
 // per-plane byte min (mm[0..3]) and max (mm[4..7]) of the planar volume; mm
 // must hold 0xffffffff x 4 then 0 x 4 (atomicMin / atomicMax)
 hipError_t launch_plane_minmax(const uint8_t* d_planar, long long total, unsigned* mm, hipStream_t s);

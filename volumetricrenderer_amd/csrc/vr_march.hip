@@ -181,27 +181,15 @@ bool pair_layout(int layout)
     return layout == LAYOUT_COL48 || layout == LAYOUT_BRICK4832 || layout == LAYOUT_CORNERH;
 }
 
-hipError_t launch_march_pair(const MarchArgs& a0, const MarchArgs& a1, int layout, bool early, const Schedule& sc, int deal,
-                             hipStream_t s)
-{
-    if (a0.width <= 0 || a0.out_rows <= 0) return hipSuccess;
-    switch (layout) {
-    case LAYOUT_COL48: return launch_pair_lw<LAYOUT_COL48, WRAP_CLAMP>(a0, a1, early, sc, deal, s);
-    case LAYOUT_BRICK4832: return launch_pair_lw<LAYOUT_BRICK4832, WRAP_CLAMP>(a0, a1, early, sc, deal, s);
-    case LAYOUT_CORNERH: return launch_march_pair_cornerh(a0, a1, early, sc, deal, s);   // vr_march_c8.hip
-    default: return hipErrorInvalidValue;   // no paired kernel: the caller renders the frames one by one
-    }
-}
-
-hipError_t launch_march_group(const MarchArgs& a, const FrameArgs fr[kGroupFrames], int layout, bool early,
-                              const Schedule& sc, hipStream_t s)
+hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
+                               int deal, hipStream_t s)
 {
     if (a.width <= 0 || a.out_rows <= 0) return hipSuccess;
     switch (layout) {
-    case LAYOUT_COL48: return launch_group_lw<LAYOUT_COL48, WRAP_CLAMP>(a, fr, early, sc, s);
-    case LAYOUT_BRICK4832: return launch_group_lw<LAYOUT_BRICK4832, WRAP_CLAMP>(a, fr, early, sc, s);
-    case LAYOUT_CORNERH: return launch_march_group_cornerh(a, fr, early, sc, s);   // vr_march_c8.hip
-    default: return hipErrorInvalidValue;   // no grouped kernel: the caller renders the frames one by one
+    case LAYOUT_COL48: return launch_frames_l<LAYOUT_COL48, WRAP_CLAMP>(a, fr, nf, early, sc, deal, s);
+    case LAYOUT_BRICK4832: return launch_frames_l<LAYOUT_BRICK4832, WRAP_CLAMP>(a, fr, nf, early, sc, deal, s);
+    case LAYOUT_CORNERH: return launch_march_frames_cornerh(a, fr, nf, early, sc, deal, s);   // vr_march_c8.hip
+    default: return hipErrorInvalidValue;   // no multi-frame kernel: the caller renders the frames one by one
     }
 }
 

@@ -15,16 +15,10 @@ hipError_t launch_march_corner8(const MarchArgs& a, int layout, bool early, cons
     return launch_lw<LAYOUT_CORNER8, WRAP_CLAMP>(a, early, sc, s);
 }
 
-hipError_t launch_march_pair_cornerh(const MarchArgs& a0, const MarchArgs& a1, bool early, const Schedule& sc, int deal,
-                                     hipStream_t s)
+hipError_t launch_march_frames_cornerh(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc,
+                                       int deal, hipStream_t s)
 {
-    return launch_pair_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a0, a1, early, sc, deal, s);
-}
-
-hipError_t launch_march_group_cornerh(const MarchArgs& a, const FrameArgs fr[kGroupFrames], bool early, const Schedule& sc,
-                                      hipStream_t s)
-{
-    return launch_group_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a, fr, early, sc, s);
+    return launch_frames_l<LAYOUT_CORNERH, WRAP_CLAMP>(a, fr, nf, early, sc, deal, s);
 }
 
 }  // namespace vr

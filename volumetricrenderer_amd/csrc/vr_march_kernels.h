@@ -1188,22 +1188,45 @@ __global__ __launch_bounds__(kThreads) VR_UM_ATTR void march_regions_u(const Mar
     regions_body<LAYOUT, WRAP, EARLY, ZO, kThreads / 64, UM>(a, tiles, hdr, nwx, lds);
 }
 
-// ---- two frames in one launch (vr_render_pair) ----
-// The regions schedule over one list and one header for two frames: a wave
-// takes (list entry, frame f) and marches the entry with frame f's arguments,
-// so both frames read an entry's bricks at the same moment on the same XCD.
-// a0 and a1 differ only in the camera (ray basis, r2 / r3, cam, tap_T), the
-// target buffer, empty_fill and step_counter (vr_api.cpp pair_compatible);
-// the lists are frame 0's.  f is wave-uniform and picks one of two inlined
-// copies of the march, each reading its own kernarg block as march_regions does.
-//   deal 0: f = the wave's parity in its workgroup -- a workgroup is 2
-//           consecutive entries x 2 frames, both readers on one CU (L1 and L2)
-//   deal 1: f = the workgroup's parity on its XCD -- a workgroup keeps 4
-//           consecutive entries (the 2x2 supertile) of one frame; L2 only
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
-__device__ __forceinline__ void pair_frame(const MarchArgs& a, FastCtx f, const unsigned* __restrict__ tiles, int begin,
-                                           int count, int w, int nwx)
+// ---- NF queued frames in one launch (vr_render_pair: 2, vr_render_group: 4;
+// DESIGN.md sec. 5.1.7 - 5.1.9) ----
+// The regions schedule over one list and one header (frame 0's) for NF frames: a wave takes
+// (list entry, frame f) and marches the entry with frame f's arguments, so the frames read
+// an entry's bricks at the same moment on the same XCD.  The frames travel as one MarchArgs
+// (frame 0's: the launch's common part) and FrameArgs fr[NF] (vr_internal.h).  There is one
+// copy of the march: wave f's MarchArgs is the common part with fr[f] laid over it -- scalar
+// loads at the wave-uniform index f -- and equals what a plain render of frame f passes.
+// A workgroup is 4 waves = 4 / NF entry waves x NF frames; XCD x's entry wave w takes the
+// entries w, w + nwx, ...
+//   NF 4:         f = the wave; workgroup g is entry wave g -- all four readers of an
+//                 entry's bricks sit behind one L1
+//   NF 2, deal 0: f = the wave's parity in its workgroup -- a workgroup is 2 consecutive
+//                 entry waves x 2 frames, both readers on one CU (L1 and L2)
+//   NF 2, deal 1: f = the workgroup's parity on its XCD -- a workgroup keeps 4 consecutive
+//                 entry waves (the 2x2 supertile) of one frame; L2 only (option pair_deal)
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF>
+__device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, const unsigned* __restrict__ tiles,
+                                                    const int* __restrict__ hdr, int nwx, int deal, unsigned* lds)
 {
+    static_assert(NF == 2 || NF == 4, "a 4-wave workgroup is 4 / NF entry waves x NF frames");
+    const int xcd = blockIdx.x & 7, wg = (int)(blockIdx.x >> 3);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int fr = wave, first = wg, w = wg;   // the frame, the workgroup's first entry wave, this wave's
+    if constexpr (NF == 2) {
+        fr = deal ? (wg & 1) : (wave & 1);
+        first = deal ? (wg >> 1) * 4 : wg * 2;
+        w = first + (deal ? wave : (wave >> 1));
+    }
+    const int begin = hdr[xcd], all = hdr[xcd + 1] - begin;
+    const int marched = min(hdr[kRegionWork + xcd], all);
+    MarchArgs a = g.c;
+    set_frame(&a, g.fr[fr]);
+    const int count = a.empty_fill ? marched : all;
+    if (a.empty_fill) fill_empty_tiles(a, tiles, begin, count, all, w, nwx);
+    bool every = g.fr[0].empty_fill;   // the largest of the frames' marched counts: marched <= all
+    for (int k = 1; k < NF; ++k) every = every && g.fr[k].empty_fill;
+    if (first >= (every ? marched : all)) return;   // whole workgroup, before the barrier
+    FastCtx f = fast_prologue<LAYOUT>(g.c, lds);   // volume and layout geometry: the frames' common part
     if constexpr (LAYOUT == LAYOUT_CORNERH)   // the one per-frame part of the prologue
         for (int c = 0; c < 4; ++c) f.oz[c] = noise::in_vgpr(a.tap_T[c][2]);
     const int lane = threadIdx.x & 63;
@@ -1216,85 +1239,20 @@ __device__ __forceinline__ void pair_frame(const MarchArgs& a, FastCtx f, const 
     }
     if (a.step_counter) add_steps(a, steps);
 }
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
-__device__ __forceinline__ void regions_pair_body(const MarchArgs& a0, const MarchArgs& a1, const unsigned* __restrict__ tiles,
-                                                  const int* __restrict__ hdr, int nwx, int deal, unsigned* lds)
-{
-    const int xcd = blockIdx.x & 7, g = (int)(blockIdx.x >> 3);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int fr = deal ? (g & 1) : (wave & 1);
-    const int first = deal ? (g >> 1) * 4 : g * 2;   // the workgroup's first entry wave
-    const int w = first + (deal ? wave : (wave >> 1));
-    const int begin = hdr[xcd], all = hdr[xcd + 1] - begin;
-    const int marched = min(hdr[kRegionWork + xcd], all);
-    const int count0 = a0.empty_fill ? marched : all, count1 = a1.empty_fill ? marched : all;
-    if (fr) {
-        if (a1.empty_fill) fill_empty_tiles(a1, tiles, begin, count1, all, w, nwx);
-    } else {
-        if (a0.empty_fill) fill_empty_tiles(a0, tiles, begin, count0, all, w, nwx);
-    }
-    if (first >= max(count0, count1)) return;   // whole workgroup (either deal), before the barrier
-    const FastCtx f = fast_prologue<LAYOUT>(a0, lds);   // volume and layout geometry: the frames' common part
-    if (fr) pair_frame<LAYOUT, WRAP, EARLY, ZO, UM>(a1, f, tiles, begin, count1, w, nwx);
-    else pair_frame<LAYOUT, WRAP, EARLY, ZO, UM>(a0, f, tiles, begin, count0, w, nwx);
-}
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO>
-__global__ __launch_bounds__(kThreads) void march_regions_pair(const MarchArgs a0, const MarchArgs a1,
-                                                              const unsigned* __restrict__ tiles,
-                                                              const int* __restrict__ hdr, int nwx, int deal)
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF>
+__global__ __launch_bounds__(kThreads) void march_regions_frames(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
+                                                                const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_pair_body<LAYOUT, WRAP, EARLY, ZO, 0>(a0, a1, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF>(g, tiles, hdr, nwx, deal, lds);
 }
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
-__global__ __launch_bounds__(kThreads) VR_UM_ATTR void march_regions_pair_u(const MarchArgs a0, const MarchArgs a1,
-                                                                           const unsigned* __restrict__ tiles,
-                                                                           const int* __restrict__ hdr, int nwx, int deal)
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF>
+__global__ __launch_bounds__(kThreads) VR_UM_ATTR void march_regions_frames_u(const FramesArgs<NF> g,
+                                                                             const unsigned* __restrict__ tiles,
+                                                                             const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_pair_body<LAYOUT, WRAP, EARLY, ZO, UM>(a0, a1, tiles, hdr, nwx, deal, lds);
-}
-
-// ---- four frames in one launch (vr_render_group) ----
-// A workgroup is one list entry x four frames: wave f of it marches the entry with frame
-// f's arguments, so all four readers of the entry's bricks sit behind one L1.  The frames
-// travel as one MarchArgs (frame 0's: the launch's common part) and FrameArgs fr[4]
-// (vr_internal.h).  There is one copy of the march: wave f's MarchArgs is the common part
-// with fr[f] laid over it -- scalar loads at the wave-uniform index f -- and equals what a
-// plain render of frame f passes.  XCD x runs nwx workgroups; workgroup w takes the entries
-// w, w + nwx, ...
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
-__device__ __forceinline__ void regions_group_body(const GroupArgs& g, const unsigned* __restrict__ tiles,
-                                                   const int* __restrict__ hdr, int nwx, unsigned* lds)
-{
-    const int xcd = blockIdx.x & 7, w = (int)(blockIdx.x >> 3);
-    const int fr = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int begin = hdr[xcd], all = hdr[xcd + 1] - begin;
-    const int marched = min(hdr[kRegionWork + xcd], all);
-    MarchArgs a = g.c;
-    set_frame(&a, g.fr[fr]);
-    const int count = a.empty_fill ? marched : all;
-    if (a.empty_fill) fill_empty_tiles(a, tiles, begin, count, all, w, nwx);
-    // the largest of the four frames' marched counts
-    const bool every = g.fr[0].empty_fill && g.fr[1].empty_fill && g.fr[2].empty_fill && g.fr[3].empty_fill;
-    if (w >= (every ? marched : all)) return;   // whole workgroup, before the barrier
-    const FastCtx f = fast_prologue<LAYOUT>(g.c, lds);   // volume and layout geometry: the frames' common part
-    pair_frame<LAYOUT, WRAP, EARLY, ZO, UM>(a, f, tiles, begin, count, w, nwx);
-}
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO>
-__global__ __launch_bounds__(kThreads) void march_regions_group(const GroupArgs g, const unsigned* __restrict__ tiles,
-                                                               const int* __restrict__ hdr, int nwx)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_group_body<LAYOUT, WRAP, EARLY, ZO, 0>(g, tiles, hdr, nwx, lds);
-}
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM>
-__global__ __launch_bounds__(kThreads) VR_UM_ATTR void march_regions_group_u(const GroupArgs g,
-                                                                            const unsigned* __restrict__ tiles,
-                                                                            const int* __restrict__ hdr, int nwx)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_group_body<LAYOUT, WRAP, EARLY, ZO, UM>(g, tiles, hdr, nwx, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF>(g, tiles, hdr, nwx, deal, lds);
 }
 
 
@@ -2202,72 +2160,50 @@ hipError_t launch_lw(const MarchArgs& a, bool early, const Schedule& sc, hipStre
     return hipGetLastError();
 }
 
-// The paired launch (march_regions_pair): the kernels of launch_lw's one-lane regions
-// dispatch above -- one uniform channel (_u) or the general kernel -- for two frames.
+// The multi-frame launch (march_regions_frames): the kernels of launch_lw's one-lane regions
+// dispatch above -- one uniform channel (_u) or the general kernel -- for NF frames.
 // The caller has checked that the frames share the plan and everything but the per-frame
-// arguments (vr_api.cpp), that sc is a regions schedule without split, slab or wide
-// workgroups, and that L is one of the three layouts instantiated here.
-template <int L, int W>
-hipError_t launch_pair_lw(const MarchArgs& a0, const MarchArgs& a1, bool early, const Schedule& sc, int deal, hipStream_t s)
+// arguments (vr_render.cpp), that sc is a regions schedule without split, slab or wide
+// workgroups, and that L is one of the three layouts instantiated here.  XCD x runs
+// sc.map.nwx entry waves, 4 / NF to a workgroup (regions_frames_body).
+template <int L, int W, int NF>
+hipError_t launch_frames_lw(const MarchArgs& a, const FrameArgs* fr, bool early, const Schedule& sc, int deal, hipStream_t s)
 {
-    static_assert(2 * sizeof(MarchArgs) + 64 <= 4096, "two MarchArgs travel in the 4-KiB kernarg segment");
-    const size_t lds = L == LAYOUT_CORNERH ? 0 : (size_t)(a0.nx + a0.ny + a0.nz + 3) * sizeof(unsigned);
-    const dim3 block(kThreads);
-    const int nwx = sc.map.nwx;
-    const dim3 grid((unsigned)(deal ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
-    const int um = a0.umask;
-    if (!early && a0.zero_offsets && (um == 1 || um == 2 || um == 4 || um == 8)) {
-#define VR_UMP(U) hipLaunchKernelGGL((march_regions_pair_u<L, W, false, true, U>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal)
-        if (um == 1) VR_UMP(1);
-        else if (um == 2) VR_UMP(2);
-        else if (um == 4) VR_UMP(4);
-        else VR_UMP(8);
-#undef VR_UMP
-        return hipGetLastError();
-    }
-    if (early && a0.zero_offsets)
-        hipLaunchKernelGGL((march_regions_pair<L, W, true, true>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
-    else if (early)
-        hipLaunchKernelGGL((march_regions_pair<L, W, true, false>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
-    else if (a0.zero_offsets)
-        hipLaunchKernelGGL((march_regions_pair<L, W, false, true>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
-    else
-        hipLaunchKernelGGL((march_regions_pair<L, W, false, false>), grid, block, lds, s, a0, a1, sc.tiles, sc.hdr, nwx, deal);
-    return hipGetLastError();
-}
-
-// The grouped launch (march_regions_group): launch_pair_lw's dispatch for four frames, a
-// workgroup per list entry wave -- XCD x runs sc.map.nwx workgroups of four waves.
-template <int L, int W>
-hipError_t launch_group_lw(const MarchArgs& a, const FrameArgs fr[kGroupFrames], bool early, const Schedule& sc, hipStream_t s)
-{
-    GroupArgs g;
+    FramesArgs<NF> g;
     g.c = a;
-    for (int k = 0; k < kGroupFrames; ++k) g.fr[k] = fr[k];
+    for (int k = 0; k < NF; ++k) g.fr[k] = fr[k];
     const size_t lds = L == LAYOUT_CORNERH ? 0 : (size_t)(a.nx + a.ny + a.nz + 3) * sizeof(unsigned);
     const dim3 block(kThreads);
-    static_assert(kThreads == 64 * kGroupFrames, "a workgroup is one entry x four frames");
+    static_assert(kThreads == 64 * 4, "a workgroup is 4 / NF entry waves x NF frames");
     const int nwx = sc.map.nwx;
-    const dim3 grid((unsigned)(8 * nwx));
+    if (NF == 4) deal = 0;   // the four-frame kernel has one deal
+    const dim3 grid((unsigned)(NF == 4 ? 8 * nwx : deal ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
     const int um = a.umask;
     if (!early && a.zero_offsets && (um == 1 || um == 2 || um == 4 || um == 8)) {
-#define VR_UMG(U) hipLaunchKernelGGL((march_regions_group_u<L, W, false, true, U>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx)
-        if (um == 1) VR_UMG(1);
-        else if (um == 2) VR_UMG(2);
-        else if (um == 4) VR_UMG(4);
-        else VR_UMG(8);
-#undef VR_UMG
+#define VR_UMF(U) hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal)
+        if (um == 1) VR_UMF(1);
+        else if (um == 2) VR_UMF(2);
+        else if (um == 4) VR_UMF(4);
+        else VR_UMF(8);
+#undef VR_UMF
         return hipGetLastError();
     }
     if (early && a.zero_offsets)
-        hipLaunchKernelGGL((march_regions_group<L, W, true, true>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx);
+        hipLaunchKernelGGL((march_regions_frames<L, W, true, true, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal);
     else if (early)
-        hipLaunchKernelGGL((march_regions_group<L, W, true, false>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx);
+        hipLaunchKernelGGL((march_regions_frames<L, W, true, false, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal);
     else if (a.zero_offsets)
-        hipLaunchKernelGGL((march_regions_group<L, W, false, true>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx);
+        hipLaunchKernelGGL((march_regions_frames<L, W, false, true, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal);
     else
-        hipLaunchKernelGGL((march_regions_group<L, W, false, false>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx);
+        hipLaunchKernelGGL((march_regions_frames<L, W, false, false, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal);
     return hipGetLastError();
+}
+template <int L, int W>
+hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc, int deal, hipStream_t s)
+{
+    if (nf == 2) return launch_frames_lw<L, W, 2>(a, fr, early, sc, deal, s);
+    if (nf == kGroupFrames) return launch_frames_lw<L, W, kGroupFrames>(a, fr, early, sc, deal, s);
+    return hipErrorInvalidValue;   // no kernel for this many frames
 }
 
 }  // namespace

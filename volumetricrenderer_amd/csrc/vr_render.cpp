@@ -2,7 +2,7 @@
 // vr_render_sequence, vr_render_pair and vr_render_group (include/vr.h).
 //
 // A grid frame goes from a vr_target to a launch in named steps, which
-// vr_render, vr_render_pair and vr_render_group call:
+// vr_render and render_frames (vr_render_pair, vr_render_group) call:
 //   check_target -> honour_inject_throw -> cache_hit, or else
 //   grid_frame_args -> attach_regions (regions schedule) -> launch_frame,
 // where launch_frame remembers a planned frame in the launch cache.  A
@@ -249,7 +249,7 @@ vr_status render_procedural_frame(Ctx* c, const vr_target* t, const TargetInfo& 
     return render_procedural(c, a, pl.early, hs);
 }
 
-// vr_render_pair's first frame, planned as vr_render plans it (the checks,
+// render_frames' first frame, planned as vr_render plans it (the checks,
 // inject_throw, the cached frame or a planned one with its lists) but not
 // launched.  Its errors are vr_render's, a caught exception included.
 vr_status plan_first_frame(Ctx* c, const vr_target* t, hipStream_t hs, TargetInfo* ti, GridFrame* f)
@@ -298,6 +298,102 @@ bool same_region_camera(const GridFrame& f0, const GridFrame& f1)
            std::memcmp(a.r3, b.r3, sizeof a.r3) == 0;
 }
 
+// vr_render_pair's and vr_render_group's targets: one geometry, format, band selection and
+// step counter, n buffers (t[0] itself is checked by frame 0's plan)
+vr_status check_targets_agree(const char* fn, const vr_target* t, int n)
+{
+    for (int k = 1; k < n; ++k) {
+        // field by field: the structs' padding is the caller's
+        const vr_target &a = t[0], &b = t[k];
+        if (a.width != b.width || a.height != b.height || a.format != b.format || a.band_rows != b.band_rows ||
+            a.band_stride != b.band_stride || a.band_first != b.band_first || a.row_pitch != b.row_pitch ||
+            a.step_counter != b.step_counter || a.band_flip != b.band_flip || a.reserved != b.reserved)
+            return fail(VR_ERR_INVALID, "%s: the targets must agree in everything but pixels", fn);
+        const int f = a.format & ~(VR_TARGET_BANDS_IN_PLACE | VR_TARGET_ROW_RANGE);
+        if (!b.pixels || (f >= 0 && f <= 5 && (uintptr_t)b.pixels % format_bytes(f) != 0))
+            return fail(VR_ERR_INVALID, "%s: target %d's pixels are null or misaligned", fn, k);
+    }
+    return VR_OK;
+}
+
+// Frames i..n-1 as ordinary renders, in order, each with its own shader data
+vr_status render_plain(void* p, const vr_target* t, int i, int n, const vr_object_shader_data* osd,
+                       const vr_global_shader_data* gsd, void* stream)
+{
+    vr_status st = VR_OK;
+    for (; i < n && st == VR_OK; ++i) {
+        if (osd) st = vr_set_shader_data(p, &osd[i], &gsd[i]);
+        if (st == VR_OK) st = vr_render(p, &t[i], stream);
+    }
+    return st;
+}
+
+// n = 2 or 4 queued frames in one launch (vr_render_pair, vr_render_group), or as ordinary
+// renders where there is no such launch for them.  The targets agree (check_targets_agree).
+vr_status render_frames(void* p, const vr_target* t, int n, const vr_object_shader_data* osd,
+                        const vr_global_shader_data* gsd, void* stream)
+{
+    Ctx* c = as_ctx(p);
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (c->proc.enabled) return render_plain(p, t, 0, n, osd, gsd, stream);   // a procedural medium
+    if (osd) {
+        const vr_status st = vr_set_shader_data(p, &osd[0], &gsd[0]);
+        if (st != VR_OK) return st;
+    }
+    // frame 0: vr_render's whole path (checks, plan, region lists) up to the launch
+    TargetInfo ti;
+    GridFrame f[VR_MAX_GROUP];
+    vr_status st = plan_first_frame(c, &t[0], hs, &ti, &f[0]);
+    if (st != VR_OK) return st;
+    const unsigned long long gen0 = c->gen;
+    // launched alone it is remembered under gen0, unless it came from the cache: no second entry for it
+    const auto frame0_alone = [&] {
+        return launch_frame(c, f[0], cached_frame(c, &t[0], hs, gen0) ? nullptr : &t[0], gen0, hs);
+    };
+    const bool groupable = f[0].kind == SCHED_REGIONS && f[0].sc.split <= 1 && !f[0].sc.slab && f[0].sc.wg_waves == 4 &&
+                           pair_layout(f[0].pl.layout) && f[0].pl.wrap == WRAP_CLAMP;
+    bool grouped = groupable;
+    for (int k = 1; k < n && groupable; ++k) {
+        // frame k: its arguments and plan only (the lists are frame 0's); t[k] passed t[0]'s checks
+        if (osd) st = vr_set_shader_data(p, &osd[k], &gsd[k]);
+        if (st == VR_OK) st = grid_frame_args(c, &t[k], ti, &f[k]);
+        if (st != VR_OK) {   // frames 0..k-1 still render (frame 0 is planned and counted)
+            const std::string msg = g_err;
+            vr_status rs = frame0_alone();
+            if (rs == VR_OK) rs = render_plain(p, t, 1, k, osd, gsd, stream);
+            if (osd) (void)vr_set_shader_data(p, &osd[k], &gsd[k]);   // the ctx holds what the failed frame set
+            g_err = msg;
+            return st;
+        }
+        grouped = grouped && f[k].kind == f[0].kind && pair_compatible(f[0], f[k]);
+    }
+    if (!grouped) {
+        // no multi-frame kernel for this plan (split rays, the slab, an experiment schedule, a
+        // layout without an instance), or frames whose plans differ: the ordinary renders
+        st = frame0_alone();
+        return st == VR_OK ? render_plain(p, t, 1, n, osd, gsd, stream) : st;
+    }
+    // frame k fills the lists' empty tiles only where they are its own (attach_regions'
+    // region_exact rule); a launch one frame of which marches every entry keeps the
+    // unreduced wave count
+    const Ctx::RegionBuf& rb = c->region[c->region_cur];
+    FrameArgs fr[VR_MAX_GROUP];
+    bool every = f[0].a.empty_fill != 0;
+    for (int k = 0; k < n; ++k) {
+        if (k > 0) f[k].a.empty_fill = f[0].a.empty_fill && same_region_camera(f[0], f[k]) ? 1 : 0;
+        every = every && f[k].a.empty_fill;
+        fr[k] = frame_part(f[k].a);
+    }
+    Schedule sc = f[0].sc;
+    if (f[0].a.empty_fill && !every) sc.map.nwx = std::max(1, rb.map.nwx);
+    HIP_TRY(launch_march_frames(f[0].a, fr, n, f[0].pl.layout, f[0].pl.early, sc, c->pair_deal, hs));
+    c->group_launches += n == VR_MAX_GROUP;
+    c->pair_launches += n / 2;   // (pairs of frames that shared a launch)
+    c->renders_since_build += n - 1;   // the later renders with these lists (build_regions counted the first)
+    c->region_slot = f[0].slot;
+    return note_region_render(c, hs);
+}
+
 }  // namespace
 
 extern "C" {
@@ -343,66 +439,9 @@ vr_status vr_render_pair(void* p, const vr_target* t0, const vr_target* t1, cons
                          const vr_global_shader_data* gsd, void* stream)
 try {
     if (!p || !t0 || !t1 || (!osd) != (!gsd)) return fail(VR_ERR_INVALID, "vr_render_pair: bad argument");
-    // field by field: the structs' padding is the caller's
-    if (t0->width != t1->width || t0->height != t1->height || t0->format != t1->format || t0->band_rows != t1->band_rows ||
-        t0->band_stride != t1->band_stride || t0->band_first != t1->band_first || t0->row_pitch != t1->row_pitch ||
-        t0->step_counter != t1->step_counter || t0->band_flip != t1->band_flip || t0->reserved != t1->reserved)
-        return fail(VR_ERR_INVALID, "vr_render_pair: the two targets must agree in everything but pixels");
-    {
-        const int f = t0->format & ~(VR_TARGET_BANDS_IN_PLACE | VR_TARGET_ROW_RANGE);
-        if (!t1->pixels || (f >= 0 && f <= 5 && (uintptr_t)t1->pixels % format_bytes(f) != 0))
-            return fail(VR_ERR_INVALID, "vr_render_pair: the second target's pixels are null or misaligned");
-    }
-    Ctx* c = as_ctx(p);
-    const hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (osd) {
-        const vr_status st = vr_set_shader_data(p, &osd[0], &gsd[0]);
-        if (st != VR_OK) return st;
-    }
-    if (c->proc.enabled) {   // a procedural medium: the two ordinary renders
-        vr_status st = vr_render(p, t0, stream);
-        if (st == VR_OK && osd) st = vr_set_shader_data(p, &osd[1], &gsd[1]);
-        return st == VR_OK ? vr_render(p, t1, stream) : st;
-    }
-    // frame 0: vr_render's whole path (checks, plan, region lists) up to the launch
-    TargetInfo ti;
-    GridFrame f0, f1;
-    vr_status st = plan_first_frame(c, t0, hs, &ti, &f0);
-    if (st != VR_OK) return st;
-    const unsigned long long gen0 = c->gen;
-    // launched alone it is remembered under gen0, unless it came from the cache: no second entry for it
-    const auto frame0_alone = [&] { return launch_frame(c, f0, cached_frame(c, t0, hs, gen0) ? nullptr : t0, gen0, hs); };
-    const bool pairable = f0.kind == SCHED_REGIONS && f0.sc.split <= 1 && !f0.sc.slab && f0.sc.wg_waves == 4 &&
-                          pair_layout(f0.pl.layout) && f0.pl.wrap == WRAP_CLAMP;
-    bool paired = false;
-    if (pairable) {
-        // frame 1: its arguments and plan only (the lists are frame 0's); t1 passed t0's checks
-        if (osd) st = vr_set_shader_data(p, &osd[1], &gsd[1]);
-        if (st == VR_OK) st = grid_frame_args(c, t1, ti, &f1);
-        if (st != VR_OK) {   // frame 0 is planned and counted: it still renders
-            (void)frame0_alone();
-            return st;
-        }
-        paired = f1.kind == f0.kind && pair_compatible(f0, f1);
-    }
-    if (!paired) {
-        // no paired kernel for this plan (split rays, the slab, an experiment schedule, a
-        // layout without an instance, frames whose plans differ): the two ordinary renders
-        st = frame0_alone();
-        if (st == VR_OK && osd && !pairable) st = vr_set_shader_data(p, &osd[1], &gsd[1]);
-        return st == VR_OK ? vr_render(p, t1, stream) : st;
-    }
-    // frame 1 fills the lists' empty tiles only where they are its own (attach_regions'
-    // region_exact rule); a frame that marches every entry keeps the unreduced wave count
-    const Ctx::RegionBuf& rb = c->region[c->region_cur];
-    f1.a.empty_fill = f0.a.empty_fill && same_region_camera(f0, f1) ? 1 : 0;
-    Schedule sc = f0.sc;
-    if (f0.a.empty_fill && !f1.a.empty_fill) sc.map.nwx = std::max(1, rb.map.nwx);
-    HIP_TRY(launch_march_pair(f0.a, f1.a, f0.pl.layout, f0.pl.early, sc, c->pair_deal, hs));
-    ++c->pair_launches;
-    ++c->renders_since_build;   // the second render with these lists (build_regions counted the first)
-    c->region_slot = f0.slot;
-    return note_region_render(c, hs);
+    const vr_target t[2] = {*t0, *t1};
+    if (const vr_status st = check_targets_agree("vr_render_pair", t, 2)) return st;
+    return render_frames(p, t, 2, osd, gsd, stream);
 } catch (...) {
     return caught_exception("vr_render_pair");
 }
@@ -411,99 +450,20 @@ vr_status vr_render_group(void* p, const vr_target* t, int n, const vr_object_sh
                           const vr_global_shader_data* gsd, void* stream)
 try {
     if (!p || !t || n < 1 || n > VR_MAX_GROUP || (!osd) != (!gsd)) return fail(VR_ERR_INVALID, "vr_render_group: bad argument");
-    // frames i..n-1 as ordinary renders, in order, each with its own shader data
-    const auto plain_from = [&](int i) {
-        vr_status st = VR_OK;
-        for (; i < n && st == VR_OK; ++i) {
-            if (osd) st = vr_set_shader_data(p, &osd[i], &gsd[i]);
-            if (st == VR_OK) st = vr_render(p, &t[i], stream);
-        }
-        return st;
-    };
-    for (int k = 1; k < n; ++k) {
-        // field by field: the structs' padding is the caller's
-        const vr_target &a = t[0], &b = t[k];
-        if (a.width != b.width || a.height != b.height || a.format != b.format || a.band_rows != b.band_rows ||
-            a.band_stride != b.band_stride || a.band_first != b.band_first || a.row_pitch != b.row_pitch ||
-            a.step_counter != b.step_counter || a.band_flip != b.band_flip || a.reserved != b.reserved)
-            return fail(VR_ERR_INVALID, "vr_render_group: the targets must agree in everything but pixels");
-        const int f = a.format & ~(VR_TARGET_BANDS_IN_PLACE | VR_TARGET_ROW_RANGE);
-        if (!b.pixels || (f >= 0 && f <= 5 && (uintptr_t)b.pixels % format_bytes(f) != 0))
-            return fail(VR_ERR_INVALID, "vr_render_group: target %d's pixels are null or misaligned", k);
-    }
+    if (const vr_status st = check_targets_agree("vr_render_group", t, n)) return st;
     int launches[3];
     const int nl = vr_group_split(n, launches);
-    if (launches[0] != VR_MAX_GROUP) {   // n < 4: a pair and / or a plain render, vr_render_pair's and vr_render's paths
-        int i = 0;
-        for (int l = 0; l < nl; ++l) {
-            const vr_status st = launches[l] == 2 ? vr_render_pair(p, &t[i], &t[i + 1], osd ? &osd[i] : nullptr,
-                                                                   gsd ? &gsd[i] : nullptr, stream)
-                                                  : plain_from(i);
-            if (st != VR_OK) return st;
-            i += launches[l];
-        }
-        return VR_OK;
-    }
-    Ctx* c = as_ctx(p);
-    const hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (c->proc.enabled) return plain_from(0);   // a procedural medium: the ordinary renders
-    if (osd) {
-        const vr_status st = vr_set_shader_data(p, &osd[0], &gsd[0]);
+    if (launches[0] == VR_MAX_GROUP) return render_frames(p, t, n, osd, gsd, stream);
+    // n < 4: a pair and / or a plain render, vr_render_pair's and vr_render's paths
+    int i = 0;
+    for (int l = 0; l < nl; ++l) {
+        const vr_status st = launches[l] == 2 ? vr_render_pair(p, &t[i], &t[i + 1], osd ? &osd[i] : nullptr,
+                                                               gsd ? &gsd[i] : nullptr, stream)
+                                              : render_plain(p, t, i, n, osd, gsd, stream);
         if (st != VR_OK) return st;
+        i += launches[l];
     }
-    // frame 0: vr_render's whole path (checks, plan, region lists) up to the launch
-    TargetInfo ti;
-    GridFrame f[VR_MAX_GROUP];
-    vr_status st = plan_first_frame(c, &t[0], hs, &ti, &f[0]);
-    if (st != VR_OK) return st;
-    const unsigned long long gen0 = c->gen;
-    const auto frame0_alone = [&] {
-        return launch_frame(c, f[0], cached_frame(c, &t[0], hs, gen0) ? nullptr : &t[0], gen0, hs);
-    };
-    const bool groupable = f[0].kind == SCHED_REGIONS && f[0].sc.split <= 1 && !f[0].sc.slab && f[0].sc.wg_waves == 4 &&
-                           pair_layout(f[0].pl.layout) && f[0].pl.wrap == WRAP_CLAMP;
-    bool grouped = groupable;
-    for (int k = 1; k < n && groupable; ++k) {
-        // frame k: its arguments and plan only (the lists are frame 0's); t[k] passed t[0]'s checks
-        if (osd) st = vr_set_shader_data(p, &osd[k], &gsd[k]);
-        if (st == VR_OK) st = grid_frame_args(c, &t[k], ti, &f[k]);
-        if (st != VR_OK) {   // frames 0..k-1 still render (frame 0 is planned and counted)
-            const std::string msg = g_err;
-            vr_status rs = frame0_alone();
-            for (int j = 1; j < k && rs == VR_OK; ++j) {
-                if (osd) rs = vr_set_shader_data(p, &osd[j], &gsd[j]);
-                if (rs == VR_OK) rs = vr_render(p, &t[j], stream);
-            }
-            if (osd) (void)vr_set_shader_data(p, &osd[k], &gsd[k]);   // the ctx holds what the failed frame set
-            g_err = msg;
-            return st;
-        }
-        grouped = grouped && f[k].kind == f[0].kind && pair_compatible(f[0], f[k]);
-    }
-    if (!grouped) {
-        // no grouped kernel for this plan, or frames whose plans differ: the ordinary renders
-        st = frame0_alone();
-        return st == VR_OK ? plain_from(1) : st;
-    }
-    // frame k fills the lists' empty tiles only where they are its own (attach_regions'
-    // region_exact rule); a group one frame of which marches every entry keeps the
-    // unreduced wave count
-    const Ctx::RegionBuf& rb = c->region[c->region_cur];
-    FrameArgs fr[kGroupFrames];
-    bool every = f[0].a.empty_fill != 0;
-    for (int k = 0; k < n; ++k) {
-        if (k > 0) f[k].a.empty_fill = f[0].a.empty_fill && same_region_camera(f[0], f[k]) ? 1 : 0;
-        every = every && f[k].a.empty_fill;
-        fr[k] = frame_part(f[k].a);
-    }
-    Schedule sc = f[0].sc;
-    if (f[0].a.empty_fill && !every) sc.map.nwx = std::max(1, rb.map.nwx);
-    HIP_TRY(launch_march_group(f[0].a, fr, f[0].pl.layout, f[0].pl.early, sc, hs));
-    ++c->group_launches;
-    c->pair_launches += 2;   // (two pairs of frames shared this launch)
-    c->renders_since_build += n - 1;   // the later renders with these lists (build_regions counted the first)
-    c->region_slot = f[0].slot;
-    return note_region_render(c, hs);
+    return VR_OK;
 } catch (...) {
     return caught_exception("vr_render_group");
 }
