@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "vr_dispatch.h"
 
 namespace vr {
 
@@ -78,13 +79,35 @@ __host__ __device__ constexpr bool is_b4_family(int l)
 #ifndef VR_EXPERIMENTS
 #define VR_EXPERIMENTS 0
 #endif
-__host__ __device__ constexpr bool layout_built(int l)
-{
-    return VR_EXPERIMENTS || l == LAYOUT_PLANAR || l == LAYOUT_CORNER8 || l == LAYOUT_CORNERH || l == LAYOUT_COL48 ||
-           l == LAYOUT_BRICK4832;
-}
+// The layouts each march translation unit instantiates; a launcher reaches a kernel only
+// through with_layout over one of these (vr_dispatch.h), so a layout outside its unit's
+// list is an error there, never another kernel.
+#if VR_EXPERIMENTS
+using ExperimentLayouts = value_list<LAYOUT_BRICK4, LAYOUT_BRICK448, LAYOUT_BRICK488, LAYOUT_BRICK4816, LAYOUT_BRICK4864,
+                                     LAYOUT_BRICK41616, LAYOUT_COL48Z, LAYOUT_ZPAIR, LAYOUT_BRICK5, LAYOUT_BRICK8,
+                                     LAYOUT_BRICK16>;
+#else
+using ExperimentLayouts = value_list<>;
+#endif
+using MarchLayouts = list_cat_t<value_list<LAYOUT_PLANAR, LAYOUT_COL48, LAYOUT_BRICK4832>, ExperimentLayouts>;   // vr_march.hip
+using CornerLayouts = value_list<LAYOUT_CORNER8, LAYOUT_CORNERH>;   // vr_march_c8.hip, compiled in parallel with it
+using BuiltLayouts = list_cat_t<MarchLayouts, CornerLayouts>;       // every layout of this build: vr_march_rect.hip
+// the multi-frame kernels (march_regions_frames); CORNERH's are vr_march_c8.hip's
+using FrameLayouts = value_list<LAYOUT_COL48, LAYOUT_BRICK4832, LAYOUT_CORNERH>;
+constexpr bool layout_built(int l) { return list_has(BuiltLayouts{}, l); }
 
 enum Wrap : int { WRAP_CLAMP = 0, WRAP_MIRROR = 1 };
+// with_layout, and the wrap mode: f(layout tag, wrap tag).  Only PLANAR has WRAP_MIRROR;
+// the fast layouts store clamp-to-edge footprints and run where the two agree.
+template <class LayoutList, class F>
+hipError_t with_layout_wrap(int layout, int wrap, F&& f)
+{
+    return with_layout<LayoutList>(layout, [&](auto L) {
+        if constexpr (L == LAYOUT_PLANAR)
+            if (wrap != WRAP_CLAMP) return f(L, std::integral_constant<int, WRAP_MIRROR>{});
+        return f(L, std::integral_constant<int, WRAP_CLAMP>{});
+    });
+}
 
 // Geometry of a fast layout for one channel (host and device).
 struct LayoutGeom {
@@ -216,6 +239,31 @@ struct MarchArgs {
     ProcParams proc;
     int slab_cap;                // LDS slab march (COL48): chunks per channel the slab holds
 };
+
+// Dynamic LDS of a march kernel: the per-axis offset tables of fast_prologue
+// (vr_march_kernels.h; COL48Z keeps a second set for channel 3's ZPAIR plane);
+// PLANAR and CORNERH compute their offsets
+template <int L>
+constexpr size_t march_lds_bytes(const MarchArgs& a)
+{
+    if (L == LAYOUT_PLANAR || L == LAYOUT_CORNERH) return 0;
+    return (size_t)(a.nx + a.ny + a.nz + 3) * sizeof(unsigned) * (L == LAYOUT_COL48Z ? 2 : 1);
+}
+
+// The _u kernels (march_regions_u, march_regions_frames_u, march_regions_split's UM): a
+// regions march that skips the loads of one uniform channel.  They are built for these
+// layouts, without early-out, for zero tap offsets and for exactly one uniform channel;
+// every other case runs the general kernel, which is exact too.  u_kernel_channel: the
+// channel a _u kernel skips (the kernel's UM is 1 << channel = umask), or -1 for none.
+constexpr bool has_u_kernels(int l)
+{
+    return l == LAYOUT_COL48 || l == LAYOUT_BRICK4832 || l == LAYOUT_CORNERH || l == LAYOUT_COL48Z;
+}
+constexpr int u_kernel_channel(bool early, bool zero_offsets, int umask)
+{
+    if (early || !zero_offsets) return -1;
+    return umask == 1 ? 0 : umask == 2 ? 1 : umask == 4 ? 2 : umask == 8 ? 3 : -1;
+}
 
 // The part of MarchArgs that differs between the frames of one multi-frame launch
 // (vr_render_pair, vr_render_group): the camera (ray basis, r2 / r3, cam, tap_T), the
@@ -435,7 +483,7 @@ hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, co
 // arguments, fr[k] frame k's per-frame part (the frames differ in nothing else), sc is a
 // regions schedule with one lane per ray (no split, no slab, 4-wave workgroups); deal
 // (nf = 2 only) 0 = the frame in the wave's parity, 1 = in the workgroup's (vr_march_kernels.h)
-bool pair_layout(int layout);
+constexpr bool pair_layout(int layout) { return list_has(FrameLayouts{}, layout); }
 hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
                                int deal, hipStream_t s);
 hipError_t launch_march_frames_cornerh(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc,

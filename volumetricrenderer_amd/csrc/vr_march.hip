@@ -40,8 +40,7 @@ hipError_t launch_march_procedural(const MarchArgs& a, bool early, void* sort_bu
 {
     if (a.width <= 0 || a.out_rows <= 0) return hipSuccess;
     const bool shadow = a.proc.shadow_steps > 0;
-    const size_t wt_bytes =
-        a.proc.wt_n > 0 ? ((size_t)a.proc.wt_n * a.proc.wt_pz + 512) * sizeof(float4) : 0;
+    const size_t wt_bytes = worley_table_bytes(a.proc);
     if (sort_buf) {
         const SortLayout L = sort_layout(a.width, a.out_rows);
         char* sb = static_cast<char*>(sort_buf);
@@ -79,46 +78,34 @@ hipError_t launch_march_procedural(const MarchArgs& a, bool early, void* sort_bu
         // tables: 2 = the fixed 9-cell Worley geometry (compile-time offsets), 1 = runtime geometry,
         // 3 = 2 + the Perlin lattice table
         const int tm = wt_bytes ? (a.proc.wt_fixed ? (a.proc.lat ? 3 : 2) : 1) : 0;
+        const bool stale = reuse_sort == SORT_STALE;
         if (shadow && defer && tm >= 2) {   // deferred shadow rays: three passes (vr_march_kernels.h)
             const ShadowDefer d = *defer;
-            const bool stale = reuse_sort == SORT_STALE;
-#define VR_PD(E, T)                                                                                                  \
-    do {                                                                                                             \
-        hipLaunchKernelGGL((march_proc_defer<E, T>), g4, dim3(kThreads), wt_bytes, s, a, order, total, keys,        \
-                           positions, march_blocks, stale, d);                                                       \
-        hipLaunchKernelGGL(proc_shadow_scan, dim3(1), dim3(kScanThreads), 0, s, total, d);                          \
-        hipLaunchKernelGGL(proc_shadow_map, dim3((d.waves + 3) / 4), dim3(kThreads), 0, s, total, d);               \
-        if (d.worley_cache == 2) hipLaunchKernelGGL((proc_shadow_eval8<T>), dim3(d.eval_blocks ? d.eval_blocks : kShadowEvalBlocks), dim3(kThreads), wt_bytes, s, a, d); \
-        else if (d.worley_cache) hipLaunchKernelGGL((proc_shadow_eval<T, true>), dim3(d.eval_blocks ? d.eval_blocks : kShadowEvalBlocks), dim3(kThreads), wt_bytes, s, a, d); \
-        else hipLaunchKernelGGL((proc_shadow_eval<T, false>), dim3(d.eval_blocks ? d.eval_blocks : kShadowEvalBlocks), dim3(kThreads), wt_bytes, s, a, d); \
-    } while (0)
-            if (tm == 3) {
-                if (early) VR_PD(true, 3); else VR_PD(false, 3);
-            } else {
-                if (early) VR_PD(true, 2); else VR_PD(false, 2);
-            }
-#undef VR_PD
-            hipLaunchKernelGGL(proc_shadow_resolve, dim3(march_blocks), dim3(kThreads), 0, s, a, order, total, d);
-            return hipGetLastError();
+            const dim3 eval_grid(d.eval_blocks ? d.eval_blocks : kShadowEvalBlocks);
+            return with_value<2, 3>(tm, [&](auto T) {
+                with_bool(early, [&](auto E) {
+                    hipLaunchKernelGGL((march_proc_defer<E, T>), g4, dim3(kThreads), wt_bytes, s, a, order, total, keys,
+                                       positions, march_blocks, stale, d);
+                });
+                hipLaunchKernelGGL(proc_shadow_scan, dim3(1), dim3(kScanThreads), 0, s, total, d);
+                hipLaunchKernelGGL(proc_shadow_map, dim3((d.waves + 3) / 4), dim3(kThreads), 0, s, total, d);
+                if (d.worley_cache == 2)
+                    hipLaunchKernelGGL((proc_shadow_eval8<T>), eval_grid, dim3(kThreads), wt_bytes, s, a, d);
+                else
+                    with_bool(d.worley_cache != 0, [&](auto C) {
+                        hipLaunchKernelGGL((proc_shadow_eval<T, C>), eval_grid, dim3(kThreads), wt_bytes, s, a, d);
+                    });
+                hipLaunchKernelGGL(proc_shadow_resolve, dim3(march_blocks), dim3(kThreads), 0, s, a, order, total, d);
+                return hipGetLastError();
+            }, hipErrorInvalidValue);
         }
-        const int v = (shadow ? 4 : 0) | (early ? 2 : 0);
-#define VR_PS(S, E, T) \
-    hipLaunchKernelGGL((march_proc_sorted<S, E, T>), g4, dim3(kThreads), wt_bytes, s, a, order, total, keys, positions, \
-                       march_blocks, reuse_sort == SORT_STALE)
-#define VR_PS3(S, E) \
-    if (tm == 3) VR_PS(S, E, 3); \
-    else if (tm == 2) VR_PS(S, E, 2); \
-    else if (tm == 1) VR_PS(S, E, 1); \
-    else VR_PS(S, E, 0)
-        switch (v) {
-        case 0: VR_PS3(false, false); break;
-        case 2: VR_PS3(false, true); break;
-        case 4: VR_PS3(true, false); break;
-        default: VR_PS3(true, true); break;
-        }
-#undef VR_PS3
-#undef VR_PS
-        return hipGetLastError();
+        return with_bool(shadow, [&](auto S) { return with_bool(early, [&](auto E) {
+            return with_value<0, 1, 2, 3>(tm, [&](auto T) {
+                hipLaunchKernelGGL((march_proc_sorted<S, E, T>), g4, dim3(kThreads), wt_bytes, s, a, order, total, keys,
+                                   positions, march_blocks, stale);
+                return hipGetLastError();
+            }, hipErrorInvalidValue);
+        }); });
     }
     const int tiles_x8 = (a.width + 7) >> 3, rows8 = (a.out_rows + 7) >> 3;
     long long waves = (long long)tiles_x8 * rows8;
@@ -131,66 +118,31 @@ hipError_t launch_march_procedural(const MarchArgs& a, bool early, void* sort_bu
     }
     const dim3 grid((unsigned)((waves + 3) / 4)), block(kThreads);
     // the fixed geometry is also a valid runtime geometry (n = 9, pz = 83)
-    const int v = (shadow ? 4 : 0) | (early ? 2 : 0) | (wt_bytes ? 1 : 0);
-#define VR_PT(S, E, T) hipLaunchKernelGGL((march_proc<S, E, T>), grid, block, wt_bytes, s, a, cx, cy)
-    switch (v) {
-    case 0: VR_PT(false, false, 0); break;
-    case 1: VR_PT(false, false, 1); break;
-    case 2: VR_PT(false, true, 0); break;
-    case 3: VR_PT(false, true, 1); break;
-    case 4: VR_PT(true, false, 0); break;
-    case 5: VR_PT(true, false, 1); break;
-    case 6: VR_PT(true, true, 0); break;
-    default: VR_PT(true, true, 1); break;
-    }
-#undef VR_PT
-    return hipGetLastError();
+    return with_proc_variant(a, early, [&](auto S, auto E, auto T, size_t wt) {
+        hipLaunchKernelGGL((march_proc<S, E, T>), grid, block, wt, s, a, cx, cy);
+    });
 }
 
 hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, const Schedule& sc, hipStream_t s)
 {
     if (a.width <= 0 || a.out_rows <= 0) return hipSuccess;
-    switch (layout) {
-    case LAYOUT_BRICK4832: return launch_lw<LAYOUT_BRICK4832, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_COL48:
-        if (sc.kind == SCHED_REGIONS && sc.slab && sc.split <= 1) return launch_march_slab(a, early, sc, s);
-        return launch_lw<LAYOUT_COL48, WRAP_CLAMP>(a, early, sc, s);
-#if VR_EXPERIMENTS
-    case LAYOUT_BRICK4: return launch_lw<LAYOUT_BRICK4, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_BRICK448: return launch_lw<LAYOUT_BRICK448, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_BRICK488: return launch_lw<LAYOUT_BRICK488, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_BRICK4816: return launch_lw<LAYOUT_BRICK4816, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_BRICK4864: return launch_lw<LAYOUT_BRICK4864, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_BRICK41616: return launch_lw<LAYOUT_BRICK41616, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_COL48Z: return launch_lw<LAYOUT_COL48Z, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_ZPAIR: return launch_lw<LAYOUT_ZPAIR, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_BRICK5: return launch_lw<LAYOUT_BRICK5, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_BRICK8: return launch_lw<LAYOUT_BRICK8, WRAP_CLAMP>(a, early, sc, s);
-    case LAYOUT_BRICK16: return launch_lw<LAYOUT_BRICK16, WRAP_CLAMP>(a, early, sc, s);
-#endif
-    case LAYOUT_CORNER8:
-    case LAYOUT_CORNERH: return launch_march_corner8(a, layout, early, sc, s);   // vr_march_c8.hip
-    default: break;
-    }
-    if (wrap == WRAP_CLAMP) return launch_lw<LAYOUT_PLANAR, WRAP_CLAMP>(a, early, sc, s);
-    return launch_lw<LAYOUT_PLANAR, WRAP_MIRROR>(a, early, sc, s);
-}
-
-bool pair_layout(int layout)
-{
-    return layout == LAYOUT_COL48 || layout == LAYOUT_BRICK4832 || layout == LAYOUT_CORNERH;
+    if (list_has(CornerLayouts{}, layout)) return launch_march_corner8(a, layout, early, sc, s);   // vr_march_c8.hip
+    return with_layout_wrap<MarchLayouts>(layout, wrap, [&](auto L, auto W) {
+        if constexpr (L == LAYOUT_COL48)
+            if (sc.kind == SCHED_REGIONS && sc.slab && sc.split <= 1) return launch_march_slab(a, early, sc, s);
+        return launch_lw<L, W>(a, early, sc, s);
+    });
 }
 
 hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
                                int deal, hipStream_t s)
 {
     if (a.width <= 0 || a.out_rows <= 0) return hipSuccess;
-    switch (layout) {
-    case LAYOUT_COL48: return launch_frames_l<LAYOUT_COL48, WRAP_CLAMP>(a, fr, nf, early, sc, deal, s);
-    case LAYOUT_BRICK4832: return launch_frames_l<LAYOUT_BRICK4832, WRAP_CLAMP>(a, fr, nf, early, sc, deal, s);
-    case LAYOUT_CORNERH: return launch_march_frames_cornerh(a, fr, nf, early, sc, deal, s);   // vr_march_c8.hip
-    default: return hipErrorInvalidValue;   // no multi-frame kernel: the caller renders the frames one by one
-    }
+    // a layout without a multi-frame kernel is an error: the caller renders the frames one by one
+    return with_layout<FrameLayouts>(layout, [&](auto L) {
+        if constexpr (list_has(CornerLayouts{}, L)) return launch_march_frames_cornerh(a, fr, nf, early, sc, deal, s);   // vr_march_c8.hip
+        else return launch_frames_l<L, WRAP_CLAMP>(a, fr, nf, early, sc, deal, s);
+    });
 }
 
 }  // namespace vr

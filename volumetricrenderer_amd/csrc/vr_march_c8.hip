@@ -11,8 +11,7 @@ namespace vr {
 
 hipError_t launch_march_corner8(const MarchArgs& a, int layout, bool early, const Schedule& sc, hipStream_t s)
 {
-    if (layout == LAYOUT_CORNERH) return launch_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a, early, sc, s);
-    return launch_lw<LAYOUT_CORNER8, WRAP_CLAMP>(a, early, sc, s);
+    return with_layout<CornerLayouts>(layout, [&](auto L) { return launch_lw<L, WRAP_CLAMP>(a, early, sc, s); });
 }
 
 hipError_t launch_march_frames_cornerh(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc,

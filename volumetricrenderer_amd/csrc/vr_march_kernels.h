@@ -1359,30 +1359,24 @@ __global__ __launch_bounds__(kThreads) void march_regions_split(const MarchArgs 
     if (a.step_counter) add_steps(a, steps);
 }
 
-template <int L, int K>
-void launch_regions_split(const MarchArgs& a, bool early, const Schedule& sc, dim3 grid, size_t lds, hipStream_t s)
+// sc.split (2, 4 or 8) lanes per ray; one uniform channel: no loads for it (has_u_kernels)
+template <int L>
+hipError_t launch_regions_split(const MarchArgs& a, bool early, const Schedule& sc, size_t lds, hipStream_t s)
 {
-    const dim3 block(kThreads);
-    if constexpr (L == LAYOUT_COL48 || L == LAYOUT_BRICK4832 || L == LAYOUT_CORNERH || L == LAYOUT_COL48Z) {
-        const int um = a.umask;   // one uniform channel: no loads for it (march_regions' launcher)
-        if (!early && a.zero_offsets && (um == 1 || um == 2 || um == 4 || um == 8)) {
-#define VR_UMS(U) hipLaunchKernelGGL((march_regions_split<L, false, true, K, U>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx)
-            if (um == 1) VR_UMS(1);
-            else if (um == 2) VR_UMS(2);
-            else if (um == 4) VR_UMS(4);
-            else VR_UMS(8);
-#undef VR_UMS
-            return;
-        }
-    }
-    if (early && a.zero_offsets)
-        hipLaunchKernelGGL((march_regions_split<L, true, true, K>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-    else if (early)
-        hipLaunchKernelGGL((march_regions_split<L, true, false, K>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-    else if (a.zero_offsets)
-        hipLaunchKernelGGL((march_regions_split<L, false, true, K>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-    else
-        hipLaunchKernelGGL((march_regions_split<L, false, false, K>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
+    const dim3 grid((unsigned)(8 * ((sc.map.nwx + 3) / 4))), block(kThreads);
+    return with_value<2, 4, 8>(sc.split, [&](auto K) {
+        auto launch = [&](auto E, auto Z, auto U) {
+            hipLaunchKernelGGL((march_regions_split<L, E, Z, K, U>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
+            return hipGetLastError();
+        };
+        if constexpr (has_u_kernels(L))
+            if (u_kernel_channel(early, a.zero_offsets, a.umask) >= 0)
+                return with_value<1, 2, 4, 8>(a.umask, [&](auto U) { return launch(std::false_type{}, std::true_type{}, U); },
+                                              hipErrorInvalidValue);
+        return with_bool(early, [&](auto E) {
+            return with_bool(a.zero_offsets, [&](auto Z) { return launch(E, Z, std::integral_constant<int, 0>{}); });
+        });
+    }, hipErrorInvalidValue);
 }
 
 // XCD-row schedule: one 8x8 tile per wave, 4 horizontally adjacent tiles per
@@ -2034,23 +2028,49 @@ constexpr int kResolveBatch = 32;
     }
 }
 
+// Dynamic LDS of a procedural kernel: the Worley cell table (worley_table), if any
+inline size_t worley_table_bytes(const ProcParams& p)
+{
+    return p.wt_n > 0 ? ((size_t)p.wt_n * p.wt_pz + 512) * sizeof(float4) : 0;
+}
+// The variant of a procedural tile kernel (march_proc, march_proc_rect, march_proc_rects):
+// launch(SHADOW, EARLY, TABLE, LDS bytes), TABLE 1 = the Worley cells from LDS at runtime geometry
+template <class F>
+hipError_t with_proc_variant(const MarchArgs& a, bool early, F&& launch)
+{
+    const size_t wt_bytes = worley_table_bytes(a.proc);
+    return with_bool(a.proc.shadow_steps > 0, [&](auto S) { return with_bool(early, [&](auto E) {
+        return with_value<0, 1>(wt_bytes ? 1 : 0, [&](auto T) {
+            launch(S, E, T, wt_bytes);
+            return hipGetLastError();
+        }, hipErrorInvalidValue);
+    }); });
+}
+
 template <int L, int W>
 hipError_t launch_lw(const MarchArgs& a, bool early, const Schedule& sc, hipStream_t s)
 {
-    const size_t lds = L == LAYOUT_PLANAR || L == LAYOUT_CORNERH ? 0
-                     : (size_t)(a.nx + a.ny + a.nz + 3) * sizeof(unsigned) * (L == LAYOUT_COL48Z ? 2 : 1);
+    const size_t lds = march_lds_bytes<L>(a);
     const dim3 block(kThreads);
+    const bool zo = a.zero_offsets;
+    // the regions march, one lane per ray, G waves per workgroup: XCD x runs sc.map.nwx waves
+    auto regions = [&](auto G) {
+        const dim3 grid((unsigned)(8 * ((sc.map.nwx + G - 1) / G)));
+        return with_bool(early, [&](auto E) { return with_bool(zo, [&](auto Z) {
+            hipLaunchKernelGGL((march_regions<L, W, E, Z, G>), grid, dim3(64 * G), lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
+            return hipGetLastError();
+        }); });
+    };
 #if VR_EXPERIMENTS
     if (sc.kind == SCHED_STRIDED) {
         const int tiles = ((a.width + 7) >> 3) * ((a.out_rows + 7) >> 3);
         const int tpw = sc.tiles_per_wave > 0 ? sc.tiles_per_wave : 1;
         const int nw = (tiles + tpw - 1) / tpw;
         const dim3 grid((nw + 3) / 4);
-        if (early)
-            hipLaunchKernelGGL((march_strided<L, W, true>), grid, block, lds, s, a, 4 * (int)grid.x);
-        else
-            hipLaunchKernelGGL((march_strided<L, W, false>), grid, block, lds, s, a, 4 * (int)grid.x);
-        return hipGetLastError();
+        return with_bool(early, [&](auto E) {
+            hipLaunchKernelGGL((march_strided<L, W, E>), grid, block, lds, s, a, 4 * (int)grid.x);
+            return hipGetLastError();
+        });
     }
 #endif
     if (sc.kind == SCHED_RINGS) {
@@ -2061,149 +2081,94 @@ hipError_t launch_lw(const MarchArgs& a, bool early, const Schedule& sc, hipStre
         const int tpw = sc.tiles_per_wave > 0 ? sc.tiles_per_wave : 1;
         const dim3 grid((unsigned)(((npos + tpw - 1) / tpw + 3) / 4));
         const int nw = 4 * (int)grid.x;
-        if (early && a.zero_offsets)
-            hipLaunchKernelGGL((march_rings<L, W, true, true>), grid, block, lds, s, a, cx, cy, nw, npos);
-        else if (early)
-            hipLaunchKernelGGL((march_rings<L, W, true, false>), grid, block, lds, s, a, cx, cy, nw, npos);
-        else if (a.zero_offsets)
-            hipLaunchKernelGGL((march_rings<L, W, false, true>), grid, block, lds, s, a, cx, cy, nw, npos);
-        else
-            hipLaunchKernelGGL((march_rings<L, W, false, false>), grid, block, lds, s, a, cx, cy, nw, npos);
-        return hipGetLastError();
+        return with_bool(early, [&](auto E) { return with_bool(zo, [&](auto Z) {
+            hipLaunchKernelGGL((march_rings<L, W, E, Z>), grid, block, lds, s, a, cx, cy, nw, npos);
+            return hipGetLastError();
+        }); });
     }
     if constexpr (is_b4_family(L) || L == LAYOUT_ZPAIR || L == LAYOUT_CORNER8 || L == LAYOUT_CORNERH ||
                   L == LAYOUT_COL48Z) {
-        if (sc.kind == SCHED_REGIONS && sc.split > 1) {
-            const dim3 grid((unsigned)(8 * ((sc.map.nwx + 3) / 4)));
-            if (sc.split == 2) launch_regions_split<L, 2>(a, early, sc, grid, lds, s);
-            else if (sc.split == 4) launch_regions_split<L, 4>(a, early, sc, grid, lds, s);
-            else launch_regions_split<L, 8>(a, early, sc, grid, lds, s);
-            return hipGetLastError();
-        }
+        if (sc.kind == SCHED_REGIONS && sc.split > 1) return launch_regions_split<L>(a, early, sc, lds, s);
     }
 #if VR_EXPERIMENTS
     if constexpr (L == LAYOUT_COL48 || L == LAYOUT_BRICK4832 || L == LAYOUT_CORNERH) {
-        if (sc.kind == SCHED_REGIONS && (sc.wg_waves == 8 || sc.wg_waves == 16)) {
-            const int g = sc.wg_waves;
-            const dim3 grid((unsigned)(8 * ((sc.map.nwx + g - 1) / g))), blk(64 * g);
-#define VR_RW(G) \
-    if (early && a.zero_offsets) hipLaunchKernelGGL((march_regions<L, W, true, true, G>), grid, blk, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx); \
-    else if (early) hipLaunchKernelGGL((march_regions<L, W, true, false, G>), grid, blk, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx); \
-    else if (a.zero_offsets) hipLaunchKernelGGL((march_regions<L, W, false, true, G>), grid, blk, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx); \
-    else hipLaunchKernelGGL((march_regions<L, W, false, false, G>), grid, blk, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx)
-            if (g == 8) { VR_RW(8); } else { VR_RW(16); }
-#undef VR_RW
-            return hipGetLastError();
-        }
+        if (sc.kind == SCHED_REGIONS && (sc.wg_waves == 8 || sc.wg_waves == 16))
+            return with_value<8, 16>(sc.wg_waves, regions, hipErrorInvalidValue);
     }
 #endif
-    if constexpr (L == LAYOUT_COL48 || L == LAYOUT_BRICK4832 || L == LAYOUT_CORNERH || L == LAYOUT_COL48Z) {
+    if constexpr (has_u_kernels(L)) {
         // one uniform channel (the reference recipe's G, TestMain.cpp:60/76):
         // its loads are skipped; other masks run the general kernel (exact too)
-        const int um = a.umask;
-        if (sc.kind == SCHED_REGIONS && !early && a.zero_offsets && (um == 1 || um == 2 || um == 4 || um == 8)) {
-            const dim3 grid((unsigned)(8 * ((sc.map.nwx + 3) / 4)));
-#define VR_UM(U) hipLaunchKernelGGL((march_regions_u<L, W, false, true, U>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx)
-            if (um == 1) VR_UM(1);
-            else if (um == 2) VR_UM(2);
-            else if (um == 4) VR_UM(4);
-            else VR_UM(8);
-#undef VR_UM
-            return hipGetLastError();
-        }
+        const dim3 grid((unsigned)(8 * ((sc.map.nwx + 3) / 4)));
+        if (sc.kind == SCHED_REGIONS && u_kernel_channel(early, zo, a.umask) >= 0)
+            return with_value<1, 2, 4, 8>(a.umask, [&](auto U) {
+                hipLaunchKernelGGL((march_regions_u<L, W, false, true, U>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
+                return hipGetLastError();
+            }, hipErrorInvalidValue);
 #ifdef VR_UM_EXPERIMENT
-        if (sc.kind == SCHED_REGIONS && !early && a.zero_offsets && um == 10) {   // G and A (timing experiment)
-            const dim3 grid((unsigned)(8 * ((sc.map.nwx + 3) / 4)));
+        if (sc.kind == SCHED_REGIONS && !early && zo && a.umask == 10) {   // G and A (timing experiment)
             hipLaunchKernelGGL((march_regions_u<L, W, false, true, 10>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
             return hipGetLastError();
         }
 #endif
     }
-    if (sc.kind == SCHED_REGIONS) {
-        const dim3 grid((unsigned)(8 * ((sc.map.nwx + 3) / 4)));
-        if (early && a.zero_offsets)
-            hipLaunchKernelGGL((march_regions<L, W, true, true>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-        else if (early)
-            hipLaunchKernelGGL((march_regions<L, W, true, false>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-        else if (a.zero_offsets)
-            hipLaunchKernelGGL((march_regions<L, W, false, true>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-        else
-            hipLaunchKernelGGL((march_regions<L, W, false, false>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-        return hipGetLastError();
-    }
+    if (sc.kind == SCHED_REGIONS) return regions(std::integral_constant<int, 4>{});
 #if VR_EXPERIMENTS
     if (sc.kind == SCHED_XCDROWS) {
         const int groups = (((a.width + 7) >> 3) + 3) >> 2, rows8 = (a.out_rows + 7) >> 3;
         const dim3 grid(8 * ((rows8 + 7) / 8) * groups);
-        if (early)
-            hipLaunchKernelGGL((march_xcdrows<L, W, true>), grid, block, lds, s, a);
-        else
-            hipLaunchKernelGGL((march_xcdrows<L, W, false>), grid, block, lds, s, a);
-        return hipGetLastError();
+        return with_bool(early, [&](auto E) {
+            hipLaunchKernelGGL((march_xcdrows<L, W, E>), grid, block, lds, s, a);
+            return hipGetLastError();
+        });
     }
     if (sc.kind == SCHED_QUEUE) {
         hipError_t e = hipMemsetAsync(sc.heads, 0, 32, s);
         if (e != hipSuccess) return e;
         const dim3 grid(256 * sc.waves_per_simd);
-        if (early)
-            hipLaunchKernelGGL((march_queue<L, W, true>), grid, block, lds, s, a, sc.heads);
-        else
-            hipLaunchKernelGGL((march_queue<L, W, false>), grid, block, lds, s, a, sc.heads);
-        return hipGetLastError();
+        return with_bool(early, [&](auto E) {
+            hipLaunchKernelGGL((march_queue<L, W, E>), grid, block, lds, s, a, sc.heads);
+            return hipGetLastError();
+        });
     }
 #endif
     const dim3 grid(a.num_blocks);
-    if (early)
-        hipLaunchKernelGGL((march_grid<L, W, true>), grid, block, lds, s, a);
-    else
-        hipLaunchKernelGGL((march_grid<L, W, false>), grid, block, lds, s, a);
-    return hipGetLastError();
+    return with_bool(early, [&](auto E) {
+        hipLaunchKernelGGL((march_grid<L, W, E>), grid, block, lds, s, a);
+        return hipGetLastError();
+    });
 }
 
 // The multi-frame launch (march_regions_frames): the kernels of launch_lw's one-lane regions
-// dispatch above -- one uniform channel (_u) or the general kernel -- for NF frames.
+// dispatch above -- one uniform channel (_u) or the general kernel -- for nf = 2 or 4 frames.
 // The caller has checked that the frames share the plan and everything but the per-frame
 // arguments (vr_render.cpp), that sc is a regions schedule without split, slab or wide
-// workgroups, and that L is one of the three layouts instantiated here.  XCD x runs
+// workgroups, and that L is one of FrameLayouts.  XCD x runs
 // sc.map.nwx entry waves, 4 / NF to a workgroup (regions_frames_body).
-template <int L, int W, int NF>
-hipError_t launch_frames_lw(const MarchArgs& a, const FrameArgs* fr, bool early, const Schedule& sc, int deal, hipStream_t s)
-{
-    FramesArgs<NF> g;
-    g.c = a;
-    for (int k = 0; k < NF; ++k) g.fr[k] = fr[k];
-    const size_t lds = L == LAYOUT_CORNERH ? 0 : (size_t)(a.nx + a.ny + a.nz + 3) * sizeof(unsigned);
-    const dim3 block(kThreads);
-    static_assert(kThreads == 64 * 4, "a workgroup is 4 / NF entry waves x NF frames");
-    const int nwx = sc.map.nwx;
-    if (NF == 4) deal = 0;   // the four-frame kernel has one deal
-    const dim3 grid((unsigned)(NF == 4 ? 8 * nwx : deal ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
-    const int um = a.umask;
-    if (!early && a.zero_offsets && (um == 1 || um == 2 || um == 4 || um == 8)) {
-#define VR_UMF(U) hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal)
-        if (um == 1) VR_UMF(1);
-        else if (um == 2) VR_UMF(2);
-        else if (um == 4) VR_UMF(4);
-        else VR_UMF(8);
-#undef VR_UMF
-        return hipGetLastError();
-    }
-    if (early && a.zero_offsets)
-        hipLaunchKernelGGL((march_regions_frames<L, W, true, true, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal);
-    else if (early)
-        hipLaunchKernelGGL((march_regions_frames<L, W, true, false, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal);
-    else if (a.zero_offsets)
-        hipLaunchKernelGGL((march_regions_frames<L, W, false, true, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal);
-    else
-        hipLaunchKernelGGL((march_regions_frames<L, W, false, false, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, deal);
-    return hipGetLastError();
-}
 template <int L, int W>
 hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc, int deal, hipStream_t s)
 {
-    if (nf == 2) return launch_frames_lw<L, W, 2>(a, fr, early, sc, deal, s);
-    if (nf == kGroupFrames) return launch_frames_lw<L, W, kGroupFrames>(a, fr, early, sc, deal, s);
-    return hipErrorInvalidValue;   // no kernel for this many frames
+    return with_value<2, kGroupFrames>(nf, [&](auto NF) {
+        FramesArgs<NF> g;
+        g.c = a;
+        for (int k = 0; k < NF; ++k) g.fr[k] = fr[k];
+        const size_t lds = march_lds_bytes<L>(a);
+        const dim3 block(kThreads);
+        static_assert(has_u_kernels(L), "every multi-frame layout has the _u kernels");
+        static_assert(kThreads == 64 * 4, "a workgroup is 4 / NF entry waves x NF frames");
+        const int nwx = sc.map.nwx;
+        const int dl = NF == 4 ? 0 : deal;   // the four-frame kernel has one deal
+        const dim3 grid((unsigned)(NF == 4 ? 8 * nwx : dl ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
+        if (u_kernel_channel(early, a.zero_offsets, a.umask) >= 0)
+            return with_value<1, 2, 4, 8>(a.umask, [&](auto U) {
+                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+                return hipGetLastError();
+            }, hipErrorInvalidValue);
+        return with_bool(early, [&](auto E) { return with_bool(a.zero_offsets, [&](auto Z) {
+            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+            return hipGetLastError();
+        }); });
+    }, hipErrorInvalidValue);   // no kernel for this many frames
 }
 
 }  // namespace

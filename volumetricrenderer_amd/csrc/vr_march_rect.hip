@@ -134,30 +134,22 @@ inline bool rects_launchable(const RectList& rl)
     return rl.count >= 0 && rl.count <= kMaxRects && rl.tile_begin[rl.count] <= 0x7fffffffu;
 }
 
-template <int L, int W>
-hipError_t launch_rects_lw(const MarchArgs& a, bool early, const RectList& rl, hipStream_t s)
-{
-    const size_t lds = L == LAYOUT_PLANAR || L == LAYOUT_CORNERH ? 0
-                     : (size_t)(a.nx + a.ny + a.nz + 3) * sizeof(unsigned) * (L == LAYOUT_COL48Z ? 2 : 1);
-    if (early) hipLaunchKernelGGL((march_rects<L, W, true>), rects_grid(rl), dim3(kThreads), lds, s, a, rl);
-    else hipLaunchKernelGGL((march_rects<L, W, false>), rects_grid(rl), dim3(kThreads), lds, s, a, rl);
-    return hipGetLastError();
-}
-
 inline dim3 rect_grid(const RectArgs& rc)
 {
     const long long waves = (long long)rc.tiles_x * (((rc.y1 + 7) >> 3) - (rc.y0 >> 3));
     return dim3((unsigned)((waves + 3) / 4));
 }
 
-template <int L, int W>
-hipError_t launch_rect_lw(const MarchArgs& a, bool early, const RectArgs& rc, hipStream_t s)
+// The layout x wrap x EARLY choice of march_rect and march_rects: launch(L, W, E, LDS bytes)
+template <class F>
+hipError_t with_rect_variant(const MarchArgs& a, int layout, int wrap, bool early, F&& launch)
 {
-    const size_t lds = L == LAYOUT_PLANAR || L == LAYOUT_CORNERH ? 0
-                     : (size_t)(a.nx + a.ny + a.nz + 3) * sizeof(unsigned) * (L == LAYOUT_COL48Z ? 2 : 1);
-    if (early) hipLaunchKernelGGL((march_rect<L, W, true>), rect_grid(rc), dim3(kThreads), lds, s, a, rc);
-    else hipLaunchKernelGGL((march_rect<L, W, false>), rect_grid(rc), dim3(kThreads), lds, s, a, rc);
-    return hipGetLastError();
+    return with_layout_wrap<BuiltLayouts>(layout, wrap, [&](auto L, auto W) {
+        return with_bool(early, [&](auto E) {
+            launch(L, W, E, march_lds_bytes<L>(a));
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace
@@ -172,52 +164,18 @@ RectArgs rect_args(int x, int y, int width, int height)
 hipError_t launch_march_rect(const MarchArgs& a, int layout, int wrap, bool early, const RectArgs& rc, hipStream_t s)
 {
     if (rc.x1 <= rc.x0 || rc.y1 <= rc.y0) return hipSuccess;
-    switch (layout) {
-    case LAYOUT_BRICK4832: return launch_rect_lw<LAYOUT_BRICK4832, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_COL48: return launch_rect_lw<LAYOUT_COL48, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_CORNER8: return launch_rect_lw<LAYOUT_CORNER8, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_CORNERH: return launch_rect_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a, early, rc, s);
-#if VR_EXPERIMENTS
-    case LAYOUT_BRICK4: return launch_rect_lw<LAYOUT_BRICK4, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_BRICK448: return launch_rect_lw<LAYOUT_BRICK448, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_BRICK488: return launch_rect_lw<LAYOUT_BRICK488, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_BRICK4816: return launch_rect_lw<LAYOUT_BRICK4816, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_BRICK4864: return launch_rect_lw<LAYOUT_BRICK4864, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_BRICK41616: return launch_rect_lw<LAYOUT_BRICK41616, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_COL48Z: return launch_rect_lw<LAYOUT_COL48Z, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_ZPAIR: return launch_rect_lw<LAYOUT_ZPAIR, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_BRICK5: return launch_rect_lw<LAYOUT_BRICK5, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_BRICK8: return launch_rect_lw<LAYOUT_BRICK8, WRAP_CLAMP>(a, early, rc, s);
-    case LAYOUT_BRICK16: return launch_rect_lw<LAYOUT_BRICK16, WRAP_CLAMP>(a, early, rc, s);
-#endif
-    case LAYOUT_PLANAR:
-        if (wrap == WRAP_CLAMP) return launch_rect_lw<LAYOUT_PLANAR, WRAP_CLAMP>(a, early, rc, s);
-        return launch_rect_lw<LAYOUT_PLANAR, WRAP_MIRROR>(a, early, rc, s);
-    default: break;
-    }
-    return hipErrorInvalidValue;   // a layout this build does not hold: an error, never another kernel
+    return with_rect_variant(a, layout, wrap, early, [&](auto L, auto W, auto E, size_t lds) {
+        hipLaunchKernelGGL((march_rect<L, W, E>), rect_grid(rc), dim3(kThreads), lds, s, a, rc);
+    });
 }
 
+// the fixed Worley geometry is also a valid runtime geometry (n = 9, pz = 83), as for march_proc
 hipError_t launch_march_proc_rect(const MarchArgs& a, bool early, const RectArgs& rc, hipStream_t s)
 {
     if (rc.x1 <= rc.x0 || rc.y1 <= rc.y0) return hipSuccess;
-    const bool shadow = a.proc.shadow_steps > 0;
-    // the fixed geometry is also a valid runtime geometry (n = 9, pz = 83), as for march_proc
-    const size_t wt_bytes = a.proc.wt_n > 0 ? ((size_t)a.proc.wt_n * a.proc.wt_pz + 512) * sizeof(float4) : 0;
-    const int v = (shadow ? 4 : 0) | (early ? 2 : 0) | (wt_bytes ? 1 : 0);
-#define VR_PR(S, E, T) hipLaunchKernelGGL((march_proc_rect<S, E, T>), rect_grid(rc), dim3(kThreads), wt_bytes, s, a, rc)
-    switch (v) {
-    case 0: VR_PR(false, false, 0); break;
-    case 1: VR_PR(false, false, 1); break;
-    case 2: VR_PR(false, true, 0); break;
-    case 3: VR_PR(false, true, 1); break;
-    case 4: VR_PR(true, false, 0); break;
-    case 5: VR_PR(true, false, 1); break;
-    case 6: VR_PR(true, true, 0); break;
-    default: VR_PR(true, true, 1); break;
-    }
-#undef VR_PR
-    return hipGetLastError();
+    return with_proc_variant(a, early, [&](auto S, auto E, auto T, size_t wt_bytes) {
+        hipLaunchKernelGGL((march_proc_rect<S, E, T>), rect_grid(rc), dim3(kThreads), wt_bytes, s, a, rc);
+    });
 }
 
 bool rect_list_add(RectList* rl, int x, int y, int width, int height)
@@ -236,52 +194,18 @@ hipError_t launch_march_rects(const MarchArgs& a, int layout, int wrap, bool ear
 {
     if (!rects_launchable(rl)) return hipErrorInvalidValue;
     if (rl.count == 0) return hipSuccess;
-    switch (layout) {
-    case LAYOUT_BRICK4832: return launch_rects_lw<LAYOUT_BRICK4832, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_COL48: return launch_rects_lw<LAYOUT_COL48, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_CORNER8: return launch_rects_lw<LAYOUT_CORNER8, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_CORNERH: return launch_rects_lw<LAYOUT_CORNERH, WRAP_CLAMP>(a, early, rl, s);
-#if VR_EXPERIMENTS
-    case LAYOUT_BRICK4: return launch_rects_lw<LAYOUT_BRICK4, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_BRICK448: return launch_rects_lw<LAYOUT_BRICK448, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_BRICK488: return launch_rects_lw<LAYOUT_BRICK488, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_BRICK4816: return launch_rects_lw<LAYOUT_BRICK4816, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_BRICK4864: return launch_rects_lw<LAYOUT_BRICK4864, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_BRICK41616: return launch_rects_lw<LAYOUT_BRICK41616, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_COL48Z: return launch_rects_lw<LAYOUT_COL48Z, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_ZPAIR: return launch_rects_lw<LAYOUT_ZPAIR, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_BRICK5: return launch_rects_lw<LAYOUT_BRICK5, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_BRICK8: return launch_rects_lw<LAYOUT_BRICK8, WRAP_CLAMP>(a, early, rl, s);
-    case LAYOUT_BRICK16: return launch_rects_lw<LAYOUT_BRICK16, WRAP_CLAMP>(a, early, rl, s);
-#endif
-    case LAYOUT_PLANAR:
-        if (wrap == WRAP_CLAMP) return launch_rects_lw<LAYOUT_PLANAR, WRAP_CLAMP>(a, early, rl, s);
-        return launch_rects_lw<LAYOUT_PLANAR, WRAP_MIRROR>(a, early, rl, s);
-    default: break;
-    }
-    return hipErrorInvalidValue;   // a layout this build does not hold: an error, never another kernel
+    return with_rect_variant(a, layout, wrap, early, [&](auto L, auto W, auto E, size_t lds) {
+        hipLaunchKernelGGL((march_rects<L, W, E>), rects_grid(rl), dim3(kThreads), lds, s, a, rl);
+    });
 }
 
 hipError_t launch_march_proc_rects(const MarchArgs& a, bool early, const RectList& rl, hipStream_t s)
 {
     if (!rects_launchable(rl)) return hipErrorInvalidValue;
     if (rl.count == 0) return hipSuccess;
-    const bool shadow = a.proc.shadow_steps > 0;
-    const size_t wt_bytes = a.proc.wt_n > 0 ? ((size_t)a.proc.wt_n * a.proc.wt_pz + 512) * sizeof(float4) : 0;
-    const int v = (shadow ? 4 : 0) | (early ? 2 : 0) | (wt_bytes ? 1 : 0);
-#define VR_PR(S, E, T) hipLaunchKernelGGL((march_proc_rects<S, E, T>), rects_grid(rl), dim3(kThreads), wt_bytes, s, a, rl)
-    switch (v) {
-    case 0: VR_PR(false, false, 0); break;
-    case 1: VR_PR(false, false, 1); break;
-    case 2: VR_PR(false, true, 0); break;
-    case 3: VR_PR(false, true, 1); break;
-    case 4: VR_PR(true, false, 0); break;
-    case 5: VR_PR(true, false, 1); break;
-    case 6: VR_PR(true, true, 0); break;
-    default: VR_PR(true, true, 1); break;
-    }
-#undef VR_PR
-    return hipGetLastError();
+    return with_proc_variant(a, early, [&](auto S, auto E, auto T, size_t wt_bytes) {
+        hipLaunchKernelGGL((march_proc_rects<S, E, T>), rects_grid(rl), dim3(kThreads), wt_bytes, s, a, rl);
+    });
 }
 
 }  // namespace vr

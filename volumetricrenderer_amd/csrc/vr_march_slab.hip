@@ -247,15 +247,10 @@ hipError_t launch_march_slab(const MarchArgs& a, bool early, const Schedule& sc,
 {
     const dim3 grid((unsigned)(8 * ((sc.map.nwx + 3) / 4))), block(kThreads);
     const size_t lds = slab_lds_bytes(a.nx, a.ny);
-    if (early && a.zero_offsets)
-        hipLaunchKernelGGL((march_regions_slab<true, true>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-    else if (early)
-        hipLaunchKernelGGL((march_regions_slab<true, false>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-    else if (a.zero_offsets)
-        hipLaunchKernelGGL((march_regions_slab<false, true>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-    else
-        hipLaunchKernelGGL((march_regions_slab<false, false>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
-    return hipGetLastError();
+    return with_bool(early, [&](auto E) { return with_bool(a.zero_offsets, [&](auto Z) {
+        hipLaunchKernelGGL((march_regions_slab<E, Z>), grid, block, lds, s, a, sc.tiles, sc.hdr, sc.map.nwx);
+        return hipGetLastError();
+    }); });
 }
 
 }  // namespace vr

@@ -298,12 +298,9 @@ try {
     if (pl.layout == LAYOUT_COL48 && c->slab && kind == SCHED_REGIONS && c->split <= 1)
         return pl.early ? "grid_col48_slab_clamp_early" : "grid_col48_slab_clamp";
     const int um = c->uniform_skip ? c->uniform_mask : 0;
-    int ch = -1;   // one uniform channel, no loads for it (launch_lw / launch_lat_kd): "_u" + the channel
-    if (kind == SCHED_REGIONS && !pl.early && a.zero_offsets && c->wg_waves == 4 &&
-        (um == 1 || um == 2 || um == 4 || um == 8) &&
-        (pl.layout == LAYOUT_COL48 || pl.layout == LAYOUT_BRICK4832 || pl.layout == LAYOUT_CORNERH ||
-         pl.layout == LAYOUT_COL48Z))
-        ch = um == 1 ? 0 : um == 2 ? 1 : um == 4 ? 2 : 3;
+    int ch = -1;   // one uniform channel, no loads for it (launch_lw's _u kernels, vr_internal.h): "_u" + the channel
+    if (kind == SCHED_REGIONS && c->wg_waves == 4 && has_u_kernels(pl.layout))
+        ch = u_kernel_channel(pl.early, a.zero_offsets, um);
     if (ch < 0) return variant_name(pl);
     // built once, thread-safe (a function-local static): every layout x early x channel
     struct Names {
