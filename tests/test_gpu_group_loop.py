@@ -159,6 +159,71 @@ def test_pairing_off_ignores_frame_group(scene, pipe):
     assert launches(r) == (g0, p0)
 
 
+H5 = 76   # five 16-row bands: rank 0 of two serpentine renderers holds bands 0, 3 and 4
+
+
+@pytest.fixture(scope="module")
+def tall(scene):
+    """(cameras, plain renders of them) for the W x H5 frame of the solo rehearsals, made once."""
+    r = scene[0]
+    cams = [vr.reference_shader_data(W / H5, 1.6 * i, 15.0) for i in range(3)]
+    refs = []
+    for c in cams:
+        r.set_shader_data(*c)
+        refs.append(r.render(W, H5, FMT).cpu().numpy())
+    return cams, refs
+
+
+def own_rows(pl, height, band_rows=16):
+    """The frame rows of the pipeline's own band set (vr.h vr_target.band_flip), in the set's order."""
+    nb = (height + band_rows - 1) // band_rows
+    bands = [b for k in range(nb + 1) for b in [pl.band_first + k * pl.band_stride + (pl.band_flip if k % 2 else 0)]
+             if b < nb]
+    return [y for b in bands for y in range(b * band_rows, min(height, (b + 1) * band_rows))]
+
+
+@pytest.mark.parametrize("pairing", [1, 2])
+@pytest.mark.parametrize("n", [2, 3])
+def test_solo_rank0_pairs_in_place_and_assembles(scene, tall, pairing, n):
+    """Rank 0 of two, rehearsed alone: its frames go two at a time into its own rows of the frame
+    buffers (in place), each followed by an assembly, an odd last frame alone.  Its band set of the
+    last frame equals the same rows of a plain render of that frame's camera."""
+    r = scene[0]
+    cams, refs = tall
+    pl = RcclBandPipeline(r, W, H5, FMT, band_rows=16, world=2, rank=0, loopback=True, solo=True, render_streams=2)
+    try:
+        pl.pairing = pairing
+        assert (pl.band_stride, pl.band_first, pl.band_flip) == (2, 0, 1) and not pl.compositor
+        rows = own_rows(pl, H5)
+        assert len(rows) == 16 + 16 + 12   # bands 0, 3 and the partial band 4
+        assert pl.my_rows == vr.band_rows_packed(H5, 16, 2, 0, 1)
+        pl.run_frames(n, cameras=cams[:n])
+        got = frame_of(pl)
+        assert got.shape == refs[n - 1].shape
+        assert np.array_equal(got[rows], refs[n - 1][rows])
+    finally:
+        pl.close()
+
+
+def test_solo_compositor_rank0_carries_the_camera(scene, tall):
+    """Rank 0 as a compositor without lead rows renders nothing: its rehearsal only assembles, and
+    leaves the context with the last frame's shader data, through no shared launch."""
+    r = scene[0]
+    cams, refs = tall
+    pl = RcclBandPipeline(r, W, H5, FMT, band_rows=16, world=2, rank=0, loopback=True, solo=True, compositor=True,
+                          render_streams=2, lead_pct=None)
+    try:
+        assert pl.compositor and pl.my_rows == 0 and pl.lead_rows == 0
+        r.set_shader_data(*cams[0])
+        g0, p0 = launches(r)
+        pl.run_frames(3, cameras=cams[:3])
+        assert launches(r) == (g0, p0)
+        got = r.render(W, H5, FMT).cpu().numpy()
+        assert np.array_equal(got, refs[2])
+    finally:
+        pl.close()
+
+
 def test_loopback_ranks_ignore_frame_group():
     """Two ranks in one process: the multi-rank path keeps one launch per frame whatever the options say."""
     Wl, Hl = 500, 283

@@ -203,15 +203,15 @@ struct vr_shard {
     int last = -1;                    // buffer set of the last frame: 0..3, and 4..7 (frame_more, read through
                                       // frame_set) after a run of four-frame launches on two streams -- every
                                       // other path sets it below kMaxFramesInFlight before it indexes done[] / pending[]
-    // frames two at a time through vr_render_pair (the ctx's option "frame_pairing", read
-    // at every run): 1 = successive pairs on render stream 0 with buffer sets 0 / 1; 2 =
-    // pairs alternating over render streams 0 and 1, stream q with buffer sets 2q / 2q + 1
-    int pairing = -1;                 // the last run's (-1: none yet)
-    int pairs_run = 0;                // pairs queued so far (the alternation carries over between runs)
-    // frames four at a time through vr_render_group (the ctx's option "frame_group" = 4, one
-    // rank): one stream = buffer sets 0..3; two streams = stream q owns sets 4q..4q + 3, the
-    // sets 4..7 being frame_more[], allocated by the first run of that mode
-    int group = -1;                   // the last run's frame_group (-1: none yet)
+    // One rank of a grid medium on 2+ render streams takes its frames in chunks of G = the ctx's
+    // option "frame_group" (4: a one-rank communicator only; else 2), one vr_render_group per
+    // chunk, where the option "frame_pairing" S is 1 or 2 (both read at every run).  The set rule
+    // (kArrangements): S = 1, every chunk on render stream 0 with buffer sets 0..G-1 (pairs: from
+    // the set after the last frame's); S = 2, chunks alternate over streams 0 and 1, stream q with
+    // sets Gq..Gq + G-1 (the sets 4..7 are frame_more[], allocated by the first run that needs them).
+    int pairing = -1;                 // the last run's frame_pairing (-1: none yet)
+    int pairs_run = 0;                // chunks queued so far (the alternation carries over between runs)
+    int group = -1;                   // the last run's G (-1: none yet)
     uint8_t* frame_more[kMaxFramesInFlight] = {};
     bool loopback = false;            // one process emulates all ranks (no RCCL)
     bool solo = false;                // loopback rehearsal of one rank: its own band set only, no exchange
@@ -447,42 +447,80 @@ vr_status assemble(vr_shard* sh, int p, hipStream_t s)
     return VR_OK;
 }
 
+// This rank's own target for buffer set `set`: rank 0 renders its rows straight into the
+// frame, in the frame's format (sets 4..7: frame_more); the others a grey band set.
+uint8_t* frame_set(const vr_shard* sh, int p) { return p < kMaxFramesInFlight ? sh->frame[p] : sh->frame_more[p - kMaxFramesInFlight]; }
+vr_target own_target(const vr_shard* sh, int set)
+{
+    vr_target t = target_of(sh, sh->rank);
+    if (sh->rank == 0) {
+        t.format = sh->format | VR_TARGET_BANDS_IN_PLACE | range_flag(sh, sh->rank);
+        t.pixels = frame_set(sh, set);
+        t.row_pitch = sh->pitch;
+    } else {
+        t.format = sh->gformat | range_flag(sh, sh->rank);
+        t.pixels = sh->local[set];
+        t.row_pitch = sh->gpitch;
+    }
+    return t;
+}
+
+// The other ranks' band sets, rendered here (loopback) into their gather slots of set p
+vr_status render_others_here(vr_shard* sh, int p, hipStream_t s)
+{
+    for (int r = 1; r < sh->nranks; ++r) {
+        vr_target t = target_of(sh, r);
+        t.format = sh->gformat | range_flag(sh, r);
+        t.row_pitch = sh->gpitch;
+        t.pixels = slot_of(sh, p, r);
+        if (sh->rows_of[r] > 0) VR_TRY(vr_render(sh->ctx, &t, s));
+    }
+    return VR_OK;
+}
+
+// One frame's renders into buffer set p on s: this rank's rows between the timing events of a
+// sampled frame, then (loopback) the other ranks'.
+vr_status render_set(vr_shard* sh, int p, hipStream_t s, hipEvent_t t0, hipEvent_t t1)
+{
+    const vr_target t = own_target(sh, p);
+    if (t0) HIP_TRY(hipEventRecord(t0, s));
+    if (sh->my_rows > 0) VR_TRY(vr_render(sh->ctx, &t, s));
+    if (t1) HIP_TRY(hipEventRecord(t1, s));
+    return others_here(sh) ? render_others_here(sh, p, s) : VR_OK;
+}
+
+// The exchange of the band sets of set p: rank 0 receives into its gather slots, the others
+// send, in one group on `stream` over `comm` (loopback and one rank: nothing to move).
+vr_status exchange(vr_shard* sh, int p, ncclComm_t comm, hipStream_t stream)
+{
+    if (sh->nranks == 1 || sh->loopback) return VR_OK;
+    NCCL_TRY(ncclGroupStart());
+    if (sh->rank == 0) {
+        for (int r = 1; r < sh->nranks; ++r)
+            if (sh->rows_of[r] > 0)
+                NCCL_TRY(ncclRecv(slot_of(sh, p, r), (size_t)sh->rows_of[r] * sh->gpitch, ncclUint8, r, comm, stream));
+    } else if (sh->my_rows > 0) {
+        NCCL_TRY(ncclSend(sh->local[p], (size_t)sh->my_rows * sh->gpitch, ncclUint8, 0, comm, stream));
+    }
+    NCCL_TRY(ncclGroupEnd());
+    return VR_OK;
+}
+
 // The render-stream half of frame (parity p): wait for the exchange that last
 // read the parity's buffers (not rank 0, which renders in place), render, and
 // (not rank 0) mark the render for the exchange.
 vr_status render_half(vr_shard* sh, int p, hipStream_t s, hipEvent_t t0, hipEvent_t t1)
 {
-    const bool r0 = sh->rank == 0, here = others_here(sh);
-    if ((!r0 || here) && sh->pending[p]) HIP_TRY(hipStreamWaitEvent(s, sh->done[p], 0));
-    vr_target t = target_of(sh, sh->rank);
-    if (r0) {   // in place: the frame's own rows, the frame's format
-        t.format = sh->format | VR_TARGET_BANDS_IN_PLACE | range_flag(sh, sh->rank);
-        t.pixels = sh->frame[p];
-        t.row_pitch = sh->pitch;
-    } else {
-        t.format = sh->gformat | range_flag(sh, sh->rank);
-        t.pixels = sh->local[p];
-        t.row_pitch = sh->gpitch;
-    }
-    if (t0) HIP_TRY(hipEventRecord(t0, s));
-    if (sh->my_rows > 0) VR_TRY(vr_render(sh->ctx, &t, s));
-    if (t1) HIP_TRY(hipEventRecord(t1, s));
-    if (here) {   // the other ranks' band sets, rendered here into their gather slots
-        for (int r = 1; r < sh->nranks; ++r) {
-            t = target_of(sh, r);
-            t.format = sh->gformat | range_flag(sh, r);
-            t.row_pitch = sh->gpitch;
-            t.pixels = slot_of(sh, p, r);
-            if (sh->rows_of[r] > 0) VR_TRY(vr_render(sh->ctx, &t, s));
-        }
-    }
-    if (!r0 || here) HIP_TRY(hipEventRecord(sh->rendered[p], s));
+    const bool marks = sh->rank != 0 || others_here(sh);
+    if (marks && sh->pending[p]) HIP_TRY(hipStreamWaitEvent(s, sh->done[p], 0));
+    SH_TRY(render_set(sh, p, s, t0, t1));
+    if (marks) HIP_TRY(hipEventRecord(sh->rendered[p], s));
     return VR_OK;
 }
 
-// The communication-stream half: the exchange of the band sets (rank 0 receives
-// into its gather slots, the others send), rank 0's assembly of the other
-// ranks' rows, and (not rank 0) the mark that frees the parity's buffers.
+// The communication-stream half: the exchange of the band sets, rank 0's
+// assembly of the other ranks' rows, and (not rank 0) the mark that frees the
+// parity's buffers.
 vr_status comm_half(vr_shard* sh, int p)
 {
     const bool r0 = sh->rank == 0, here = others_here(sh);
@@ -491,19 +529,7 @@ vr_status comm_half(vr_shard* sh, int p)
         HIP_TRY(hipStreamWaitEvent(sh->comm_stream, sh->done[p], 0));
         sh->pending[p] = false;
     }
-    if (sh->nranks > 1 && !sh->loopback) {
-        NCCL_TRY(ncclGroupStart());
-        if (r0) {
-            for (int r = 1; r < sh->nranks; ++r)
-                if (sh->rows_of[r] > 0)
-                    NCCL_TRY(ncclRecv(slot_of(sh, p, r), (size_t)sh->rows_of[r] * sh->gpitch, ncclUint8, r, sh->comm,
-                                      sh->comm_stream));
-        } else if (sh->my_rows > 0) {
-            NCCL_TRY(ncclSend(sh->local[p], (size_t)sh->my_rows * sh->gpitch, ncclUint8, 0, sh->comm,
-                              sh->comm_stream));
-        }
-        NCCL_TRY(ncclGroupEnd());
-    }
+    SH_TRY(exchange(sh, p, sh->comm, sh->comm_stream));
     if (r0 && sh->nranks > 1)   // (a solo rehearsal expands whatever its slots hold: the same work)
         SH_TRY(assemble(sh, p, sh->comm_stream));
     if (!r0 || here) {
@@ -526,97 +552,33 @@ vr_status one_frame(vr_shard* sh, int p, hipStream_t s, hipEvent_t t0, hipEvent_
 // communicator -> (rank 0) assembly, in rs's order.  The next frame of the
 // parity follows in the same order, so no event is recorded or waited for;
 // the other parity's frame overlaps on the other stream and communicator.
+ncclComm_t& comm_of(vr_shard* sh, int p) { return p == 0 ? sh->comm : p == 1 ? sh->comm2 : sh->comm_more[p - 2]; }
 vr_status one_frame_on_render(vr_shard* sh, int p, hipStream_t rs, hipEvent_t t0, hipEvent_t t1)
 {
-    const bool r0 = sh->rank == 0, here = others_here(sh);
-    vr_target t = target_of(sh, sh->rank);
-    if (r0) {
-        t.format = sh->format | VR_TARGET_BANDS_IN_PLACE | range_flag(sh, sh->rank);
-        t.pixels = sh->frame[p];
-        t.row_pitch = sh->pitch;
-    } else {
-        t.format = sh->gformat | range_flag(sh, sh->rank);
-        t.pixels = sh->local[p];
-        t.row_pitch = sh->gpitch;
-    }
-    if (t0) HIP_TRY(hipEventRecord(t0, rs));
-    if (sh->my_rows > 0) VR_TRY(vr_render(sh->ctx, &t, rs));
-    if (t1) HIP_TRY(hipEventRecord(t1, rs));
-    if (here) {
-        for (int r = 1; r < sh->nranks; ++r) {
-            t = target_of(sh, r);
-            t.format = sh->gformat | range_flag(sh, r);
-            t.row_pitch = sh->gpitch;
-            t.pixels = slot_of(sh, p, r);
-            if (sh->rows_of[r] > 0) VR_TRY(vr_render(sh->ctx, &t, rs));
-        }
-    }
-    if (sh->nranks > 1 && !sh->loopback) {
-        ncclComm_t c = p == 0 ? sh->comm : p == 1 ? sh->comm2 : sh->comm_more[p - 2];
-        NCCL_TRY(ncclGroupStart());
-        if (r0) {
-            for (int r = 1; r < sh->nranks; ++r)
-                if (sh->rows_of[r] > 0)
-                    NCCL_TRY(ncclRecv(slot_of(sh, p, r), (size_t)sh->rows_of[r] * sh->gpitch, ncclUint8, r, c, rs));
-        } else if (sh->my_rows > 0) {
-            NCCL_TRY(ncclSend(sh->local[p], (size_t)sh->my_rows * sh->gpitch, ncclUint8, 0, c, rs));
-        }
-        NCCL_TRY(ncclGroupEnd());
-    }
-    if (r0 && sh->nranks > 1) SH_TRY(assemble(sh, p, rs));
+    SH_TRY(render_set(sh, p, rs, t0, t1));
+    SH_TRY(exchange(sh, p, comm_of(sh, p), rs));
+    if (sh->rank == 0 && sh->nranks > 1) SH_TRY(assemble(sh, p, rs));
     sh->last = p;
     return VR_OK;
 }
 
-// Frames (buffer sets p0, p1) through one vr_render_pair on rs -- one rank, no exchange:
-// frame j with (osd[j], gsd[j]), or both with the current shader data.  Rank 0 of a solo
-// rehearsal still assembles each frame.  A sampled pair is bracketed by one event pair.
-vr_status pair_on_render(vr_shard* sh, int p0, int p1, hipStream_t rs, const vr_object_shader_data* osd,
-                         const vr_global_shader_data* gsd, hipEvent_t t0, hipEvent_t t1)
+// m = 1..VR_MAX_GROUP frames of one rank (no exchange) through one vr_render_group on rs --
+// four in one launch, two as vr_render_pair, one as vr_render: frame j into buffer set
+// sets[j] with (osd[j], gsd[j]), or all with the current shader data.  One event pair
+// brackets a sampled launch.  A rank without rows only carries the last camera forward; rank 0
+// of a solo rehearsal still assembles each frame.
+vr_status frames_on_render(vr_shard* sh, const int* sets, int m, hipStream_t rs, const vr_object_shader_data* osd,
+                           const vr_global_shader_data* gsd, hipEvent_t t0, hipEvent_t t1)
 {
-    const bool r0 = sh->rank == 0;
-    vr_target t = target_of(sh, sh->rank);
-    if (r0) {
-        t.format = sh->format | VR_TARGET_BANDS_IN_PLACE | range_flag(sh, sh->rank);
-        t.row_pitch = sh->pitch;
-    } else {
-        t.format = sh->gformat | range_flag(sh, sh->rank);
-        t.row_pitch = sh->gpitch;
-    }
-    vr_target ta = t, tb = t;
-    ta.pixels = r0 ? sh->frame[p0] : sh->local[p0];
-    tb.pixels = r0 ? sh->frame[p1] : sh->local[p1];
-    if (t0) HIP_TRY(hipEventRecord(t0, rs));
-    if (sh->my_rows > 0) VR_TRY(vr_render_pair(sh->ctx, &ta, &tb, osd, gsd, rs));
-    else if (osd) VR_TRY(vr_set_shader_data(sh->ctx, &osd[1], &gsd[1]));
-    if (t1) HIP_TRY(hipEventRecord(t1, rs));
-    if (r0 && sh->nranks > 1) {
-        SH_TRY(assemble(sh, p0, rs));
-        SH_TRY(assemble(sh, p1, rs));
-    }
-    sh->last = p1;
-    return VR_OK;
-}
-
-// m = 1..4 frames of a one-rank communicator (no exchange, no assembly) through one
-// vr_render_group on rs: frame j into buffer set base + j (sets 4..7: frame_more) with
-// (osd[j], gsd[j]), or all with the current shader data.  One event pair brackets the launch.
-uint8_t* frame_set(vr_shard* sh, int p) { return p < kMaxFramesInFlight ? sh->frame[p] : sh->frame_more[p - kMaxFramesInFlight]; }
-vr_status group_on_render(vr_shard* sh, int base, int m, hipStream_t rs, const vr_object_shader_data* osd,
-                          const vr_global_shader_data* gsd, hipEvent_t t0, hipEvent_t t1)
-{
-    vr_target t = target_of(sh, sh->rank);
-    t.format = sh->format | VR_TARGET_BANDS_IN_PLACE | range_flag(sh, sh->rank);
-    t.row_pitch = sh->pitch;
     vr_target ts[VR_MAX_GROUP];
-    for (int j = 0; j < m; ++j) {
-        ts[j] = t;
-        ts[j].pixels = frame_set(sh, base + j);
-    }
+    for (int j = 0; j < m; ++j) ts[j] = own_target(sh, sets[j]);
     if (t0) HIP_TRY(hipEventRecord(t0, rs));
-    VR_TRY(vr_render_group(sh->ctx, ts, m, osd, gsd, rs));
+    if (sh->my_rows > 0) VR_TRY(vr_render_group(sh->ctx, ts, m, osd, gsd, rs));
+    else if (osd) VR_TRY(vr_set_shader_data(sh->ctx, &osd[m - 1], &gsd[m - 1]));
     if (t1) HIP_TRY(hipEventRecord(t1, rs));
-    sh->last = base + m - 1;
+    if (sh->rank == 0 && sh->nranks > 1)
+        for (int j = 0; j < m; ++j) SH_TRY(assemble(sh, sets[j], rs));
+    sh->last = sets[m - 1];
     return VR_OK;
 }
 
@@ -685,6 +647,362 @@ bool wait_host(F ready, const std::atomic<bool>& stop, double timeout_s)
             std::this_thread::yield();
         }
     }
+}
+
+// ---- vr_shard_run_frames: one run's arguments and state, and its steps ----
+struct Run {
+    int frames;
+    const vr_object_shader_data* osd;   // per-frame cameras, or null: the ctx's current shader data
+    const vr_global_shader_data* gsd;
+    hipStream_t s;                      // the caller's stream
+    int sample_every;                   // 0: no render is sampled
+    int next = 0;                       // sampled launches so far: timing[2k], timing[2k + 1]
+    int P = 1;                          // render streams the frames alternate over
+    bool two = false;                   // P >= 2: frames overlap
+    std::chrono::steady_clock::time_point h0{};
+};
+
+// The timing events around the launch of frames [i, i + m) where the run samples one of them
+void sample_events(vr_shard* sh, Run& run, int i, int m, hipEvent_t* t0, hipEvent_t* t1)
+{
+    bool samp = false;
+    for (int j = i; j < i + m && run.sample_every > 0; ++j) samp = samp || j % run.sample_every == 0;
+    *t0 = samp ? sh->timing[2 * run.next] : nullptr;
+    *t1 = samp ? sh->timing[2 * run.next + 1] : nullptr;
+    if (samp) ++run.next;
+}
+
+// The buffer sets were last used by frames of another arrangement, if any: the render streams
+// wait for what read them (each set's done[] covers its render, exchange and assembly)
+vr_status drain_pending(vr_shard* sh)
+{
+    for (int q = 0; q < kMaxFramesInFlight; ++q)
+        if (sh->pending[q]) {
+            for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->done[q], 0));
+            sh->pending[q] = false;
+        }
+    return VR_OK;
+}
+
+// The caller's stream after the last frames of render streams 0..n-1
+vr_status join_render_streams(vr_shard* sh, hipStream_t s, int n)
+{
+    for (int q = 0; q < n; ++q) {
+        HIP_TRY(hipEventRecord(sh->tail[q], sh->render_stream[q]));
+        HIP_TRY(hipStreamWaitEvent(s, sh->tail[q], 0));
+    }
+    return VR_OK;
+}
+
+// A later frame of another arrangement that uses buffer set b waits for this record
+vr_status mark_done(vr_shard* sh, int b, hipStream_t s)
+{
+    HIP_TRY(hipEventRecord(sh->done[b], s));
+    sh->pending[b] = true;
+    return VR_OK;
+}
+
+// The timing events, P, the ctx's frames_overlap option and the fence of a run of frames > 0
+vr_status begin_run(vr_shard* sh, Run& run)
+{
+    const int nsamp = run.sample_every > 0 ? (run.frames + run.sample_every - 1) / run.sample_every : 0;
+    while ((int)sh->timing.size() < 2 * nsamp) {
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreate(&ev));
+        sh->timing.push_back(ev);
+    }
+    run.h0 = std::chrono::steady_clock::now();
+    // a procedural medium with deferred shadow rays renders on one stream:
+    // its frames could overlap since round 6 (a frame that reuses the cost
+    // order writes only its stream's deferred scratch set), but two in flight
+    // measured slower (config 3: 0.783 against 0.756 ms, profiles/r06/c10)
+    run.P = vr_get_option(sh->ctx, "procedural") == 2 ? 1
+            : sh->on_render ? sh->render_streams : std::min(sh->render_streams, 2);
+    run.two = run.P >= 2;
+    sh->started = true;   // the band geometry is fixed from here
+    if (!run.two) return VR_OK;
+    // two render streams: tell the ctx its consecutive renders overlap (its
+    // auto split rule), from this pipeline's first such run until it is
+    // destroyed or set to one render stream (restore_overlap)
+    if (sh->overlap_prev < 0) {
+        sh->overlap_prev = vr_get_option(sh->ctx, "frames_overlap");
+        if (sh->overlap_prev == 0) VR_TRY(vr_set_option(sh->ctx, "frames_overlap", 1));
+    }
+    // the render streams start after the caller's queued work (e.g. the volume)
+    HIP_TRY(hipEventRecord(sh->fence, run.s));
+    for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->fence, 0));
+    return VR_OK;
+}
+
+// How a grouped run lays its chunks out (vr_shard::pairing / group).  A chunk of up to `group`
+// frames goes to render stream q = pairs_run & 1 (pairing 2) or 0, into the buffer sets
+// first[q] + (k + j) % group, j = 0..m-1: k = 0, or with `follow_last` the set after the last
+// frame's (one stream of pairs keeps alternating 0 / 1 across an odd last frame and across
+// runs).  The run ends with a record of done[b] on render stream done_stream[b] (-1: none).
+struct Arrangement {
+    int group, pairing;
+    int first[2];
+    bool follow_last;
+    int done_stream[kMaxFramesInFlight];
+};
+constexpr Arrangement kArrangements[] = {
+    {4, 1, {0, 0}, false, {0, 0, 0, 0}},
+    {4, 2, {0, 4}, false, {0, 1, 0, 1}},   // the sets 4..7 are frame_more[]
+    {2, 1, {0, 0}, true, {0, 0, -1, -1}},
+    {2, 2, {0, 2}, false, {0, 0, 1, 1}},
+};
+
+// The second stream's sets past the per-frame ones (frame_more[]), allocated by the first run that uses them
+vr_status alloc_frame_more(vr_shard* sh)
+{
+    if (sh->frame_more[0]) return VR_OK;
+    for (int p = 0; p < kMaxFramesInFlight; ++p) {
+        const hipError_t e = hipMalloc(&sh->frame_more[p], (size_t)sh->height * sh->pitch);
+        if (e != hipSuccess) {
+            sh->frame_more[p] = nullptr;
+            for (int k = 0; k < p; ++k) {
+                (void)hipFree(sh->frame_more[k]);
+                sh->frame_more[k] = nullptr;
+            }
+            return fail(e == hipErrorOutOfMemory ? VR_ERR_OOM : VR_ERR_HIP, "vr_shard_run: frame buffers: %s",
+                        hipGetErrorString(e));
+        }
+    }
+    return VR_OK;
+}
+
+// The arrangement of this run's frames if they are grouped, else null (one launch per frame):
+// one rank rendering a grid on 2+ render streams takes its frames two at a time; multi-rank
+// pipelines and loopback keep one launch per frame.  frame_group 4: a one-rank communicator
+// takes them four at a time; a solo rehearsal keeps its pairs.
+vr_status choose_arrangement(vr_shard* sh, const Run& run, const Arrangement** out)
+{
+    *out = nullptr;
+    const bool one_rank = sh->nranks == 1 || (sh->loopback && sh->solo);
+    const int pairing = vr_get_option(sh->ctx, "frame_pairing");
+    const bool pairs = pairing > 0 && run.two && one_rank && !others_here(sh) && vr_get_option(sh->ctx, "procedural") == 0;
+    const int group = pairs && sh->nranks == 1 && sh->my_rows > 0 ? vr_get_option(sh->ctx, "frame_group") : 2;
+    if (one_rank) {
+        if (sh->last >= 0 && ((sh->pairing >= 0 && pairing != sh->pairing) || (sh->group >= 0 && group != sh->group))) {
+            // frames of the old arrangement may still be in flight (vr_shard_set_render_streams)
+            for (int p = 0; p < kMaxFramesInFlight; ++p)
+                if (sh->pending[p]) SH_TRY(wait_event(sh, sh->done[p], "vr_shard_run: frame_pairing changed"));
+        }
+        sh->pairing = pairing;
+        sh->group = group;
+    }
+    if (!pairs) return VR_OK;
+    for (const Arrangement& a : kArrangements)
+        if (a.group == group && a.pairing == pairing) *out = &a;
+    if (!*out) return fail(VR_ERR_INVALID, "vr_shard_run: internal: no arrangement for frame_group %d, frame_pairing %d", group, pairing);
+    if ((*out)->first[1] + group > kMaxFramesInFlight) SH_TRY(alloc_frame_more(sh));
+    return VR_OK;
+}
+
+// The grouped loop: chunks of a.group frames, each one vr_render_group on its stream
+vr_status run_grouped(vr_shard* sh, Run& run, const Arrangement& a)
+{
+    SH_TRY(drain_pending(sh));
+    for (int i = 0; i < run.frames;) {
+        const int m = std::min(run.frames - i, a.group);
+        hipEvent_t t0, t1;
+        sample_events(sh, run, i, m, &t0, &t1);
+        const int q = a.pairing == 2 ? (sh->pairs_run & 1) : 0;
+        const int k = a.follow_last && sh->last >= 0 ? (sh->last + 1) % a.group : 0;
+        int sets[VR_MAX_GROUP];
+        for (int j = 0; j < m; ++j) sets[j] = a.first[q] + (k + j) % a.group;
+        SH_TRY(frames_on_render(sh, sets, m, sh->render_stream[q], run.osd ? &run.osd[i] : nullptr,
+                                run.gsd ? &run.gsd[i] : nullptr, t0, t1));
+        i += m;
+        ++sh->pairs_run;
+    }
+    SH_TRY(join_render_streams(sh, run.s, 2));
+    for (int b = 0; b < kMaxFramesInFlight; ++b)
+        if (a.done_stream[b] >= 0) SH_TRY(mark_done(sh, b, sh->render_stream[a.done_stream[b]]));
+    return VR_OK;
+}
+
+// The communicators of streams 1..P-1, once each, split from the first (collective: every
+// rank runs its first such frames together, in the same order; a one-rank communicator
+// splits too, so its test covers the call)
+vr_status split_comms(vr_shard* sh, int P)
+{
+    for (int q = 1; q < P && !sh->loopback; ++q) {
+        ncclComm_t& cq = comm_of(sh, q);
+        if (cq) continue;
+        ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
+        cfg.blocking = 0;
+        const ncclResult_t r = ncclCommSplit(sh->comm, 0, sh->rank, &cq, &cfg);
+        if (r != ncclSuccess && r != ncclInProgress) {
+            cq = nullptr;
+            abort_comm(sh);
+            return fail(VR_ERR_COMM, "vr_shard_run: ncclCommSplit: %s; communicator aborted", ncclGetErrorString(r));
+        }
+        SH_TRY(settle(sh, "vr_shard_run: ncclCommSplit"));
+    }
+    return VR_OK;
+}
+
+// One launch per frame, each frame's exchange and assembly on its render stream (one_frame_on_render)
+vr_status run_on_render(vr_shard* sh, Run& run)
+{
+    SH_TRY(split_comms(sh, run.P));
+    SH_TRY(drain_pending(sh));
+    for (int i = 0; i < run.frames; ++i) {
+        const int p = sh->last < 0 ? 0 : (sh->last + 1) % run.P;
+        hipEvent_t t0, t1;
+        sample_events(sh, run, i, 1, &t0, &t1);
+        if (run.osd) VR_TRY(vr_set_shader_data(sh->ctx, &run.osd[i], &run.gsd[i]));   // this frame's camera
+        SH_TRY(one_frame_on_render(sh, p, sh->render_stream[p], t0, t1));
+    }
+    SH_TRY(join_render_streams(sh, run.s, run.P));
+    for (int q = 0; q < run.P; ++q) SH_TRY(mark_done(sh, q, sh->render_stream[q]));
+    return VR_OK;
+}
+
+// Two host threads: this one issues the render halves, a worker the
+// exchange halves, so a frame's host time is the longer half, not the
+// sum (an event record or a launch costs ~3-5 us).
+// Frame i's exchange is issued after its render (rendered[p] recorded);
+// frame i's render after frame i-2's exchange (done[p] recorded, and
+// rendered[p] no longer awaited).
+vr_status run_two_threads(vr_shard* sh, Run& run)
+{
+    const int frames = run.frames;
+    const int p0 = sh->last < 0 ? 0 : (sh->last + 1) % 2;
+    std::atomic<int> rdone{0}, cdone{0};
+    std::atomic<bool> stop{false};
+    vr_status wst = VR_OK;
+    std::string werr;
+    std::thread worker([&] {
+        if (hipSetDevice(sh->device) != hipSuccess) {
+            wst = fail(VR_ERR_HIP, "vr_shard_run: worker hipSetDevice");
+        } else {
+            for (int i = 0; i < frames; ++i) {
+                if (!wait_host([&] { return rdone.load(std::memory_order_acquire) > i; }, stop, sh->timeout_s)) {
+                    if (!stop.load()) wst = fail(VR_ERR_TIMEOUT, "vr_shard_run: render thread stalled");
+                    break;
+                }
+                wst = comm_half(sh, (p0 + i) & 1);
+                if (wst != VR_OK) break;
+                cdone.store(i + 1, std::memory_order_release);
+            }
+        }
+        if (wst != VR_OK) {
+            werr = g_err;
+            stop.store(true, std::memory_order_release);
+        }
+    });
+    // if anything below throws, the worker is stopped and joined before
+    // the exception leaves (a joinable std::thread's destructor would
+    // call std::terminate past the function-try-block)
+    struct JoinGuard {
+        std::thread& t;
+        std::atomic<bool>& stop;
+        ~JoinGuard()
+        {
+            if (t.joinable()) {
+                stop.store(true, std::memory_order_release);
+                t.join();
+            }
+        }
+    } join_guard{worker, stop};
+    vr_status mst = VR_OK;
+    for (int i = 0; i < frames && mst == VR_OK; ++i) {
+        if (i >= 2 && !wait_host([&] { return cdone.load(std::memory_order_acquire) >= i - 1; }, stop, sh->timeout_s))
+            break;   // the worker failed (its status is reported) or stalled
+        const int p = (p0 + i) & 1;
+        hipEvent_t t0, t1;
+        sample_events(sh, run, i, 1, &t0, &t1);
+        if (run.osd) {
+            mst = vr_set_shader_data(sh->ctx, &run.osd[i], &run.gsd[i]);
+            if (mst != VR_OK) mst = fail(mst, "vr_set_shader_data: %s", vr_last_error());
+        }
+        if (mst == VR_OK) mst = render_half(sh, p, run.two ? sh->render_stream[p] : run.s, t0, t1);
+        if (mst == VR_OK) rdone.store(i + 1, std::memory_order_release);
+    }
+    if (mst != VR_OK) stop.store(true, std::memory_order_release);
+    worker.join();
+    if (mst != VR_OK) return mst;
+    if (wst != VR_OK) {
+        g_err = werr;
+        return wst;
+    }
+    if (cdone.load() != frames) return fail(VR_ERR_TIMEOUT, "vr_shard_run: render thread stalled");
+    sh->last = (p0 + frames - 1) & 1;
+    return VR_OK;
+}
+
+// One launch per frame, the exchange and assembly on the communication stream (one_frame)
+vr_status run_comm_stream(vr_shard* sh, Run& run)
+{
+    for (int i = 0; i < run.frames; ++i) {
+        const int p = sh->last < 0 ? 0 : (sh->last + 1) % 2;
+        hipEvent_t t0, t1;
+        sample_events(sh, run, i, 1, &t0, &t1);
+        if (run.osd) VR_TRY(vr_set_shader_data(sh->ctx, &run.osd[i], &run.gsd[i]));   // this frame's camera
+        SH_TRY(one_frame(sh, p, run.two ? sh->render_stream[p] : run.s, t0, t1));
+    }
+    return VR_OK;
+}
+
+// After frames of the communication-stream paths: the caller's stream sees the last frame
+vr_status show_last_frame(vr_shard* sh, const Run& run)
+{
+    if (sh->last < 0) return VR_OK;
+    if (sh->last >= kMaxFramesInFlight)   // (only a run of four-frame launches leaves such a set: not these paths)
+        return fail(VR_ERR_INVALID, "vr_shard_run: internal: buffer set %d outside the per-frame events", sh->last);
+    if (sh->rank == 0 && !others_here(sh)) {
+        // rank 0 recorded no event per frame: join the exchange / assembly
+        // stream and the render streams now (the render streams' frames
+        // are the rank's own rows of the frames)
+        SH_TRY(mark_done(sh, sh->last, sh->comm_stream));
+        if (run.two) SH_TRY(join_render_streams(sh, run.s, 2));   // (the comm-stream paths use streams 0 and 1)
+    }
+    HIP_TRY(hipStreamWaitEvent(run.s, sh->done[sh->last], 0));
+    return VR_OK;
+}
+
+// The union of intervals (start, end) -- overlapping ones count once -- and first start ->
+// last end.  Sorts iv.
+void interval_union(std::vector<std::pair<double, double>>& iv, double* busy, double* span)
+{
+    std::sort(iv.begin(), iv.end());
+    double sum = 0.0, lo = 0.0, hi = -1.0, end = 0.0;
+    for (const auto& x : iv) {
+        if (x.first > hi) {
+            if (hi >= lo) sum += hi - lo;
+            lo = x.first;
+            hi = x.second;
+        } else {
+            hi = std::max(hi, x.second);
+        }
+        end = std::max(end, x.second);
+    }
+    if (hi >= lo && !iv.empty()) sum += hi - lo;
+    *busy = sum;
+    *span = iv.empty() ? 0.0 : end - iv.front().first;
+}
+
+// The run's n sampled launches: their mean duration, and the busy time and span of their
+// intervals on one clock (ms after the first start; vr_shard_sampled_busy) -- with
+// sample_every = 1, the GPU time the run's renders held the machine
+vr_status reduce_samples(vr_shard* sh, int n, float* kernel_ms)
+{
+    double sum = 0.0;
+    std::vector<std::pair<double, double>> iv;
+    for (int k = 0; k < n; ++k) {
+        SH_TRY(wait_event(sh, sh->timing[2 * k + 1], "vr_shard_run: sampled render"));
+        float ms = 0.0f, a = 0.0f, b = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, sh->timing[2 * k], sh->timing[2 * k + 1]));
+        HIP_TRY(hipEventElapsedTime(&a, sh->timing[0], sh->timing[2 * k]));
+        HIP_TRY(hipEventElapsedTime(&b, sh->timing[0], sh->timing[2 * k + 1]));
+        sum += ms;
+        iv.emplace_back(a, b);
+    }
+    *kernel_ms = n ? (float)(sum / n) : 0.0f;
+    interval_union(iv, &sh->sampled_busy_ms, &sh->sampled_span_ms);
+    return VR_OK;
 }
 
 }  // namespace
@@ -838,301 +1156,22 @@ try {
     if (sh->loopback && sh->rank != 0 && !sh->solo)
         return fail(VR_ERR_INVALID, "vr_shard_run: rank %d is not connected (vr_shard_connect)", sh->rank);
     SH_TRY(check_usable(sh, "vr_shard_run"));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nsamp = kernel_ms ? (frames + sample_every - 1) / sample_every : 0;
-    while ((int)sh->timing.size() < 2 * nsamp) {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreate(&ev));
-        sh->timing.push_back(ev);
-    }
-    int next = 0;
-    const auto h0 = std::chrono::steady_clock::now();
-    // a procedural medium with deferred shadow rays renders on one stream:
-    // its frames could overlap since round 6 (a frame that reuses the cost
-    // order writes only its stream's deferred scratch set), but two in flight
-    // measured slower (config 3: 0.783 against 0.756 ms, profiles/r06/c10)
-    const int P = vr_get_option(sh->ctx, "procedural") == 2 ? 1
-                  : sh->on_render ? sh->render_streams : std::min(sh->render_streams, 2);
-    const bool two = P >= 2;   // frames overlap on P render streams
-    if (frames > 0) sh->started = true;   // the band geometry is fixed from here
-    // two render streams: tell the ctx its consecutive renders overlap (its
-    // auto split rule), from this pipeline's first such run until it is
-    // destroyed or set to one render stream (restore_overlap)
-    if (two && frames > 0 && sh->overlap_prev < 0) {
-        sh->overlap_prev = vr_get_option(sh->ctx, "frames_overlap");
-        if (sh->overlap_prev == 0) VR_TRY(vr_set_option(sh->ctx, "frames_overlap", 1));
-    }
-    if (two && frames > 0) {   // the render streams start after the caller's queued work (e.g. the volume)
-        HIP_TRY(hipEventRecord(sh->fence, s));
-        for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->fence, 0));
-    }
-    const bool on_render = sh->on_render && two;
-    // one rank rendering a grid on 2+ render streams: frames two at a time, each pair one
-    // launch (vr_render_pair); multi-rank pipelines and loopback keep one launch per frame
-    const bool one_rank = sh->nranks == 1 || (sh->loopback && sh->solo);
-    const int pairing = vr_get_option(sh->ctx, "frame_pairing");
-    const bool pairs = pairing > 0 && two && one_rank && !others_here(sh) && vr_get_option(sh->ctx, "procedural") == 0;
-    // frame_group 4: a one-rank communicator takes them four at a time (vr_render_group), the
-    // remainder as a pair and / or a single frame; a solo rehearsal keeps its pairs
-    const int group = pairs && sh->nranks == 1 && sh->my_rows > 0 ? vr_get_option(sh->ctx, "frame_group") : 2;
-    if (one_rank && frames > 0) {
-        if (sh->last >= 0 && ((sh->pairing >= 0 && pairing != sh->pairing) || (sh->group >= 0 && group != sh->group))) {
-            // frames of the old arrangement may still be in flight (vr_shard_set_render_streams)
-            for (int p = 0; p < kMaxFramesInFlight; ++p)
-                if (sh->pending[p]) SH_TRY(wait_event(sh, sh->done[p], "vr_shard_run: frame_pairing changed"));
-        }
-        sh->pairing = pairing;
-        sh->group = group;
-    }
-    if (pairs && group == 4 && pairing == 2 && frames > 0 && !sh->frame_more[0]) {   // the second stream's four sets
-        for (int p = 0; p < kMaxFramesInFlight; ++p) {
-            const hipError_t e = hipMalloc(&sh->frame_more[p], (size_t)sh->height * sh->pitch);
-            if (e != hipSuccess) {
-                sh->frame_more[p] = nullptr;
-                for (int k = 0; k < p; ++k) {
-                    (void)hipFree(sh->frame_more[k]);
-                    sh->frame_more[k] = nullptr;
-                }
-                return fail(e == hipErrorOutOfMemory ? VR_ERR_OOM : VR_ERR_HIP, "vr_shard_run: frame buffers: %s",
-                            hipGetErrorString(e));
-            }
-        }
-    }
-    if (pairs && group == 4 && frames > 0) {
-        for (int q = 0; q < kMaxFramesInFlight; ++q)   // (as below: buffer sets last used by other paths' frames)
-            if (sh->pending[q]) {
-                for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->done[q], 0));
-                sh->pending[q] = false;
-            }
-        const bool alt = pairing == 2;
-        for (int i = 0; i < frames;) {
-            const int m = std::min(frames - i, VR_MAX_GROUP);
-            bool samp = false;
-            for (int j = i; j < i + m && kernel_ms; ++j) samp = samp || j % sample_every == 0;
-            hipEvent_t t0 = samp ? sh->timing[2 * next] : nullptr, t1 = samp ? sh->timing[2 * next + 1] : nullptr;
-            if (samp) ++next;
-            const int q = alt ? (sh->pairs_run & 1) : 0;
-            SH_TRY(group_on_render(sh, alt ? kMaxFramesInFlight * q : 0, m, sh->render_stream[q], osd ? &osd[i] : nullptr,
-                                   gsd ? &gsd[i] : nullptr, t0, t1));
-            i += m;
-            ++sh->pairs_run;
-        }
-        for (int q = 0; q < 2; ++q) {   // join: the caller's stream after both streams' last frames
-            HIP_TRY(hipEventRecord(sh->tail[q], sh->render_stream[q]));
-            HIP_TRY(hipStreamWaitEvent(s, sh->tail[q], 0));
-        }
-        for (int b = 0; b < kMaxFramesInFlight; ++b) {   // a later frame of another arrangement waits for these
-            HIP_TRY(hipEventRecord(sh->done[b], sh->render_stream[alt ? b & 1 : 0]));
-            sh->pending[b] = true;
-        }
-    } else if (pairs && frames > 0) {
-        for (int q = 0; q < kMaxFramesInFlight; ++q)   // (as below: buffer sets last used by comm-stream frames)
-            if (sh->pending[q]) {
-                for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->done[q], 0));
-                sh->pending[q] = false;
-            }
-        const bool alt = pairing == 2;
-        for (int i = 0; i < frames;) {
-            const bool pair = i + 1 < frames;
-            const bool samp = kernel_ms && (i % sample_every == 0 || (pair && (i + 1) % sample_every == 0));
-            hipEvent_t t0 = samp ? sh->timing[2 * next] : nullptr, t1 = samp ? sh->timing[2 * next + 1] : nullptr;
-            if (samp) ++next;
-            const int q = alt ? (sh->pairs_run & 1) : 0;
-            hipStream_t rs = sh->render_stream[q];
-            // one stream: the buffer sets alternate 0 / 1 in its order; two: stream q owns sets 2q, 2q + 1
-            const int p0 = alt ? 2 * q : (sh->last < 0 ? 0 : (sh->last + 1) % 2);
-            if (pair) {
-                SH_TRY(pair_on_render(sh, p0, alt ? p0 + 1 : p0 ^ 1, rs, osd ? &osd[i] : nullptr, gsd ? &gsd[i] : nullptr,
-                                      t0, t1));
-                i += 2;
-            } else {   // an odd last frame renders alone, in the pairs' order
-                if (osd) VR_TRY(vr_set_shader_data(sh->ctx, &osd[i], &gsd[i]));
-                SH_TRY(one_frame_on_render(sh, p0, rs, t0, t1));
-                i += 1;
-            }
-            ++sh->pairs_run;
-        }
-        for (int q = 0; q < 2; ++q) {   // join: the caller's stream after both streams' last frames
-            HIP_TRY(hipEventRecord(sh->tail[q], sh->render_stream[q]));
-            HIP_TRY(hipStreamWaitEvent(s, sh->tail[q], 0));
-        }
-        for (int b = 0; b < (alt ? 4 : 2); ++b) {   // a later unpaired frame of set b waits for these
-            HIP_TRY(hipEventRecord(sh->done[b], sh->render_stream[alt ? b >> 1 : 0]));
-            sh->pending[b] = true;
-        }
-    } else if (on_render && frames > 0) {
-        // the communicators of streams 1..P-1, once each, split from the
-        // first (collective: every rank runs its first such frames together,
-        // in the same order; a one-rank communicator splits too, so its test
-        // covers the call)
-        for (int q = 1; q < P && !sh->loopback; ++q) {
-            ncclComm_t& cq = q == 1 ? sh->comm2 : sh->comm_more[q - 2];
-            if (cq) continue;
-            ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
-            cfg.blocking = 0;
-            const ncclResult_t r = ncclCommSplit(sh->comm, 0, sh->rank, &cq, &cfg);
-            if (r != ncclSuccess && r != ncclInProgress) {
-                cq = nullptr;
-                abort_comm(sh);
-                return fail(VR_ERR_COMM, "vr_shard_run: ncclCommSplit: %s; communicator aborted", ncclGetErrorString(r));
-            }
-            SH_TRY(settle(sh, "vr_shard_run: ncclCommSplit"));
-        }
-        // the buffer sets were last used by frames of the comm-stream path,
-        // if any: their exchanges must be done
-        for (int q = 0; q < kMaxFramesInFlight; ++q)
-            if (sh->pending[q]) {
-                for (hipStream_t rs : sh->render_stream) HIP_TRY(hipStreamWaitEvent(rs, sh->done[q], 0));
-                sh->pending[q] = false;
-            }
-        for (int i = 0; i < frames; ++i) {
-            const int p = sh->last < 0 ? 0 : (sh->last + 1) % P;
-            const bool samp = kernel_ms && i % sample_every == 0;
-            hipEvent_t t0 = samp ? sh->timing[2 * next] : nullptr, t1 = samp ? sh->timing[2 * next + 1] : nullptr;
-            if (samp) ++next;
-            if (osd) VR_TRY(vr_set_shader_data(sh->ctx, &osd[i], &gsd[i]));   // this frame's camera
-            SH_TRY(one_frame_on_render(sh, p, sh->render_stream[p], t0, t1));
-        }
-        // join: the caller's stream after every render stream's last frame
-        for (int q = 0; q < P; ++q) {
-            HIP_TRY(hipEventRecord(sh->tail[q], sh->render_stream[q]));
-            HIP_TRY(hipStreamWaitEvent(s, sh->tail[q], 0));
-            // a later comm-stream frame of parity q waits for this one
-            HIP_TRY(hipEventRecord(sh->done[q], sh->render_stream[q]));
-            sh->pending[q] = true;
-        }
-    } else if (sh->host_threads == 2 && frames > 1) {
-        // Two host threads: this one issues the render halves, a worker the
-        // exchange halves, so a frame's host time is the longer half, not the
-        // sum (an event record or a launch costs ~3-5 us).
-        // Frame i's exchange is issued after its render (rendered[p] recorded);
-        // frame i's render after frame i-2's exchange (done[p] recorded, and
-        // rendered[p] no longer awaited).
-        const int p0 = sh->last < 0 ? 0 : (sh->last + 1) % 2;
-        std::atomic<int> rdone{0}, cdone{0};
-        std::atomic<bool> stop{false};
-        vr_status wst = VR_OK;
-        std::string werr;
-        std::thread worker([&] {
-            if (hipSetDevice(sh->device) != hipSuccess) {
-                wst = fail(VR_ERR_HIP, "vr_shard_run: worker hipSetDevice");
-            } else {
-                for (int i = 0; i < frames; ++i) {
-                    if (!wait_host([&] { return rdone.load(std::memory_order_acquire) > i; }, stop, sh->timeout_s)) {
-                        if (!stop.load()) wst = fail(VR_ERR_TIMEOUT, "vr_shard_run: render thread stalled");
-                        break;
-                    }
-                    wst = comm_half(sh, (p0 + i) & 1);
-                    if (wst != VR_OK) break;
-                    cdone.store(i + 1, std::memory_order_release);
-                }
-            }
-            if (wst != VR_OK) {
-                werr = g_err;
-                stop.store(true, std::memory_order_release);
-            }
-        });
-        // if anything below throws, the worker is stopped and joined before
-        // the exception leaves (a joinable std::thread's destructor would
-        // call std::terminate past the function-try-block)
-        struct JoinGuard {
-            std::thread& t;
-            std::atomic<bool>& stop;
-            ~JoinGuard()
-            {
-                if (t.joinable()) {
-                    stop.store(true, std::memory_order_release);
-                    t.join();
-                }
-            }
-        } join_guard{worker, stop};
-        vr_status mst = VR_OK;
-        for (int i = 0; i < frames && mst == VR_OK; ++i) {
-            if (i >= 2 && !wait_host([&] { return cdone.load(std::memory_order_acquire) >= i - 1; }, stop, sh->timeout_s))
-                break;   // the worker failed (its status is reported) or stalled
-            const int p = (p0 + i) & 1;
-            const bool samp = kernel_ms && i % sample_every == 0;
-            hipEvent_t t0 = samp ? sh->timing[2 * next] : nullptr, t1 = samp ? sh->timing[2 * next + 1] : nullptr;
-            if (samp) ++next;
-            if (osd) {
-                mst = vr_set_shader_data(sh->ctx, &osd[i], &gsd[i]);
-                if (mst != VR_OK) mst = fail(mst, "vr_set_shader_data: %s", vr_last_error());
-            }
-            if (mst == VR_OK) mst = render_half(sh, p, two ? sh->render_stream[p] : s, t0, t1);
-            if (mst == VR_OK) rdone.store(i + 1, std::memory_order_release);
-        }
-        if (mst != VR_OK) stop.store(true, std::memory_order_release);
-        worker.join();
-        if (mst != VR_OK) return mst;
-        if (wst != VR_OK) {
-            g_err = werr;
-            return wst;
-        }
-        if (cdone.load() != frames) return fail(VR_ERR_TIMEOUT, "vr_shard_run: render thread stalled");
-        sh->last = (p0 + frames - 1) & 1;
-    } else {
-        for (int i = 0; i < frames; ++i) {
-            const int p = sh->last < 0 ? 0 : (sh->last + 1) % 2;
-            const bool samp = kernel_ms && i % sample_every == 0;
-            hipEvent_t t0 = samp ? sh->timing[2 * next] : nullptr, t1 = samp ? sh->timing[2 * next + 1] : nullptr;
-            if (samp) ++next;
-            if (osd) VR_TRY(vr_set_shader_data(sh->ctx, &osd[i], &gsd[i]));   // this frame's camera
-            const vr_status st = one_frame(sh, p, two ? sh->render_stream[p] : s, t0, t1);
-            if (st != VR_OK) return st;
-        }
-    }
-    if (sh->last >= 0 && frames > 0 && !on_render && !pairs) {   // the caller's stream sees the frame
-        if (sh->last >= kMaxFramesInFlight)   // (only a run of four-frame launches leaves such a set: not this path)
-            return fail(VR_ERR_INVALID, "vr_shard_run: internal: buffer set %d outside the per-frame events", sh->last);
-        if (sh->rank == 0 && !others_here(sh)) {
-            // rank 0 recorded no event per frame: join the exchange / assembly
-            // stream and the render streams now (the render streams' frames
-            // are the rank's own rows of the frames)
-            HIP_TRY(hipEventRecord(sh->done[sh->last], sh->comm_stream));
-            sh->pending[sh->last] = true;
-            if (two)
-                for (int q = 0; q < 2; ++q) {   // (the comm-stream paths use streams 0 and 1)
-                    HIP_TRY(hipEventRecord(sh->tail[q], sh->render_stream[q]));
-                    HIP_TRY(hipStreamWaitEvent(s, sh->tail[q], 0));
-                }
-        }
-        HIP_TRY(hipStreamWaitEvent(s, sh->done[sh->last], 0));
+    Run run{frames, osd, gsd, static_cast<hipStream_t>(stream), kernel_ms ? sample_every : 0};
+    if (frames > 0) {
+        SH_TRY(begin_run(sh, run));
+        const Arrangement* grouped = nullptr;
+        SH_TRY(choose_arrangement(sh, run, &grouped));
+        const bool on_render = sh->on_render && run.two;
+        if (grouped) SH_TRY(run_grouped(sh, run, *grouped));
+        else if (on_render) SH_TRY(run_on_render(sh, run));
+        else if (sh->host_threads == 2 && frames > 1) SH_TRY(run_two_threads(sh, run));
+        else SH_TRY(run_comm_stream(sh, run));
+        if (!grouped && !on_render) SH_TRY(show_last_frame(sh, run));
     }
     if (host_ms)
-        *host_ms = frames ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count() / frames
+        *host_ms = frames ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - run.h0).count() / frames
                           : 0.0;
-    if (kernel_ms) {
-        double sum = 0.0;
-        std::vector<std::pair<double, double>> iv;   // sampled renders on one clock: ms after the first start
-        for (int k = 0; k < next; ++k) {
-            SH_TRY(wait_event(sh, sh->timing[2 * k + 1], "vr_shard_run: sampled render"));
-            float ms = 0.0f, a = 0.0f, b = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, sh->timing[2 * k], sh->timing[2 * k + 1]));
-            HIP_TRY(hipEventElapsedTime(&a, sh->timing[0], sh->timing[2 * k]));
-            HIP_TRY(hipEventElapsedTime(&b, sh->timing[0], sh->timing[2 * k + 1]));
-            sum += ms;
-            iv.emplace_back(a, b);
-        }
-        *kernel_ms = next ? (float)(sum / next) : 0.0f;
-        // busy: the union of the sampled intervals (overlapping renders on
-        // several streams count once); with sample_every = 1, the GPU time
-        // the run's renders held the machine
-        std::sort(iv.begin(), iv.end());
-        double busy = 0.0, lo = 0.0, hi = -1.0, end = 0.0;
-        for (const auto& x : iv) {
-            if (x.first > hi) {
-                if (hi >= lo) busy += hi - lo;
-                lo = x.first;
-                hi = x.second;
-            } else {
-                hi = std::max(hi, x.second);
-            }
-            end = std::max(end, x.second);
-        }
-        if (hi >= lo && !iv.empty()) busy += hi - lo;
-        sh->sampled_busy_ms = busy;
-        sh->sampled_span_ms = iv.empty() ? 0.0 : end - iv.front().first;
-    }
+    if (kernel_ms) SH_TRY(reduce_samples(sh, run.next, kernel_ms));
     return VR_OK;
 } catch (...) {
     return caught_exception("vr_shard_run_frames");
