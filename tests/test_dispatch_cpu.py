@@ -26,8 +26,8 @@ def test_dispatch_check_builds_and_passes(tmp_path, experiments):
 
 
 def test_no_launch_macros_in_csrc():
-    """#define VR_R* / VR_U* / VR_P* in csrc are build knobs only (VR_PIPE, VR_PROC_*, VR_PHASE_FENCE,
-    VR_UM_ATTR, VR_UM_WAVES ...): none takes arguments and launches a kernel."""
+    """No #define VR_R* / VR_U* / VR_P* in csrc takes arguments and launches a kernel, and the launch
+    macros the dispatcher replaced stay gone."""
     gone = {"VR_RW", "VR_UM", "VR_UMS", "VR_UMF", "VR_PD", "VR_PS", "VR_PS3", "VR_PT", "VR_PR"}
     found = []
     for name in sorted(os.listdir(CSRC)):
@@ -38,4 +38,22 @@ def test_no_launch_macros_in_csrc():
             macro, params, body = m.group(1), m.group(2), m.group(3)
             if macro in gone or (params and "hipLaunchKernelGGL" in body):
                 found.append((name, macro))
+    assert not found, found
+
+
+def test_no_retired_build_knobs_in_csrc():
+    """The build knobs whose measured winner became the plain code are named
+    nowhere in csrc, comments included: the record of what they tried is DESIGN.md's."""
+    retired = ["VR_PIPE", "VR_LANEMAP", "VR_PROC_WAVES", "VR_PROC_ATTR", "VR_DEFER_UNROLL", "VR_DEFER_ATTR",
+               "VR_FBM_UNROLL", "VR_FBM_UNROLL_BY", "VR_FBM_PREFETCH", "VR_FBM_FENCE", "VR_PROC_PHASES",
+               "VR_PHASE_FENCE", "VR_UM_ATTR", "VR_UM_WAVES", "VR_SHADOW_PHASED", "VR_SHADOW_WAVES",
+               "VR_SHADOW_ATTR", "VR_CUBE_BATCH"]
+    pattern = re.compile(r"\b(" + "|".join(retired) + r")\b")
+    found = []
+    for name in sorted(os.listdir(CSRC)):
+        path = os.path.join(CSRC, name)
+        if not os.path.isfile(path) or name.endswith((".o", ".so")):
+            continue
+        for m in pattern.finditer(open(path, errors="replace").read()):
+            found.append((name, m.group(1)))
     assert not found, found

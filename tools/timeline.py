@@ -4,7 +4,7 @@
     VR_LIB=volumetricrenderer_amd/libvr_tl.so python tools/timeline.py [--size 512] [--layout 12]
 
 Each wave of the launch records its start and end (s_memrealtime, 100 MHz),
-its XCD and its executed lane-steps (vr_march_kernels.h VR_TIMELINE).  Prints
+its XCD and its executed lane-steps (vr_march_common.h VR_TIMELINE).  Prints
 the launch span, the longest wave, the number of waves resident over time
 and per-XCD spans: whether the frame is bound by throughput (many waves to
 the end) or by the critical path of its longest rays (a tail of few waves).

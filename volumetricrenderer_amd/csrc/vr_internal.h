@@ -360,7 +360,7 @@ struct RegionBuild {
     int order;             // option region_order: 0 inside-out, 1 longest tile first, 2 longest S x S block first
 };
 // True when no ray of tile (tx, ty) of the target can be covered (setup_ray,
-// vr_march_kernels.h), so the march would write the uncovered value at every
+// vr_march_common.h), so the march would write the uncovered value at every
 // pixel of it.  Conservative, in double: the box lies wholly in front of the
 // camera (clip w > 0 at its 8 corners: no line through the eye meets it
 // behind), and one side plane of the tile's frustum -- through the eye and
@@ -449,7 +449,7 @@ struct SortLayout {
 };
 SortLayout sort_layout(int width, int out_rows);
 
-// Deferred shadow rays (vr_march_kernels.h march_proc_defer): device scratch,
+// Deferred shadow rays (vr_proc_kernels.h march_proc_defer): device scratch,
 // sized from the frame (vr_api.cpp ensure_defer).  Sorted wave w appends at most
 // went[w + 1] - went[w] entries (the sum of its lanes' step counts, bounded by
 // their cost keys) and marches at most wrec[w + 1] - wrec[w] wave-steps (its

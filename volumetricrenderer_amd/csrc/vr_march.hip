@@ -11,6 +11,7 @@
 // lerps per instruction.  Built with -ffp-contract=off: the only fused ops
 // are the explicit fma calls.
 #include "vr_march_kernels.h"
+#include "vr_proc_kernels.h"
 
 namespace vr {
 
@@ -79,7 +80,7 @@ hipError_t launch_march_procedural(const MarchArgs& a, bool early, void* sort_bu
         // 3 = 2 + the Perlin lattice table
         const int tm = wt_bytes ? (a.proc.wt_fixed ? (a.proc.lat ? 3 : 2) : 1) : 0;
         const bool stale = reuse_sort == SORT_STALE;
-        if (shadow && defer && tm >= 2) {   // deferred shadow rays: three passes (vr_march_kernels.h)
+        if (shadow && defer && tm >= 2) {   // deferred shadow rays: three passes (vr_proc_kernels.h)
             const ShadowDefer d = *defer;
             const dim3 eval_grid(d.eval_blocks ? d.eval_blocks : kShadowEvalBlocks);
             return with_value<2, 3>(tm, [&](auto T) {

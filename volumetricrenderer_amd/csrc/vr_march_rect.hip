@@ -5,8 +5,9 @@
 // One wave renders one 8x8 tile; the tiles are anchored at the rectangle's
 // origin rounded down to a multiple of 8, so a pixel sits in the lane it has
 // under vr_render's tilings.  The kernels are the shared device functions of
-// vr_march_kernels.h (fast_prologue, march_pixel, march_pixel_proc,
-// worley_table, add_steps, lane_x / lane_y) behind another tile map:
+// vr_march_kernels.h (fast_prologue, march_pixel), vr_proc_kernels.h
+// (march_pixel_proc, worley_table) and vr_march_common.h (add_steps,
+// lane_x / lane_y) behind another tile map:
 // MarchArgs still describes the whole frame, so setup_ray and store_pixel
 // compute frame coordinates as they do for vr_render, and a pixel's
 // arithmetic is vr_render's.  A lane outside the rectangle is handed the
@@ -21,6 +22,7 @@
 // Built with -fno-slp-vectorize like vr_march.hip and vr_march_c8.hip
 // (Makefile FLAGS_*), whose code generation these instantiations share.
 #include "vr_march_kernels.h"
+#include "vr_proc_kernels.h"
 
 namespace vr {
 namespace {

@@ -258,7 +258,7 @@ vr_status render_procedural(Ctx* c, const MarchArgs& a, bool early, hipStream_t 
     void* sort_buf = nullptr;
     Schedule sc{c->schedule == SCHED_RINGS ? SCHED_RINGS : SCHED_STATIC, 0, 0, 1, 1, nullptr, nullptr, {}, 1, 0, 4, nullptr};
     if (sc.kind == SCHED_RINGS) box_centre_pixel(c, a, &sc.center_x, &sc.center_y);
-    // the sort passes enumerate whole 64x64 regions (vr_march_kernels.h sort_pixel)
+    // the sort passes enumerate whole 64x64 regions (vr_proc_kernels.h sort_pixel)
     if (c->schedule != SCHED_STATIC && c->schedule != SCHED_RINGS && a.width < 65536 && a.out_rows < 65536 &&
         (long long)((a.width + 63) / 64) * ((a.out_rows + 63) / 64) * 4096 < (1ll << 31)) {
         const size_t need = sort_layout(a.width, a.out_rows).bytes;
