@@ -423,6 +423,75 @@ vr_status vr_volume_box_footprint(const vr_object_shader_data* osd, const vr_glo
 vr_status vr_update_footprint(void* ctx, int width, int height,
                               int x0, int y0, int z0, int bx, int by, int bz, vr_rect* out);
 
+/* ---- the ray query: which part of the volume does a pixel see?  The
+ *      opposite question to vr_update_footprint, and no reference counterpart:
+ *      the reference's fragment keeps only outColor (frag.glsl:80).  One
+ *      record is one ray as vr_render marches it.  64 bytes.               */
+typedef struct {
+    int32_t steps;          /* executed ray-steps (frag.glsl:46 actualSteps, fewer
+                               where early_out stops the ray): exactly what this
+                               pixel adds to step_counter under option "count" 0;
+                               -1 = the pixel is not covered (vr_render writes
+                               the background there)                         */
+    int32_t hit_step;       /* first step that passes `threshold`, see below;
+                               -1 = none                                     */
+    float   value;          /* the pixel's VR_FMT_R32F value, bit for bit
+                               (frag.glsl:79-80)                             */
+    float   optical_depth;  /* acc * step_size of the view ray (frag.glsl:76), fp32 */
+    float   entry[3];       /* Pin in [0,1]^3 after frag.glsl:49-53          */
+    float   reserved0;      /* 0                                             */
+    float   step[3];        /* stepVec after frag.glsl:54                    */
+    float   reserved1;      /* 0                                             */
+    float   hit[3];         /* sample point of step hit_step (Pin at that
+                               iteration of frag.glsl:64-75); zeros if none  */
+    float   reserved2;      /* 0                                             */
+} vr_ray_record;
+/* Write the records of the pixels [x, x+width) x [y, y+height) of the
+ * width x height frame to `d_records`, a DEVICE buffer of rect->height rows of
+ * row_pitch_records records (0 = tightly packed, rect->width), 16-byte
+ * aligned: the rectangle's pixel (x + i, y + j) is record j * pitch + i.
+ * Pixels outside the rectangle have no record and nothing else of the buffer
+ * is written.  No pixel buffer is involved.
+ *
+ * value is what vr_render of the same context stores at that pixel in
+ * VR_FMT_R32F, bit for bit: the query's march repeats the render's fp32
+ * operations in the render's order.  entry, step and steps are the ray setup
+ * of frag.glsl:36-55; optical_depth the accumulated `accumulatedTransmission *
+ * stepSize` of :76.  A pixel the box does not cover has steps = hit_step = -1,
+ * value = the background (0) and zeros elsewhere; a covered ray too short for
+ * one step has steps = 0.
+ *
+ * `threshold` has the meaning and the validation of
+ * vr_march_params.early_out: a transmittance in [0,1), 0 = off, and it needs
+ * density > 0.  Its accumulator limit L is computed by the expression that
+ * turns early_out into the march's own limit; hit_step is the smallest step
+ * index i such that the fp32 accumulator AFTER step i exceeds L, and hit the
+ * fp32 sample point of that step as marched (entry with step added hit_step
+ * times, in that order).  So a query with threshold T on a context without
+ * early_out names the step after which a context with early_out = T stops
+ * the ray: that context executes hit_step + 1 steps.  The search covers
+ * executed steps only; the context's own early_out, if set, ends it.
+ *
+ * Procedural medium (with and without shadow rays): value is the rendered
+ * radiance; optical_depth, hit_step and hit refer to the VIEW ray's
+ * accumulator; steps counts ray-steps whatever option "count" says.
+ *
+ * An empty rectangle is VR_OK and does nothing.  VR_ERR_INVALID: a null
+ * pointer, a non-positive frame size, a rectangle that is negative or leaves
+ * the frame, a pitch below the rectangle's width, a misaligned buffer, a bad
+ * threshold; VR_ERR_NO_VOLUME and VR_ERR_NO_CAMERA as for vr_render.  A
+ * refused call writes nothing.
+ *
+ * Otherwise the contract is vr_render_rect's: asynchronous on `stream`;
+ * allocates nothing and NEVER waits on the host; one wave per 8x8 tile of the
+ * rectangle; uses and disturbs none of the context's cached launches, region
+ * lists, cost-sort or deferred-shadow scratch, nor the pending
+ * uniform-channel read-back; every channel marched with loads; option
+ * "inject_throw" honoured.                                                 */
+vr_status vr_query_rect(void* ctx, int width, int height, const vr_rect* rect,
+                        float threshold, void* d_records, size_t row_pitch_records,
+                        void* stream);
+
 /* ---- multi-GPU frame assembly.  The band sets of `nranks` ranks are
  *      gathered into one device buffer, d_gathered = [rank][packed rows].
  *      Each rank's set holds `rows_per_rank` rows.  This call scatters them

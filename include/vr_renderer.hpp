@@ -181,6 +181,17 @@ public:
         Check(vr_update_footprint(ctx_, frame.width, frame.height, x0, y0, z0, bx, by, bz, &r), "vr_update_footprint");
         return r;
     }
+    // The opposite question: which part of the volume does a pixel see?  One
+    // vr_ray_record per pixel of `scissor` into the device buffer d_records
+    // (scissor.height rows of row_pitch_records records, 0 = scissor.width):
+    // steps, depth, the render's R32F value and, with a transmittance
+    // `threshold`, the first step and point that pass it (vr_query_rect).
+    void QueryRect(const Rect2D& frame, const vr_rect& scissor, float threshold, vr_ray_record* d_records,
+                   size_t row_pitch_records = 0, void* stream = nullptr)
+    {
+        Check(vr_query_rect(ctx_, frame.width, frame.height, &scissor, threshold, d_records, row_pitch_records, stream),
+              "vr_query_rect");
+    }
     const char* KernelVariant() const { return vr_kernel_variant(ctx_); }
     void* Handle() const { return ctx_; }
 

@@ -7,14 +7,15 @@ interface (renderer) and the multi-GPU band sharding (distributed).
 """
 from ._lib import (FMT_R8_SRGB, FMT_R8_UNORM, FMT_R32F, FMT_RGBA8_SRGB, FMT_RGBA8_UNORM, FMT_RGBA32F,  # noqa: F401
                    GREY_OF, GlobalShaderData, MarchParams, ObjectShaderData, Target, VolumeRecipe, VRError)
-from ._lib import VR_MAX_RECTS, Procedural, Rect  # noqa: F401
-from .renderer import (Renderer, band_rows_packed, coalesce_rects, march_defaults, procedural_defaults,  # noqa: F401
-                       reference_shader_data, scaled_recipe, shader_data_arrays, volume_box_footprint,
+from ._lib import VR_MAX_RECTS, Procedural, RayRecord, Rect  # noqa: F401
+from .renderer import (RAY_RECORD_DTYPE, Renderer, band_rows_packed, coalesce_rects, march_defaults,  # noqa: F401
+                       procedural_defaults, ray_records, reference_shader_data, scaled_recipe, shader_data_arrays,
+                       volume_box_footprint,
                        volume_recipe_defaults)
 
 __all__ = [
     "Renderer", "VRError", "march_defaults", "procedural_defaults", "Procedural", "reference_shader_data", "volume_recipe_defaults",
     "scaled_recipe", "band_rows_packed", "shader_data_arrays", "FMT_RGBA32F", "FMT_RGBA8_UNORM",
     "FMT_RGBA8_SRGB", "FMT_R8_UNORM", "FMT_R8_SRGB", "FMT_R32F", "GREY_OF", "ObjectShaderData", "GlobalShaderData", "MarchParams", "VolumeRecipe", "Target",
-    "Rect", "volume_box_footprint", "coalesce_rects", "VR_MAX_RECTS",
+    "Rect", "volume_box_footprint", "coalesce_rects", "VR_MAX_RECTS", "RayRecord", "RAY_RECORD_DTYPE", "ray_records",
 ]

@@ -106,6 +106,17 @@ class Rect(ctypes.Structure):
 
 VR_MAX_RECTS = 64   # vr.h: the longest list vr_render_rects takes
 
+
+class RayRecord(ctypes.Structure):
+    """vr_ray_record: one ray as vr_render marches it (vr_query_rect).  64 bytes."""
+    _fields_ = [("steps", ctypes.c_int32), ("hit_step", ctypes.c_int32), ("value", ctypes.c_float),
+                ("optical_depth", ctypes.c_float), ("entry", ctypes.c_float * 3), ("reserved0", ctypes.c_float),
+                ("step", ctypes.c_float * 3), ("reserved1", ctypes.c_float), ("hit", ctypes.c_float * 3),
+                ("reserved2", ctypes.c_float)]
+
+
+RAY_RECORD_WORDS = ctypes.sizeof(RayRecord) // 4   # a record as int32 words: query_rect's last axis
+
 _vp = ctypes.c_void_p
 _SIGS = {
     "vr_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_vp)]),
@@ -151,6 +162,8 @@ _SIGS = {
                                                ctypes.POINTER(MarchParams)] + [ctypes.c_int] * 11
                                 + [ctypes.POINTER(Rect)]),
     "vr_update_footprint": (ctypes.c_int, [_vp] + [ctypes.c_int] * 8 + [ctypes.POINTER(Rect)]),
+    "vr_query_rect": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Rect), ctypes.c_float, _vp,
+                                     ctypes.c_size_t, _vp]),
     "vr_assemble_bands": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "vr_assemble_frame": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,

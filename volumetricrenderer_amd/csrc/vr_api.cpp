@@ -264,9 +264,7 @@ bool frame_args(const Ctx* c, int width, int height, MarchArgs* ap)
     a.density = m.density;
     a.scale = m.scale;
     a.max_steps = m.max_steps;
-    a.acc_limit = m.early_out > 0.0f
-                      ? (float)(-std::log((double)m.early_out) / ((double)m.density * (double)a.step_size))
-                      : INFINITY;
+    a.acc_limit = acc_limit_of(m.early_out, m.density, a.step_size);
     return true;
 }
 

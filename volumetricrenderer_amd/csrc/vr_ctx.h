@@ -295,6 +295,13 @@ bool clamp_is_exact(const Ctx* c, const float S[4][3], const float T[4][3]);
 int band_rows_packed(int height, int band_rows, int band_stride, int band_first, int band_flip = 0);
 vr_status make_plan(Ctx* c, MarchArgs* a, Plan* p);
 bool frame_args(const Ctx* c, int width, int height, MarchArgs* a);
+// The accumulator value above which a ray's transmittance is below `transmittance` (MarchArgs.acc_limit
+// for vr_march_params.early_out; vr_query_rect's hit limit for its threshold): INFINITY for 0 = off.
+inline float acc_limit_of(float transmittance, float density, float step_size)
+{
+    return transmittance > 0.0f ? (float)(-std::log((double)transmittance) / ((double)density * (double)step_size))
+                                : INFINITY;
+}
 void proc_args(const Ctx* c, MarchArgs* a);
 void volume_args(const Ctx* c, const Plan& pl, MarchArgs* a);
 const char* variant_name(const Plan& p);
@@ -315,6 +322,9 @@ void honour_inject_throw(Ctx* c);   // option inject_throw: consumed, then throw
 // The whole frame's MarchArgs up to the schedule: ray basis and march constants, the procedural parameters or the
 // grid plan, volume buffers, target geometry; every channel loaded (umask 0).  *pl = layout, wrap, early-out variant.
 vr_status frame_march_args(const char* fn, Ctx* c, const vr_target* t, const TargetInfo& ti, MarchArgs* a, Plan* pl);
+
+// ---- vr_rect.cpp: shared with vr_query.cpp
+bool rect_in_frame(int width, int height, const vr_rect* r);   // non-negative and inside the width x height frame
 
 // ---- vr_regions_host.cpp
 inline int wedges_of(const Ctx* c)

@@ -509,6 +509,20 @@ struct RectArgs {
 RectArgs rect_args(int x, int y, int width, int height);
 hipError_t launch_march_rect(const MarchArgs& a, int layout, int wrap, bool early, const RectArgs& rc, hipStream_t s);
 hipError_t launch_march_proc_rect(const MarchArgs& a, bool early, const RectArgs& rc, hipStream_t s);
+// vr_query_rect (vr_march_query.hip): what the query kernels need beyond MarchArgs and RectArgs, by
+// value next to them.  The record of the rectangle's pixel (col, row) is the 64 bytes at
+// rec + 4 * (row * pitch + col) (include/vr.h vr_ray_record; pitch in records, >= the rectangle's
+// width; rec 16-byte aligned).  limit: the accumulator value the hit search compares with
+// (acc_limit's expression, vr_ctx.h acc_limit_of; INFINITY = no search).  `a` as for launch_march_rect,
+// with no pixel buffer and no step counter: neither is touched.
+struct QueryArgs {
+    float4* rec;
+    long long pitch;
+    float limit;
+};
+hipError_t launch_march_query(const MarchArgs& a, int layout, int wrap, bool early, const RectArgs& rc, const QueryArgs& q,
+                              hipStream_t s);
+hipError_t launch_march_proc_query(const MarchArgs& a, bool early, const RectArgs& rc, const QueryArgs& q, hipStream_t s);
 // vr_render_rects (vr_march_rect.hip): a list of rectangles in one launch, by value in the
 // kernarg segment next to MarchArgs.  Rectangle k is the pixels [e[k][0], e[k][2]) x
 // [e[k][1], e[k][3]); its 8x8 tiles are anchored as RectArgs anchors them and numbered

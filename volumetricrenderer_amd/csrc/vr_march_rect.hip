@@ -7,7 +7,7 @@
 // under vr_render's tilings.  The kernels are the shared device functions of
 // vr_march_kernels.h (fast_prologue, march_pixel), vr_proc_kernels.h
 // (march_pixel_proc, worley_table) and vr_march_common.h (add_steps,
-// lane_x / lane_y) behind another tile map:
+// lane_x / lane_y) behind another tile map (rect_pixel, vr_rect_tiles.h):
 // MarchArgs still describes the whole frame, so setup_ray and store_pixel
 // compute frame coordinates as they do for vr_render, and a pixel's
 // arithmetic is vr_render's.  A lane outside the rectangle is handed the
@@ -23,24 +23,10 @@
 // (Makefile FLAGS_*), whose code generation these instantiations share.
 #include "vr_march_kernels.h"
 #include "vr_proc_kernels.h"
+#include "vr_rect_tiles.h"
 
 namespace vr {
 namespace {
-
-// The frame pixel of this lane, or (a.width, 0) outside the rectangle.
-// tiles_x = 8-px tile columns the rectangle spans from its anchor.
-template <int LAYOUT>
-__device__ __forceinline__ void rect_pixel(const MarchArgs& a, const RectArgs& rc, int* x, int* y)
-{
-    const int lane = threadIdx.x & 63;
-    const int t = (int)blockIdx.x * (kThreads / 64) + (int)(threadIdx.x >> 6);
-    const int ty = t / rc.tiles_x, tx = t - ty * rc.tiles_x;
-    const int px = (rc.x0 & ~7) + tx * 8 + lane_x<LAYOUT>(lane);
-    const int py = (rc.y0 & ~7) + ty * 8 + lane_y<LAYOUT>(lane);
-    const bool in = px >= rc.x0 && px < rc.x1 && py >= rc.y0 && py < rc.y1;
-    *x = in ? px : a.width;
-    *y = in ? py : 0;
-}
 
 // No wave leaves before the prologue's barrier: the waves of a last, partly
 // used workgroup march pixels outside the rectangle (not live).
@@ -134,24 +120,6 @@ inline dim3 rects_grid(const RectList& rl)
 inline bool rects_launchable(const RectList& rl)
 {
     return rl.count >= 0 && rl.count <= kMaxRects && rl.tile_begin[rl.count] <= 0x7fffffffu;
-}
-
-inline dim3 rect_grid(const RectArgs& rc)
-{
-    const long long waves = (long long)rc.tiles_x * (((rc.y1 + 7) >> 3) - (rc.y0 >> 3));
-    return dim3((unsigned)((waves + 3) / 4));
-}
-
-// The layout x wrap x EARLY choice of march_rect and march_rects: launch(L, W, E, LDS bytes)
-template <class F>
-hipError_t with_rect_variant(const MarchArgs& a, int layout, int wrap, bool early, F&& launch)
-{
-    return with_layout_wrap<BuiltLayouts>(layout, wrap, [&](auto L, auto W) {
-        return with_bool(early, [&](auto E) {
-            launch(L, W, E, march_lds_bytes<L>(a));
-            return hipGetLastError();
-        });
-    });
 }
 
 }  // namespace

@@ -10,6 +10,16 @@
 // load every channel (umask 0), which is exact whatever the read-back will say.
 #include "vr_ctx.h"
 
+namespace vrapi {
+
+bool rect_in_frame(int width, int height, const vr_rect* r)
+{
+    return r->x >= 0 && r->y >= 0 && r->width >= 0 && r->height >= 0 && r->width <= width - r->x &&
+           r->height <= height - r->y;
+}
+
+}  // namespace vrapi
+
 using namespace vrapi;
 
 namespace {
@@ -30,12 +40,6 @@ vr_status check_frame_target(const char* fn, const Ctx* c, const vr_target* t, T
     return check_pixels(fn, t, t->format, &ti->pitch);
 }
 
-bool rect_in_frame(const vr_target* t, const vr_rect* r)
-{
-    return r->x >= 0 && r->y >= 0 && r->width >= 0 && r->height >= 0 && r->width <= t->width - r->x &&
-           r->height <= t->height - r->y;
-}
-
 bool holds(const vr_rect& a, const vr_rect& b)   // a contains b, both non-empty
 {
     return a.x <= b.x && a.y <= b.y && b.x + b.width <= a.x + a.width && b.y + b.height <= a.y + a.height;
@@ -51,7 +55,7 @@ try {
     Ctx* c = as_ctx(p);
     TargetInfo ti;
     if (const vr_status st = check_frame_target("vr_render_rect", c, t, &ti)) return st;
-    if (!rect_in_frame(t, r))
+    if (!rect_in_frame(t->width, t->height, r))
         return fail(VR_ERR_INVALID, "vr_render_rect: rectangle %dx%d at (%d, %d) leaves the %dx%d frame", r->width,
                     r->height, r->x, r->y, t->width, t->height);
     honour_inject_throw(c);
@@ -81,7 +85,7 @@ try {
     TargetInfo ti;
     if (const vr_status st = check_frame_target("vr_render_rects", c, t, &ti)) return st;
     for (int i = 0; i < count; ++i)
-        if (!rect_in_frame(t, &rects[i]))
+        if (!rect_in_frame(t->width, t->height, &rects[i]))
             return fail(VR_ERR_INVALID, "vr_render_rects: rectangle %d, %dx%d at (%d, %d), leaves the %dx%d frame", i,
                         rects[i].width, rects[i].height, rects[i].x, rects[i].y, t->width, t->height);
     honour_inject_throw(c);

@@ -33,8 +33,8 @@ import torch
 
 from . import _lib
 from ._lib import (BYTES_PER_PIXEL, CHANNELS, FLOAT_FORMATS, FMT_RGBA8_SRGB, FMT_RGBA8_UNORM, FMT_RGBA32F,  # noqa: F401
-                   GREY_OF, GlobalShaderData, MarchParams, ObjectShaderData, Procedural, Rect, Target, VolumeRecipe,
-                   VR_MAX_RECTS, VRError, call)
+                   GREY_OF, RAY_RECORD_WORDS, GlobalShaderData, MarchParams, ObjectShaderData, Procedural, RayRecord,
+                   Rect, Target, VolumeRecipe, VR_MAX_RECTS, VRError, call)
 
 _lib.load()  # fail at import if the HIP library is missing
 
@@ -150,6 +150,23 @@ def coalesce_rects(rects, max_out: int = VR_MAX_RECTS) -> list[tuple[int, int, i
     n = ctypes.c_int(0)
     call("vr_rects_coalesce", arr, len(arr), int(max_out), out, ctypes.byref(n))
     return [(out[i].x, out[i].y, out[i].width, out[i].height) for i in range(n.value)]
+
+
+# vr_ray_record as a numpy structured type (the layout of _lib.RayRecord)
+RAY_RECORD_DTYPE = np.dtype([("steps", "<i4"), ("hit_step", "<i4"), ("value", "<f4"), ("optical_depth", "<f4"),
+                             ("entry", "<f4", (3,)), ("reserved0", "<f4"), ("step", "<f4", (3,)), ("reserved1", "<f4"),
+                             ("hit", "<f4", (3,)), ("reserved2", "<f4")])
+assert RAY_RECORD_DTYPE.itemsize == ctypes.sizeof(RayRecord) == 4 * RAY_RECORD_WORDS
+
+
+def ray_records(words) -> np.ndarray:
+    """:meth:`Renderer.query_rect`'s int32 tensor (or array) [..., 16] on the
+    host, viewed as records with named fields (``steps``, ``hit_step``,
+    ``value``, ``optical_depth``, ``entry``, ``step``, ``hit``): shape [...]."""
+    a = words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words)
+    if a.dtype != np.int32 or a.shape[-1] != RAY_RECORD_WORDS:
+        raise ValueError(f"ray records are int32 [..., {RAY_RECORD_WORDS}], got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a).view(RAY_RECORD_DTYPE).reshape(a.shape[:-1])
 
 
 def shader_data_arrays(osd: ObjectShaderData, gsd: GlobalShaderData):
@@ -477,6 +494,62 @@ class Renderer:
         r = Rect()
         call("vr_update_footprint", self._ctx, int(width), int(height), x0, y0, z0, bx, by, bz, ctypes.byref(r))
         return r.x, r.y, r.width, r.height
+
+    def query_rect(self, rect, width: int, height: int, threshold: float = 0.0, stream=None,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+        """vr_query_rect: the ray records of the pixels rect = (x, y, w, h) of
+        the width x height frame, as a ``torch.int32`` tensor [h, w, 16] on the
+        GPU (one vr_ray_record per pixel; :func:`ray_records` names its fields
+        on the host).  ``value`` is :meth:`render`'s FMT_R32F pixel bit for bit;
+        ``threshold`` (a transmittance, as march.early_out; 0 = off) selects
+        ``hit_step`` / ``hit``.  `out`: an int32 tensor [>= h, >= w, 16] on this
+        device with contiguous records to write into (its rows may be wider
+        than the rectangle; only the rectangle's records are written).
+        Asynchronous on `stream`."""
+        x, y, w, h = (int(v) for v in rect)
+        if out is None:
+            out = torch.empty((max(h, 0), max(w, 0), RAY_RECORD_WORDS), dtype=torch.int32,
+                              device=torch.device("cuda", self.device))
+            if out.numel() == 0:   # no buffer to hand over: validate with a one-record stand-in, which stays unwritten
+                spare = torch.empty((1, 1, RAY_RECORD_WORDS), dtype=torch.int32, device=out.device)
+                call("vr_query_rect", self._ctx, int(width), int(height), ctypes.byref(Rect(x, y, w, h)),
+                     ctypes.c_float(threshold), ctypes.c_void_p(spare.data_ptr()), 0, _stream_handle(stream))
+                return out
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != self.device
+                or out.dtype != torch.int32 or out.dim() != 3 or out.shape[2] != RAY_RECORD_WORDS
+                or out.stride(2) != 1 or out.stride(1) != RAY_RECORD_WORDS or out.stride(0) % RAY_RECORD_WORDS != 0
+                or out.shape[0] < h or out.shape[1] < w or out.stride(0) < out.shape[1] * RAY_RECORD_WORDS):
+            raise ValueError(f"query_rect: out must be an int32 tensor (>= {h}, >= {w}, {RAY_RECORD_WORDS}) on "
+                             f"cuda:{self.device} with contiguous records")
+        call("vr_query_rect", self._ctx, int(width), int(height), ctypes.byref(Rect(x, y, w, h)),
+             ctypes.c_float(threshold), ctypes.c_void_p(out.data_ptr()), out.stride(0) // RAY_RECORD_WORDS,
+             _stream_handle(stream))
+        return out
+
+    def pick(self, x: int, y: int, width: int, height: int, threshold: float):
+        """The ray of pixel (x, y) of the width x height frame (a 1 x 1
+        :meth:`query_rect`; waits for it): ``(record, texel)``.  `record` is
+        the pixel's vr_ray_record as a numpy record.  `texel` is None unless the
+        ray has a hit (``hit_step >= 0``) and a volume is installed; then it is
+        the texel (ix, iy, iz) of tap 0 (frag.glsl:66: Pin + MediaScroll[.].x *
+        tap_weight[0], scaled by tap_scale[0]) that ``hit`` falls in, clamped to
+        the volume -- where an editor paints."""
+        rec = ray_records(self.query_rect((x, y, 1, 1), width, height, threshold))[0, 0]
+        if rec["hit_step"] < 0:
+            return rec, None
+        try:
+            dims = self.volume_dims()
+        except VRError:
+            return rec, None
+        if min(dims) <= 0:
+            return rec, None
+        gsd = getattr(self, "gsd", None)
+        texel = []
+        for ax in range(3):
+            off = float(gsd.media_scroll[ax * 4 + 0]) * float(self.march.tap_weight[0]) if gsd is not None else 0.0
+            u = float(rec["hit"][ax]) * float(self.march.tap_scale[0]) + off
+            texel.append(int(min(max(np.floor(u * dims[ax]), 0), dims[ax] - 1)))
+        return rec, tuple(texel)
 
     def render_rows(self, width: int, height: int, fmt: int, first_row: int, rows: int,
                     out: torch.Tensor | None = None, in_place: bool = False, stream=None) -> torch.Tensor:
