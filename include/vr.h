@@ -224,6 +224,77 @@ vr_status vr_update_volume_device(void* ctx, const void* d_rgba8, int x0, int y0
 /* read the volume back as RGBA8 (host); for tests and tools             */
 vr_status vr_get_volume(void* ctx, uint8_t* rgba8_out);
 vr_status vr_volume_dims(void* ctx, int* nx, int* ny, int* nz);
+/* The read-back counterpart of vr_update_volume: the texel box [x0,x0+bx) x
+ * [y0,y0+by) x [z0,z0+bz) of the installed volume as bx*by*bz RGBA8 texels,
+ * tightly packed, x fastest -- what vr_update_volume takes, so saving a box,
+ * editing it and handing the saved bytes back restores it (undo).  The box is
+ * validated as vr_update_volume validates it and the cost follows the box.
+ * The host call is synchronous; the device variant writes to DEVICE memory
+ * and is asynchronous on `stream` (no allocation, no host wait).            */
+vr_status vr_get_volume_box(void* ctx, int x0, int y0, int z0, int bx, int by, int bz, uint8_t* rgba8_out);
+vr_status vr_get_volume_box_device(void* ctx, int x0, int y0, int z0, int bx, int by, int bz, void* d_rgba8_out,
+                                   void* stream);
+
+/* ---- the brush: a read-modify-write of the installed volume on the device.
+ *      No reference counterpart (the reference uploads its texture once).
+ *      vr_update_volume overwrites a box with bytes the caller has finished;
+ *      a brush blends into what is there, so an editor needs no read-back:
+ *      vr_query_rect (pick) -> vr_paint -> vr_update_footprint ->
+ *      vr_render_rect queue on one stream with no host round trip.
+ *
+ * Everything is defined in integers.  For the texel at
+ * offset (dx, dy, dz) from `centre`, with D_a = 2 radius[a] + 1, in unsigned
+ * 64-bit arithmetic:
+ *   S = Dx^2 Dy^2 Dz^2
+ *   Q = (2dx)^2 Dy^2 Dz^2 + (2dy)^2 Dx^2 Dz^2 + (2dz)^2 Dx^2 Dy^2
+ * The texel is inside iff |d_a| <= radius[a] on every axis and Q <= S; radius
+ * (0, 0, 0) is exactly one texel.  Weight w = 256 for a hard edge (falloff 0);
+ * for a smooth one (falloff 1) w = 256 - (256 Q) / (S + 1), integer division:
+ * 256 at the centre, 1 on the rim.  Per channel c, a = w * strength[c]
+ * (0..65280) and d = (value[c] a + 32640) / 65280:
+ *   VR_BRUSH_SET  new = (old (65280 - a) + value[c] a + 32640) / 65280
+ *   VR_BRUSH_ADD  new = min(255, old + d)
+ *   VR_BRUSH_SUB  new = max(0, old - d)
+ * Texels outside the ellipsoid, and texels of it outside the volume, are not
+ * touched; a channel with strength 0 is neither read nor written.           */
+typedef enum { VR_BRUSH_SET = 0, VR_BRUSH_ADD = 1, VR_BRUSH_SUB = 2 } vr_brush_op;
+#define VR_BRUSH_MAX_RADIUS 255
+typedef struct {              /* 48 bytes */
+    int32_t centre[3];        /* texel (x, y, z); may lie outside the volume */
+    int32_t radius[3];        /* semi-axes in texels, 0..VR_BRUSH_MAX_RADIUS; per axis,
+                                 because a non-cubic volume fills the same [0,1]^3 box */
+    int32_t op;               /* vr_brush_op */
+    int32_t falloff;          /* 0 = hard edge, 1 = smooth (linear in squared distance) */
+    uint8_t value[4];         /* per channel R, G, B, A */
+    uint8_t strength[4];      /* per channel, 0..255; 0 leaves the channel as it is */
+    int32_t reserved[2];      /* must be 0 */
+} vr_brush;
+/* Apply the brush to the installed volume, in place.  Afterwards the ctx
+ * renders, and vr_get_volume reads, bit for bit what a vr_set_volume of the
+ * painted volume would give.  The contract is vr_update_volume_device's:
+ * asynchronous on `stream`, nothing allocated, no host wait; the device
+ * layouts are rebuilt over the brush's clipped bounding box (plus the halo);
+ * cached launches, region lists and the uniform-channel read-back are treated
+ * exactly as the update treats them -- the new bytes are folded into the
+ * channels' byte ranges, so a uniform channel the brush changes loses its bit
+ * before the next render, and one it leaves alone (strength 0, or a result
+ * equal to what was there) keeps it.  A brush that misses the volume is VR_OK
+ * and launches nothing.
+ * VR_ERR_INVALID: a null pointer, a bad op or falloff, a radius outside
+ * 0..VR_BRUSH_MAX_RADIUS, non-zero reserved; VR_ERR_NO_VOLUME before an
+ * install and while a procedural medium is enabled.  A refused call leaves
+ * the volume untouched.                                                     */
+vr_status vr_paint(void* ctx, const vr_brush* brush, void* stream);
+/* The brush's bounding box [centre - radius, centre + radius] clipped to an
+ * nx x ny x nz volume: what vr_paint rewrites, and what to hand to
+ * vr_update_footprint.  extent = (0, 0, 0) (and origin 0) when the brush
+ * misses the volume.  Pure host code: no context, no device.  The brush is
+ * validated as by vr_paint; VR_ERR_INVALID also for a non-positive dimension. */
+vr_status vr_brush_box(const vr_brush* brush, int nx, int ny, int nz, int origin[3], int extent[3]);
+/* The same brush applied to a HOST RGBA8 volume (x fastest, the order of
+ * vr_set_volume), for callers without a device: the CPU statement of the
+ * arithmetic above, which vr_paint reproduces bit for bit.  Pure host code.  */
+vr_status vr_brush_apply(const vr_brush* brush, uint8_t* rgba8, int nx, int ny, int nz);
 /* 1 if vr_set_volume / vr_set_volume_device accept an nx x ny x nz extent
  * (the device layouts index a plane with 32-bit offsets), else 0          */
 int       vr_volume_extent_ok(int nx, int ny, int nz);

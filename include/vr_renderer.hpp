@@ -54,6 +54,15 @@ inline std::vector<vr_rect> CoalesceRects(const std::vector<vr_rect>& rects, int
     return out;
 }
 
+// The brush's bounding box clipped to an nx x ny x nz volume (vr_brush_box):
+// what Renderer::Paint rewrites and what Renderer::UpdateFootprint takes;
+// false (and a zero extent) when the brush misses the volume.  Host code only.
+inline bool BrushBox(const vr_brush& brush, int nx, int ny, int nz, int origin[3], int extent[3])
+{
+    Check(vr_brush_box(&brush, nx, ny, nz, origin, extent), "vr_brush_box");
+    return extent[0] > 0;
+}
+
 class Renderer {
 public:
     explicit Renderer(int device = 0) { Check(vr_create(device, &ctx_), "vr_create"); }
@@ -75,6 +84,21 @@ public:
     void UpdateVolumeDevice(const void* d_rgba, int x0, int y0, int z0, int bx, int by, int bz, void* stream = nullptr)
     {
         Check(vr_update_volume_device(ctx_, d_rgba, x0, y0, z0, bx, by, bz, stream), "vr_update_volume_device");
+    }
+    // Blend a brush into the installed volume on the device, asynchronous on
+    // `stream` (vr_paint): pick (QueryRect), Paint, UpdateFootprint of
+    // BrushBox, RenderRect queue on one stream with no host round trip.
+    void Paint(const vr_brush& brush, void* stream = nullptr) { Check(vr_paint(ctx_, &brush, stream), "vr_paint"); }
+    // The read-back counterpart of UpdateVolume (vr_get_volume_box): save a
+    // box, Paint, UpdateVolume the saved box -- undo.
+    void GetVolumeBox(int x0, int y0, int z0, int bx, int by, int bz, uint8_t* rgba_out) const
+    {
+        Check(vr_get_volume_box(ctx_, x0, y0, z0, bx, by, bz, rgba_out), "vr_get_volume_box");
+    }
+    void GetVolumeBoxDevice(int x0, int y0, int z0, int bx, int by, int bz, void* d_rgba_out,
+                            void* stream = nullptr) const
+    {
+        Check(vr_get_volume_box_device(ctx_, x0, y0, z0, bx, by, bz, d_rgba_out, stream), "vr_get_volume_box_device");
     }
     void GenerateVolume(const vr_volume_recipe& r, void* stream = nullptr)
     {

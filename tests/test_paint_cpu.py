@@ -1,0 +1,240 @@
+"""vr_paint and its host companions (vr_brush_box, vr_brush_apply,
+vr_get_volume_box), the checks that need no GPU: the struct layout in the
+header, the ctypes mirror and the C++ wrapper; the prototypes and exports; the
+argument checks that come before any device work; and vr_brush_apply /
+vr_brush_box against the numpy restatement of the brush (tests/paint_spec.py)
+on every brush x op x falloff of the issue's table."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import paint_spec as ps  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("vr_paint", "vr_brush_box", "vr_brush_apply", "vr_get_volume_box", "vr_get_volume_box_device")
+FIELDS = ("centre", "radius", "op", "falloff", "value", "strength", "reserved")
+OFFSETS = [0, 12, 24, 28, 32, 36, 40]
+
+
+def header_source():
+    src = open(os.path.join(ROOT, "include", "vr.h")).read()
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def brush(centre, radius, op=0, falloff=0, value=ps.VALUE, strength=ps.STRENGTH):
+    import volumetricrenderer_amd as vr
+    return vr.make_brush(centre, radius, op, falloff, value, strength)
+
+
+@pytest.fixture(scope="module")
+def base():
+    return ps.base_volume()
+
+
+def test_brush_layout_in_header_ctypes_and_hpp(tmp_path):
+    from volumetricrenderer_amd import _lib
+    assert ctypes.sizeof(_lib.Brush) == 48
+    assert [getattr(_lib.Brush, f).offset for f in FIELDS] == OFFSETS
+    offs = ", ".join(f"offsetof(vr_brush, {f})" for f in FIELDS)
+    fmt = " ".join(["%zu"] * (len(FIELDS) + 1))
+    body = (f'int main(void){{printf("{fmt} %d %d %d %d\\n", sizeof(vr_brush), {offs}, (int)VR_BRUSH_SET, '
+            "(int)VR_BRUSH_ADD, (int)VR_BRUSH_SUB, (int)VR_BRUSH_MAX_RADIUS); return 0;}\n")
+    want = [48] + OFFSETS + [0, 1, 2, 255]
+    c = tmp_path / "brush.c"
+    c.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "vr.h"\n' + body)
+    cpp = tmp_path / "brush.cpp"   # the C++ wrapper's view of the same struct
+    cpp.write_text('#include <cstdio>\n#include <cstddef>\n#include "vr_renderer.hpp"\n'
+                   "static_assert(sizeof(vr_brush) == 48, \"vr_brush\");\n"
+                   "void (vr::Renderer::*paint_fn)(const vr_brush&, void*) = &vr::Renderer::Paint;\n"   # they exist
+                   "bool (*brush_box_fn)(const vr_brush&, int, int, int, int*, int*) = &vr::BrushBox;\n"
+                   "void (vr::Renderer::*get_box_fn)(int, int, int, int, int, int, uint8_t*) const = "
+                   "&vr::Renderer::GetVolumeBox;\n" + body)
+    for src, cc, std in ((c, "gcc", "-std=c99"), (cpp, "g++", "-std=c++17")):
+        exe = tmp_path / (src.name + ".exe")
+        libdir = os.path.join(ROOT, "volumetricrenderer_amd")
+        subprocess.run([cc, std, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe), "-L", libdir, "-lvr",
+                        "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], check=True)
+        got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+        assert got == want, (cc, got)
+    assert (_lib.BRUSH_SET, _lib.BRUSH_ADD, _lib.BRUSH_SUB, _lib.BRUSH_MAX_RADIUS) == (0, 1, 2, 255)
+
+
+def test_prototypes_exports_and_signatures():
+    from volumetricrenderer_amd import _lib
+    lib = _lib.load()
+    src = header_source()
+    declared = set(re.findall(r"\b(vr_[a-z_0-9]+)\s*\(", src))
+    for name in NEW:
+        assert name in declared, name
+        assert name in _lib.exported_symbols(), name
+        assert hasattr(lib, name), name
+    for name, nargs in (("vr_paint", 3), ("vr_brush_box", 6), ("vr_brush_apply", 5), ("vr_get_volume_box", 8),
+                        ("vr_get_volume_box_device", 9)):
+        m = re.search(r"vr_status\s+" + name + r"\s*\(([^)]*)\)", src)
+        assert m, name
+        assert len(m.group(1).split(",")) == nargs == len(_lib._SIGS[name][1]), name
+        assert _lib._SIGS[name][0] is ctypes.c_int
+    assert re.search(r"vr_status\s+vr_paint\s*\(\s*void\*\s*ctx,\s*const vr_brush\*\s*brush,\s*void\*\s*stream\)", src)
+    assert _lib.load().vr_abi_version() == 2
+
+
+def test_null_arguments_are_invalid_with_a_message():
+    from volumetricrenderer_amd import _lib
+    lib = _lib.load()
+    b = brush((0, 0, 0), (1, 1, 1))
+    texel = (ctypes.c_uint8 * 4)()
+    o, e = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+    cases = [
+        ("vr_paint", (None, ctypes.byref(b), None)),
+        ("vr_paint", (ctypes.c_void_p(8), None, None)),     # a null brush is refused before the context is read
+        ("vr_get_volume_box", (None, 0, 0, 0, 1, 1, 1, texel)),
+        ("vr_get_volume_box", (ctypes.c_void_p(8), 0, 0, 0, 1, 1, 1, None)),
+        ("vr_get_volume_box_device", (None, 0, 0, 0, 1, 1, 1, texel, None)),
+        ("vr_get_volume_box_device", (ctypes.c_void_p(8), 0, 0, 0, 1, 1, 1, None, None)),
+        ("vr_brush_box", (None, 4, 4, 4, o, e)),
+        ("vr_brush_box", (ctypes.byref(b), 4, 4, 4, None, e)),
+        ("vr_brush_box", (ctypes.byref(b), 4, 4, 4, o, None)),
+        ("vr_brush_apply", (None, texel, 1, 1, 1)),
+        ("vr_brush_apply", (ctypes.byref(b), None, 1, 1, 1)),
+    ]
+    for name, args in cases:
+        assert getattr(lib, name)(*args) == 1, (name, args)   # VR_ERR_INVALID
+        msg = lib.vr_last_error().decode()
+        assert name + ":" in msg and "null" in msg, msg
+    with pytest.raises(_lib.VRError) as err:
+        _lib.call("vr_paint", None, None, None)
+    assert err.value.status == 1 and "vr_paint" in str(err.value)
+
+
+@pytest.mark.parametrize("name", list(ps.BRUSHES))
+def test_brush_box_matches_numpy_clip(name):
+    import volumetricrenderer_amd as vr
+    centre, radius = ps.BRUSHES[name]
+    want = ps.spec_box(centre, radius)
+    assert vr.brush_box(brush(centre, radius), (ps.NX, ps.NY, ps.NZ)) == want
+    assert (want is None) == (name == "miss")
+    o, e = (ctypes.c_int * 3)(7, 7, 7), (ctypes.c_int * 3)(7, 7, 7)
+    b = brush(centre, radius)
+    vr._lib.call("vr_brush_box", ctypes.byref(b), ps.NX, ps.NY, ps.NZ, o, e)
+    if want is None:
+        assert tuple(e) == (0, 0, 0)
+    else:
+        assert (tuple(o), tuple(e)) == want
+
+
+def test_brush_box_far_centres_and_small_volumes():
+    import volumetricrenderer_amd as vr
+    big, small = 2**31 - 1, -2**31
+    assert vr.brush_box(brush((big, big, big), (255, 255, 255)), (8, 8, 8)) is None
+    assert vr.brush_box(brush((small, small, small), (255, 255, 255)), (8, 8, 8)) is None
+    assert vr.brush_box(brush((small, 3, 3), (255, 1, 1)), (8, 8, 8)) is None
+    assert vr.brush_box(brush((0, 0, 0), (0, 0, 0)), (1, 1, 1)) == ((0, 0, 0), (1, 1, 1))
+    assert vr.brush_box(brush((200, -200, 0), (255, 255, 255)), (1, 1, 1)) == ((0, 0, 0), (1, 1, 1))
+    assert vr.brush_box(brush((-255, 0, 0), (255, 0, 0)), (4, 4, 4)) == ((0, 0, 0), (1, 1, 1))
+    assert vr.brush_box(brush((-256, 0, 0), (255, 0, 0)), (4, 4, 4)) is None
+    assert vr.brush_box(brush((5, 2, 9), (2, 7, 1)), (9, 6, 10)) == ((3, 0, 8), (5, 6, 2))
+
+
+def bad_brushes():
+    out = []
+    for op in (-1, 3, 2**31 - 1):
+        out.append(brush((1, 1, 1), (1, 1, 1), op=op))
+    for falloff in (-1, 2):
+        out.append(brush((1, 1, 1), (1, 1, 1), falloff=falloff))
+    for ax in range(3):
+        for rad in (-1, 256, 2**31 - 1, -2**31):
+            rr = [1, 1, 1]
+            rr[ax] = rad
+            out.append(brush((1, 1, 1), rr))
+    for k in range(2):
+        b = brush((1, 1, 1), (1, 1, 1))
+        b.reserved[k] = 1
+        out.append(b)
+    return out
+
+
+def test_host_calls_refuse_bad_brushes_and_dimensions():
+    from volumetricrenderer_amd import _lib
+    lib = _lib.load()
+    vol = np.full((4, 4, 4, 4), 9, np.uint8)
+    o, e = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+    vp = vol.ctypes.data_as(ctypes.c_void_p)
+    for b in bad_brushes():
+        assert lib.vr_brush_box(ctypes.byref(b), 4, 4, 4, o, e) == 1
+        assert "vr_brush_box:" in lib.vr_last_error().decode()
+        assert lib.vr_brush_apply(ctypes.byref(b), vp, 4, 4, 4) == 1
+        assert "vr_brush_apply:" in lib.vr_last_error().decode()
+    good = brush((1, 1, 1), (1, 1, 1))
+    for dims in ((0, 4, 4), (4, 0, 4), (4, 4, 0), (-1, 4, 4), (4, 4, -7)):
+        assert lib.vr_brush_box(ctypes.byref(good), *dims, o, e) == 1
+        assert lib.vr_brush_apply(ctypes.byref(good), vp, *dims) == 1
+    assert (vol == 9).all()   # a refused call has touched nothing
+    assert lib.vr_paint(None, ctypes.byref(bad_brushes()[0]), None) == 1
+
+
+@pytest.mark.parametrize("falloff,fname", ps.FALLOFFS, ids=[n for _, n in ps.FALLOFFS])
+@pytest.mark.parametrize("op,oname", ps.OPS, ids=[n for _, n in ps.OPS])
+@pytest.mark.parametrize("name", list(ps.BRUSHES))
+def test_brush_apply_matches_the_numpy_restatement(base, name, op, oname, falloff, fname):
+    import volumetricrenderer_amd as vr
+    centre, radius = ps.BRUSHES[name]
+    want = ps.spec_apply(base, centre, radius, op, falloff)
+    got = vr.brush_apply(brush(centre, radius, op, falloff), base.copy())
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
+    # the conditions on the inputs: a weaker input must not hide a failure
+    inside, w = ps.spec_weights(base.shape[:3], centre, radius, falloff)
+    assert (want[..., 3] == base[..., 3]).all(), "channel A has strength 0"
+    assert (want[~inside] == base[~inside]).all()
+    if name == "miss":
+        assert not inside.any() and (want == base).all()
+        return
+    assert (want != base).any()
+    count = {"interior": 171, "straddle": 801, "outside_centre": 9, "texel": 1}
+    if name in count:
+        assert int(inside.sum()) == count[name]
+    if falloff and name == "outside_centre":
+        assert w[inside].min() == 4 and w[inside].max() == 92
+    if falloff and name == "straddle":
+        assert w[inside].min() == 3
+    if op == ps.ADD:
+        # old + d passed 255 somewhere: the clamp is exercised
+        assert clamped(base, inside, w, +1), "no texel clamps to 255"
+    if op == ps.SUB and not (falloff and name == "outside_centre"):
+        assert clamped(base, inside, w, -1), "no texel clamps to 0"
+
+
+def clamped(base, inside, w, sign):
+    """Does some inside texel's unclamped result old +- d leave 0..255 in a painted channel?"""
+    for c in range(3):
+        a = w * ps.STRENGTH[c]
+        d = (ps.VALUE[c] * a + 32640) // 65280
+        r = base[..., c].astype(np.int64) + sign * d
+        if ((r > 255) | (r < 0))[inside].any():
+            return True
+    return False
+
+
+def test_brush_apply_set_endpoints_and_identity(base):
+    """Full weight and strength give value exactly; a zero weight product keeps old; strength 0 writes nothing."""
+    import volumetricrenderer_amd as vr
+    got = vr.brush_apply(brush((5, 5, 5), (0, 0, 0), ps.SET, 0, (1, 2, 3, 4), (255, 255, 255, 255)), base.copy())
+    assert tuple(got[5, 5, 5]) == (1, 2, 3, 4)
+    got[5, 5, 5] = base[5, 5, 5]
+    assert (got == base).all()
+    for op, _ in ps.OPS:
+        for falloff, _ in ps.FALLOFFS:
+            got = vr.brush_apply(brush((18, 11, 22), (40, 40, 40), op, falloff, ps.VALUE, (0, 0, 0, 0)), base.copy())
+            assert (got == base).all()
+    small = np.zeros((1, 1, 1, 4), np.uint8)   # a 1 x 1 x 1 volume under the largest brush, centre off the volume
+    vr.brush_apply(brush((100, -100, 7), (255, 255, 255), ps.ADD, 1, (255, 255, 255, 255), (255, 255, 255, 255)), small)
+    assert (small == ps.spec_apply(np.zeros((1, 1, 1, 4), np.uint8), (100, -100, 7), (255, 255, 255), ps.ADD, 1,
+                                   (255,) * 4, (255,) * 4)).all() and small.any()
+    with pytest.raises(ValueError):
+        vr.brush_apply(brush((0, 0, 0), (1, 1, 1)), np.zeros((2, 2, 2, 3), np.uint8))

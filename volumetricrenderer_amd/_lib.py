@@ -115,6 +115,16 @@ class RayRecord(ctypes.Structure):
                 ("reserved2", ctypes.c_float)]
 
 
+class Brush(ctypes.Structure):
+    """vr_brush: an ellipsoidal brush in texels (vr_paint, vr_brush_box, vr_brush_apply).  48 bytes."""
+    _fields_ = [("centre", ctypes.c_int32 * 3), ("radius", ctypes.c_int32 * 3), ("op", ctypes.c_int32),
+                ("falloff", ctypes.c_int32), ("value", ctypes.c_uint8 * 4), ("strength", ctypes.c_uint8 * 4),
+                ("reserved", ctypes.c_int32 * 2)]
+
+
+BRUSH_SET, BRUSH_ADD, BRUSH_SUB = 0, 1, 2   # vr.h vr_brush_op
+BRUSH_MAX_RADIUS = 255                      # vr.h VR_BRUSH_MAX_RADIUS
+
 RAY_RECORD_WORDS = ctypes.sizeof(RayRecord) // 4   # a record as int32 words: query_rect's last axis
 
 _vp = ctypes.c_void_p
@@ -130,6 +140,11 @@ _SIGS = {
     "vr_update_volume_device": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [_vp]),
     "vr_get_volume": (ctypes.c_int, [_vp, _vp]),
     "vr_volume_dims": (ctypes.c_int, [_vp, c_int_p, c_int_p, c_int_p]),
+    "vr_get_volume_box": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_vp]),
+    "vr_get_volume_box_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_vp, _vp]),
+    "vr_paint": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp]),
+    "vr_brush_box": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p]),
+    "vr_brush_apply": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vr_volume_extent_ok": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vr_volume_recipe_defaults": (ctypes.c_int, [ctypes.POINTER(VolumeRecipe)]),
     "vr_generate_volume": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeRecipe), _vp]),

@@ -13,6 +13,7 @@
 // region lists / row partition and the procedural scratch live in
 // vr_options.cpp, vr_regions_host.cpp and vr_proc_host.cpp; the scissored
 // renders in vr_rect.cpp.
+#include "vr_brush.h"
 #include "vr_ctx.h"
 
 namespace vrapi {
@@ -495,18 +496,17 @@ static vr_status check_update(const char* fn, void* p, const void* data, int x0,
     return VR_OK;
 }
 
-// Patch the planes and the held fast layout on `s`: launches only, no
-// allocation, no host wait.  The scatter folds the box's byte range into d_mm,
-// so a uniform channel (uniform_mask, which the _uX kernels sample as a
-// constant) can only be lost: while some channel is uniform, or the install's
-// scan is still unresolved, the read-back is re-armed and the next render /
-// vr_kernel_variant / vr_get_option resolves it as after an install.  With no
-// uniform channel left nothing can change: no read-back, no `gen` bump, and
-// the cached launches stay valid (same buffers, same geometry).
-static vr_status update_volume_device(Ctx* c, const uint8_t* d_box, int x0, int y0, int z0, int bx, int by, int bz,
-                                      hipStream_t s)
+// What follows a kernel that has rewritten texels of the box in the planes and
+// folded their byte range into d_mm (the update's scatter, the brush), on `s`:
+// launches only, no allocation, no host wait.  The held fast layout is rebuilt
+// over the box.  A uniform channel (uniform_mask, which the _uX kernels sample
+// as a constant) can only be lost: while some channel is uniform, or the
+// install's scan is still unresolved, the read-back is re-armed and the next
+// render / vr_kernel_variant / vr_get_option resolves it as after an install.
+// With no uniform channel left nothing can change: no read-back, no `gen`
+// bump, and the cached launches stay valid (same buffers, same geometry).
+static vr_status box_edited(Ctx* c, int x0, int y0, int z0, int bx, int by, int bz, hipStream_t s)
 {
-    HIP_TRY(launch_update_planar(d_box, c->nx, c->ny, c->nz, x0, y0, z0, bx, by, bz, c->d_planar, c->d_mm, s));
     if (c->fast_layout)
         HIP_TRY(launch_build_layout_box(c->fast_layout, c->d_planar, c->nx, c->ny, c->nz, c->d_fast, x0, y0, z0, bx,
                                         by, bz, s));
@@ -516,6 +516,14 @@ static vr_status update_volume_device(Ctx* c, const uint8_t* d_box, int x0, int 
         c->mm_pending = true;
     }
     return VR_OK;
+}
+
+// Patch the planes (the scatter folds the box's byte range into d_mm) and the held fast layout on `s`.
+static vr_status update_volume_device(Ctx* c, const uint8_t* d_box, int x0, int y0, int z0, int bx, int by, int bz,
+                                      hipStream_t s)
+{
+    HIP_TRY(launch_update_planar(d_box, c->nx, c->ny, c->nz, x0, y0, z0, bx, by, bz, c->d_planar, c->d_mm, s));
+    return box_edited(c, x0, y0, z0, bx, by, bz, s);
 }
 
 }  // namespace vrapi
@@ -582,6 +590,63 @@ try {
     return VR_OK;
 } catch (...) {
     return caught_exception("vr_get_volume");
+}
+
+vr_status vr_get_volume_box(void* p, int x0, int y0, int z0, int bx, int by, int bz, uint8_t* out)
+try {
+    if (vr_status st = check_update("vr_get_volume_box", p, out, x0, y0, z0, bx, by, bz)) return st;
+    Ctx* c = as_ctx(p);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)bx * by * bz * 4;
+    uint8_t* staging = nullptr;   // the box, not the volume
+    HIP_TRY(hipMalloc(&staging, bytes));
+    hipError_t e = launch_unpack_box(c->d_planar, c->nx, c->ny, c->nz, x0, y0, z0, bx, by, bz, staging, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, staging, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(staging);
+    if (e != hipSuccess) return fail(VR_ERR_HIP, "vr_get_volume_box: %s", hipGetErrorString(e));
+    return VR_OK;
+} catch (...) {
+    return caught_exception("vr_get_volume_box");
+}
+
+vr_status vr_get_volume_box_device(void* p, int x0, int y0, int z0, int bx, int by, int bz, void* d_out, void* stream)
+try {
+    if (vr_status st = check_update("vr_get_volume_box_device", p, d_out, x0, y0, z0, bx, by, bz)) return st;
+    Ctx* c = as_ctx(p);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_unpack_box(c->d_planar, c->nx, c->ny, c->nz, x0, y0, z0, bx, by, bz, static_cast<uint8_t*>(d_out),
+                              static_cast<hipStream_t>(stream)));
+    return VR_OK;
+} catch (...) {
+    return caught_exception("vr_get_volume_box_device");
+}
+
+// The brush on the device: k_paint_planar over the clipped bounding box, then what follows an update of that box.
+vr_status vr_paint(void* p, const vr_brush* b, void* stream)
+try {
+    if (!p || !b) return fail(VR_ERR_INVALID, "vr_paint: null argument");
+    if (const char* why = vr::brush::invalid(b)) return fail(VR_ERR_INVALID, "vr_paint: %s", why);
+    Ctx* c = as_ctx(p);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_paint: no volume set");
+    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_paint: a procedural medium is enabled (it reads no volume)");
+    PaintArgs a{};
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
+    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    a.s = t.s;
+    for (int ax = 0; ax < 3; ++ax) {
+        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
+        a.k[ax] = t.k[ax];
+    }
+    a.op = b->op;
+    a.falloff = b->falloff;
+    for (int ch = 0; ch < 4; ++ch) { a.value[ch] = b->value[ch]; a.strength[ch] = b->strength[ch]; }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(launch_paint_planar(a, c->d_planar, c->d_mm, s));
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+} catch (...) {
+    return caught_exception("vr_paint");
 }
 
 vr_status vr_noise_grid(void* p, int kind, void* d_out, int x0, int y0, int z0, int nx, int ny, int nz,

@@ -1,0 +1,74 @@
+// vr_brush.cpp -- vr_brush_box and vr_brush_apply: the brush of vr_paint on
+// the host (include/vr.h).
+//
+// Pure host code in integers: no context, no device, no HIP call.  The
+// arithmetic is vr_brush.h's, which the paint kernel (vr_volume.hip) includes
+// too; vr_brush_apply is its CPU statement, what vr_paint must reproduce bit
+// for bit.  tools/brush_check.cpp compiles this file alone
+// (-DVR_BRUSH_STANDALONE, which only drops the vr_last_error text) under the
+// address and undefined-behaviour sanitizers.
+#include <cstdint>
+
+#include "vr_brush.h"
+
+#ifdef VR_BRUSH_STANDALONE
+namespace {
+vr_status fail(vr_status st, const char*, ...) { return st; }
+}
+#else
+#include "vr_ctx.h"
+using vrapi::fail;
+#endif
+
+namespace {
+
+vr_status check(const char* fn, const vr_brush* b, int nx, int ny, int nz)
+{
+    if (!b) return fail(VR_ERR_INVALID, "%s: null argument", fn);
+    if (const char* why = vr::brush::invalid(b)) return fail(VR_ERR_INVALID, "%s: %s", fn, why);
+    if (nx <= 0 || ny <= 0 || nz <= 0) return fail(VR_ERR_INVALID, "%s: bad extent %dx%dx%d", fn, nx, ny, nz);
+    return VR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+vr_status vr_brush_box(const vr_brush* b, int nx, int ny, int nz, int origin[3], int extent[3])
+{
+    if (!origin || !extent) return fail(VR_ERR_INVALID, "vr_brush_box: null argument");
+    if (vr_status st = check("vr_brush_box", b, nx, ny, nz)) return st;
+    (void)vr::brush::clip(b, nx, ny, nz, origin, extent);
+    return VR_OK;
+}
+
+vr_status vr_brush_apply(const vr_brush* b, uint8_t* rgba8, int nx, int ny, int nz)
+{
+    if (!rgba8) return fail(VR_ERR_INVALID, "vr_brush_apply: null argument");
+    if (vr_status st = check("vr_brush_apply", b, nx, ny, nz)) return st;
+    int o[3], e[3];
+    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    // inside the clipped box every offset is within the radius: at most 255 in magnitude
+    for (int z = o[2]; z < o[2] + e[2]; ++z) {
+        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
+        for (int y = o[1]; y < o[1] + e[1]; ++y) {
+            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
+            if (qyz > t.s) continue;
+            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
+            for (int x = o[0]; x < o[0] + e[0]; ++x) {
+                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
+                if (q > t.s) continue;
+                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
+                for (int c = 0; c < 4; ++c) {
+                    if (!b->strength[c]) continue;
+                    uint8_t* p = row + (size_t)x * 4 + c;
+                    *p = (uint8_t)vr::brush::blend(b->op, *p, b->value[c], w * b->strength[c]);
+                }
+            }
+        }
+    }
+    return VR_OK;
+}
+
+}  // extern "C"

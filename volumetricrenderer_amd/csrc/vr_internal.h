@@ -578,6 +578,20 @@ size_t layout_plane_bytes(int layout, int nx, int ny, int nz);
 size_t layout_total_bytes(int layout, int nx, int ny, int nz);
 hipError_t launch_unpack(const uint8_t* d_planar, int nx, int ny, int nz, uint8_t* d_rgba,
                          hipStream_t s);
+// vr_get_volume_box: the planes' texel box (inside the volume) -> tightly packed RGBA8, x fastest
+hipError_t launch_unpack_box(const uint8_t* d_planar, int nx, int ny, int nz, int x0, int y0, int z0, int bx, int by,
+                             int bz, uint8_t* d_box, hipStream_t s);
+// vr_paint: a validated brush (vr.h vr_brush) and its bounding box clipped to the volume (vr_brush.h clip)
+struct PaintArgs {
+    int nx, ny, nz;
+    int o[3], e[3];               // the clipped box: origin and extent (e > 0)
+    int d0[3];                    // o - centre: the offset of the box's first texel from the centre, per axis
+    int op, falloff;
+    unsigned value[4], strength[4];
+    unsigned long long s, k[3];   // vr_brush.h Terms of the radii
+};
+// Blend the brush into the planar planes in place and fold the new bytes' per-channel min / max into mm
+hipError_t launch_paint_planar(const PaintArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s);
 // Perlin lattice table: entry (x, y, z) - lo of n^3 = noise::perlin_lattice_entry(seed, x, y, z)
 hipError_t launch_perlin_lattice(uint2* d_out, int seed, int lo, int n, hipStream_t s);
 hipError_t launch_noise(int kind, float* d_out, int x0, int y0, int z0, int nx, int ny, int nz,

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "vr_brush.h"
 #include "vr_internal.h"
 #include "vr_noise.h"
 
@@ -34,33 +35,12 @@ __global__ __launch_bounds__(kBlock) void k_repack_planar(const uchar4* __restri
     }
 }
 
-// vr_update_volume: scatter a tightly packed RGBA8 box (bx x by x bz texels at
-// texel (x0, y0, z0), x fastest) into the four planes.  One thread per texel,
-// consecutive lanes on consecutive x of a box row: a 4-B load, then one byte
-// store per plane -- the plane rows start at any byte (x0 and nx are
-// arbitrary), so nothing wider is assumed.  Each workgroup folds its texels'
-// per-channel byte min / max into mm (k_plane_minmax's [min x 4, max x 4]):
-// both only move outwards, so a channel can lose min == max but never gain it.
-__global__ __launch_bounds__(kBlock) void k_update_planar(const uchar4* __restrict__ src, int nx, int ny, int nz,
-                                                          int x0, int y0, int z0, int bx, int by, int bz,
-                                                          uint8_t* __restrict__ dst, unsigned* __restrict__ mm)
+// The fold of a workgroup's per-channel byte min / max (lo, hi: each thread's
+// own, 255 / 0 where it saw nothing) into mm (k_plane_minmax's [min x 4,
+// max x 4]) -- the tail of the kernels that write texels into the planes
+// (k_update_planar, k_paint_planar).  Every thread of the workgroup calls it.
+__device__ __forceinline__ void fold_minmax(unsigned (&lo)[4], unsigned (&hi)[4], unsigned* __restrict__ mm)
 {
-    const unsigned total = (unsigned)bx * (unsigned)by * (unsigned)bz;   // < 2^31 (inside the volume)
-    const long long plane = (long long)nx * ny * nz;
-    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
-    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
-        const unsigned t = i / (unsigned)bx;
-        const int x = (int)(i - t * (unsigned)bx), y = (int)(t % (unsigned)by), z = (int)(t / (unsigned)by);
-        const uchar4 v = src[i];
-        const long long d = ((long long)(z0 + z) * ny + (y0 + y)) * nx + (x0 + x);
-        dst[d] = v.x;
-        dst[d + plane] = v.y;
-        dst[d + 2 * plane] = v.z;
-        dst[d + 3 * plane] = v.w;
-        const unsigned c[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { lo[k] = min(lo[k], c[k]); hi[k] = max(hi[k], c[k]); }
-    }
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         for (int off = 32; off > 0; off >>= 1) {
@@ -87,6 +67,96 @@ __global__ __launch_bounds__(kBlock) void k_update_planar(const uchar4* __restri
         } else {
             if (v > mm[k]) atomicMax(&mm[k], v);
         }
+    }
+}
+
+// vr_update_volume: scatter a tightly packed RGBA8 box (bx x by x bz texels at
+// texel (x0, y0, z0), x fastest) into the four planes.  One thread per texel,
+// consecutive lanes on consecutive x of a box row: a 4-B load, then one byte
+// store per plane -- the plane rows start at any byte (x0 and nx are
+// arbitrary), so nothing wider is assumed.  Each workgroup folds its texels'
+// per-channel byte min / max into mm (fold_minmax):
+// both only move outwards, so a channel can lose min == max but never gain it.
+__global__ __launch_bounds__(kBlock) void k_update_planar(const uchar4* __restrict__ src, int nx, int ny, int nz,
+                                                          int x0, int y0, int z0, int bx, int by, int bz,
+                                                          uint8_t* __restrict__ dst, unsigned* __restrict__ mm)
+{
+    const unsigned total = (unsigned)bx * (unsigned)by * (unsigned)bz;   // < 2^31 (inside the volume)
+    const long long plane = (long long)nx * ny * nz;
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
+        const unsigned t = i / (unsigned)bx;
+        const int x = (int)(i - t * (unsigned)bx), y = (int)(t % (unsigned)by), z = (int)(t / (unsigned)by);
+        const uchar4 v = src[i];
+        const long long d = ((long long)(z0 + z) * ny + (y0 + y)) * nx + (x0 + x);
+        dst[d] = v.x;
+        dst[d + plane] = v.y;
+        dst[d + 2 * plane] = v.z;
+        dst[d + 3 * plane] = v.w;
+        const unsigned c[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { lo[k] = min(lo[k], c[k]); hi[k] = max(hi[k], c[k]); }
+    }
+    fold_minmax(lo, hi, mm);
+}
+
+// vr_paint: blend a brush (vr.h vr_brush; the arithmetic is vr_brush.h's, in
+// integers and exact) into the planes, in place, over its bounding box clipped
+// to the volume.  One thread per texel of the box: a wave takes a box row
+// (y, z) at a time, consecutive lanes on consecutive x.  Q's y and z terms
+// belong to the row -- wave-uniform, computed once per row, and a row they
+// already put outside the ellipsoid costs nothing more; a texel outside it is
+// left before any load.  An inside texel loads one byte per painted channel
+// (strength != 0), blends, and stores only where the byte changed.  The NEW
+// bytes go into mm as k_update_planar's do: a channel the brush leaves alone
+// folds nothing, and a result equal to the old byte lies inside the range
+// already, so neither can cost a uniform channel its bit.
+__global__ __launch_bounds__(kBlock) void k_paint_planar(PaintArgs a, uint8_t* __restrict__ dst,
+                                                         unsigned* __restrict__ mm)
+{
+    constexpr unsigned kWaves = kBlock / 64;
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned rows = (unsigned)a.e[1] * (unsigned)a.e[2];   // <= 511^2
+    for (unsigned r = blockIdx.x * kWaves + wave; r < rows; r += gridDim.x * kWaves) {
+        const int z = (int)(r / (unsigned)a.e[1]), y = (int)(r - (unsigned)z * (unsigned)a.e[1]);
+        const unsigned long long qyz = brush::axis_term(a.d0[1] + y, a.k[1]) + brush::axis_term(a.d0[2] + z, a.k[2]);
+        if (qyz > a.s) continue;
+        uint8_t* __restrict__ row = dst + ((long long)(a.o[2] + z) * a.ny + (a.o[1] + y)) * a.nx + a.o[0];
+        for (int x = lane; x < a.e[0]; x += 64) {
+            const unsigned long long q = qyz + brush::axis_term(a.d0[0] + x, a.k[0]);
+            if (q > a.s) continue;
+            const unsigned w = brush::weight(q, a.s, a.falloff);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (a.strength[c] == 0u) continue;
+                uint8_t* p = row + x + c * plane;
+                const unsigned old = *p;
+                const unsigned nw = brush::blend(a.op, old, a.value[c], w * a.strength[c]);
+                if (nw != old) *p = (uint8_t)nw;
+                lo[c] = min(lo[c], nw);
+                hi[c] = max(hi[c], nw);
+            }
+        }
+    }
+    fold_minmax(lo, hi, mm);
+}
+
+// vr_get_volume_box: the planes' texel box -> tightly packed RGBA8 (what
+// k_update_planar reads).  One thread per texel, one 4-byte store each.
+__global__ __launch_bounds__(kBlock) void k_unpack_box(const uint8_t* __restrict__ src, int nx, int ny, int nz,
+                                                       int x0, int y0, int z0, int bx, int by, int bz,
+                                                       uchar4* __restrict__ dst)
+{
+    const unsigned total = (unsigned)bx * (unsigned)by * (unsigned)bz;   // < 2^31 (inside the volume)
+    const long long plane = (long long)nx * ny * nz;
+    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
+        const unsigned t = i / (unsigned)bx;
+        const int x = (int)(i - t * (unsigned)bx), y = (int)(t % (unsigned)by), z = (int)(t / (unsigned)by);
+        const long long s = ((long long)(z0 + z) * ny + (y0 + y)) * nx + (x0 + x);
+        dst[i] = make_uchar4(src[s], src[s + plane], src[s + 2 * plane], src[s + 3 * plane]);
     }
 }
 
@@ -634,6 +704,22 @@ hipError_t launch_update_planar(const uint8_t* d_box, int nx, int ny, int nz, in
 {
     hipLaunchKernelGGL(k_update_planar, dim3(grid_for((long long)bx * by * bz)), dim3(kBlock), 0, s,
                        reinterpret_cast<const uchar4*>(d_box), nx, ny, nz, x0, y0, z0, bx, by, bz, d_planar, mm);
+    return hipGetLastError();
+}
+
+// a wave per box row, a workgroup per kBlock / 64 rows, grid-stride past 4096 workgroups
+hipError_t launch_paint_planar(const PaintArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s)
+{
+    const long long rows = (long long)a.e[1] * a.e[2];
+    hipLaunchKernelGGL(k_paint_planar, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a, d_planar, mm);
+    return hipGetLastError();
+}
+
+hipError_t launch_unpack_box(const uint8_t* d_planar, int nx, int ny, int nz, int x0, int y0, int z0, int bx, int by,
+                             int bz, uint8_t* d_box, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_unpack_box, dim3(grid_for((long long)bx * by * bz)), dim3(kBlock), 0, s, d_planar, nx, ny, nz,
+                       x0, y0, z0, bx, by, bz, reinterpret_cast<uchar4*>(d_box));
     return hipGetLastError();
 }
 

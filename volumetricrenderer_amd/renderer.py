@@ -32,8 +32,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (BYTES_PER_PIXEL, CHANNELS, FLOAT_FORMATS, FMT_RGBA8_SRGB, FMT_RGBA8_UNORM, FMT_RGBA32F,  # noqa: F401
-                   GREY_OF, RAY_RECORD_WORDS, GlobalShaderData, MarchParams, ObjectShaderData, Procedural, RayRecord,
+from ._lib import (BRUSH_ADD, BRUSH_SET, BRUSH_SUB, BYTES_PER_PIXEL, CHANNELS, FLOAT_FORMATS, FMT_RGBA8_SRGB,  # noqa: F401
+                   FMT_RGBA8_UNORM, FMT_RGBA32F, Brush, GREY_OF, RAY_RECORD_WORDS, GlobalShaderData, MarchParams, ObjectShaderData, Procedural, RayRecord,
                    Rect, Target, VolumeRecipe, VR_MAX_RECTS, VRError, call)
 
 _lib.load()  # fail at import if the HIP library is missing
@@ -152,6 +152,48 @@ def coalesce_rects(rects, max_out: int = VR_MAX_RECTS) -> list[tuple[int, int, i
     return [(out[i].x, out[i].y, out[i].width, out[i].height) for i in range(n.value)]
 
 
+_BRUSH_OPS = {"set": BRUSH_SET, "add": BRUSH_ADD, "sub": BRUSH_SUB}
+
+
+def make_brush(centre, radius, op=BRUSH_SET, falloff: int = 0, value=(255, 255, 255, 255),
+               strength=(255, 255, 255, 255)) -> Brush:
+    """A vr_brush: `centre` = texel (x, y, z), `radius` = semi-axes in texels (one
+    int for a sphere of texels, or three), `op` BRUSH_SET / BRUSH_ADD / BRUSH_SUB
+    (or "set" / "add" / "sub"), `falloff` 0 hard or 1 smooth, `value` and
+    `strength` per channel R, G, B, A (one int = every channel)."""
+    b = Brush()
+    b.centre[:] = [int(v) for v in centre]
+    b.radius[:] = [int(radius)] * 3 if np.isscalar(radius) else [int(v) for v in radius]
+    b.op = _BRUSH_OPS[op] if isinstance(op, str) else int(op)
+    b.falloff = int(falloff)
+    b.value[:] = [int(value)] * 4 if np.isscalar(value) else [int(v) for v in value]
+    b.strength[:] = [int(strength)] * 4 if np.isscalar(strength) else [int(v) for v in strength]
+    return b
+
+
+def brush_box(brush: Brush, dims):
+    """vr_brush_box: ``(origin, extent)`` = ((x0, y0, z0), (bx, by, bz)) of the
+    brush's bounding box clipped to a volume of `dims` = (nx, ny, nz) -- what
+    :meth:`Renderer.paint` rewrites and what :meth:`Renderer.update_footprint`
+    takes -- or None when the brush misses the volume.  Host code only."""
+    nx, ny, nz = (int(v) for v in dims)
+    o, e = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+    call("vr_brush_box", ctypes.byref(brush), nx, ny, nz, o, e)
+    return (tuple(o), tuple(e)) if e[0] > 0 else None
+
+
+def brush_apply(brush: Brush, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_apply: the brush applied IN PLACE to a host RGBA8 volume shaped
+    (nz, ny, nx, 4) (a contiguous uint8 array), the CPU statement of what
+    :meth:`Renderer.paint` does on the device; returns `rgba`."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    call("vr_brush_apply", ctypes.byref(brush), rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz)
+    return rgba
+
+
 # vr_ray_record as a numpy structured type (the layout of _lib.RayRecord)
 RAY_RECORD_DTYPE = np.dtype([("steps", "<i4"), ("hit_step", "<i4"), ("value", "<f4"), ("optical_depth", "<f4"),
                              ("entry", "<f4", (3,)), ("reserved0", "<f4"), ("step", "<f4", (3,)), ("reserved1", "<f4"),
@@ -245,6 +287,53 @@ class Renderer:
             raise ValueError("box must be shaped (bz, by, bx, 4)")
         bz, by, bx, _ = a.shape
         call("vr_update_volume", self._ctx, a.ctypes.data_as(ctypes.c_void_p), x0, y0, z0, bx, by, bz)
+
+    def paint(self, centre, radius, op=BRUSH_SET, falloff: int = 0, value=(255, 255, 255, 255),
+              strength=(255, 255, 255, 255), stream=None):
+        """Blend an ellipsoidal brush into the installed volume on the device
+        (vr_paint; the arguments are :func:`make_brush`'s): the renderer then
+        holds the painted volume, bit for bit what :func:`brush_apply` gives on
+        the host.  Returns ``(origin, extent)`` of the clipped bounding box it
+        rewrote -- what :meth:`update_footprint` takes -- or None when the brush
+        misses the volume.  Queued on `stream` (default: the current stream);
+        with a stream given nothing waits, so pick, paint and render queue
+        back to back on it."""
+        b = make_brush(centre, radius, op, falloff, value, strength)
+        call("vr_paint", self._ctx, ctypes.byref(b), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return brush_box(b, self.volume_dims())
+
+    def get_volume_box(self, origin, extent, out=None, stream=None):
+        """The texel box `extent` = (bx, by, bz) at `origin` = (x0, y0, z0) of the
+        installed volume, shaped (bz, by, bx, 4) -- what :meth:`update_volume`
+        takes back (undo: save the box, paint, update_volume the saved box).
+        With no `out` and no `stream`: a numpy array, through the synchronous
+        host call (vr_get_volume_box).  With `out` a CUDA uint8 tensor of that
+        shape, or a `stream`: a CUDA tensor, written on `stream` (default: the
+        current stream, which is then waited for) by vr_get_volume_box_device."""
+        x0, y0, z0 = (int(v) for v in origin)
+        bx, by, bz = (int(v) for v in extent)
+        shape = (max(bz, 0), max(by, 0), max(bx, 0), 4)
+        if isinstance(out, torch.Tensor) or (out is None and stream is not None):
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self.device))
+            if (not out.is_cuda or out.device.index != self.device or out.dtype != torch.uint8
+                    or tuple(out.shape) != shape or not out.is_contiguous()):
+                raise ValueError(f"get_volume_box: out must be a contiguous uint8 tensor {shape} on cuda:{self.device}")
+            # an empty box has no buffer to hand over: the library refuses the extent either way
+            ptr = ctypes.c_void_p(out.data_ptr()) if out.numel() else ctypes.c_void_p(1)
+            call("vr_get_volume_box_device", self._ctx, x0, y0, z0, bx, by, bz, ptr, _stream_handle(stream))
+            if stream is None:
+                torch.cuda.current_stream().synchronize()
+            return out
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        if (not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != shape
+                or not out.flags.c_contiguous or not out.flags.writeable):
+            raise ValueError(f"get_volume_box: out must be a writeable contiguous uint8 array {shape}")
+        call("vr_get_volume_box", self._ctx, x0, y0, z0, bx, by, bz, out.ctypes.data_as(ctypes.c_void_p))
+        return out
 
     def generate_volume(self, recipe: VolumeRecipe | None = None) -> None:
         """Build the TestMain.cpp:43-92 volume on the GPU."""
