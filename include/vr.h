@@ -295,6 +295,70 @@ vr_status vr_brush_box(const vr_brush* brush, int nx, int ny, int nz, int origin
  * vr_set_volume), for callers without a device: the CPU statement of the
  * arithmetic above, which vr_paint reproduces bit for bit.  Pure host code.  */
 vr_status vr_brush_apply(const vr_brush* brush, uint8_t* rgba8, int nx, int ny, int nz);
+
+/* A brush stroke: dabs[0..count) applied in ONE paint launch.  Afterwards the
+ * ctx renders, and vr_get_volume reads, bit for bit what
+ *   for (i = 0; i < count; ++i) vr_paint(ctx, &dabs[i], stream);
+ * would leave -- the order of the list included (SET then ADD is not ADD then
+ * SET) -- but every texel is loaded and stored once, however many dabs cover
+ * it, and the device layouts are rebuilt over at most 8 boxes that cover the
+ * dabs' clipped bounding boxes (vr_boxes_coalesce), not dab by dab.
+ * Everything else is vr_paint's contract: asynchronous on `stream`, nothing
+ * allocated, no host wait, region lists untouched, cached launches and the
+ * uniform-channel read-back treated as after an update.
+ *
+ * Uniform channels: only the FINAL byte of each texel the stroke touched is
+ * folded into the channels' byte ranges, not the intermediate ones.  A channel
+ * whose texels all end equal to its uniform value keeps its bit (strength 0;
+ * an ADD undone by a later SUB); one with a changed final byte loses it before
+ * the next render.  The stroke may thus keep a bit that count separate
+ * vr_paint calls would have dropped; the output is exact either way (see
+ * vr_update_volume), only the loads are skipped.
+ *
+ * count == 0 is VR_OK and launches nothing (dabs may then be NULL).  Dabs that
+ * miss the volume are dropped; if all miss, VR_OK and no launch.
+ * VR_ERR_INVALID: a null ctx, count < 0, count > VR_MAX_DABS, dabs NULL with
+ * count > 0, ANY dab vr_paint would refuse (the message names its index);
+ * VR_ERR_NO_VOLUME as for vr_paint.  A refused call has launched nothing, not
+ * even the valid dabs before the bad one.  More than VR_MAX_DABS dabs: split
+ * the list.                                                                 */
+#define VR_MAX_DABS 64
+vr_status vr_paint_stroke(void* ctx, const vr_brush* dabs, int count, void* stream);
+/* The dabs of a drag from brush->centre to the texel `to`.  With d = to -
+ * centre per axis (64 bits) and n = max(1, ceil(max_a |d_a| / spacing)), dab
+ * i = 0..n is a copy of `brush` whose centre is moved by
+ * floor((2 i d_a + n) / (2 n)) on axis a (floor division, also for negative
+ * numerators: the nearest texel of the segment, halves upwards); dab 0 is the
+ * brush itself and dab n is centred on `to`.  skip_first = 1 omits dab 0, so
+ * that the joint of two segments is not dabbed twice.  *out_count is the
+ * number of dabs required, n + 1 - skip_first; they are written to `out`
+ * (room for max_out).  Pure host code: no context, no device.
+ * VR_ERR_INVALID: a null brush, to or out_count, a brush vr_paint would
+ * refuse, spacing < 1, skip_first not 0 or 1, n above 2^20, max_out < 0, out
+ * NULL with max_out > 0, and more dabs than max_out -- nothing is then written
+ * to `out` and *out_count is still the number required (max_out = 0 asks for
+ * the number alone); for every other refusal *out_count, when given, is 0.  */
+vr_status vr_brush_line(const vr_brush* brush, const int32_t to[3], int spacing, int skip_first, vr_brush* out,
+                        int max_out, int* out_count);
+/* A texel box [x, x + bx) x [y, y + by) x [z, z + bz) */
+typedef struct { int32_t x, y, z, bx, by, bz; } vr_box;
+/* vr_rects_coalesce in three dimensions, with volumes in place of areas:
+ * writes at most max_out (>= 1) boxes to `out` (room for min(count, max_out))
+ * and their number to *out_count.  Their union contains the union of the
+ * input, and each lies inside the bounding box of the non-empty inputs.  Empty
+ * inputs are dropped, and so are inputs contained in another input (of
+ * identical ones the first is kept); what remains keeps its order.  While more
+ * than max_out remain, the pair whose bounding box adds the least volume
+ * beyond the two boxes' own volumes is merged into that bounding box, at the
+ * place of the pair's first (ties: the lowest pair of indices), and whatever
+ * the new box contains is dropped.  Deterministic; edges and sums in 64 bits,
+ * volumes (up to 2^93) in 128.  Pure host code: no context, no device; lists
+ * of up to VR_MAX_DABS boxes allocate nothing.  vr_paint_stroke uses it for
+ * its layout rebuilds.
+ * VR_ERR_INVALID: count < 0, max_out < 1, a null pointer with count > 0, a
+ * negative coordinate or extent, x + bx, y + by or z + bz above INT32_MAX.
+ * count == 0 is VR_OK; *out_count, when given, is then 0.                  */
+vr_status vr_boxes_coalesce(const vr_box* in, int count, int max_out, vr_box* out, int* out_count);
 /* 1 if vr_set_volume / vr_set_volume_device accept an nx x ny x nz extent
  * (the device layouts index a plane with 32-bit offsets), else 0          */
 int       vr_volume_extent_ok(int nx, int ny, int nz);

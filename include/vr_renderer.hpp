@@ -63,6 +63,20 @@ inline bool BrushBox(const vr_brush& brush, int nx, int ny, int nz, int origin[3
     return extent[0] > 0;
 }
 
+// The dabs of a drag from brush.centre to the texel `to`, at most `spacing`
+// texels apart (vr_brush_line): what Renderer::PaintStroke takes.  skip_first
+// omits the dab on the brush's own centre, the joint of two segments.  Host
+// code only.
+inline std::vector<vr_brush> BrushLine(const vr_brush& brush, const int32_t to[3], int spacing, bool skip_first = false)
+{
+    int n = 0;
+    const vr_status st = vr_brush_line(&brush, to, spacing, skip_first ? 1 : 0, nullptr, 0, &n);   // the number alone
+    if (n <= 0) Check(st, "vr_brush_line");
+    std::vector<vr_brush> out((size_t)n);
+    Check(vr_brush_line(&brush, to, spacing, skip_first ? 1 : 0, out.data(), n, &n), "vr_brush_line");
+    return out;
+}
+
 class Renderer {
 public:
     explicit Renderer(int device = 0) { Check(vr_create(device, &ctx_), "vr_create"); }
@@ -89,6 +103,16 @@ public:
     // `stream` (vr_paint): pick (QueryRect), Paint, UpdateFootprint of
     // BrushBox, RenderRect queue on one stream with no host round trip.
     void Paint(const vr_brush& brush, void* stream = nullptr) { Check(vr_paint(ctx_, &brush, stream), "vr_paint"); }
+    // A stroke: at most VR_MAX_DABS dabs applied in order in one paint launch
+    // (vr_paint_stroke), bit for bit what Paint of each in turn leaves.
+    void PaintStroke(const vr_brush* dabs, int count, void* stream = nullptr)
+    {
+        Check(vr_paint_stroke(ctx_, dabs, count, stream), "vr_paint_stroke");
+    }
+    void PaintStroke(const std::vector<vr_brush>& dabs, void* stream = nullptr)
+    {
+        PaintStroke(dabs.data(), (int)dabs.size(), stream);
+    }
     // The read-back counterpart of UpdateVolume (vr_get_volume_box): save a
     // box, Paint, UpdateVolume the saved box -- undo.
     void GetVolumeBox(int x0, int y0, int z0, int bx, int by, int bz, uint8_t* rgba_out) const

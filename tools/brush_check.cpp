@@ -1,5 +1,5 @@
-// brush_check -- stand-alone host check of vr_brush_box / vr_brush_apply
-// (volumetricrenderer_amd/csrc/vr_brush.cpp), built with
+// brush_check -- stand-alone host check of vr_brush_box / vr_brush_apply /
+// vr_brush_line (volumetricrenderer_amd/csrc/vr_brush.cpp), built with
 // -fsanitize=address,undefined and run on the CPU (`make check-brush` builds
 // and runs it).  It links the brush's translation unit only: no libvr.so, no
 // HIP, no device.
@@ -10,7 +10,14 @@
 // volume and at INT32_MAX / INT32_MIN, 1 x 1 x 1 volumes, every op and falloff.
 // Each result is compared with a texel-by-texel restatement of vr.h that uses
 // unsigned __int128 for Q and S (so that it cannot share an overflow).
+//
+// vr_brush_line: drags between centres anywhere in int32 -- INT32_MIN to
+// INT32_MAX apart, refused through the limit on n unless the spacing is long
+// enough -- every direction sign, spacing 1, skip_first, `out` allocated at
+// exactly the room given; each dab is compared with a restatement in __int128.
+#include <algorithm>
 #include <climits>
+#include <cstring>
 #include <cstdint>
 #include <cstdio>
 #include <random>
@@ -50,6 +57,23 @@ void restate(const vr_brush& b, std::vector<uint8_t>& v, int nx, int ny, int nz)
                     if (b.strength[c]) p[c] = (uint8_t)nw;
                 }
             }
+}
+
+// include/vr.h, literally, in 128 bits: n, and dab i's centre
+__int128 floor_div(__int128 a, __int128 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }   // b > 0
+__int128 line_n(const vr_brush& b, const int32_t to[3], int spacing)
+{
+    __int128 longest = 0;
+    for (int a = 0; a < 3; ++a) {
+        const __int128 d = (__int128)to[a] - b.centre[a];
+        longest = std::max(longest, d < 0 ? -d : d);
+    }
+    return std::max<__int128>(1, (longest + spacing - 1) / spacing);
+}
+long long line_centre(const vr_brush& b, const int32_t to[3], __int128 n, __int128 i, int a)
+{
+    const __int128 d = (__int128)to[a] - b.centre[a];
+    return (long long)(b.centre[a] + floor_div(2 * i * d + n, 2 * n));
 }
 
 long failures = 0;
@@ -141,6 +165,92 @@ int main()
             expect(vr_brush_apply(&b, vol.data(), nx, ny, nz) == VR_OK && vol == want, "the largest brush differs", op * 2 + falloff);
             ++applied;
         }
+    // vr_brush_line
+    long lines = 0, dabs = 0, too_long = 0, line_refused = 0;
+    const int ends[] = {INT32_MIN, INT32_MAX, INT32_MIN + 1, INT32_MAX - 1, 0, -1, 1, 1 << 20, -(1 << 20), (1 << 20) + 1};
+    for (int it = 0; it < 4000; ++it) {
+        const int kind = it % 8;
+        vr_brush b{};
+        int32_t to[3];
+        for (int a = 0; a < 3; ++a) {
+            b.radius[a] = pick(0, VR_BRUSH_MAX_RADIUS);
+            b.centre[a] = kind == 0 ? ends[pick(0, 9)] : pick(-300, 300);
+            // every direction sign (it / 8 % 8), now and then no movement on an axis; kind 0 and 1: the ends of int32
+            const int len = kind == 2 ? 0 : kind == 3 ? pick(0, 3) : pick(0, 90);
+            to[a] = kind <= 1 ? ends[pick(0, 9)] : b.centre[a] + ((it / 8 >> a) & 1 ? -len : len);
+        }
+        b.op = it % 3; b.falloff = it % 2;
+        for (int c = 0; c < 4; ++c) { b.value[c] = (uint8_t)pick(0, 255); b.strength[c] = (uint8_t)pick(0, 255); }
+        // spacing 1, short, longer than the drag, and (the far ends) long enough for 2^20 segments or just not
+        int spacing = kind == 4 ? 1 : kind == 5 ? pick(100, 1000) : pick(1, 9);
+        if (kind <= 1) spacing = it % 400 < 2 ? 4096 : pick(1, 4095);
+        const int skip = it / 4 % 2;
+        const __int128 n = line_n(b, to, spacing);
+        const bool fits = n <= ((__int128)1 << 20);
+        const long long need = fits ? (long long)n + 1 - skip : 0;
+        // 2^20 dabs are 48 MiB: a dozen such lines are written and compared, the rest only counted (room 0)
+        const bool count_only = need > 70000 && ++too_long > 12;
+        const int room = !fits ? 4 : count_only ? 0 : it % 7 == 0 ? (int)std::max<long long>(0, need - 1 - pick(0, 2)) : (int)need;
+        std::vector<vr_brush> out((size_t)room), untouched((size_t)room);
+        if (room) std::memset(out.data(), 0xA5, out.size() * sizeof(vr_brush));
+        if (room) std::memset(untouched.data(), 0xA5, untouched.size() * sizeof(vr_brush));
+        int got = -7;
+        const vr_status st = vr_brush_line(&b, to, spacing, skip, room ? out.data() : nullptr, room, &got);
+        if (!fits) {
+            expect(st == VR_ERR_INVALID && got == 0, "vr_brush_line: more than 2^20 segments accepted", it);
+            expect(out.empty() || std::memcmp(out.data(), untouched.data(), out.size() * sizeof(vr_brush)) == 0,
+                   "a refused line wrote dabs", it);
+            ++line_refused;
+            continue;
+        }
+        if (room < need) {
+            expect(st == VR_ERR_INVALID && got == need, "vr_brush_line: too little room not refused with the number required", it);
+            expect(out.empty() || std::memcmp(out.data(), untouched.data(), out.size() * sizeof(vr_brush)) == 0,
+                   "a refused line wrote dabs", it);
+            ++line_refused;
+            continue;
+        }
+        expect(st == VR_OK && got == need, "vr_brush_line refused a valid drag", it);
+        bool same = st == VR_OK;
+        for (long long k = 0; same && k < need; ++k) {
+            const vr_brush& o = out[(size_t)k];
+            vr_brush want = b;
+            for (int a = 0; a < 3; ++a) want.centre[a] = (int32_t)line_centre(b, to, n, k + skip, a);
+            same = std::memcmp(&o, &want, sizeof(vr_brush)) == 0;
+            for (int a = 0; same && a < 3; ++a)   // no dab leaves the segment
+                same = o.centre[a] >= std::min(b.centre[a], to[a]) && o.centre[a] <= std::max(b.centre[a], to[a]);
+        }
+        expect(same, "vr_brush_line differs from the restatement", it);
+        if (same && need > 0) {
+            const vr_brush& last = out[(size_t)need - 1];
+            expect(last.centre[0] == to[0] && last.centre[1] == to[1] && last.centre[2] == to[2], "the last dab is not on `to`", it);
+            if (!skip) expect(std::memcmp(&out[0], &b, sizeof(vr_brush)) == 0, "the first dab is not the brush", it);
+        }
+        ++lines;
+        dabs += need;
+    }
+    {   // refusals
+        vr_brush b{};
+        const int32_t to[3] = {5, -5, 0};
+        vr_brush o[8];
+        int n = -7;
+        expect(vr_brush_line(nullptr, to, 1, 0, o, 8, &n) == VR_ERR_INVALID && n == 0, "null brush", 0);
+        expect(vr_brush_line(&b, nullptr, 1, 0, o, 8, &n) == VR_ERR_INVALID && n == 0, "null to", 0);
+        expect(vr_brush_line(&b, to, 1, 0, o, 8, nullptr) == VR_ERR_INVALID, "null out_count", 0);
+        expect(vr_brush_line(&b, to, 1, 0, nullptr, 8, &n) == VR_ERR_INVALID && n == 0, "null out", 0);
+        expect(vr_brush_line(&b, to, 0, 0, o, 8, &n) == VR_ERR_INVALID && n == 0, "spacing 0", 0);
+        expect(vr_brush_line(&b, to, INT32_MIN, 0, o, 8, &n) == VR_ERR_INVALID && n == 0, "negative spacing", 0);
+        expect(vr_brush_line(&b, to, 1, 2, o, 8, &n) == VR_ERR_INVALID && n == 0, "skip_first 2", 0);
+        expect(vr_brush_line(&b, to, 1, 0, o, -1, &n) == VR_ERR_INVALID && n == 0, "negative max_out", 0);
+        expect(vr_brush_line(&b, to, 1, 0, nullptr, 0, &n) == VR_ERR_INVALID && n == 6, "max_out 0 gives the number", 0);
+        expect(vr_brush_line(&b, to, 1, 1, o, 8, &n) == VR_OK && n == 5, "skip_first", 0);
+        expect(vr_brush_line(&b, to, INT32_MAX, 0, o, 8, &n) == VR_OK && n == 2, "the longest spacing", 0);
+        vr_brush bad = b;
+        bad.radius[1] = 256;
+        expect(vr_brush_line(&bad, to, 1, 0, o, 8, &n) == VR_ERR_INVALID && n == 0, "a bad brush got a line", 0);
+        line_refused += 9;
+    }
+    std::printf("brush_check: %ld lines (%ld dabs, %ld long), %ld lines refused\n", lines, dabs, too_long, line_refused);
     std::printf("brush_check: %ld applied, %ld missed, %ld refused, %ld failures\n", applied, missed, refused, failures);
     return failures ? 1 : 0;
 }

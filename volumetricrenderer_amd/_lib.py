@@ -124,6 +124,15 @@ class Brush(ctypes.Structure):
 
 BRUSH_SET, BRUSH_ADD, BRUSH_SUB = 0, 1, 2   # vr.h vr_brush_op
 BRUSH_MAX_RADIUS = 255                      # vr.h VR_BRUSH_MAX_RADIUS
+VR_MAX_DABS = 64                            # vr.h: the longest list vr_paint_stroke takes
+
+
+class Box(ctypes.Structure):
+    """vr_box: a texel box (vr_boxes_coalesce).  24 bytes."""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("z", ctypes.c_int32), ("bx", ctypes.c_int32),
+                ("by", ctypes.c_int32), ("bz", ctypes.c_int32)]
+
+
 
 RAY_RECORD_WORDS = ctypes.sizeof(RayRecord) // 4   # a record as int32 words: query_rect's last axis
 
@@ -145,6 +154,10 @@ _SIGS = {
     "vr_paint": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp]),
     "vr_brush_box": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p]),
     "vr_brush_apply": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vr_paint_stroke": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.c_int, _vp]),
+    "vr_brush_line": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
+                                     ctypes.POINTER(Brush), ctypes.c_int, c_int_p]),
+    "vr_boxes_coalesce": (ctypes.c_int, [ctypes.POINTER(Box), ctypes.c_int, ctypes.c_int, ctypes.POINTER(Box), c_int_p]),
     "vr_volume_extent_ok": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vr_volume_recipe_defaults": (ctypes.c_int, [ctypes.POINTER(VolumeRecipe)]),
     "vr_generate_volume": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeRecipe), _vp]),

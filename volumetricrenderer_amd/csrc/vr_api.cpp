@@ -505,17 +505,52 @@ static vr_status check_update(const char* fn, void* p, const void* data, int x0,
 // render / vr_kernel_variant / vr_get_option resolves it as after an install.
 // With no uniform channel left nothing can change: no read-back, no `gen`
 // bump, and the cached launches stay valid (same buffers, same geometry).
-static vr_status box_edited(Ctx* c, int x0, int y0, int z0, int bx, int by, int bz, hipStream_t s)
+//
+// The two halves, for an edit of several boxes (vr_paint_stroke): the rebuild
+// once per box, the re-armed read-back once after them.
+static vr_status rebuild_box(Ctx* c, int x0, int y0, int z0, int bx, int by, int bz, hipStream_t s)
 {
     if (c->fast_layout)
         HIP_TRY(launch_build_layout_box(c->fast_layout, c->d_planar, c->nx, c->ny, c->nz, c->d_fast, x0, y0, z0, bx,
                                         by, bz, s));
+    return VR_OK;
+}
+
+static vr_status rearm_minmax(Ctx* c, hipStream_t s)
+{
     if (c->mm_pending || c->uniform_mask != 0) {
         HIP_TRY(hipMemcpyAsync(c->h_mm, c->d_mm, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipEventRecord(c->mm_ready, s));
         c->mm_pending = true;
     }
     return VR_OK;
+}
+
+static vr_status box_edited(Ctx* c, int x0, int y0, int z0, int bx, int by, int bz, hipStream_t s)
+{
+    if (vr_status st = rebuild_box(c, x0, y0, z0, bx, by, bz, s)) return st;
+    return rearm_minmax(c, s);
+}
+
+// The layout rebuilds of a stroke: the dabs' clipped boxes coalesced to at most kStrokeRebuilds boxes
+// (a diagonal stroke's bounding box is far larger than its dabs, and a rebuild per dab repeats the shared
+// bricks).  The rebuild reads the planes, so boxes that overlap are correct.  A layout that is rebuilt
+// whole whatever the box (VR_EXPERIMENTS) gets one box.
+constexpr int kStrokeRebuilds = 8;
+static vr_status stroke_edited(Ctx* c, const vr_box* boxes, int count, hipStream_t s)
+{
+    if (c->fast_layout) {
+        vr_box merged[kStrokeRebuilds];
+        int n = 0;
+        if (vr_status st = vr_boxes_coalesce(boxes, count, layout_rebuilds_box(c->fast_layout) ? kStrokeRebuilds : 1,
+                                             merged, &n))
+            return st;
+        for (int k = 0; k < n; ++k)
+            if (vr_status st = rebuild_box(c, merged[k].x, merged[k].y, merged[k].z, merged[k].bx, merged[k].by,
+                                           merged[k].bz, s))
+                return st;
+    }
+    return rearm_minmax(c, s);
 }
 
 // Patch the planes (the scatter folds the box's byte range into d_mm) and the held fast layout on `s`.
@@ -647,6 +682,41 @@ try {
     return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
 } catch (...) {
     return caught_exception("vr_paint");
+}
+
+// A stroke on the device: every check first (a refused call has launched nothing), then k_paint_stroke over
+// the dabs that reach the volume -- they travel in its arguments -- and what follows an edit of their boxes.
+vr_status vr_paint_stroke(void* p, const vr_brush* dabs, int count, void* stream)
+try {
+    if (!p) return fail(VR_ERR_INVALID, "vr_paint_stroke: null ctx");
+    if (count < 0 || count > VR_MAX_DABS)
+        return fail(VR_ERR_INVALID, "vr_paint_stroke: count %d (0..%d)", count, VR_MAX_DABS);
+    if (count == 0) return VR_OK;
+    if (!dabs) return fail(VR_ERR_INVALID, "vr_paint_stroke: null dabs with count %d", count);
+    for (int i = 0; i < count; ++i)
+        if (const char* why = vr::brush::invalid(&dabs[i])) return fail(VR_ERR_INVALID, "vr_paint_stroke: dab %d: %s", i, why);
+    Ctx* c = as_ctx(p);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_paint_stroke: no volume set");
+    if (c->proc.enabled)
+        return fail(VR_ERR_NO_VOLUME, "vr_paint_stroke: a procedural medium is enabled (it reads no volume)");
+    StrokeArgs a{};
+    vr_box boxes[VR_MAX_DABS];
+    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
+    for (int i = 0; i < count; ++i) {
+        int o[3], e[3];
+        if (!vr::brush::clip(&dabs[i], c->nx, c->ny, c->nz, o, e)) continue;   // the dab misses the volume
+        a.dab[a.count] = dabs[i];
+        boxes[a.count] = vr_box{o[0], o[1], o[2], e[0], e[1], e[2]};
+        a.row_begin[a.count + 1] = a.row_begin[a.count] + (unsigned)e[1] * (unsigned)e[2];
+        ++a.count;
+    }
+    if (a.count == 0) return VR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(launch_paint_stroke(a, c->d_planar, c->d_mm, s));
+    return stroke_edited(c, boxes, a.count, s);
+} catch (...) {
+    return caught_exception("vr_paint_stroke");
 }
 
 vr_status vr_noise_grid(void* p, int kind, void* d_out, int x0, int y0, int z0, int nx, int ny, int nz,

@@ -1,5 +1,6 @@
 // vr_brush.cpp -- vr_brush_box and vr_brush_apply: the brush of vr_paint on
-// the host (include/vr.h).
+// the host (include/vr.h); vr_brush_line: the dabs of a
+// drag, for vr_paint_stroke (sec. 5.2.6).
 //
 // Pure host code in integers: no context, no device, no HIP call.  The
 // arithmetic is vr_brush.h's, which the paint kernel (vr_volume.hip) includes
@@ -66,6 +67,44 @@ vr_status vr_brush_apply(const vr_brush* b, uint8_t* rgba8, int nx, int ny, int 
                     *p = (uint8_t)vr::brush::blend(b->op, *p, b->value[c], w * b->strength[c]);
                 }
             }
+        }
+    }
+    return VR_OK;
+}
+
+// The dabs of a drag (include/vr.h): n segments of at most `spacing` texels on the longest axis, dab i at the
+// texel nearest to centre + i d / n.  |d_a| < 2^32 and i <= n <= 2^20: 2 i d_a + n stays below 2^54.
+vr_status vr_brush_line(const vr_brush* b, const int32_t to[3], int spacing, int skip_first, vr_brush* out, int max_out,
+                        int* out_count)
+{
+    if (out_count) *out_count = 0;
+    if (!b || !to || !out_count) return fail(VR_ERR_INVALID, "vr_brush_line: null argument");
+    if (const char* why = vr::brush::invalid(b)) return fail(VR_ERR_INVALID, "vr_brush_line: %s", why);
+    if (spacing < 1) return fail(VR_ERR_INVALID, "vr_brush_line: spacing %d (at least 1)", spacing);
+    if (skip_first != 0 && skip_first != 1) return fail(VR_ERR_INVALID, "vr_brush_line: skip_first %d", skip_first);
+    if (max_out < 0) return fail(VR_ERR_INVALID, "vr_brush_line: max_out %d", max_out);
+    if (!out && max_out > 0) return fail(VR_ERR_INVALID, "vr_brush_line: null out with max_out %d", max_out);
+    int64_t d[3], longest = 0;
+    for (int a = 0; a < 3; ++a) {
+        d[a] = (int64_t)to[a] - b->centre[a];
+        const int64_t m = d[a] < 0 ? -d[a] : d[a];
+        if (m > longest) longest = m;
+    }
+    int64_t n = (longest + spacing - 1) / spacing;
+    if (n < 1) n = 1;
+    if (n > ((int64_t)1 << 20))
+        return fail(VR_ERR_INVALID, "vr_brush_line: %lld segments (at most 2^20): a longer spacing, or split the drag",
+                    (long long)n);
+    const int64_t need = n + 1 - skip_first;
+    *out_count = (int)need;
+    if (need > max_out) return fail(VR_ERR_INVALID, "vr_brush_line: %lld dabs, room for %d", (long long)need, max_out);
+    for (int64_t i = skip_first; i <= n; ++i) {
+        vr_brush* o = out + (i - skip_first);
+        *o = *b;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t num = 2 * i * d[a] + n, den = 2 * n;
+            const int64_t q = num >= 0 ? num / den : -((-num + den - 1) / den);   // floor
+            o->centre[a] = (int32_t)(b->centre[a] + q);                           // between centre and to
         }
     }
     return VR_OK;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "../../include/vr.h"
 #include "vr_dispatch.h"
 
 namespace vr {
@@ -592,6 +593,20 @@ struct PaintArgs {
 };
 // Blend the brush into the planar planes in place and fold the new bytes' per-channel min / max into mm
 hipError_t launch_paint_planar(const PaintArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+// vr_paint_stroke: the validated dabs that reach the volume, in order, in the kernel arguments (no device
+// buffer, no copy).  The work items are the rows (y, z) of the dabs' clipped boxes: the rows of dab i are
+// [row_begin[i], row_begin[i + 1]), y fastest.
+struct StrokeArgs {
+    int nx, ny, nz;
+    int count;                              // 1..VR_MAX_DABS
+    unsigned row_begin[VR_MAX_DABS + 1];    // <= 64 * 511^2 rows in all
+    vr_brush dab[VR_MAX_DABS];              // centres within radius of the volume: offsets fit an int
+};
+static_assert(sizeof(StrokeArgs) <= 4096, "StrokeArgs travels in the kernarg segment");
+// Apply the dabs in order, every texel by one thread (k_paint_stroke), and fold the final bytes' min / max into mm
+hipError_t launch_paint_stroke(const StrokeArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+// true for the layouts launch_build_layout_box rebuilds over the box; the others it rebuilds whole
+bool layout_rebuilds_box(int layout);
 // Perlin lattice table: entry (x, y, z) - lo of n^3 = noise::perlin_lattice_entry(seed, x, y, z)
 hipError_t launch_perlin_lattice(uint2* d_out, int seed, int lo, int n, hipStream_t s);
 hipError_t launch_noise(int kind, float* d_out, int x0, int y0, int z0, int nx, int ny, int nz,

@@ -144,6 +144,93 @@ __global__ __launch_bounds__(kBlock) void k_paint_planar(PaintArgs a, uint8_t* _
     fold_minmax(lo, hi, mm);
 }
 
+// vr_paint_stroke: the dabs of a (vr_internal.h StrokeArgs: validated, every one
+// reaches the volume) applied in list order, as that many k_paint_planar
+// launches would, with every texel loaded and stored once.  Ordered overlapping
+// read-modify-writes need no atomics and no order between workgroups when every
+// texel has exactly ONE owner thread:
+//  * the work items are the rows (y, z) of each dab's clipped box; a wave takes
+//    a row, consecutive lanes consecutive x, as in k_paint_planar;
+//  * a texel reached through dab i's row is owned there iff no dab j < i has a
+//    clipped box that holds it (else dab j's row reaches it too, and the lowest
+//    such j owns it);
+//  * the owner applies, in index order, every dab k >= i whose ellipsoid holds
+//    the texel -- no dab below i can, their boxes do not hold it -- keeping each
+//    painted channel's byte in a register from its one load to its one store
+//    (only where the final byte differs); the final byte goes into lo / hi.
+// Which dabs' boxes hold a row (y, z) is wave-uniform: lane k keeps dab k's y
+// and z range, one compare per lane and a ballot give the 64-bit set in scalar
+// registers, and the walk over its bits, the dabs' Terms and the y / z terms of
+// Q are scalar work.  A candidate whose y / z terms already pass S costs a row
+// nothing further; per lane there remain the x range and Q of the others.
+__global__ __launch_bounds__(kBlock) void k_paint_stroke(StrokeArgs a, uint8_t* __restrict__ dst,
+                                                         unsigned* __restrict__ mm)
+{
+    constexpr unsigned kWaves = kBlock / 64;
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int cy = 0, ry = -1, cz = 0, rz = -1;   // lane k: dab k's rows (no dab: holds nothing)
+    if (lane < a.count) {
+        cy = a.dab[lane].centre[1]; ry = a.dab[lane].radius[1];
+        cz = a.dab[lane].centre[2]; rz = a.dab[lane].radius[2];
+    }
+    const unsigned rows = a.row_begin[a.count];
+    int i = 0;   // the dab of row r: a wave's rows ascend
+    for (unsigned r = blockIdx.x * kWaves + wave; r < rows; r += gridDim.x * kWaves) {
+        while (r >= a.row_begin[i + 1]) ++i;
+        // dab i's clipped box (vr_brush.h clip; the centre is within a radius of the volume, so ints do)
+        const vr_brush& bi = a.dab[i];
+        const int x0 = max(bi.centre[0] - bi.radius[0], 0), x1 = min(bi.centre[0] + bi.radius[0], a.nx - 1);
+        const int y0 = max(bi.centre[1] - bi.radius[1], 0), y1 = min(bi.centre[1] + bi.radius[1], a.ny - 1);
+        const int z0 = max(bi.centre[2] - bi.radius[2], 0);
+        const unsigned ey = (unsigned)(y1 - y0 + 1), rr = r - a.row_begin[i];
+        const int z = z0 + (int)(rr / ey), y = y0 + (int)(rr % ey);
+        const unsigned long long holds = __ballot(abs(y - cy) <= ry && abs(z - cz) <= rz);   // bit i is set
+        const unsigned long long below = (1ull << i) - 1ull;
+        uint8_t* __restrict__ row = dst + ((long long)z * a.ny + y) * a.nx;
+        for (int x = x0 + lane; x <= x1; x += 64) {
+            bool owned = true;
+            for (unsigned long long m = holds & below; m; m &= m - 1ull) {
+                const vr_brush& bj = a.dab[__builtin_ctzll(m)];
+                owned = owned && abs(x - bj.centre[0]) > bj.radius[0];
+            }
+            if (__ballot(owned) == 0ull) continue;
+            unsigned cur[4] = {0u, 0u, 0u, 0u}, old[4] = {0u, 0u, 0u, 0u}, have = 0u;   // have: the channels loaded
+            for (unsigned long long m = holds & ~below; m; m &= m - 1ull) {
+                const vr_brush& b = a.dab[__builtin_ctzll(m)];
+                const brush::Terms t = brush::terms(b.radius);
+                const unsigned long long qyz = brush::axis_term(y - b.centre[1], t.k[1]) +
+                                               brush::axis_term(z - b.centre[2], t.k[2]);
+                if (qyz > t.s) continue;
+                const int dx = x - b.centre[0];
+                if (!owned || abs(dx) > b.radius[0]) continue;
+                const unsigned long long q = qyz + brush::axis_term(dx, t.k[0]);
+                if (q > t.s) continue;
+                const unsigned w = brush::weight(q, t.s, b.falloff);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (b.strength[c] == 0u) continue;
+                    if (!(have & (1u << c))) {
+                        old[c] = cur[c] = row[x + c * plane];
+                        have |= 1u << c;
+                    }
+                    cur[c] = brush::blend(b.op, cur[c], b.value[c], w * b.strength[c]);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (!(have & (1u << c))) continue;
+                if (cur[c] != old[c]) row[x + c * plane] = (uint8_t)cur[c];
+                lo[c] = min(lo[c], cur[c]);
+                hi[c] = max(hi[c], cur[c]);
+            }
+        }
+    }
+    fold_minmax(lo, hi, mm);
+}
+
 // vr_get_volume_box: the planes' texel box -> tightly packed RGBA8 (what
 // k_update_planar reads).  One thread per texel, one 4-byte store each.
 __global__ __launch_bounds__(kBlock) void k_unpack_box(const uint8_t* __restrict__ src, int nx, int ny, int nz,
@@ -715,12 +802,29 @@ hipError_t launch_paint_planar(const PaintArgs& a, uint8_t* d_planar, unsigned* 
     return hipGetLastError();
 }
 
+// a wave per row of a dab's box, as launch_paint_planar; the list must hold a dab, and every dab a row
+hipError_t launch_paint_stroke(const StrokeArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s)
+{
+    if (a.count < 1 || a.count > VR_MAX_DABS) return hipErrorInvalidValue;
+    for (int i = 0; i < a.count; ++i)
+        if (a.row_begin[i + 1] <= a.row_begin[i]) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_paint_stroke, dim3(grid_for((long long)a.row_begin[a.count] * 64)), dim3(kBlock), 0, s, a,
+                       d_planar, mm);
+    return hipGetLastError();
+}
+
 hipError_t launch_unpack_box(const uint8_t* d_planar, int nx, int ny, int nz, int x0, int y0, int z0, int bx, int by,
                              int bz, uint8_t* d_box, hipStream_t s)
 {
     hipLaunchKernelGGL(k_unpack_box, dim3(grid_for((long long)bx * by * bz)), dim3(kBlock), 0, s, d_planar, nx, ny, nz,
                        x0, y0, z0, bx, by, bz, reinterpret_cast<uchar4*>(d_box));
     return hipGetLastError();
+}
+
+// the default build's layouts, which launch_build_layout_box rebuilds over a box
+bool layout_rebuilds_box(int layout)
+{
+    return layout == LAYOUT_CORNERH || layout == LAYOUT_CORNER8 || layout == LAYOUT_BRICK4832 || layout == LAYOUT_COL48;
 }
 
 // A fast layout stores texel x (padded index x + 1) under the base positions
@@ -733,7 +837,7 @@ hipError_t launch_unpack_box(const uint8_t* d_planar, int nx, int ny, int nz, in
 hipError_t launch_build_layout_box(int layout, const uint8_t* d_planar, int nx, int ny, int nz, uint8_t* d_out,
                                    int x0, int y0, int z0, int bx, int by, int bz, hipStream_t s)
 {
-    if (layout != LAYOUT_CORNERH && layout != LAYOUT_CORNER8 && layout != LAYOUT_BRICK4832 && layout != LAYOUT_COL48)
+    if (!layout_rebuilds_box(layout))
         return launch_build_layout(layout, d_planar, nx, ny, nz, d_out, s);   // VR_EXPERIMENTS layouts: all of it
     const LayoutGeom g = layout_geom(layout, nx, ny, nz);
     const int lo[3] = {x0, y0, z0}, hi[3] = {x0 + bx, y0 + by, z0 + bz};

@@ -194,6 +194,45 @@ def brush_apply(brush: Brush, rgba: np.ndarray) -> np.ndarray:
     return rgba
 
 
+def _brush_copy(b: Brush) -> Brush:
+    c = Brush()
+    ctypes.memmove(ctypes.byref(c), ctypes.byref(b), ctypes.sizeof(Brush))
+    return c
+
+
+def brush_line(brush: Brush, to, spacing: int, skip_first: bool = False) -> list[Brush]:
+    """vr_brush_line: the dabs of a drag from ``brush.centre`` to the texel `to`
+    = (x, y, z), copies of `brush` at most `spacing` texels apart on the longest
+    axis, the first on the brush's own centre (omitted with `skip_first`, so
+    that the joint of two segments is not dabbed twice) and the last on `to`.
+    What :meth:`Renderer.paint_stroke` takes.  Host code only."""
+    t = (ctypes.c_int32 * 3)(*(int(v) for v in to))
+    n = ctypes.c_int(0)
+    lib = _lib.load()
+    st = lib.vr_brush_line(ctypes.byref(brush), t, int(spacing), int(skip_first), None, 0, ctypes.byref(n))
+    if n.value <= 0:   # refused for another reason than the room
+        _lib.check(st, "vr_brush_line")
+    out = (Brush * n.value)()
+    call("vr_brush_line", ctypes.byref(brush), t, int(spacing), int(skip_first), out, n.value, ctypes.byref(n))
+    return [_brush_copy(out[i]) for i in range(n.value)]
+
+
+def coalesce_boxes(boxes, max_out: int):
+    """vr_boxes_coalesce: at most `max_out` texel boxes ``(origin, extent)`` =
+    ((x, y, z), (bx, by, bz)) whose union contains the union of `boxes` (the
+    same pairs).  Empty and contained boxes are dropped; then the pair whose
+    bounding box adds the least volume is merged until the list fits.  Host
+    code only: needs no renderer and no device."""
+    boxes = list(boxes)
+    arr = (_lib.Box * len(boxes))()
+    for i, (o, e) in enumerate(boxes):
+        arr[i] = _lib.Box(*(int(v) for v in o), *(int(v) for v in e))
+    out = (_lib.Box * max(1, min(len(arr), max(int(max_out), 0))))()
+    n = ctypes.c_int(0)
+    call("vr_boxes_coalesce", arr, len(arr), int(max_out), out, ctypes.byref(n))
+    return [((out[i].x, out[i].y, out[i].z), (out[i].bx, out[i].by, out[i].bz)) for i in range(n.value)]
+
+
 # vr_ray_record as a numpy structured type (the layout of _lib.RayRecord)
 RAY_RECORD_DTYPE = np.dtype([("steps", "<i4"), ("hit_step", "<i4"), ("value", "<f4"), ("optical_depth", "<f4"),
                              ("entry", "<f4", (3,)), ("reserved0", "<f4"), ("step", "<f4", (3,)), ("reserved1", "<f4"),
@@ -303,6 +342,28 @@ class Renderer:
         if stream is None:
             torch.cuda.current_stream().synchronize()
         return brush_box(b, self.volume_dims())
+
+    def paint_stroke(self, brushes, stream=None):
+        """Apply a list of at most VR_MAX_DABS :class:`Brush` dabs, in order, in
+        one paint launch (vr_paint_stroke): the renderer then holds, bit for bit,
+        what :meth:`paint` of each in turn would leave, with every texel loaded
+        and stored once and the device layouts rebuilt over a few boxes instead
+        of per dab.  Returns the list of ``(origin, extent)`` of the clipped
+        boxes of the dabs that reach the volume -- what
+        :meth:`update_footprints` takes, so an editor's loop is
+        ``pick -> brush_line -> paint_stroke -> update_footprints ->
+        render_rects``.  Queued on `stream` as :meth:`paint` is."""
+        brushes = list(brushes)
+        arr = (Brush * max(1, len(brushes)))()
+        for i, b in enumerate(brushes):
+            ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(b), ctypes.sizeof(Brush))
+        call("vr_paint_stroke", self._ctx, arr if brushes else None, len(brushes), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        if not brushes:
+            return []
+        dims = self.volume_dims()
+        return [box for box in (brush_box(b, dims) for b in brushes) if box is not None]
 
     def get_volume_box(self, origin, extent, out=None, stream=None):
         """The texel box `extent` = (bx, by, bz) at `origin` = (x0, y0, z0) of the
