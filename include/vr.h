@@ -286,8 +286,8 @@ typedef struct {              /* 48 bytes */
  * the volume untouched.                                                     */
 vr_status vr_paint(void* ctx, const vr_brush* brush, void* stream);
 /* The brush's bounding box [centre - radius, centre + radius] clipped to an
- * nx x ny x nz volume: what vr_paint rewrites, and what to hand to
- * vr_update_footprint.  extent = (0, 0, 0) (and origin 0) when the brush
+ * nx x ny x nz volume: what vr_paint (and vr_blur, below) rewrites, and what
+ * to hand to vr_update_footprint.  extent = (0, 0, 0) (and origin 0) when the brush
  * misses the volume.  Pure host code: no context, no device.  The brush is
  * validated as by vr_paint; VR_ERR_INVALID also for a non-positive dimension. */
 vr_status vr_brush_box(const vr_brush* brush, int nx, int ny, int nz, int origin[3], int extent[3]);
@@ -359,6 +359,55 @@ typedef struct { int32_t x, y, z, bx, by, bz; } vr_box;
  * negative coordinate or extent, x + bx, y + by or z + bz above INT32_MAX.
  * count == 0 is VR_OK; *out_count, when given, is then 0.                  */
 vr_status vr_boxes_coalesce(const vr_box* in, int count, int max_out, vr_box* out, int* out_count);
+
+/* The smoothing brush: a box filter under the brush.
+ * vr_blur is a VR_BRUSH_SET brush whose value, per texel and channel, is the
+ * mean of that channel over the texel's neighbourhood AS IT WAS BEFORE THE
+ * CALL.  In integers, with h = half_width in 1..VR_BLUR_MAX_HALF and
+ * N = (2h + 1)^3 (27, 125, 343): for a texel t inside the ellipsoid and the
+ * volume (the inside test and the weight w are the brush's, above) and a
+ * channel c with strength[c] != 0,
+ *   sum = the sum of channel c over the N texels at offsets -h..h per axis
+ *         from t, coordinates clamped to the volume (clamp-to-edge);
+ *         neighbours outside the brush's box are read like any other
+ *   m   = (sum + N / 2) / N                  (integer division, 0..255)
+ *   new = (old (65280 - a) + m a + 32640) / 65280,  a = w * strength[c]
+ * -- the SET blend, unchanged.  brush->op must be VR_BRUSH_SET; brush->value
+ * is not read.  Every mean is taken over the bytes before the call, whatever
+ * the order in which texels are processed (a Jacobi step, not an in-place
+ * sweep), so the result is deterministic and the host statement and the device
+ * agree bit for bit.  A channel whose texels are all equal has m = old
+ * everywhere: a blur never breaks a uniform channel.
+ *
+ * Device path: two launches on `stream` -- the new bytes of the clipped box
+ * are staged in a scratch buffer that belongs to the context, then committed
+ * to the planes -- followed by what follows vr_paint: the layout rebuild over
+ * the clipped box (vr_brush_box names it; hand it to vr_update_footprint) and
+ * the uniform-channel re-arm.  The scratch holds one byte per texel of the
+ * clipped box and painted channel (at most 4 x the volume).  A call that needs
+ * more than the context holds synchronises the device, frees the old buffer
+ * and allocates the need rounded up to 1 MiB -- the rule of the cost-sort
+ * scratch (top of this file); VR_ERR_OOM if that fails: nothing is then held
+ * and the volume is untouched.  Every other call allocates nothing and never
+ * waits on the host, so pick -> vr_blur -> vr_update_footprint ->
+ * vr_render_rect queue on one stream.  vr_set_option("blur_scratch_kib", k)
+ * reserves at least k KiB now, after a device synchronisation (0 frees it);
+ * vr_get_option returns the KiB held.  The scratch is kept across volume
+ * installs and freed by vr_destroy.  Two vr_blur calls of one ctx on DIFFERENT
+ * streams share it: they are the caller's to order, as renders against
+ * updates are.
+ * VR_ERR_INVALID: a null pointer, anything vr_paint refuses, op other than
+ * VR_BRUSH_SET, half_width outside 1..VR_BLUR_MAX_HALF; VR_ERR_NO_VOLUME
+ * before an install and while a procedural medium is enabled.  A brush that
+ * misses the volume is VR_OK and launches nothing.  A refused call has
+ * launched nothing and leaves the volume untouched.                         */
+#define VR_BLUR_MAX_HALF 3
+vr_status vr_blur(void* ctx, const vr_brush* brush, int half_width, void* stream);
+/* The same on a HOST RGBA8 volume (x fastest), as vr_brush_apply is for
+ * vr_paint: the CPU statement, which vr_blur reproduces bit for bit.  It works
+ * from a copy of the clipped box and its halo, never in place.  Pure host
+ * code.  VR_ERR_INVALID as above, and for a non-positive dimension.         */
+vr_status vr_brush_blur_apply(const vr_brush* brush, int half_width, uint8_t* rgba8, int nx, int ny, int nz);
 /* 1 if vr_set_volume / vr_set_volume_device accept an nx x ny x nz extent
  * (the device layouts index a plane with 32-bit offsets), else 0          */
 int       vr_volume_extent_ok(int nx, int ny, int nz);
@@ -754,6 +803,10 @@ vr_status vr_set_layout_preference(void* ctx, int pref);
  *                     G, TestMain.cpp:60) is sampled as the exact constant v/255
  *                     with no loads; 0 = every channel is loaded.
  *   "uniform_mask"    read-only (vr_get_option): bit c set = channel c uniform.
+ *   "blur_scratch_kib" vr_blur's staging scratch: set k > 0 = hold at least k
+ *                     KiB from now on (a device synchronisation, then the
+ *                     allocation, in whole MiB; never shrinks), 0 = free it;
+ *                     vr_get_option returns the KiB held now.
  *   "region_work_tiles" read-only: 8x8 tiles with estimated work in the current
  *                     region lists (what the auto split K is chosen from).
  *   "sort_reuse"      0-64, procedural sorted schedule: renders that may march

@@ -63,6 +63,13 @@ inline bool BrushBox(const vr_brush& brush, int nx, int ny, int nz, int origin[3
     return extent[0] > 0;
 }
 
+// The smoothing brush on a host RGBA8 volume (vr_brush_blur_apply): the CPU
+// statement of Renderer::Blur.  Host code only.
+inline void BrushBlurApply(const vr_brush& brush, int half_width, uint8_t* rgba, int nx, int ny, int nz)
+{
+    Check(vr_brush_blur_apply(&brush, half_width, rgba, nx, ny, nz), "vr_brush_blur_apply");
+}
+
 // The dabs of a drag from brush.centre to the texel `to`, at most `spacing`
 // texels apart (vr_brush_line): what Renderer::PaintStroke takes.  skip_first
 // omits the dab on the brush's own centre, the joint of two segments.  Host
@@ -112,6 +119,14 @@ public:
     void PaintStroke(const std::vector<vr_brush>& dabs, void* stream = nullptr)
     {
         PaintStroke(dabs.data(), (int)dabs.size(), stream);
+    }
+    // Soften the installed volume under the brush (vr_blur): a SET brush whose
+    // value is the mean of each texel's (2 half_width + 1)^3 neighbourhood as
+    // it was before the call; brush.op must be VR_BRUSH_SET.  Queued on
+    // `stream` as Paint is; BrushBox names the box it rewrites.
+    void Blur(const vr_brush& brush, int half_width = 1, void* stream = nullptr)
+    {
+        Check(vr_blur(ctx_, &brush, half_width, stream), "vr_blur");
     }
     // The read-back counterpart of UpdateVolume (vr_get_volume_box): save a
     // box, Paint, UpdateVolume the saved box -- undo.

@@ -8,8 +8,8 @@ interface (renderer) and the multi-GPU band sharding (distributed).
 from ._lib import (FMT_R8_SRGB, FMT_R8_UNORM, FMT_R32F, FMT_RGBA8_SRGB, FMT_RGBA8_UNORM, FMT_RGBA32F,  # noqa: F401
                    GREY_OF, GlobalShaderData, MarchParams, ObjectShaderData, Target, VolumeRecipe, VRError)
 from ._lib import VR_MAX_RECTS, Procedural, RayRecord, Rect  # noqa: F401
-from ._lib import BRUSH_ADD, BRUSH_MAX_RADIUS, BRUSH_SET, BRUSH_SUB, VR_MAX_DABS, Box, Brush  # noqa: F401
-from .renderer import brush_apply, brush_box, brush_line, coalesce_boxes, make_brush  # noqa: F401
+from ._lib import BLUR_MAX_HALF, BRUSH_ADD, BRUSH_MAX_RADIUS, BRUSH_SET, BRUSH_SUB, VR_MAX_DABS, Box, Brush  # noqa: F401
+from .renderer import brush_apply, brush_blur_apply, brush_box, brush_line, coalesce_boxes, make_brush  # noqa: F401
 from .renderer import (RAY_RECORD_DTYPE, Renderer, band_rows_packed, coalesce_rects, march_defaults,  # noqa: F401
                        procedural_defaults, ray_records, reference_shader_data, scaled_recipe, shader_data_arrays,
                        volume_box_footprint,
@@ -21,5 +21,5 @@ __all__ = [
     "FMT_RGBA8_SRGB", "FMT_R8_UNORM", "FMT_R8_SRGB", "FMT_R32F", "GREY_OF", "ObjectShaderData", "GlobalShaderData", "MarchParams", "VolumeRecipe", "Target",
     "Rect", "volume_box_footprint", "coalesce_rects", "VR_MAX_RECTS", "RayRecord", "RAY_RECORD_DTYPE", "ray_records",
     "Brush", "BRUSH_SET", "BRUSH_ADD", "BRUSH_SUB", "BRUSH_MAX_RADIUS", "make_brush", "brush_box", "brush_apply",
-    "brush_line", "coalesce_boxes", "VR_MAX_DABS", "Box",
+    "brush_line", "coalesce_boxes", "VR_MAX_DABS", "Box", "brush_blur_apply", "BLUR_MAX_HALF",
 ]

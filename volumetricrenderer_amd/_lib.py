@@ -125,6 +125,7 @@ class Brush(ctypes.Structure):
 BRUSH_SET, BRUSH_ADD, BRUSH_SUB = 0, 1, 2   # vr.h vr_brush_op
 BRUSH_MAX_RADIUS = 255                      # vr.h VR_BRUSH_MAX_RADIUS
 VR_MAX_DABS = 64                            # vr.h: the longest list vr_paint_stroke takes
+BLUR_MAX_HALF = 3                           # vr.h VR_BLUR_MAX_HALF: the widest box filter of vr_blur (7 texels)
 
 
 class Box(ctypes.Structure):
@@ -158,6 +159,9 @@ _SIGS = {
     "vr_brush_line": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
                                      ctypes.POINTER(Brush), ctypes.c_int, c_int_p]),
     "vr_boxes_coalesce": (ctypes.c_int, [ctypes.POINTER(Box), ctypes.c_int, ctypes.c_int, ctypes.POINTER(Box), c_int_p]),
+    "vr_blur": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.c_int, _vp]),
+    "vr_brush_blur_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int]),
     "vr_volume_extent_ok": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vr_volume_recipe_defaults": (ctypes.c_int, [ctypes.POINTER(VolumeRecipe)]),
     "vr_generate_volume": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeRecipe), _vp]),

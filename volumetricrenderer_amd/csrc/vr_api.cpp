@@ -13,6 +13,7 @@
 // region lists / row partition and the procedural scratch live in
 // vr_options.cpp, vr_regions_host.cpp and vr_proc_host.cpp; the scissored
 // renders in vr_rect.cpp.
+#include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_ctx.h"
 
@@ -414,6 +415,7 @@ try {
     if (c->d_heads) (void)hipFree(c->d_heads);
     if (c->d_sort) (void)hipFree(c->d_sort);
     (void)hipDeviceSynchronize();   // queued renders may still read the region lists and the scratch
+    if (c->d_blur) (void)hipFree(c->d_blur);
     for (const auto& ds : c->defer_sets)
         if (ds.d) (void)hipFree(ds.d);
     for (const auto& q : c->defer_retired) {
@@ -559,6 +561,34 @@ static vr_status update_volume_device(Ctx* c, const uint8_t* d_box, int x0, int 
 {
     HIP_TRY(launch_update_planar(d_box, c->nx, c->ny, c->nz, x0, y0, z0, bx, by, bz, c->d_planar, c->d_mm, s));
     return box_edited(c, x0, y0, z0, bx, by, bz, s);
+}
+
+// vr_blur's staging scratch.  A queued blur may still use the held buffer, hence the device sync before it is freed.
+vr_status release_blur(Ctx* c)
+{
+    if (!c->d_blur) return VR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    (void)hipFree(c->d_blur);
+    c->d_blur = nullptr;
+    c->blur_bytes = 0;
+    return VR_OK;
+}
+
+vr_status ensure_blur(Ctx* c, size_t need)
+{
+    if (need <= c->blur_bytes) return VR_OK;
+    if (vr_status st = release_blur(c)) return st;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t mib = (size_t)1 << 20, bytes = (need + mib - 1) / mib * mib;
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VR_ERR_OOM, "vr_blur: %zu bytes of staging scratch", bytes);
+    }
+    c->d_blur = static_cast<uint8_t*>(d);
+    c->blur_bytes = bytes;
+    return VR_OK;
 }
 
 }  // namespace vrapi
@@ -717,6 +747,40 @@ try {
     return stroke_edited(c, boxes, a.count, s);
 } catch (...) {
     return caught_exception("vr_paint_stroke");
+}
+
+// The smoothing brush on the device: every check first, the scratch (grown only when the call needs more than is
+// held), k_blur_stage from the planes to the scratch, k_blur_commit from the scratch to the planes, and what
+// follows an edit of the clipped box.
+vr_status vr_blur(void* p, const vr_brush* b, int half_width, void* stream)
+try {
+    if (!p || !b) return fail(VR_ERR_INVALID, "vr_blur: null argument");
+    if (const char* why = vr::blur::invalid(b, half_width)) return fail(VR_ERR_INVALID, "vr_blur: %s", why);
+    Ctx* c = as_ctx(p);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_blur: no volume set");
+    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_blur: a procedural medium is enabled (it reads no volume)");
+    PaintArgs a{};
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
+    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    a.s = t.s;
+    for (int ax = 0; ax < 3; ++ax) {
+        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
+        a.k[ax] = t.k[ax];
+    }
+    a.op = VR_BRUSH_SET;
+    a.falloff = b->falloff;
+    for (int ch = 0; ch < 4; ++ch) a.strength[ch] = b->strength[ch];   // value is not read
+    const size_t need = blur_stage_bytes(a);
+    if (need == 0) return VR_OK;   // every strength is 0: nothing is read or written
+    if (vr_status st = ensure_blur(c, need)) return st;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(launch_blur_stage(a, half_width, c->d_planar, c->d_blur, s));
+    HIP_TRY(launch_blur_commit(a, c->d_blur, c->d_planar, c->d_mm, s));
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+} catch (...) {
+    return caught_exception("vr_blur");
 }
 
 vr_status vr_noise_grid(void* p, int kind, void* d_out, int x0, int y0, int z0, int nx, int ny, int nz,

@@ -109,6 +109,10 @@ struct Ctx {
     uint8_t* d_fast = nullptr;     // one fast layout, built from d_planar
     int fast_layout = 0;           // which one (0 = none)
     size_t fast_plane_bytes = 0;
+    // vr_blur's staging scratch (vr.h): a byte per texel of the clipped box and painted channel; grown on demand
+    // after a device sync (ensure_blur), reserved by option "blur_scratch_kib", kept across installs
+    uint8_t* d_blur = nullptr;
+    size_t blur_bytes = 0;
     // uniforms
     bool has_camera = false;
     float obj[48];
@@ -290,6 +294,10 @@ int wanted_fast_layout(const Ctx* c);
 vr_status ensure_fast_layout(Ctx* c, hipStream_t s);
 vr_status install_volume(Ctx* c, const uint8_t* d_rgba, int nx, int ny, int nz, hipStream_t s);
 vr_status resolve_uniform(Ctx* c);
+// vr_blur's scratch: at least `need` bytes held (more than held: device sync, free, allocate need rounded up to
+// 1 MiB; VR_ERR_OOM leaves none held), and release_blur frees it after a device sync
+vr_status ensure_blur(Ctx* c, size_t need);
+vr_status release_blur(Ctx* c);
 void tap_constants(const Ctx* c, float S[4][3], float T[4][3]);
 bool clamp_is_exact(const Ctx* c, const float S[4][3], const float T[4][3]);
 int band_rows_packed(int height, int band_rows, int band_stride, int band_first, int band_flip = 0);

@@ -605,6 +605,14 @@ struct StrokeArgs {
 static_assert(sizeof(StrokeArgs) <= 4096, "StrokeArgs travels in the kernarg segment");
 // Apply the dabs in order, every texel by one thread (k_paint_stroke), and fold the final bytes' min / max into mm
 hipError_t launch_paint_stroke(const StrokeArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+// vr_blur: `a` is the brush as for launch_paint_planar (op VR_BRUSH_SET; value is not read),
+// half_width 1..VR_BLUR_MAX_HALF.  d_stage holds one slab of e[0] x e[1] x e[2] bytes (x fastest) per channel with
+// strength != 0, in channel order (blur_stage_bytes).  The stage kernel reads the planes and writes the new byte of
+// every inside texel to its slab; the commit kernel stores those bytes to the planes where they differ from the old
+// ones and folds them into mm.  Two launches: no byte a mean reads has been written by this call.
+size_t blur_stage_bytes(const PaintArgs& a);
+hipError_t launch_blur_stage(const PaintArgs& a, int half_width, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s);
+hipError_t launch_blur_commit(const PaintArgs& a, const uint8_t* d_stage, uint8_t* d_planar, unsigned* mm, hipStream_t s);
 // true for the layouts launch_build_layout_box rebuilds over the box; the others it rebuilds whole
 bool layout_rebuilds_box(int layout);
 // Perlin lattice table: entry (x, y, z) - lo of n^3 = noise::perlin_lattice_entry(seed, x, y, z)

@@ -200,6 +200,10 @@ try {
         c->count = value;
         return VR_OK;
     }
+    if (n == "blur_scratch_kib") {   // vr_blur's staging scratch: hold at least this much from now on; 0 frees it
+        if (value < 0) return fail(VR_ERR_INVALID, "vr_set_option: blur_scratch_kib >= 0");
+        return value == 0 ? release_blur(c) : ensure_blur(c, (size_t)value * 1024);
+    }
     if (n == "lattice") {
         if (value < 0 || value > 1) return fail(VR_ERR_INVALID, "vr_set_option: lattice is 0 or 1");
         c->lattice = value;
@@ -242,6 +246,7 @@ try {
         for (const auto& ds : c->defer_sets) b += ds.bytes;
         return (int)std::min<size_t>((b + 1023) / 1024, 0x7fffffff);
     }
+    if (n == "blur_scratch_kib") return (int)std::min<size_t>(c->blur_bytes / 1024, 0x7fffffff);   // the KiB held now
     if (n == "slab_cap") return c->slab_cap;
     if (n == "region_order") return c->region_order;
     if (n == "sort_reuse") return c->sort_reuse;

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_internal.h"
 #include "vr_noise.h"
@@ -225,6 +226,177 @@ __global__ __launch_bounds__(kBlock) void k_paint_stroke(StrokeArgs a, uint8_t* 
                 if (cur[c] != old[c]) row[x + c * plane] = (uint8_t)cur[c];
                 lo[c] = min(lo[c], cur[c]);
                 hi[c] = max(hi[c], cur[c]);
+            }
+        }
+    }
+    fold_minmax(lo, hi, mm);
+}
+
+// vr_blur, first launch: the new byte of every texel
+// inside the brush, from the planes AS THEY ARE -- read only -- to the staging
+// slabs (one per painted channel, shaped like the clipped box, x fastest).
+// Nothing a mean reads is written by this launch, so the result does not
+// depend on the order of the workgroups (a Jacobi step); k_blur_commit moves
+// the bytes to the planes afterwards.
+//
+// A workgroup takes a kBlurTX x kBlurTY x kBlurTZ tile of the box; thread t
+// owns the column (x, y) = (t % kBlurTX, t / kBlurTX) of it and its kBlurTZ
+// texels.  The ellipsoid test and the weights need no memory: a tile with no
+// texel inside leaves before any load.  Per painted channel:
+//  1. the tile and its halo of H texels, coordinates clamped to the volume, go
+//     from the plane to LDS once -- byte loads, the plane rows start at any
+//     byte; consecutive lanes on consecutive x;
+//  2. x: four adjacent sums of 2H + 1 bytes from the NW dwords that hold their
+//     4 + 2H bytes, one 8-byte store of four 16-bit sums (<= 7 * 255);
+//  3. y: a thread per (x, z) column of those slides the window over the
+//     kBlurTY + 2H values it has read once; 16-bit sums (<= 49 * 255);
+//  4. z: the owner slides the window over its column's kBlurTZ + 2H values --
+//     the 32-bit sum, vr_blur.h's mean, the brush's SET blend with the old
+//     byte (still in the staged tile), one byte store per inside texel.
+// Lanes of a wave read consecutive 16-bit (or, in step 2, 32-bit) LDS words:
+// no bank holds two different words of a lane group.
+constexpr int kBlurTX = 32, kBlurTY = 8, kBlurTZ = 8;
+static_assert(kBlurTX * kBlurTY == kBlock && kBlurTX % 4 == 0, "a thread per (x, y) column of the tile");
+
+template <int H>
+__global__ __launch_bounds__(kBlock) void k_blur_stage(PaintArgs a, const uint8_t* __restrict__ src,
+                                                       uint8_t* __restrict__ stage)
+{
+    constexpr int W = 2 * H + 1;
+    constexpr int XH = kBlurTX + 2 * H, YH = kBlurTY + 2 * H, ZH = kBlurTZ + 2 * H;
+    constexpr int XP = (XH + 3) / 4 * 4;    // the staged rows' pitch: whole dwords
+    constexpr int NW = (4 + 2 * H + 3) / 4;   // dwords that hold the bytes of four adjacent x sums
+    static_assert(kBlurTX - 4 + 4 * NW <= XP, "step 2 reads inside its row");
+    __shared__ uint32_t raw32[ZH * YH * XP / 4];
+    __shared__ __align__(8) uint16_t sx[ZH * YH * kBlurTX];
+    __shared__ uint16_t sxy[ZH * kBlurTY * kBlurTX];
+    uint8_t* raw = reinterpret_cast<uint8_t*>(raw32);
+
+    const int tid = threadIdx.x, lx = tid % kBlurTX, ly = tid / kBlurTX;
+    const int ntx = (a.e[0] + kBlurTX - 1) / kBlurTX, nty = (a.e[1] + kBlurTY - 1) / kBlurTY;
+    const int bt = blockIdx.x;
+    const int tx0 = (bt % ntx) * kBlurTX, ty0 = (bt / ntx % nty) * kBlurTY, tz0 = (bt / (ntx * nty)) * kBlurTZ;
+    const int x = tx0 + lx, y = ty0 + ly;   // in the box
+
+    // the weights of the owned texels: 0 outside the ellipsoid or the box (an inside texel's is at least 1)
+    unsigned wgt[kBlurTZ];
+    const bool column = x < a.e[0] && y < a.e[1];
+    const unsigned long long qxy =
+        column ? brush::axis_term(a.d0[0] + x, a.k[0]) + brush::axis_term(a.d0[1] + y, a.k[1]) : 0ull;
+    bool any = false;
+#pragma unroll
+    for (int z = 0; z < kBlurTZ; ++z) {
+        wgt[z] = 0u;
+        if (column && tz0 + z < a.e[2]) {
+            const unsigned long long q = qxy + brush::axis_term(a.d0[2] + tz0 + z, a.k[2]);
+            if (q <= a.s) wgt[z] = brush::weight(q, a.s, a.falloff);
+        }
+        any = any || wgt[z] != 0u;
+    }
+    if (!__syncthreads_or(any ? 1 : 0)) return;
+
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    const size_t slab = (size_t)a.e[0] * (size_t)a.e[1] * (size_t)a.e[2];
+    int k = 0;   // the channel's slab
+#pragma unroll 1
+    for (int c = 0; c < 4; ++c) {
+        if (a.strength[c] == 0u) continue;
+        const uint8_t* __restrict__ p = src + c * plane;
+        for (int i = tid; i < ZH * YH * XH; i += kBlock) {
+            const int xi = i % XH, t = i / XH, yi = t % YH, zi = t / YH;
+            const int gx = clampi(a.o[0] + tx0 - H + xi, 0, a.nx - 1), gy = clampi(a.o[1] + ty0 - H + yi, 0, a.ny - 1),
+                      gz = clampi(a.o[2] + tz0 - H + zi, 0, a.nz - 1);
+            raw[(zi * YH + yi) * XP + xi] = p[((long long)gz * a.ny + gy) * a.nx + gx];
+        }
+        __syncthreads();
+        for (int i = tid; i < ZH * YH * (kBlurTX / 4); i += kBlock) {
+            const int xq = i % (kBlurTX / 4), r = i / (kBlurTX / 4);   // r: the row (zi, yi)
+            const uint32_t* w32 = raw32 + r * (XP / 4) + xq;
+            unsigned b[4 * NW];
+#pragma unroll
+            for (int j = 0; j < NW; ++j) {
+                const uint32_t v = w32[j];
+                b[4 * j] = v & 255u; b[4 * j + 1] = (v >> 8) & 255u; b[4 * j + 2] = (v >> 16) & 255u; b[4 * j + 3] = v >> 24;
+            }
+            unsigned s0 = 0u;
+#pragma unroll
+            for (int j = 0; j < W; ++j) s0 += b[j];
+            const unsigned s1 = s0 - b[0] + b[W], s2 = s1 - b[1] + b[W + 1], s3 = s2 - b[2] + b[W + 2];
+            *reinterpret_cast<uint2*>(&sx[r * kBlurTX + 4 * xq]) = make_uint2(s0 | (s1 << 16), s2 | (s3 << 16));
+        }
+        __syncthreads();
+        for (int i = tid; i < ZH * kBlurTX; i += kBlock) {
+            const int xx = i % kBlurTX, zi = i / kBlurTX;
+            const uint16_t* col = sx + zi * YH * kBlurTX + xx;
+            unsigned v[YH];
+#pragma unroll
+            for (int j = 0; j < YH; ++j) v[j] = col[j * kBlurTX];
+            unsigned s = 0u;
+#pragma unroll
+            for (int j = 0; j < W; ++j) s += v[j];
+#pragma unroll
+            for (int yo = 0; yo < kBlurTY; ++yo) {
+                if (yo > 0) s += v[yo + W - 1] - v[yo - 1];
+                sxy[(zi * kBlurTY + yo) * kBlurTX + xx] = (uint16_t)s;
+            }
+        }
+        __syncthreads();
+        {
+            const uint16_t* col = sxy + ly * kBlurTX + lx;
+            unsigned v[ZH];
+#pragma unroll
+            for (int j = 0; j < ZH; ++j) v[j] = col[j * kBlurTY * kBlurTX];
+            unsigned s = 0u;
+#pragma unroll
+            for (int j = 0; j < W; ++j) s += v[j];
+            uint8_t* __restrict__ out = stage + (size_t)k * slab;
+#pragma unroll
+            for (int z = 0; z < kBlurTZ; ++z) {
+                if (z > 0) s += v[z + W - 1] - v[z - 1];
+                if (wgt[z] == 0u) continue;
+                const unsigned old = raw[((z + H) * YH + ly + H) * XP + lx + H];
+                const unsigned nw = brush::blend(VR_BRUSH_SET, old, blur::mean(s, H), wgt[z] * a.strength[c]);
+                out[((size_t)(tz0 + z) * (size_t)a.e[1] + (size_t)y) * (size_t)a.e[0] + (size_t)x] = (uint8_t)nw;
+            }
+        }
+        ++k;
+        __syncthreads();   // the next channel rewrites the tile
+    }
+}
+
+// vr_blur, second launch: k_paint_planar's rows and lanes, with the new byte
+// of an inside texel loaded from the staging slabs (k_blur_stage wrote exactly
+// those) instead of blended: a store only where it differs from the old byte,
+// and the new bytes folded into mm.
+__global__ __launch_bounds__(kBlock) void k_blur_commit(PaintArgs a, const uint8_t* __restrict__ stage,
+                                                        uint8_t* __restrict__ dst, unsigned* __restrict__ mm)
+{
+    constexpr unsigned kWaves = kBlock / 64;
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    const size_t slab = (size_t)a.e[0] * (size_t)a.e[1] * (size_t)a.e[2];
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned rows = (unsigned)a.e[1] * (unsigned)a.e[2];   // <= 511^2
+    for (unsigned r = blockIdx.x * kWaves + wave; r < rows; r += gridDim.x * kWaves) {
+        const int z = (int)(r / (unsigned)a.e[1]), y = (int)(r - (unsigned)z * (unsigned)a.e[1]);
+        const unsigned long long qyz = brush::axis_term(a.d0[1] + y, a.k[1]) + brush::axis_term(a.d0[2] + z, a.k[2]);
+        if (qyz > a.s) continue;
+        uint8_t* __restrict__ row = dst + ((long long)(a.o[2] + z) * a.ny + (a.o[1] + y)) * a.nx + a.o[0];
+        const uint8_t* __restrict__ srow = stage + (size_t)r * (size_t)a.e[0];
+        for (int x = lane; x < a.e[0]; x += 64) {
+            const unsigned long long q = qyz + brush::axis_term(a.d0[0] + x, a.k[0]);
+            if (q > a.s) continue;
+            int k = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (a.strength[c] == 0u) continue;
+                uint8_t* p = row + x + c * plane;
+                const unsigned old = *p, nw = srow[(size_t)k * slab + (size_t)x];
+                if (nw != old) *p = (uint8_t)nw;
+                lo[c] = min(lo[c], nw);
+                hi[c] = max(hi[c], nw);
+                ++k;
             }
         }
     }
@@ -810,6 +982,38 @@ hipError_t launch_paint_stroke(const StrokeArgs& a, uint8_t* d_planar, unsigned*
         if (a.row_begin[i + 1] <= a.row_begin[i]) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_paint_stroke, dim3(grid_for((long long)a.row_begin[a.count] * 64)), dim3(kBlock), 0, s, a,
                        d_planar, mm);
+    return hipGetLastError();
+}
+
+size_t blur_stage_bytes(const PaintArgs& a)
+{
+    size_t channels = 0;
+    for (int c = 0; c < 4; ++c) channels += a.strength[c] != 0u;
+    return channels * (size_t)a.e[0] * (size_t)a.e[1] * (size_t)a.e[2];
+}
+
+// a workgroup per tile of the clipped box: at most 16 x 64 x 64 of them (a box edge is at most 511 texels)
+hipError_t launch_blur_stage(const PaintArgs& a, int half_width, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s)
+{
+    if (a.e[0] < 1 || a.e[1] < 1 || a.e[2] < 1 || !d_stage) return hipErrorInvalidValue;
+    const long long tiles = (long long)((a.e[0] + kBlurTX - 1) / kBlurTX) * ((a.e[1] + kBlurTY - 1) / kBlurTY) *
+                            ((a.e[2] + kBlurTZ - 1) / kBlurTZ);
+    if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+    const dim3 g((unsigned)tiles), b(kBlock);
+    switch (half_width) {
+    case 1: hipLaunchKernelGGL(k_blur_stage<1>, g, b, 0, s, a, d_planar, d_stage); break;
+    case 2: hipLaunchKernelGGL(k_blur_stage<2>, g, b, 0, s, a, d_planar, d_stage); break;
+    case 3: hipLaunchKernelGGL(k_blur_stage<3>, g, b, 0, s, a, d_planar, d_stage); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// a wave per box row, as launch_paint_planar
+hipError_t launch_blur_commit(const PaintArgs& a, const uint8_t* d_stage, uint8_t* d_planar, unsigned* mm, hipStream_t s)
+{
+    const long long rows = (long long)a.e[1] * a.e[2];
+    hipLaunchKernelGGL(k_blur_commit, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a, d_stage, d_planar, mm);
     return hipGetLastError();
 }
 

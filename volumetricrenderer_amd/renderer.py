@@ -194,6 +194,21 @@ def brush_apply(brush: Brush, rgba: np.ndarray) -> np.ndarray:
     return rgba
 
 
+def brush_blur_apply(brush: Brush, half_width: int, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_blur_apply: the smoothing brush applied to a host RGBA8 volume
+    shaped (nz, ny, nx, 4) (a contiguous uint8 array) -- under the brush, each
+    channel with a non-zero strength is SET towards the mean of its
+    (2 half_width + 1)^3 neighbourhood as it was before the call.  The CPU
+    statement of what :meth:`Renderer.blur` does on the device; `brush.op` must
+    be BRUSH_SET and `brush.value` is not read.  Writes `rgba` and returns it."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_blur_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    call("vr_brush_blur_apply", ctypes.byref(brush), int(half_width), rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz)
+    return rgba
+
+
 def _brush_copy(b: Brush) -> Brush:
     c = Brush()
     ctypes.memmove(ctypes.byref(c), ctypes.byref(b), ctypes.sizeof(Brush))
@@ -364,6 +379,23 @@ class Renderer:
             return []
         dims = self.volume_dims()
         return [box for box in (brush_box(b, dims) for b in brushes) if box is not None]
+
+    def blur(self, centre, radius, half_width: int = 1, falloff: int = 0, strength=(255, 255, 255, 255), stream=None):
+        """Soften the installed volume under an ellipsoidal brush on the device
+        (vr_blur): each channel with a non-zero strength is SET towards the
+        mean of its (2 half_width + 1)^3 neighbourhood (half_width 1..3,
+        clamp-to-edge) as it was before the call, weighted as :meth:`paint`
+        weights a SET brush -- bit for bit what :func:`brush_blur_apply` gives
+        on the host.  Returns ``(origin, extent)`` of the clipped bounding box
+        it rewrote, or None when the brush misses the volume, and queues on
+        `stream` as :meth:`paint` does.  The staging scratch grows (after a
+        device synchronisation) only when a call needs more than the renderer
+        holds; ``set_option("blur_scratch_kib", k)`` reserves it beforehand."""
+        b = make_brush(centre, radius, BRUSH_SET, falloff, 0, strength)
+        call("vr_blur", self._ctx, ctypes.byref(b), int(half_width), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return brush_box(b, self.volume_dims())
 
     def get_volume_box(self, origin, extent, out=None, stream=None):
         """The texel box `extent` = (bx, by, bz) at `origin` = (x0, y0, z0) of the
