@@ -408,6 +408,78 @@ vr_status vr_blur(void* ctx, const vr_brush* brush, int half_width, void* stream
  * from a copy of the clipped box and its halo, never in place.  Pure host
  * code.  VR_ERR_INVALID as above, and for a non-positive dimension.         */
 vr_status vr_brush_blur_apply(const vr_brush* brush, int half_width, uint8_t* rgba8, int nx, int ny, int nz);
+
+/* The read side of the brush: what is in the volume under it (DESIGN.md sec.
+ * 5.2.8) -- the eyedropper, a histogram panel, and the answer to "has this
+ * channel become constant again?".  Everything is an integer sum, so the
+ * result does not depend on the order in which texels are visited and the
+ * host statement and the device agree in every bit.
+ *
+ * A texel is INSIDE exactly as for vr_paint: |d_a| <= radius[a] on every axis,
+ * Q <= S, and inside the volume; its weight w is the brush's (256 for a hard
+ * edge, 256 at the centre down to 1 on the rim for a smooth one).  Channel c
+ * is SELECTED iff strength[c] != 0 -- vr_paint's rule; an unselected channel
+ * is not read.  op and value are validated and then ignored.  Over a texel
+ * box (vr_box_stats) every texel of the box is inside with w = 256, and bit c
+ * of channel_mask selects channel c.
+ *   count     the inside texels
+ *   weight    the sum of w over them (256 * count for a hard edge and a box)
+ *   wsum[c]   selected c: the sum of w * byte over them; else 0
+ *   hist[c][v] selected c: the inside texels whose channel c holds v; else 0
+ * so the bins of a selected channel add up to count.  All fields are 64 bits
+ * wide: nothing in the struct can overflow (w * byte <= 65280 per texel and a
+ * volume has fewer than 2^31 texels).                                       */
+typedef struct {              /* 8240 bytes; all-zero is the empty result */
+    uint64_t count;           /* inside texels                                   */
+    uint64_t weight;          /* sum of w over them (256 * count for a hard edge) */
+    uint64_t wsum[4];         /* per selected channel: sum of w * byte; else 0   */
+    uint64_t hist[4][256];    /* per selected channel: inside texels holding byte v; else 0 */
+} vr_volume_stats;
+/* The statistics of the installed volume under the brush, into `d_stats`: a
+ * DEVICE vr_volume_stats, 8-byte aligned, which the call OVERWRITES (a
+ * hipMemsetAsync to zero on `stream`, then one kernel launch).  Asynchronous
+ * on `stream`, nothing allocated, no host wait.  It reads the planes as
+ * vr_get_volume_box_device does -- after a vr_paint on the same stream it sees
+ * the painted bytes -- and writes only `d_stats`: cached launches, region
+ * lists, scratches, the pending uniform-channel read-back and the channels'
+ * byte ranges are neither used nor disturbed, so the next render is what it
+ * would have been without the call.  A brush that misses the volume still
+ * zeroes the buffer and launches no kernel; with every strength 0, count and
+ * weight are still produced and the channels are empty.
+ * VR_ERR_INVALID: a null pointer, a brush vr_paint would refuse, d_stats not
+ * 8-byte aligned; VR_ERR_NO_VOLUME before an install and while a procedural
+ * medium is enabled.  A refused call writes nothing.                        */
+vr_status vr_brush_stats(void* ctx, const vr_brush* brush, void* d_stats, void* stream);
+/* The same over the texel box [x0,x0+bx) x [y0,y0+by) x [z0,z0+bz): the same
+ * kernel with the ellipsoid test switched off.  The box is validated as
+ * vr_update_volume validates it (the whole volume is a valid box);
+ * channel_mask outside 0..15 is VR_ERR_INVALID.  min == max of a channel (see
+ * vr_stats_summary) over the whole volume says the channel is constant again:
+ * a re-install would re-arm its uniform bit.                                */
+vr_status vr_box_stats(void* ctx, int x0, int y0, int z0, int bx, int by, int bz, int channel_mask, void* d_stats,
+                       void* stream);
+/* The same two on a HOST RGBA8 volume (x fastest): the CPU statements, which
+ * the device reproduces bit for bit, as vr_brush_apply is for vr_paint.  *out
+ * is overwritten.  Pure host code.  VR_ERR_INVALID as above, and for a
+ * non-positive dimension; a refused call leaves *out as it was.             */
+vr_status vr_brush_stats_host(const vr_brush* brush, const uint8_t* rgba8, int nx, int ny, int nz, vr_volume_stats* out);
+vr_status vr_box_stats_host(const uint8_t* rgba8, int nx, int ny, int nz, int x0, int y0, int z0, int bx, int by, int bz,
+                            int channel_mask, vr_volume_stats* out);
+/* What a caller reads off a vr_volume_stats, per channel c, with
+ * n = sum_v hist[c][v] (integer division throughout):
+ *   n[c]
+ *   min[c], max[c]   the lowest and the highest non-empty bin
+ *   mean[c]          (sum_v v hist[c][v] + n / 2) / n
+ *   wmean[c]         (wsum[c] + weight / 2) / weight -- the eyedropper's value:
+ *                    value[c] = wmean[c] for the next vr_paint
+ *   median[c]        the smallest v with 2 cum(v) >= n, cum(v) = sum_{u<=v} hist[c][u]
+ * and all five are 0 where n = 0 (an unselected channel, an empty result).
+ * Pure host code.  VR_ERR_INVALID: a null pointer.                          */
+typedef struct {              /* 112 bytes */
+    uint64_t n[4];
+    int32_t  min[4], max[4], mean[4], wmean[4], median[4];
+} vr_volume_summary;
+vr_status vr_stats_summary(const vr_volume_stats* stats, vr_volume_summary* out);
 /* 1 if vr_set_volume / vr_set_volume_device accept an nx x ny x nz extent
  * (the device layouts index a plane with 32-bit offsets), else 0          */
 int       vr_volume_extent_ok(int nx, int ny, int nz);

@@ -139,6 +139,21 @@ public:
     {
         Check(vr_get_volume_box_device(ctx_, x0, y0, z0, bx, by, bz, d_rgba_out, stream), "vr_get_volume_box_device");
     }
+    // What is in the installed volume under the brush, or in a texel box
+    // (vr_brush_stats, vr_box_stats): count, weight, weighted sums and
+    // histograms of the selected channels into a DEVICE vr_volume_stats, which
+    // the call overwrites.  Queued on `stream`; nothing of the renderer changes.
+    // vr_stats_summary reads min / max / mean / median and the eyedropper's
+    // value off a copy on the host.
+    void BrushStats(const vr_brush& brush, void* d_stats, void* stream = nullptr) const
+    {
+        Check(vr_brush_stats(ctx_, &brush, d_stats, stream), "vr_brush_stats");
+    }
+    void BoxStats(int x0, int y0, int z0, int bx, int by, int bz, int channel_mask, void* d_stats,
+                  void* stream = nullptr) const
+    {
+        Check(vr_box_stats(ctx_, x0, y0, z0, bx, by, bz, channel_mask, d_stats, stream), "vr_box_stats");
+    }
     void GenerateVolume(const vr_volume_recipe& r, void* stream = nullptr)
     {
         Check(vr_generate_volume(ctx_, &r, stream), "vr_generate_volume");

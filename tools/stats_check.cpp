@@ -1,0 +1,221 @@
+// stats_check -- stand-alone host check of vr_brush_stats_host, vr_box_stats_host
+// and vr_stats_summary (volumetricrenderer_amd/csrc/vr_brush.cpp), built with
+// -fsanitize=address,undefined and run on the CPU (`make check-stats` builds and
+// runs it).  It links the brush's translation unit only: no libvr.so, no HIP,
+// no device.
+//
+// Every volume is allocated exactly, so a read outside it trips the address
+// sanitizer: 1 x 1 x 1 and 2 x 3 x 1 volumes, centres at INT32_MAX / INT32_MIN,
+// radius 0 and 255, both falloffs, every channel mask.  Each result is compared
+// with a naive restatement of vr.h: three plain loops over the WHOLE volume, the
+// ellipsoid in unsigned __int128, the sums added field by field; the summary
+// with a sorted list of the bytes the histogram stands for.
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <random>
+#include <vector>
+
+#include "vr.h"
+
+namespace {
+
+typedef unsigned __int128 u128;
+
+// include/vr.h, literally; box = nullptr: under the brush, else inside the box {x0, y0, z0, bx, by, bz}
+vr_volume_stats restate(const vr_brush* b, const int* box, unsigned mask, const std::vector<uint8_t>& v, int nx, int ny, int nz)
+{
+    vr_volume_stats s;
+    std::memset(&s, 0, sizeof s);
+    u128 D2[3] = {1, 1, 1}, S = 1;
+    if (b) {
+        for (int a = 0; a < 3; ++a) D2[a] = (u128)(2 * b->radius[a] + 1) * (u128)(2 * b->radius[a] + 1);
+        S = D2[0] * D2[1] * D2[2];
+    }
+    for (int z = 0; z < nz; ++z)
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) {
+                unsigned w = 256u;
+                if (b) {
+                    const long long d[3] = {(long long)x - b->centre[0], (long long)y - b->centre[1], (long long)z - b->centre[2]};
+                    bool in = true;
+                    for (int a = 0; a < 3; ++a) in = in && d[a] >= -(long long)b->radius[a] && d[a] <= (long long)b->radius[a];
+                    if (!in) continue;
+                    const u128 Q = (u128)(4 * d[0] * d[0]) * D2[1] * D2[2] + (u128)(4 * d[1] * d[1]) * D2[0] * D2[2] +
+                                   (u128)(4 * d[2] * d[2]) * D2[0] * D2[1];
+                    if (Q > S) continue;
+                    if (b->falloff) w = 256u - (unsigned)((256 * Q) / (S + 1));
+                } else if (x < box[0] || x >= box[0] + box[3] || y < box[1] || y >= box[1] + box[4] || z < box[2] ||
+                           z >= box[2] + box[5]) {
+                    continue;
+                }
+                const uint8_t* p = &v[(((size_t)z * ny + y) * nx + x) * 4];
+                s.count += 1;
+                s.weight += w;
+                for (int c = 0; c < 4; ++c)
+                    if (mask >> c & 1u) {
+                        s.wsum[c] += (uint64_t)w * p[c];
+                        s.hist[c][p[c]] += 1;
+                    }
+            }
+    return s;
+}
+
+vr_volume_summary restate_summary(const vr_volume_stats& s)
+{
+    vr_volume_summary o;
+    std::memset(&o, 0, sizeof o);
+    for (int c = 0; c < 4; ++c) {
+        std::vector<int> bytes;
+        for (int v = 0; v < 256; ++v) bytes.insert(bytes.end(), (size_t)s.hist[c][v], v);
+        const uint64_t n = bytes.size();
+        o.n[c] = n;
+        if (!n) continue;
+        uint64_t sum = 0;
+        for (int v : bytes) sum += (uint64_t)v;
+        o.min[c] = bytes.front();
+        o.max[c] = bytes.back();
+        o.mean[c] = (int32_t)((sum + n / 2) / n);
+        o.wmean[c] = (int32_t)((s.wsum[c] + s.weight / 2) / s.weight);
+        o.median[c] = bytes[(n + 1) / 2 - 1];
+    }
+    return o;
+}
+
+long failures = 0;
+
+void expect(bool ok, const char* what, int it)
+{
+    if (!ok && ++failures <= 10) std::fprintf(stderr, "stats_check: %s (case %d)\n", what, it);
+}
+
+bool same(const vr_volume_stats& a, const vr_volume_stats& b) { return std::memcmp(&a, &b, sizeof a) == 0; }
+
+void check_summary(const vr_volume_stats& s, int it)
+{
+    vr_volume_summary got;
+    std::memset(&got, 0x5a, sizeof got);
+    expect(vr_stats_summary(&s, &got) == VR_OK, "vr_stats_summary refused a result", it);
+    const vr_volume_summary want = restate_summary(s);
+    expect(std::memcmp(&got, &want, sizeof got) == 0, "vr_stats_summary differs from the restatement", it);
+}
+
+}  // namespace
+
+int main()
+{
+    static_assert(sizeof(vr_volume_stats) == 8240, "vr.h states the size");
+    std::mt19937_64 rng(20240711);
+    auto pick = [&](int a, int b) { return std::uniform_int_distribution<int>(a, b)(rng); };
+    long brushes = 0, missed = 0, boxes = 0, refused = 0, smooth_lighter = 0;
+    const int far[] = {INT32_MAX, INT32_MIN, INT32_MAX - 255, INT32_MIN + 255, 1 << 30, -(1 << 30)};
+    vr_volume_stats poison;
+    std::memset(&poison, 0xa5, sizeof poison);
+    for (int it = 0; it < 640; ++it) {
+        const int kind = it % 5;
+        int nx = pick(1, 14), ny = pick(1, 14), nz = pick(1, 14);
+        if (kind == 1) nx = ny = nz = 1;
+        if (kind == 2) { nx = 2; ny = 3; nz = 1; }
+        vr_brush b{};
+        for (int a = 0; a < 3; ++a) {
+            const int n = a == 0 ? nx : a == 1 ? ny : nz;
+            b.centre[a] = pick(-3, n + 2);
+            b.radius[a] = pick(0, 6);
+        }
+        if (kind == 1 || kind == 2)
+            for (int a = 0; a < 3; ++a) { b.radius[a] = it / 160 % 2 ? VR_BRUSH_MAX_RADIUS : 0; b.centre[a] = pick(0, 1); }
+        if (kind == 3)   // the largest radius around a centre up to a radius away
+            for (int a = 0; a < 3; ++a) { b.radius[a] = VR_BRUSH_MAX_RADIUS; b.centre[a] = pick(-260, 270); }
+        if (kind == 4)   // one or more axes at the ends of int32
+            for (int a = 0; a < 3; ++a)
+                if (a == it / 5 % 3 || pick(0, 2) == 0) { b.centre[a] = far[pick(0, 5)]; b.radius[a] = pick(0, 1) ? 255 : 0; }
+        b.op = pick(0, 2);   // validated, then ignored
+        b.falloff = it / 5 % 2;
+        const unsigned mask = (unsigned)(it / 10 % 16);   // every channel mask, with both falloffs
+        for (int c = 0; c < 4; ++c) { b.value[c] = (uint8_t)pick(0, 255); b.strength[c] = mask >> c & 1u ? (uint8_t)pick(1, 255) : 0; }
+        std::vector<uint8_t> vol((size_t)nx * ny * nz * 4);
+        const int flat = pick(0, 3);   // one channel in four constant: a single bin
+        for (size_t i = 0; i < vol.size(); ++i) vol[i] = (int)(i % 4) == flat && it % 4 == 0 ? 131 : (uint8_t)pick(0, 255);
+
+        vr_volume_stats got = poison;
+        const vr_volume_stats want = restate(&b, nullptr, mask, vol, nx, ny, nz);
+        expect(vr_brush_stats_host(&b, vol.data(), nx, ny, nz, &got) == VR_OK, "vr_brush_stats_host refused a valid brush", it);
+        expect(same(got, want), "vr_brush_stats_host differs from the restatement", it);
+        int o[3], e[3];
+        expect(vr_brush_box(&b, nx, ny, nz, o, e) == VR_OK, "vr_brush_box refused a valid brush", it);
+        expect(e[0] > 0 || got.count == 0, "a brush that misses the volume counted a texel", it);   // a box's corner may hold none
+        for (int c = 0; c < 4; ++c) {
+            uint64_t n = 0;
+            for (int v = 0; v < 256; ++v) n += got.hist[c][v];
+            expect(n == (mask >> c & 1u ? got.count : 0), "a channel's bins do not add up to count", it);
+        }
+        expect(b.falloff ? got.weight <= 256 * got.count && got.weight >= got.count : got.weight == 256 * got.count,
+               "weight outside its range", it);
+        smooth_lighter += b.falloff && got.weight < 256 * got.count;
+        ++(got.count ? brushes : missed);
+        check_summary(got, it);
+
+        // a box of the same volume with the same mask
+        int box[6];
+        box[0] = pick(0, nx - 1); box[1] = pick(0, ny - 1); box[2] = pick(0, nz - 1);
+        box[3] = pick(1, nx - box[0]); box[4] = pick(1, ny - box[1]); box[5] = pick(1, nz - box[2]);
+        if (it % 3 == 0) { box[0] = box[1] = box[2] = 0; box[3] = nx; box[4] = ny; box[5] = nz; }   // the whole volume
+        got = poison;
+        const vr_volume_stats bwant = restate(nullptr, box, mask, vol, nx, ny, nz);
+        expect(vr_box_stats_host(vol.data(), nx, ny, nz, box[0], box[1], box[2], box[3], box[4], box[5], (int)mask, &got) == VR_OK,
+               "vr_box_stats_host refused a valid box", it);
+        expect(same(got, bwant), "vr_box_stats_host differs from the restatement", it);
+        expect(got.count == (uint64_t)box[3] * box[4] * box[5] && got.weight == 256 * got.count, "a box's count or weight", it);
+        ++boxes;
+        check_summary(got, it);
+
+        // refusals: *out as it was
+        got = poison;
+        vr_brush bad = b;
+        switch (it % 4) {
+        case 0: bad.op = 3; break;
+        case 1: bad.falloff = 2; break;
+        case 2: bad.radius[it % 3] = 256; break;
+        default: bad.reserved[it % 2] = 1; break;
+        }
+        expect(vr_brush_stats_host(&bad, vol.data(), nx, ny, nz, &got) == VR_ERR_INVALID && same(got, poison), "a bad brush was accepted", it);
+        expect(vr_brush_stats_host(&b, vol.data(), it % 2 ? 0 : nx, ny, it % 2 ? nz : -1, &got) == VR_ERR_INVALID && same(got, poison),
+               "bad dimensions were accepted", it);
+        expect(vr_brush_stats_host(nullptr, vol.data(), nx, ny, nz, &got) == VR_ERR_INVALID &&
+                   vr_brush_stats_host(&b, nullptr, nx, ny, nz, &got) == VR_ERR_INVALID &&
+                   vr_brush_stats_host(&b, vol.data(), nx, ny, nz, nullptr) == VR_ERR_INVALID && same(got, poison),
+               "a null pointer was accepted", it);
+        expect(vr_box_stats_host(vol.data(), nx, ny, nz, 0, 0, 0, 1, 1, 1, it % 2 ? 16 : -1, &got) == VR_ERR_INVALID && same(got, poison),
+               "a bad mask was accepted", it);
+        expect(vr_box_stats_host(vol.data(), nx, ny, nz, box[0], box[1], box[2], nx - box[0] + 1, box[4], box[5], 15, &got) == VR_ERR_INVALID &&
+                   vr_box_stats_host(vol.data(), nx, ny, nz, box[0], -1, box[2], box[3], box[4], box[5], 15, &got) == VR_ERR_INVALID &&
+                   vr_box_stats_host(vol.data(), nx, ny, nz, box[0], box[1], INT32_MAX, box[3], box[4], INT32_MAX, 15, &got) == VR_ERR_INVALID &&
+                   vr_box_stats_host(vol.data(), nx, ny, nz, box[0], box[1], box[2], box[3], 0, box[5], 15, &got) == VR_ERR_INVALID &&
+                   same(got, poison),
+               "a box that leaves the volume was accepted", it);
+        refused += 5;
+    }
+    // the summary of results put together by hand: empty, one texel, two bytes (the median is the lower one), and
+    // fields near the top of 64 bits with weight 0
+    {
+        vr_volume_stats s;
+        std::memset(&s, 0, sizeof s);
+        check_summary(s, -1);
+        s.count = 2; s.weight = 512; s.hist[1][7] = 1; s.hist[1][200] = 1; s.wsum[1] = 256 * 207;
+        check_summary(s, -2);
+        vr_volume_summary o;
+        expect(vr_stats_summary(&s, &o) == VR_OK && o.median[1] == 7 && o.mean[1] == 104 && o.wmean[1] == 104 && o.n[0] == 0 &&
+                   o.min[1] == 7 && o.max[1] == 200,
+               "the summary of two bytes", -2);
+        expect(vr_stats_summary(nullptr, &o) == VR_ERR_INVALID && vr_stats_summary(&s, nullptr) == VR_ERR_INVALID, "a null summary", -3);
+        s.weight = 0; s.hist[3][255] = UINT64_MAX / 512;
+        expect(vr_stats_summary(&s, &o) == VR_OK && o.wmean[3] == 0 && o.min[3] == 255 && o.mean[3] == 255 && o.median[3] == 255,
+               "a hand-made struct with weight 0", -4);
+    }
+    expect(brushes > 300 && missed > 10 && smooth_lighter > 30, "too few cases of a kind", (int)brushes);
+    std::printf("stats_check: %ld brushes (%ld smooth ones lighter than hard), %ld missed, %ld boxes, %ld refused, %ld failures\n",
+                brushes, smooth_lighter, missed, boxes, refused, failures);
+    return failures ? 1 : 0;
+}

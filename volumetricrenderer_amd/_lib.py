@@ -134,6 +134,18 @@ class Box(ctypes.Structure):
                 ("by", ctypes.c_int32), ("bz", ctypes.c_int32)]
 
 
+class VolumeStats(ctypes.Structure):
+    """vr_volume_stats: what vr_brush_stats / vr_box_stats produce.  8240 bytes, all 64-bit words."""
+    _fields_ = [("count", ctypes.c_uint64), ("weight", ctypes.c_uint64), ("wsum", ctypes.c_uint64 * 4),
+                ("hist", (ctypes.c_uint64 * 256) * 4)]
+
+class StatsSummary(ctypes.Structure):
+    """vr_volume_summary: what vr_stats_summary reads off a vr_volume_stats, per channel.  112 bytes."""
+    _fields_ = [("n", ctypes.c_uint64 * 4), ("min", ctypes.c_int32 * 4), ("max", ctypes.c_int32 * 4),
+                ("mean", ctypes.c_int32 * 4), ("wmean", ctypes.c_int32 * 4), ("median", ctypes.c_int32 * 4)]
+
+
+VOLUME_STATS_BYTES = ctypes.sizeof(VolumeStats)   # 8240
 
 RAY_RECORD_WORDS = ctypes.sizeof(RayRecord) // 4   # a record as int32 words: query_rect's last axis
 
@@ -162,6 +174,12 @@ _SIGS = {
     "vr_blur": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.c_int, _vp]),
     "vr_brush_blur_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int]),
+    "vr_brush_stats": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, _vp]),
+    "vr_box_stats": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp, _vp]),
+    "vr_brush_stats_host": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(VolumeStats)]),
+    "vr_box_stats_host": (ctypes.c_int, [_vp] + [ctypes.c_int] * 10 + [ctypes.POINTER(VolumeStats)]),
+    "vr_stats_summary": (ctypes.c_int, [ctypes.POINTER(VolumeStats), ctypes.POINTER(StatsSummary)]),
     "vr_volume_extent_ok": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "vr_volume_recipe_defaults": (ctypes.c_int, [ctypes.POINTER(VolumeRecipe)]),
     "vr_generate_volume": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeRecipe), _vp]),

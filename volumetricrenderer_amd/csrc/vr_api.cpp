@@ -16,6 +16,7 @@
 #include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_ctx.h"
+#include "vr_stats.h"
 
 namespace vrapi {
 
@@ -781,6 +782,65 @@ try {
     return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
 } catch (...) {
     return caught_exception("vr_blur");
+}
+
+// The statistics under a brush or in a box: every check first (a refused call writes nothing), then the buffer is
+// zeroed on the stream and k_stats adds to it.  It reads c->d_planar and touches nothing else of the context.
+static vr_status stats_target(const char* fn, const Ctx* c, const void* d_stats)
+{
+    if (((uintptr_t)d_stats & 7u) != 0) return fail(VR_ERR_INVALID, "%s: d_stats is not 8-byte aligned", fn);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "%s: no volume set", fn);
+    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "%s: a procedural medium is enabled (it reads no volume)", fn);
+    return VR_OK;
+}
+
+vr_status vr_brush_stats(void* p, const vr_brush* b, void* d_stats, void* stream)
+try {
+    if (!p || !b || !d_stats) return fail(VR_ERR_INVALID, "vr_brush_stats: null argument");
+    if (const char* why = vr::brush::invalid(b)) return fail(VR_ERR_INVALID, "vr_brush_stats: %s", why);
+    Ctx* c = as_ctx(p);
+    if (vr_status st = stats_target("vr_brush_stats", c, d_stats)) return st;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(vr_volume_stats), s));
+    StatsArgs a{};
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume: all zero
+    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    a.s = t.s;
+    for (int ax = 0; ax < 3; ++ax) {
+        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
+        a.k[ax] = t.k[ax];
+    }
+    a.ellipsoid = 1;
+    a.falloff = b->falloff;
+    a.mask = vr::stats::brush_mask(b->strength);
+    HIP_TRY(launch_stats(a, c->d_planar, static_cast<vr_volume_stats*>(d_stats), s));
+    return VR_OK;
+} catch (...) {
+    return caught_exception("vr_brush_stats");
+}
+
+vr_status vr_box_stats(void* p, int x0, int y0, int z0, int bx, int by, int bz, int channel_mask, void* d_stats,
+                       void* stream)
+try {
+    if (!p || !d_stats) return fail(VR_ERR_INVALID, "vr_box_stats: null argument");
+    if (const char* why = vr::stats::invalid_mask(channel_mask)) return fail(VR_ERR_INVALID, "vr_box_stats: %s", why);
+    Ctx* c = as_ctx(p);
+    if (vr_status st = stats_target("vr_box_stats", c, d_stats)) return st;
+    if (vr_status st = check_update("vr_box_stats", p, d_stats, x0, y0, z0, bx, by, bz)) return st;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(vr_volume_stats), s));
+    StatsArgs a{};
+    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
+    a.o[0] = x0; a.o[1] = y0; a.o[2] = z0;
+    a.e[0] = bx; a.e[1] = by; a.e[2] = bz;
+    a.mask = (unsigned)channel_mask;   // ellipsoid = 0: every texel of the box, weight 256
+    HIP_TRY(launch_stats(a, c->d_planar, static_cast<vr_volume_stats*>(d_stats), s));
+    return VR_OK;
+} catch (...) {
+    return caught_exception("vr_box_stats");
 }
 
 vr_status vr_noise_grid(void* p, int kind, void* d_out, int x0, int y0, int z0, int nx, int ny, int nz,

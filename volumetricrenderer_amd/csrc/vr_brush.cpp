@@ -1,7 +1,9 @@
 // vr_brush.cpp -- vr_brush_box and vr_brush_apply: the brush of vr_paint on
 // the host (include/vr.h); vr_brush_line: the dabs of a
 // drag, for vr_paint_stroke (sec. 5.2.6); vr_brush_blur_apply: the box-filter
-// brush of vr_blur on the host (sec. 5.2.7; the mean is vr_blur.h's).
+// brush of vr_blur on the host (sec. 5.2.7; the mean is vr_blur.h's);
+// vr_brush_stats_host, vr_box_stats_host and vr_stats_summary: the statistics
+// under a brush or in a box (sec. 5.2.8; the arithmetic is vr_stats.h's).
 //
 // Pure host code in integers: no context, no device, no HIP call.  The
 // arithmetic is vr_brush.h's, which the paint kernel (vr_volume.hip) includes
@@ -14,6 +16,7 @@
 
 #include "vr_blur.h"
 #include "vr_brush.h"
+#include "vr_stats.h"
 
 #ifdef VR_BRUSH_STANDALONE
 namespace {
@@ -130,6 +133,61 @@ vr_status vr_brush_blur_apply(const vr_brush* b, int half_width, uint8_t* rgba8,
             }
         }
     }
+    return VR_OK;
+}
+
+// The statistics under the brush on the host (include/vr.h): vr_brush_apply's walk with vr_stats.h's sums in place
+// of the blend.  *out is written only once nothing can be refused any more.
+vr_status vr_brush_stats_host(const vr_brush* b, const uint8_t* rgba8, int nx, int ny, int nz, vr_volume_stats* out)
+{
+    if (!rgba8 || !out) return fail(VR_ERR_INVALID, "vr_brush_stats_host: null argument");
+    if (vr_status st = check("vr_brush_stats_host", b, nx, ny, nz)) return st;
+    *out = vr_volume_stats{};
+    int o[3], e[3];
+    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    const unsigned mask = vr::stats::brush_mask(b->strength);
+    for (int z = o[2]; z < o[2] + e[2]; ++z) {
+        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
+        for (int y = o[1]; y < o[1] + e[1]; ++y) {
+            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
+            if (qyz > t.s) continue;
+            const uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
+            for (int x = o[0]; x < o[0] + e[0]; ++x) {
+                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
+                const unsigned w = vr::stats::texel_weight(1, q, t.s, b->falloff);
+                if (w) vr::stats::add_texel(out, mask, w, row + (size_t)x * 4);
+            }
+        }
+    }
+    return VR_OK;
+}
+
+// The same over a texel box: every texel counts, with the hard edge's weight.
+vr_status vr_box_stats_host(const uint8_t* rgba8, int nx, int ny, int nz, int x0, int y0, int z0, int bx, int by, int bz,
+                            int channel_mask, vr_volume_stats* out)
+{
+    if (!rgba8 || !out) return fail(VR_ERR_INVALID, "vr_box_stats_host: null argument");
+    if (nx <= 0 || ny <= 0 || nz <= 0) return fail(VR_ERR_INVALID, "vr_box_stats_host: bad extent %dx%dx%d", nx, ny, nz);
+    if (bx <= 0 || by <= 0 || bz <= 0) return fail(VR_ERR_INVALID, "vr_box_stats_host: bad box extent %dx%dx%d", bx, by, bz);
+    if (x0 < 0 || y0 < 0 || z0 < 0 || bx > nx - x0 || by > ny - y0 || bz > nz - z0)
+        return fail(VR_ERR_INVALID, "vr_box_stats_host: box %dx%dx%d at (%d, %d, %d) leaves the %dx%dx%d volume", bx, by, bz,
+                    x0, y0, z0, nx, ny, nz);
+    if (const char* why = vr::stats::invalid_mask(channel_mask)) return fail(VR_ERR_INVALID, "vr_box_stats_host: %s", why);
+    *out = vr_volume_stats{};
+    for (int z = z0; z < z0 + bz; ++z)
+        for (int y = y0; y < y0 + by; ++y) {
+            const uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
+            for (int x = x0; x < x0 + bx; ++x)
+                vr::stats::add_texel(out, (unsigned)channel_mask, vr::stats::texel_weight(0, 0, 0, 0), row + (size_t)x * 4);
+        }
+    return VR_OK;
+}
+
+vr_status vr_stats_summary(const vr_volume_stats* s, vr_volume_summary* out)
+{
+    if (!s || !out) return fail(VR_ERR_INVALID, "vr_stats_summary: null argument");
+    vr::stats::summary(s, out);
     return VR_OK;
 }
 

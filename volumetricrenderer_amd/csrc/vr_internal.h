@@ -613,6 +613,19 @@ hipError_t launch_paint_stroke(const StrokeArgs& a, uint8_t* d_planar, unsigned*
 size_t blur_stage_bytes(const PaintArgs& a);
 hipError_t launch_blur_stage(const PaintArgs& a, int half_width, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s);
 hipError_t launch_blur_commit(const PaintArgs& a, const uint8_t* d_stage, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+// vr_brush_stats / vr_box_stats: a texel box inside the volume and, for a brush
+// (ellipsoid != 0), the ellipsoid as in PaintArgs; for a box d0, s and k are not read.
+struct StatsArgs {
+    int nx, ny, nz;
+    int o[3], e[3];               // the box: origin and extent (e > 0)
+    int d0[3];                    // o - centre, per axis
+    int ellipsoid, falloff;
+    unsigned mask;                // bit c set = channel c is selected
+    unsigned long long s, k[3];   // vr_brush.h Terms of the radii
+};
+// Add the statistics of the box's inside texels to *d_stats (k_stats): the caller has zeroed it on `s`.  Reads the
+// planes, writes nothing else.
+hipError_t launch_stats(const StatsArgs& a, const uint8_t* d_planar, vr_volume_stats* d_stats, hipStream_t s);
 // true for the layouts launch_build_layout_box rebuilds over the box; the others it rebuilds whole
 bool layout_rebuilds_box(int layout);
 // Perlin lattice table: entry (x, y, z) - lo of n^3 = noise::perlin_lattice_entry(seed, x, y, z)

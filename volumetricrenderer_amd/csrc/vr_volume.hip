@@ -7,12 +7,14 @@
 // All are HBM-bound streaming kernels: wide coalesced accesses, grid-stride.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 
 #include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_internal.h"
 #include "vr_noise.h"
+#include "vr_stats.h"
 
 namespace vr {
 namespace {
@@ -401,6 +403,104 @@ __global__ __launch_bounds__(kBlock) void k_blur_commit(PaintArgs a, const uint8
         }
     }
     fold_minmax(lo, hi, mm);
+}
+
+// vr_brush_stats / vr_box_stats: the statistics of the
+// texels of a box that lie inside the brush (or, ellipsoid == 0, of all of
+// them) added to *out, which the caller has zeroed.  It reads the planes and
+// writes *out, nothing else.  The arithmetic is vr_stats.h's, in integers:
+// adds commute, so neither the order of the workgroups nor the grid matters.
+//
+// Rows and lanes are k_paint_planar's: a wave takes a box row (y, z) at a
+// time, consecutive lanes on consecutive x; a row outside the ellipsoid is
+// left before any load; byte loads, the plane rows start at any byte.  The x
+// loop's trip count is the wave's, not the lane's, so the ballots below see
+// every lane.
+//  * histogram: 4 x 256 32-bit bins per workgroup in LDS, added to with LDS
+//    atomics.  A workgroup sees fewer texels than a plane holds (< 2^31,
+//    dims_ok), so a bin cannot overflow.  64 lanes on one bin serialise, and
+//    that is the common case (a uniform channel, any smooth region): per
+//    channel the wave takes its first inside lane's byte, ballots the inside
+//    lanes that hold the same byte, and that first lane adds their number in
+//    ONE atomic while only the lanes holding another byte add 1 each -- one
+//    ds_add instruction either way, with a single active lane when the row
+//    segment is constant.
+//  * count, weight, wsum[c]: 64-bit per lane, reduced over the wave with
+//    shuffles and over the workgroup through LDS.
+// After one barrier the workgroup adds its non-zero bins and sums to *out
+// with 64-bit global atomics: at most 1030 per workgroup.
+constexpr int kStatsMaxGrid = 1024;   // workgroups: bounds the flush at 1024 x 1030 atomics (launch_stats)
+
+__global__ __launch_bounds__(kBlock) void k_stats(StatsArgs a, const uint8_t* __restrict__ src,
+                                                  vr_volume_stats* __restrict__ out)
+{
+    constexpr unsigned kWaves = kBlock / 64;
+    __shared__ unsigned bins[4 * 256];
+    __shared__ unsigned long long red[kWaves][6];
+    for (int i = threadIdx.x; i < 4 * 256; i += kBlock) bins[i] = 0u;
+    __syncthreads();
+
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned rows = (unsigned)a.e[1] * (unsigned)a.e[2];   // < 2^31 (inside the volume)
+    unsigned long long sum[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};   // count, weight, wsum[4]
+    for (unsigned r = blockIdx.x * kWaves + wave; r < rows; r += gridDim.x * kWaves) {
+        const int z = (int)(r / (unsigned)a.e[1]), y = (int)(r - (unsigned)z * (unsigned)a.e[1]);
+        unsigned long long qyz = 0ull;
+        if (a.ellipsoid) {
+            qyz = brush::axis_term(a.d0[1] + y, a.k[1]) + brush::axis_term(a.d0[2] + z, a.k[2]);
+            if (qyz > a.s) continue;
+        }
+        const uint8_t* __restrict__ row = src + ((long long)(a.o[2] + z) * a.ny + (a.o[1] + y)) * a.nx + a.o[0];
+        for (int x0 = 0; x0 < a.e[0]; x0 += 64) {
+            const int x = x0 + lane;
+            unsigned w = 0u;   // 0 = this lane's texel does not count
+            if (x < a.e[0])
+                w = stats::texel_weight(a.ellipsoid, a.ellipsoid ? qyz + brush::axis_term(a.d0[0] + x, a.k[0]) : 0ull,
+                                        a.s, a.falloff);
+            const bool in = w != 0u;
+            const unsigned long long act = __ballot(in);
+            if (act == 0ull) continue;
+            const int first = __builtin_amdgcn_readfirstlane(__ffsll((long long)act) - 1);
+            sum[0] += in ? 1ull : 0ull;
+            sum[1] += w;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (!stats::selected(a.mask, c)) continue;
+                unsigned v = 0u;
+                if (in) v = row[x + c * plane];
+                sum[2 + c] += stats::wsum_term(w, v);
+                const unsigned head = (unsigned)__builtin_amdgcn_readlane((int)v, first);
+                const unsigned long long same = __ballot(in && v == head);
+                if (in && (lane == first || v != head))
+                    atomicAdd(&bins[c * 256 + (int)v], lane == first ? (unsigned)__popcll(same) : 1u);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        for (int off = 32; off > 0; off >>= 1) sum[k] += __shfl_xor(sum[k], off);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) red[wave][k] = sum[k];
+    }
+    __syncthreads();
+    // *out as its 1030 64-bit words: count, weight, wsum[4], hist[4][256]
+    static_assert(sizeof(vr_volume_stats) == 8 * (6 + 4 * 256) && offsetof(vr_volume_stats, hist) == 48 &&
+                      offsetof(vr_volume_stats, wsum) == 16 && sizeof(unsigned long long) == 8,
+                  "vr_volume_stats is 1030 packed 64-bit words");
+    unsigned long long* __restrict__ words = reinterpret_cast<unsigned long long*>(out);
+    for (int i = threadIdx.x; i < 4 * 256; i += kBlock) {
+        const unsigned n = bins[i];
+        if (n != 0u) atomicAdd(&words[6 + i], (unsigned long long)n);
+    }
+    if (threadIdx.x < 6) {
+        const int k = threadIdx.x;
+        unsigned long long v = red[0][k];
+        for (unsigned wv = 1; wv < kWaves; ++wv) v += red[wv][k];
+        if (v != 0ull) atomicAdd(&words[k], v);
+    }
 }
 
 // vr_get_volume_box: the planes' texel box -> tightly packed RGBA8 (what
@@ -1014,6 +1114,17 @@ hipError_t launch_blur_commit(const PaintArgs& a, const uint8_t* d_stage, uint8_
 {
     const long long rows = (long long)a.e[1] * a.e[2];
     hipLaunchKernelGGL(k_blur_commit, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a, d_stage, d_planar, mm);
+    return hipGetLastError();
+}
+
+// a wave per box row, a workgroup per kBlock / 64 rows, grid-stride past kStatsMaxGrid workgroups: every workgroup
+// ends in up to 1030 global atomics, which the cap bounds whatever the box
+hipError_t launch_stats(const StatsArgs& a, const uint8_t* d_planar, vr_volume_stats* d_stats, hipStream_t s)
+{
+    if (a.e[0] < 1 || a.e[1] < 1 || a.e[2] < 1 || !d_planar || !d_stats) return hipErrorInvalidValue;
+    const long long rows = (long long)a.e[1] * a.e[2];
+    const long long g = std::min<long long>((rows + kBlock / 64 - 1) / (kBlock / 64), kStatsMaxGrid);
+    hipLaunchKernelGGL(k_stats, dim3((unsigned)g), dim3(kBlock), 0, s, a, d_planar, d_stats);
     return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@ libvr.so, and a missing library raises at import.  Errors are raised as
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -35,6 +36,7 @@ from . import _lib
 from ._lib import (BRUSH_ADD, BRUSH_SET, BRUSH_SUB, BYTES_PER_PIXEL, CHANNELS, FLOAT_FORMATS, FMT_RGBA8_SRGB,  # noqa: F401
                    FMT_RGBA8_UNORM, FMT_RGBA32F, Brush, GREY_OF, RAY_RECORD_WORDS, GlobalShaderData, MarchParams, ObjectShaderData, Procedural, RayRecord,
                    Rect, Target, VolumeRecipe, VR_MAX_RECTS, VRError, call)
+from ._lib import VOLUME_STATS_BYTES, StatsSummary, VolumeStats
 
 _lib.load()  # fail at import if the HIP library is missing
 
@@ -207,6 +209,95 @@ def brush_blur_apply(brush: Brush, half_width: int, rgba: np.ndarray) -> np.ndar
     nz, ny, nx, _ = rgba.shape
     call("vr_brush_blur_apply", ctypes.byref(brush), int(half_width), rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz)
     return rgba
+
+
+class Stats(NamedTuple):
+    """A vr_volume_stats on the host: `count` and `weight` as ints, `wsum` (4,) and
+    `hist` (4, 256) as uint64 arrays."""
+    count: int
+    weight: int
+    wsum: np.ndarray
+    hist: np.ndarray
+
+
+class Summary(NamedTuple):
+    """vr_stats_summary's result: per channel, (4,) int64 arrays."""
+    n: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    mean: np.ndarray
+    wmean: np.ndarray
+    median: np.ndarray
+
+
+def unpack_stats(buf) -> Stats:
+    """The :class:`Stats` in a vr_volume_stats given as a :class:`VolumeStats`, or as
+    its 8240 bytes in a uint8 numpy array or tensor (a CUDA tensor is copied to
+    the host, which waits for the work queued before the copy on the current
+    stream)."""
+    if isinstance(buf, VolumeStats):
+        words = np.frombuffer(bytes(buf), np.uint64)
+    else:
+        if isinstance(buf, torch.Tensor):
+            buf = buf.cpu().numpy()
+        if not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 or buf.size != VOLUME_STATS_BYTES:
+            raise ValueError(f"unpack_stats: a VolumeStats or {VOLUME_STATS_BYTES} uint8 bytes")
+        words = np.ascontiguousarray(buf).reshape(-1).view(np.uint64)
+    return Stats(int(words[0]), int(words[1]), words[2:6].copy(), words[6:].reshape(4, 256).copy())
+
+
+def _pack_stats(stats) -> VolumeStats:
+    if isinstance(stats, VolumeStats):
+        return stats
+    if not isinstance(stats, Stats):
+        stats = unpack_stats(stats)
+    s = VolumeStats()
+    words = np.concatenate([np.array([stats.count, stats.weight], np.uint64), np.asarray(stats.wsum, np.uint64).reshape(4),
+                            np.asarray(stats.hist, np.uint64).reshape(1024)])
+    ctypes.memmove(ctypes.byref(s), words.ctypes.data, VOLUME_STATS_BYTES)
+    return s
+
+
+def _host_volume(fn: str, rgba) -> tuple:
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous):
+        raise ValueError(f"{fn}: a contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    return nx, ny, nz
+
+
+def brush_stats_host(brush: Brush, rgba: np.ndarray) -> Stats:
+    """vr_brush_stats_host: the statistics of a host RGBA8 volume shaped
+    (nz, ny, nx, 4) under the brush -- the inside texels and their weights are
+    :func:`brush_apply`'s, a channel is selected iff its strength is not 0, `op`
+    and `value` are not used.  The CPU statement of :meth:`Renderer.brush_stats`."""
+    nx, ny, nz = _host_volume("brush_stats_host", rgba)
+    s = VolumeStats()
+    call("vr_brush_stats_host", ctypes.byref(brush), rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz, ctypes.byref(s))
+    return unpack_stats(s)
+
+
+def box_stats_host(rgba: np.ndarray, origin, extent, channels: int = 0xF) -> Stats:
+    """vr_box_stats_host: the statistics of the texel box `extent` = (bx, by, bz)
+    at `origin` = (x0, y0, z0) of a host RGBA8 volume shaped (nz, ny, nx, 4);
+    bit c of `channels` selects channel c.  The CPU statement of
+    :meth:`Renderer.box_stats`."""
+    nx, ny, nz = _host_volume("box_stats_host", rgba)
+    s = VolumeStats()
+    call("vr_box_stats_host", rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz, *(int(v) for v in origin),
+         *(int(v) for v in extent), int(channels), ctypes.byref(s))
+    return unpack_stats(s)
+
+
+def stats_summary(stats) -> Summary:
+    """vr_stats_summary: per channel the number of texels counted, the lowest and
+    highest byte, the rounded mean, the weighted mean (the eyedropper's value:
+    ``value=summary.wmean`` for the next paint) and the median -- all 0 for a
+    channel with nothing counted.  `stats` is a :class:`Stats`, a
+    :class:`VolumeStats` or whatever :func:`unpack_stats` takes."""
+    s, out = _pack_stats(stats), StatsSummary()
+    call("vr_stats_summary", ctypes.byref(s), ctypes.byref(out))
+    return Summary(*(np.array(list(getattr(out, k)), np.int64) for k in Summary._fields))
 
 
 def _brush_copy(b: Brush) -> Brush:
@@ -396,6 +487,51 @@ class Renderer:
         if stream is None:
             torch.cuda.current_stream().synchronize()
         return brush_box(b, self.volume_dims())
+
+    def _stats_out(self, fn: str, out):
+        if out is None:
+            return torch.empty(VOLUME_STATS_BYTES, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != self.device
+                or out.dtype != torch.uint8 or out.numel() != VOLUME_STATS_BYTES or not out.is_contiguous()):
+            raise ValueError(f"{fn}: out must be a contiguous uint8 tensor of {VOLUME_STATS_BYTES} bytes on cuda:{self.device}")
+        return out
+
+    def brush_stats(self, centre, radius, falloff: int = 0, strength=(255, 255, 255, 255), stream=None, out=None):
+        """What is in the installed volume under an ellipsoidal brush
+        (vr_brush_stats): the number of inside texels, the sum of their weights
+        and, per channel with a non-zero strength, the weighted byte sum and
+        the 256-bin histogram -- bit for bit what :func:`brush_stats_host`
+        gives on the host.  The brush is :meth:`paint`'s; nothing is written
+        but the result.  Without `out`: a :class:`Stats` on the host, after a
+        synchronise of `stream` (default: the current stream).  With `out`, a
+        CUDA uint8 tensor of 8240 bytes (8-byte aligned): the call is queued on
+        `stream`, nothing waits and `out` is returned -- :func:`unpack_stats`
+        reads it later, :func:`stats_summary` gives min / max / mean / median
+        and the eyedropper's value."""
+        b = make_brush(centre, radius, BRUSH_SET, falloff, 0, strength)
+        buf = self._stats_out("brush_stats", out)
+        call("vr_brush_stats", self._ctx, ctypes.byref(b), ctypes.c_void_p(buf.data_ptr()), _stream_handle(stream))
+        return buf if out is not None else self._stats_host(buf, stream)
+
+    def box_stats(self, origin, extent, channels: int = 0xF, stream=None, out=None):
+        """The same over the texel box `extent` = (bx, by, bz) at `origin` =
+        (x0, y0, z0) (vr_box_stats): every texel counts with weight 256; bit c
+        of `channels` selects channel c.  ``box_stats((0, 0, 0),
+        volume_dims())`` with min == max in its summary says a channel is
+        constant again.  `stream` and `out` as for :meth:`brush_stats`."""
+        buf = self._stats_out("box_stats", out)
+        call("vr_box_stats", self._ctx, *(int(v) for v in origin), *(int(v) for v in extent), int(channels),
+             ctypes.c_void_p(buf.data_ptr()), _stream_handle(stream))
+        return buf if out is not None else self._stats_host(buf, stream)
+
+    @staticmethod
+    def _stats_host(buf, stream) -> Stats:
+        s = torch.cuda.current_stream() if stream is None else stream
+        if isinstance(s, torch.cuda.Stream):
+            s.synchronize()
+        else:
+            torch.cuda.synchronize()
+        return unpack_stats(buf)
 
     def get_volume_box(self, origin, extent, out=None, stream=None):
         """The texel box `extent` = (bx, by, bz) at `origin` = (x0, y0, z0) of the
