@@ -409,6 +409,55 @@ vr_status vr_blur(void* ctx, const vr_brush* brush, int half_width, void* stream
  * code.  VR_ERR_INVALID as above, and for a non-positive dimension.         */
 vr_status vr_brush_blur_apply(const vr_brush* brush, int half_width, uint8_t* rgba8, int nx, int ny, int nz);
 
+/* The grow / shrink brush: erode and dilate under the brush (DESIGN.md sec.
+ * 5.2.9).  vr_morph is a VR_BRUSH_SET brush whose value, per texel and
+ * channel, is the MINIMUM (VR_MORPH_ERODE) or the MAXIMUM (VR_MORPH_DILATE) of
+ * that channel over the texel's neighbourhood AS IT WAS BEFORE THE CALL.  In
+ * integers, with h = half_width in 1..VR_MORPH_MAX_HALF: for a texel t inside
+ * the ellipsoid and the volume (the inside test and the weight w are the
+ * brush's, above) and a channel c with strength[c] != 0,
+ *   m   = the minimum / maximum of channel c over the (2h + 1)^3 texels at
+ *         offsets -h..h per axis from t, coordinates clamped to the volume
+ *         (clamp-to-edge); neighbours outside the brush's box are read like
+ *         any other
+ *   new = (old (65280 - a) + m a + 32640) / 65280,  a = w * strength[c]
+ * -- the SET blend, unchanged.  brush->op must be VR_BRUSH_SET; brush->value
+ * is not read.  The structuring element is the CUBE, not a ball, because the
+ * extremum over a cube is separable: the extremum over z of the extremum over
+ * y of the extremum over x, all of them bytes.  Every extremum is taken over
+ * the bytes before the call, whatever the order in which texels are processed
+ * (a Jacobi step, not an in-place sweep), so the result is deterministic and
+ * the host statement and the device agree bit for bit.  A channel whose texels
+ * are all equal has m = old everywhere: a morph never breaks a uniform
+ * channel.
+ *
+ * Device path: vr_blur's -- a stage launch from the planes to the context's
+ * staging scratch, vr_blur's commit launch, the layout rebuild over the
+ * clipped box (vr_brush_box names it) and the uniform-channel re-arm.
+ * vr_morph and vr_blur SHARE the scratch: the need is the same (one byte per
+ * texel of the clipped box and painted channel), so are the growth rule
+ * (device synchronisation, whole MiB, VR_ERR_OOM holds nothing and leaves the
+ * volume untouched) and option "blur_scratch_kib", which reserves, frees and
+ * reports it for both.  Every call within what is held allocates nothing and
+ * never waits on the host, so pick -> vr_morph -> vr_update_footprint ->
+ * vr_render_rect queue on one stream.  Two vr_morph / vr_blur calls of one ctx
+ * on DIFFERENT streams share the scratch: they are the caller's to order.
+ * VR_ERR_INVALID: a null pointer, anything vr_paint refuses, brush->op other
+ * than VR_BRUSH_SET, op outside vr_morph_op, half_width outside
+ * 1..VR_MORPH_MAX_HALF; VR_ERR_NO_VOLUME before an install and while a
+ * procedural medium is enabled.  A brush that misses the volume, or whose
+ * strengths are all 0, is VR_OK and launches nothing.  A refused call has
+ * launched nothing and leaves the volume untouched.                         */
+typedef enum { VR_MORPH_ERODE = 0, VR_MORPH_DILATE = 1 } vr_morph_op;
+#define VR_MORPH_MAX_HALF 3
+vr_status vr_morph(void* ctx, const vr_brush* brush, int op, int half_width, void* stream);
+/* The same on a HOST RGBA8 volume (x fastest): the CPU statement, which
+ * vr_morph reproduces bit for bit.  It works from a copy of the clipped box
+ * and its halo, never in place.  Pure host code.  VR_ERR_INVALID as above, and
+ * for a non-positive dimension; a refused call leaves the array as it was.  */
+vr_status vr_brush_morph_apply(const vr_brush* brush, int op, int half_width,
+                               uint8_t* rgba8, int nx, int ny, int nz);
+
 /* The read side of the brush: what is in the volume under it (DESIGN.md sec.
  * 5.2.8) -- the eyedropper, a histogram panel, and the answer to "has this
  * channel become constant again?".  Everything is an integer sum, so the

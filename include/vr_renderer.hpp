@@ -70,6 +70,13 @@ inline void BrushBlurApply(const vr_brush& brush, int half_width, uint8_t* rgba,
     Check(vr_brush_blur_apply(&brush, half_width, rgba, nx, ny, nz), "vr_brush_blur_apply");
 }
 
+// The erode / dilate brush on a host RGBA8 volume (vr_brush_morph_apply): the
+// CPU statement of Renderer::Morph.  Host code only.
+inline void BrushMorphApply(const vr_brush& brush, int op, int half_width, uint8_t* rgba, int nx, int ny, int nz)
+{
+    Check(vr_brush_morph_apply(&brush, op, half_width, rgba, nx, ny, nz), "vr_brush_morph_apply");
+}
+
 // The dabs of a drag from brush.centre to the texel `to`, at most `spacing`
 // texels apart (vr_brush_line): what Renderer::PaintStroke takes.  skip_first
 // omits the dab on the brush's own centre, the joint of two segments.  Host
@@ -127,6 +134,15 @@ public:
     void Blur(const vr_brush& brush, int half_width = 1, void* stream = nullptr)
     {
         Check(vr_blur(ctx_, &brush, half_width, stream), "vr_blur");
+    }
+    // Grow or shrink the installed volume under the brush (vr_morph): a SET
+    // brush whose value is the minimum (VR_MORPH_ERODE) or maximum
+    // (VR_MORPH_DILATE) of each texel's (2 half_width + 1)^3 cube as it was
+    // before the call; brush.op must be VR_BRUSH_SET.  Queued on `stream` as
+    // Blur is, through the same staging scratch.
+    void Morph(const vr_brush& brush, int op, int half_width = 1, void* stream = nullptr)
+    {
+        Check(vr_morph(ctx_, &brush, op, half_width, stream), "vr_morph");
     }
     // The read-back counterpart of UpdateVolume (vr_get_volume_box): save a
     // box, Paint, UpdateVolume the saved box -- undo.

@@ -11,6 +11,8 @@ from ._lib import VR_MAX_RECTS, Procedural, RayRecord, Rect  # noqa: F401
 from ._lib import BLUR_MAX_HALF, BRUSH_ADD, BRUSH_MAX_RADIUS, BRUSH_SET, BRUSH_SUB, VR_MAX_DABS, Box, Brush  # noqa: F401
 from ._lib import VOLUME_STATS_BYTES, StatsSummary, VolumeStats  # noqa: F401
 from .renderer import Stats, Summary, box_stats_host, brush_stats_host, stats_summary, unpack_stats  # noqa: F401
+from ._lib import MORPH_DILATE, MORPH_ERODE, MORPH_MAX_HALF  # noqa: F401
+from .renderer import brush_morph_apply  # noqa: F401
 from .renderer import brush_apply, brush_blur_apply, brush_box, brush_line, coalesce_boxes, make_brush  # noqa: F401
 from .renderer import (RAY_RECORD_DTYPE, Renderer, band_rows_packed, coalesce_rects, march_defaults,  # noqa: F401
                        procedural_defaults, ray_records, reference_shader_data, scaled_recipe, shader_data_arrays,
@@ -24,6 +26,7 @@ __all__ = [
     "Rect", "volume_box_footprint", "coalesce_rects", "VR_MAX_RECTS", "RayRecord", "RAY_RECORD_DTYPE", "ray_records",
     "Brush", "BRUSH_SET", "BRUSH_ADD", "BRUSH_SUB", "BRUSH_MAX_RADIUS", "make_brush", "brush_box", "brush_apply",
     "brush_line", "coalesce_boxes", "VR_MAX_DABS", "Box", "brush_blur_apply", "BLUR_MAX_HALF",
+    "brush_morph_apply", "MORPH_ERODE", "MORPH_DILATE", "MORPH_MAX_HALF",
     "VolumeStats", "StatsSummary", "VOLUME_STATS_BYTES", "Stats", "Summary", "brush_stats_host", "box_stats_host",
     "stats_summary", "unpack_stats",
 ]

@@ -126,6 +126,8 @@ BRUSH_SET, BRUSH_ADD, BRUSH_SUB = 0, 1, 2   # vr.h vr_brush_op
 BRUSH_MAX_RADIUS = 255                      # vr.h VR_BRUSH_MAX_RADIUS
 VR_MAX_DABS = 64                            # vr.h: the longest list vr_paint_stroke takes
 BLUR_MAX_HALF = 3                           # vr.h VR_BLUR_MAX_HALF: the widest box filter of vr_blur (7 texels)
+MORPH_ERODE, MORPH_DILATE = 0, 1            # vr.h vr_morph_op
+MORPH_MAX_HALF = 3                          # vr.h VR_MORPH_MAX_HALF: the widest cube of vr_morph (7 texels)
 
 
 class Box(ctypes.Structure):
@@ -174,6 +176,9 @@ _SIGS = {
     "vr_blur": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.c_int, _vp]),
     "vr_brush_blur_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int]),
+    "vr_morph": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, _vp]),
+    "vr_brush_morph_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int]),
     "vr_brush_stats": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, _vp]),
     "vr_box_stats": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp, _vp]),
     "vr_brush_stats_host": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -16,6 +16,7 @@
 #include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_ctx.h"
+#include "vr_morph.h"
 #include "vr_stats.h"
 
 namespace vrapi {
@@ -782,6 +783,39 @@ try {
     return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
 } catch (...) {
     return caught_exception("vr_blur");
+}
+
+// The erode / dilate brush on the device: vr_blur's sequence with k_morph_stage as the first launch.  The staging
+// scratch is the blur's (same need, same growth rule, same option).
+vr_status vr_morph(void* p, const vr_brush* b, int op, int half_width, void* stream)
+try {
+    if (!p || !b) return fail(VR_ERR_INVALID, "vr_morph: null argument");
+    if (const char* why = vr::morph::invalid(b, op, half_width)) return fail(VR_ERR_INVALID, "vr_morph: %s", why);
+    Ctx* c = as_ctx(p);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_morph: no volume set");
+    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_morph: a procedural medium is enabled (it reads no volume)");
+    PaintArgs a{};
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
+    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    a.s = t.s;
+    for (int ax = 0; ax < 3; ++ax) {
+        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
+        a.k[ax] = t.k[ax];
+    }
+    a.op = VR_BRUSH_SET;
+    a.falloff = b->falloff;
+    for (int ch = 0; ch < 4; ++ch) a.strength[ch] = b->strength[ch];   // value is not read
+    const size_t need = blur_stage_bytes(a);
+    if (need == 0) return VR_OK;   // every strength is 0: nothing is read or written
+    if (vr_status st = ensure_blur(c, need)) return st;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(launch_morph_stage(a, op, half_width, c->d_planar, c->d_blur, s));
+    HIP_TRY(launch_blur_commit(a, c->d_blur, c->d_planar, c->d_mm, s));
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+} catch (...) {
+    return caught_exception("vr_morph");
 }
 
 // The statistics under a brush or in a box: every check first (a refused call writes nothing), then the buffer is

@@ -613,6 +613,10 @@ hipError_t launch_paint_stroke(const StrokeArgs& a, uint8_t* d_planar, unsigned*
 size_t blur_stage_bytes(const PaintArgs& a);
 hipError_t launch_blur_stage(const PaintArgs& a, int half_width, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s);
 hipError_t launch_blur_commit(const PaintArgs& a, const uint8_t* d_stage, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+// vr_morph: launch_blur_stage's contract and slabs with the minimum (op VR_MORPH_ERODE) or
+// maximum (VR_MORPH_DILATE) over the cube as the value; launch_blur_commit follows it.
+hipError_t launch_morph_stage(const PaintArgs& a, int op, int half_width, const uint8_t* d_planar, uint8_t* d_stage,
+                              hipStream_t s);
 // vr_brush_stats / vr_box_stats: a texel box inside the volume and, for a brush
 // (ellipsoid != 0), the ellipsoid as in PaintArgs; for a box d0, s and k are not read.
 struct StatsArgs {

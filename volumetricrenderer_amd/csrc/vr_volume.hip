@@ -13,6 +13,7 @@
 #include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_internal.h"
+#include "vr_morph.h"
 #include "vr_noise.h"
 #include "vr_stats.h"
 
@@ -403,6 +404,223 @@ __global__ __launch_bounds__(kBlock) void k_blur_commit(PaintArgs a, const uint8
         }
     }
     fold_minmax(lo, hi, mm);
+}
+
+// vr_morph, first launch: k_blur_stage's contract --
+// the planes read only, the new byte of every inside texel to the staging
+// slabs in the same shape, so k_blur_commit follows unchanged -- with the
+// minimum (erode) or maximum (dilate) over the (2H + 1)^3 cube as the value.
+//
+// Every partial result is a byte, so the kernel works on dwords of four
+// adjacent x throughout.  A dword is split once into its even and its odd
+// bytes, each pair in the 16-bit halves of a register (Quad), and the extremum
+// of two Quads is two packed 16-bit instructions for four texels.  Min and max
+// are idempotent, so a window is covered by overlapping parts: pairs, pairs of
+// pairs, and two of those (morph_window) -- 2, 3, 3 extrema per output for
+// W = 3, 5, 7.
+//
+// The tile is k_blur_stage's, kMorphTX x kMorphTY x kMorphTZ = 32 x 8 x 8;
+// thread t owns the four x of dword t % 8 in row t / 8 % 8 at the two z of its
+// wave (t / 64).  A tile with no texel inside leaves before any load.  Per
+// painted channel:
+//  1. tile and halo, coordinates clamped to the volume, from the plane to LDS:
+//     four byte loads and ONE dword store per lane (the plane rows start at
+//     any byte);
+//  2. the owners take their old bytes into registers; x: a lane per dword of a
+//     staged row reads the NW dwords that hold its 4 + 2H bytes and stores the
+//     four extrema as one dword -- the pairs of even bytes (2k, 2k + 2) and of
+//     odd bytes (2k + 1, 2k + 3) are the operands, 2H + 1 packed extrema;
+//  3. y: a lane per (dword, z row, half of the tile's y) reads 4 + 2H dwords
+//     down the column and stores four; the result overwrites the staged tile,
+//     which nothing reads any more;
+//  4. z: the owner reads 2 + 2H dwords down its column, blends (the brush's
+//     SET blend) and stores the new bytes of its inside texels: one dword
+//     where all four are inside and the address allows it, else bytes.
+// The z pitch of both partial arrays is padded by 8 dwords: the four z rows
+// that a 32-lane group of step 3 touches then fall on different banks.
+constexpr int kMorphTX = 32, kMorphTY = 8, kMorphTZ = 8;
+constexpr int kMorphQ = kMorphTX / 4;   // dwords per tile row
+static_assert(kMorphQ * kMorphTY * (kMorphTZ / 2) == kBlock && kMorphTY % 4 == 0, "a thread per dword and z pair of the tile");
+
+typedef unsigned short morph_u16x2 __attribute__((ext_vector_type(2)));
+struct Quad {
+    morph_u16x2 e, o;   // bytes 0, 2 and bytes 1, 3 of a dword
+};
+
+template <bool DILATE>
+__device__ __forceinline__ morph_u16x2 morph_ext(morph_u16x2 a, morph_u16x2 b)
+{
+    return DILATE ? __builtin_elementwise_max(a, b) : __builtin_elementwise_min(a, b);
+}
+template <bool DILATE>
+__device__ __forceinline__ uint32_t morph_ext(uint32_t a, uint32_t b)   // two 16-bit lanes in a dword
+{
+    return __builtin_bit_cast(uint32_t, morph_ext<DILATE>(__builtin_bit_cast(morph_u16x2, a), __builtin_bit_cast(morph_u16x2, b)));
+}
+template <bool DILATE>
+__device__ __forceinline__ Quad morph_ext(Quad a, Quad b)
+{
+    return Quad{morph_ext<DILATE>(a.e, b.e), morph_ext<DILATE>(a.o, b.o)};
+}
+__device__ __forceinline__ Quad morph_split(uint32_t v)
+{
+    return Quad{__builtin_bit_cast(morph_u16x2, v & 0x00ff00ffu), __builtin_bit_cast(morph_u16x2, (v >> 8) & 0x00ff00ffu)};
+}
+__device__ __forceinline__ uint32_t morph_join(Quad q)
+{
+    return __builtin_bit_cast(uint32_t, q.e) | (__builtin_bit_cast(uint32_t, q.o) << 8);
+}
+
+// out[j] = the extremum of in[j .. j + W - 1], W = 3, 5 or 7
+template <int W, int N, bool DILATE>
+__device__ __forceinline__ void morph_window(const Quad (&in)[N + W - 1], Quad (&out)[N])
+{
+    constexpr int L = N + W - 1;
+    Quad m2[L - 1];
+#pragma unroll
+    for (int j = 0; j < L - 1; ++j) m2[j] = morph_ext<DILATE>(in[j], in[j + 1]);
+    if constexpr (W < 4) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) out[j] = morph_ext<DILATE>(m2[j], m2[j + W - 2]);
+    } else {
+        Quad m4[L - 3];
+#pragma unroll
+        for (int j = 0; j < L - 3; ++j) m4[j] = morph_ext<DILATE>(m2[j], m2[j + 2]);
+#pragma unroll
+        for (int j = 0; j < N; ++j) out[j] = morph_ext<DILATE>(m4[j], m4[j + W - 4]);
+    }
+}
+
+template <int H, bool DILATE>
+__global__ __launch_bounds__(kBlock) void k_morph_stage(PaintArgs a, const uint8_t* __restrict__ src,
+                                                        uint8_t* __restrict__ stage)
+{
+    constexpr int W = 2 * H + 1;
+    constexpr int XH = kMorphTX + 2 * H, YH = kMorphTY + 2 * H, ZH = kMorphTZ + 2 * H;
+    constexpr int XPW = (XH + 3) / 4;      // dwords of a staged row
+    constexpr int NW = (H + 1) / 2 + 1;    // dwords that hold the 4 + 2H bytes of four adjacent windows
+    constexpr int RAW = ZH * YH * XPW;     // the staged tile, in dwords
+    constexpr int EXZ = YH * kMorphQ + 8;  // z pitch of the x extrema
+    constexpr int EXYZ = kMorphTY * kMorphQ + 8;   // z pitch of the x-y extrema
+    static_assert(kMorphQ - 1 + NW <= XPW, "step 2 reads inside its row");
+    static_assert(ZH * EXYZ <= RAW, "the x-y extrema fit in the staged tile they overwrite");
+    __shared__ uint32_t lds[RAW + ZH * EXZ];
+    uint32_t* const raw32 = lds;
+    uint32_t* const ex = lds + RAW;
+    uint32_t* const exy = lds;
+
+    const int tid = threadIdx.x, xq = tid % kMorphQ, ly = tid / kMorphQ % kMorphTY, zp = tid / (kMorphQ * kMorphTY);
+    const int ntx = (a.e[0] + kMorphTX - 1) / kMorphTX, nty = (a.e[1] + kMorphTY - 1) / kMorphTY;
+    const int bt = blockIdx.x;
+    const int tx0 = (bt % ntx) * kMorphTX, ty0 = (bt / ntx % nty) * kMorphTY, tz0 = (bt / (ntx * nty)) * kMorphTZ;
+    const int x = tx0 + 4 * xq, y = ty0 + ly, z = tz0 + 2 * zp;   // the first owned texel, in the box
+
+    // the weights of the owned texels: 0 outside the ellipsoid or the box (an inside texel's is at least 1)
+    unsigned wgt[2][4];
+    const unsigned long long qy = y < a.e[1] ? brush::axis_term(a.d0[1] + y, a.k[1]) : 0ull;
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            wgt[i][j] = 0u;
+            if (y < a.e[1] && z + i < a.e[2] && x + j < a.e[0]) {
+                const unsigned long long q =
+                    qy + brush::axis_term(a.d0[0] + x + j, a.k[0]) + brush::axis_term(a.d0[2] + z + i, a.k[2]);
+                if (q <= a.s) wgt[i][j] = brush::weight(q, a.s, a.falloff);
+            }
+            any = any || wgt[i][j] != 0u;
+        }
+    if (!__syncthreads_or(any ? 1 : 0)) return;
+
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    const size_t slab = (size_t)a.e[0] * (size_t)a.e[1] * (size_t)a.e[2];
+    int k = 0;   // the channel's slab
+#pragma unroll 1
+    for (int c = 0; c < 4; ++c) {
+        if (a.strength[c] == 0u) continue;
+        const uint8_t* __restrict__ p = src + c * plane;
+        for (int i = tid; i < RAW; i += kBlock) {
+            const int xw = i % XPW, t = i / XPW, yi = t % YH, zi = t / YH;
+            const int gy = clampi(a.o[1] + ty0 - H + yi, 0, a.ny - 1), gz = clampi(a.o[2] + tz0 - H + zi, 0, a.nz - 1);
+            const uint8_t* __restrict__ row = p + ((long long)gz * a.ny + gy) * a.nx;
+            const int gx = a.o[0] + tx0 - H + 4 * xw;
+            uint32_t v = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v |= (uint32_t)row[clampi(gx + j, 0, a.nx - 1)] << (8 * j);
+            raw32[i] = v;
+        }
+        __syncthreads();
+        uint32_t old[2];   // the owned texels' bytes before the call
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const uint32_t* w32 = raw32 + ((2 * zp + i + H) * YH + ly + H) * XPW + xq;
+            old[i] = (uint32_t)((((unsigned long long)w32[1] << 32) | w32[0]) >> (8 * H));
+        }
+        for (int i = tid; i < ZH * YH * kMorphQ; i += kBlock) {
+            const int q = i % kMorphQ, r = i / kMorphQ, yi = r % YH, zi = r / YH;   // r: the row (zi, yi)
+            const uint32_t* w32 = raw32 + r * XPW + q;
+            uint32_t ev[NW], od[NW];
+#pragma unroll
+            for (int j = 0; j < NW; ++j) {
+                const uint32_t v = w32[j];
+                ev[j] = v & 0x00ff00ffu;
+                od[j] = (v >> 8) & 0x00ff00ffu;
+            }
+            // pe[n] = bytes (2n, 2n + 2), po[n] = bytes (2n + 1, 2n + 3) of the row from the dword's first byte on
+            uint32_t pe[H + 1], po[H + 1];
+#pragma unroll
+            for (int n = 0; n <= H; ++n) {
+                pe[n] = n % 2 ? (ev[n / 2] >> 16) | (ev[n / 2 + 1] << 16) : ev[n / 2];
+                po[n] = n % 2 ? (od[n / 2] >> 16) | (od[n / 2 + 1] << 16) : od[n / 2];
+            }
+            // texels 0 and 2 see bytes 0..2H and 2..2H + 2: pe[0..H] and po[0..H - 1]; texels 1 and 3: po[0..H], pe[1..H]
+            uint32_t both = morph_ext<DILATE>(pe[1], po[0]);
+#pragma unroll
+            for (int n = 1; n < H; ++n) both = morph_ext<DILATE>(both, morph_ext<DILATE>(pe[n + 1], po[n]));
+            ex[zi * EXZ + yi * kMorphQ + q] = morph_ext<DILATE>(both, pe[0]) | (morph_ext<DILATE>(both, po[H]) << 8);
+        }
+        __syncthreads();
+        for (int i = tid; i < ZH * kMorphQ * (kMorphTY / 4); i += kBlock) {
+            const int q = i % kMorphQ, t = i / kMorphQ, zi = t % ZH, yq = t / ZH;
+            const uint32_t* col = ex + zi * EXZ + 4 * yq * kMorphQ + q;
+            Quad in[4 + W - 1], out[4];
+#pragma unroll
+            for (int j = 0; j < 4 + W - 1; ++j) in[j] = morph_split(col[j * kMorphQ]);
+            morph_window<W, 4, DILATE>(in, out);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) exy[zi * EXYZ + (4 * yq + j) * kMorphQ + q] = morph_join(out[j]);
+        }
+        __syncthreads();
+        {
+            const uint32_t* col = exy + 2 * zp * EXYZ + ly * kMorphQ + xq;
+            Quad in[2 + W - 1], out[2];
+#pragma unroll
+            for (int j = 0; j < 2 + W - 1; ++j) in[j] = morph_split(col[j * EXYZ]);
+            morph_window<W, 2, DILATE>(in, out);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if ((wgt[i][0] | wgt[i][1] | wgt[i][2] | wgt[i][3]) == 0u) continue;
+                const uint32_t m = morph_join(out[i]);
+                uint32_t nw = 0u;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    nw |= brush::blend(VR_BRUSH_SET, (old[i] >> (8 * j)) & 255u, (m >> (8 * j)) & 255u, wgt[i][j] * a.strength[c])
+                          << (8 * j);
+                uint8_t* __restrict__ o8 =
+                    stage + (size_t)k * slab + ((size_t)(z + i) * (size_t)a.e[1] + (size_t)y) * (size_t)a.e[0] + (size_t)x;
+                if (wgt[i][0] && wgt[i][1] && wgt[i][2] && wgt[i][3] && (reinterpret_cast<uintptr_t>(o8) & 3u) == 0u) {
+                    *reinterpret_cast<uint32_t*>(o8) = nw;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (wgt[i][j]) o8[j] = (uint8_t)(nw >> (8 * j));
+                }
+            }
+        }
+        ++k;
+        __syncthreads();   // the next channel rewrites the tile
+    }
 }
 
 // vr_brush_stats / vr_box_stats: the statistics of the
@@ -1104,6 +1322,27 @@ hipError_t launch_blur_stage(const PaintArgs& a, int half_width, const uint8_t* 
     case 1: hipLaunchKernelGGL(k_blur_stage<1>, g, b, 0, s, a, d_planar, d_stage); break;
     case 2: hipLaunchKernelGGL(k_blur_stage<2>, g, b, 0, s, a, d_planar, d_stage); break;
     case 3: hipLaunchKernelGGL(k_blur_stage<3>, g, b, 0, s, a, d_planar, d_stage); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// the blur's grid over the morph's tile, one instantiation per half width and extremum
+hipError_t launch_morph_stage(const PaintArgs& a, int op, int half_width, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s)
+{
+    if (a.e[0] < 1 || a.e[1] < 1 || a.e[2] < 1 || !d_stage) return hipErrorInvalidValue;
+    if (op != VR_MORPH_ERODE && op != VR_MORPH_DILATE) return hipErrorInvalidValue;
+    const long long tiles = (long long)((a.e[0] + kMorphTX - 1) / kMorphTX) * ((a.e[1] + kMorphTY - 1) / kMorphTY) *
+                            ((a.e[2] + kMorphTZ - 1) / kMorphTZ);
+    if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+    const dim3 g((unsigned)tiles), b(kBlock);
+    switch (2 * half_width + (op == VR_MORPH_DILATE)) {
+    case 2: hipLaunchKernelGGL((k_morph_stage<1, false>), g, b, 0, s, a, d_planar, d_stage); break;
+    case 3: hipLaunchKernelGGL((k_morph_stage<1, true>), g, b, 0, s, a, d_planar, d_stage); break;
+    case 4: hipLaunchKernelGGL((k_morph_stage<2, false>), g, b, 0, s, a, d_planar, d_stage); break;
+    case 5: hipLaunchKernelGGL((k_morph_stage<2, true>), g, b, 0, s, a, d_planar, d_stage); break;
+    case 6: hipLaunchKernelGGL((k_morph_stage<3, false>), g, b, 0, s, a, d_planar, d_stage); break;
+    case 7: hipLaunchKernelGGL((k_morph_stage<3, true>), g, b, 0, s, a, d_planar, d_stage); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

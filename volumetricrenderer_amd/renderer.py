@@ -300,6 +300,23 @@ def stats_summary(stats) -> Summary:
     return Summary(*(np.array(list(getattr(out, k)), np.int64) for k in Summary._fields))
 
 
+def brush_morph_apply(brush: Brush, op: int, half_width: int, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_morph_apply: the erode / dilate brush applied to a host RGBA8
+    volume shaped (nz, ny, nx, 4) (a contiguous uint8 array) -- under the brush,
+    each channel with a non-zero strength is SET towards the minimum
+    (MORPH_ERODE) or maximum (MORPH_DILATE) of its (2 half_width + 1)^3 cube as
+    it was before the call.  The CPU statement of what :meth:`Renderer.morph`
+    does on the device; `brush.op` must be BRUSH_SET and `brush.value` is not
+    read.  Writes `rgba` and returns it."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_morph_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    call("vr_brush_morph_apply", ctypes.byref(brush), int(op), int(half_width), rgba.ctypes.data_as(ctypes.c_void_p),
+         nx, ny, nz)
+    return rgba
+
+
 def _brush_copy(b: Brush) -> Brush:
     c = Brush()
     ctypes.memmove(ctypes.byref(c), ctypes.byref(b), ctypes.sizeof(Brush))
@@ -532,6 +549,24 @@ class Renderer:
         else:
             torch.cuda.synchronize()
         return unpack_stats(buf)
+
+    def morph(self, centre, radius, op, half_width: int = 1, falloff: int = 0, strength=(255, 255, 255, 255),
+              stream=None):
+        """Grow or shrink the installed volume under an ellipsoidal brush on the
+        device (vr_morph): each channel with a non-zero strength is SET towards
+        the minimum (`op` = MORPH_ERODE) or maximum (MORPH_DILATE) of its
+        (2 half_width + 1)^3 cube (half_width 1..3, clamp-to-edge) as it was
+        before the call, weighted as :meth:`paint` weights a SET brush -- bit
+        for bit what :func:`brush_morph_apply` gives on the host.  Returns
+        ``(origin, extent)`` of the clipped bounding box it rewrote, or None
+        when the brush misses the volume, and queues on `stream` as
+        :meth:`paint` does.  The staging scratch is :meth:`blur`'s
+        (``blur_scratch_kib``) and grows by the same rule."""
+        b = make_brush(centre, radius, BRUSH_SET, falloff, 0, strength)
+        call("vr_morph", self._ctx, ctypes.byref(b), int(op), int(half_width), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return brush_box(b, self.volume_dims())
 
     def get_volume_box(self, origin, extent, out=None, stream=None):
         """The texel box `extent` = (bx, by, bz) at `origin` = (x0, y0, z0) of the
