@@ -458,6 +458,93 @@ vr_status vr_morph(void* ctx, const vr_brush* brush, int op, int half_width, voi
 vr_status vr_brush_morph_apply(const vr_brush* brush, int op, int half_width,
                                uint8_t* rgba8, int nx, int ny, int nz);
 
+/* Brushes whose value is read from texels: the clone
+ * stamp, push / smudge, mirror (vr_clone) and the paste of a block with a soft
+ * edge (vr_stamp).  A SOURCE BRUSH is a vr_brush used as vr_paint uses it: the
+ * inside test, the clipped box (vr_brush_box), the weight w, a = w *
+ * strength[c] and all three ops with their blends are the same; only value[c]
+ * is replaced by a per-texel byte v_c(t).  brush->value is validated like the
+ * rest of the brush and never read.  A channel with strength 0 is neither read
+ * nor written.
+ *
+ * vr_clone: v_c(t) is channel c of the installed volume's own texel s, AS IT
+ * WAS BEFORE THE CALL, where per axis a, in 64-bit arithmetic,
+ *   s_a = mirror[a] ? offset[a] - t_a : t_a + offset[a]
+ * clamped to [0, n_a - 1] (clamp-to-edge, as vr_blur and vr_morph read).  A
+ * Jacobi step, whatever the order texels are processed in, so the host
+ * statement and the device agree bit for bit.  Every int32 offset is legal.
+ * The identity map with VR_BRUSH_SET leaves every byte as it was ((old 65280 +
+ * 32640) / 65280 == old), so a SET clone never breaks a uniform channel; ADD
+ * and SUB can, and fold their new bytes into the byte ranges as vr_paint does.
+ * A mirror about the plane through a brush centred at cx is mirror[0] = 1,
+ * offset[0] = 2 cx; a push by one texel is offset -1 or +1 on an axis.
+ *
+ * Device path, chosen on the host in integers; both give the same bytes.
+ *   direct: when the clamped source range of the clipped box, [min s_a, max
+ *     s_a], misses the box on at least one axis, no texel that is read is
+ *     written: ONE launch from the planes to the planes -- no scratch, nothing
+ *     allocated, no host wait.  The clone stamp whose offset is larger than
+ *     the brush.
+ *   staged: otherwise (push, mirror in place, short offsets) a stage launch
+ *     from the planes to the context's staging scratch and vr_blur's commit
+ *     launch.  The scratch is vr_blur's and vr_morph's: the same need (one
+ *     byte per texel of the clipped box and painted channel), growth rule
+ *     (device synchronisation, whole MiB, VR_ERR_OOM holds nothing and leaves
+ *     the volume untouched) and option "blur_scratch_kib".
+ * Both end with the layout rebuild over the clipped box (vr_brush_box names
+ * it) and treat cached launches, region lists and the uniform-channel
+ * read-back exactly as vr_paint does.
+ * VR_ERR_INVALID: a null pointer, anything vr_paint refuses, a mirror other
+ * than 0 or 1, non-zero reserved; VR_ERR_NO_VOLUME before an install and while
+ * a procedural medium is enabled.  A brush that misses the volume, or whose
+ * strengths are all 0, is VR_OK and launches nothing.  A refused call has
+ * launched nothing and leaves the volume untouched.                          */
+typedef struct {              /* 32 bytes */
+    int32_t offset[3];
+    int32_t mirror[3];        /* 0 or 1 per axis */
+    int32_t reserved[2];      /* must be 0 */
+} vr_clone_map;
+vr_status vr_clone(void* ctx, const vr_brush* brush, const vr_clone_map* map, void* stream);
+/* The same on a HOST RGBA8 volume (x fastest): the CPU statement, which
+ * vr_clone reproduces bit for bit.  It works from a copy of what it reads,
+ * never in place.  Pure host code.  VR_ERR_INVALID as above, and for a
+ * non-positive dimension; a refused call leaves the array as it was.        */
+vr_status vr_brush_clone_apply(const vr_brush* brush, const vr_clone_map* map,
+                               uint8_t* rgba8, int nx, int ny, int nz);
+
+/* vr_stamp: v_c(t) is channel c of a texel of the caller's DEVICE box: bx * by
+ * * bz RGBA8 texels, tightly packed, x fastest -- what vr_update_volume takes
+ * and vr_get_volume_box_device writes.  Stamp texel (i, j, k) lies on volume
+ * texel (placement.x + i, .y + j, .z + k); x, y, z may be any int32 (the stamp
+ * may hang over a face or miss the volume; x + bx and the like are formed in
+ * 64 bits), the extents must be positive.  A texel is touched if and only if
+ * it is inside the ellipsoid, inside the volume and inside the placement:
+ * a bitmap brush with the ellipsoid as its mask.  The edited box is the
+ * brush's clipped box intersected with the placement: vr_stamp_box names it,
+ * and it is what to hand to vr_update_footprint.  When it is empty, or every
+ * strength is 0, the call is VR_OK and launches nothing.
+ * One launch and the layout rebuild over the edited box: asynchronous on
+ * `stream`, nothing allocated, no host wait, no scratch; everything else as
+ * after vr_paint.  d_rgba8 must be 4-byte aligned and stay valid until the
+ * launch has run.  vr_get_volume_box_device(a box) followed by vr_stamp
+ * elsewhere on one stream is a copy and paste with a soft edge; stamping a
+ * saved box back through a soft brush is a feathered undo.
+ * VR_ERR_INVALID: a null pointer, anything vr_paint refuses, a non-positive
+ * stamp extent, a misaligned d_rgba8; VR_ERR_NO_VOLUME as for vr_paint.  A
+ * refused call has launched nothing and leaves the volume untouched.        */
+vr_status vr_stamp(void* ctx, const vr_brush* brush, const void* d_rgba8, const vr_box* placement, void* stream);
+/* The same on a HOST RGBA8 volume with a HOST stamp: the CPU statement, which
+ * vr_stamp reproduces bit for bit.  Pure host code; the stamp is copied first,
+ * so it may lie inside rgba8.  VR_ERR_INVALID as above (no alignment is
+ * asked), and for a non-positive dimension; a refused call leaves the array as
+ * it was.                                                                    */
+vr_status vr_brush_stamp_apply(const vr_brush* brush, const uint8_t* stamp_rgba8, const vr_box* placement,
+                               uint8_t* rgba8, int nx, int ny, int nz);
+/* The edited box of a stamp in an nx x ny x nz volume; extent = (0, 0, 0) (and
+ * origin 0) when it is empty.  Pure host code, validated as above.          */
+vr_status vr_stamp_box(const vr_brush* brush, const vr_box* placement, int nx, int ny, int nz,
+                       int origin[3], int extent[3]);
+
 /* The read side of the brush: what is in the volume under it (DESIGN.md sec.
  * 5.2.8) -- the eyedropper, a histogram panel, and the answer to "has this
  * channel become constant again?".  Everything is an integer sum, so the

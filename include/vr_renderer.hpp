@@ -77,6 +77,31 @@ inline void BrushMorphApply(const vr_brush& brush, int op, int half_width, uint8
     Check(vr_brush_morph_apply(&brush, op, half_width, rgba, nx, ny, nz), "vr_brush_morph_apply");
 }
 
+// The clone brush on a host RGBA8 volume (vr_brush_clone_apply): the CPU
+// statement of Renderer::Clone.  Host code only.
+inline void BrushCloneApply(const vr_brush& brush, const vr_clone_map& map, uint8_t* rgba, int nx, int ny, int nz)
+{
+    Check(vr_brush_clone_apply(&brush, &map, rgba, nx, ny, nz), "vr_brush_clone_apply");
+}
+
+// The stamp brush on a host RGBA8 volume with a host stamp
+// (vr_brush_stamp_apply): the CPU statement of Renderer::Stamp.  Host code only.
+inline void BrushStampApply(const vr_brush& brush, const uint8_t* stamp_rgba, const vr_box& placement, uint8_t* rgba,
+                            int nx, int ny, int nz)
+{
+    Check(vr_brush_stamp_apply(&brush, stamp_rgba, &placement, rgba, nx, ny, nz), "vr_brush_stamp_apply");
+}
+
+// What a stamp edits in an nx x ny x nz volume (vr_stamp_box): the brush's
+// clipped box intersected with the placement, what Renderer::UpdateFootprint
+// takes after Renderer::Stamp; false (and a zero extent) when it is empty.
+// Host code only.
+inline bool StampBox(const vr_brush& brush, const vr_box& placement, int nx, int ny, int nz, int origin[3], int extent[3])
+{
+    Check(vr_stamp_box(&brush, &placement, nx, ny, nz, origin, extent), "vr_stamp_box");
+    return extent[0] > 0;
+}
+
 // The dabs of a drag from brush.centre to the texel `to`, at most `spacing`
 // texels apart (vr_brush_line): what Renderer::PaintStroke takes.  skip_first
 // omits the dab on the brush's own centre, the joint of two segments.  Host
@@ -143,6 +168,24 @@ public:
     void Morph(const vr_brush& brush, int op, int half_width = 1, void* stream = nullptr)
     {
         Check(vr_morph(ctx_, &brush, op, half_width, stream), "vr_morph");
+    }
+    // Paint under the brush with the volume's own texels from elsewhere
+    // (vr_clone): the value of texel t is the texel at t + map.offset (per
+    // axis map.offset - t where map.mirror is 1), clamped to the volume, as it
+    // was before the call -- clone stamp, push, mirror.  Queued on `stream` as
+    // Paint is; a source that meets the brush's box goes through Blur's
+    // staging scratch.
+    void Clone(const vr_brush& brush, const vr_clone_map& map, void* stream = nullptr)
+    {
+        Check(vr_clone(ctx_, &brush, &map, stream), "vr_clone");
+    }
+    // Paint under the brush with the texels of a device RGBA8 box laid on the
+    // volume at `placement` (vr_stamp): GetVolumeBoxDevice's format, 4-byte
+    // aligned, alive until the launch has run.  One launch on `stream`;
+    // StampBox names the box it edits.
+    void Stamp(const vr_brush& brush, const void* d_rgba, const vr_box& placement, void* stream = nullptr)
+    {
+        Check(vr_stamp(ctx_, &brush, d_rgba, &placement, stream), "vr_stamp");
     }
     // The read-back counterpart of UpdateVolume (vr_get_volume_box): save a
     // box, Paint, UpdateVolume the saved box -- undo.

@@ -136,6 +136,11 @@ class Box(ctypes.Structure):
                 ("by", ctypes.c_int32), ("bz", ctypes.c_int32)]
 
 
+class CloneMap(ctypes.Structure):
+    """vr_clone_map: where vr_clone reads a texel's value -- per axis t + offset, or offset - t with mirror.  32 bytes."""
+    _fields_ = [("offset", ctypes.c_int32 * 3), ("mirror", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32 * 2)]
+
+
 class VolumeStats(ctypes.Structure):
     """vr_volume_stats: what vr_brush_stats / vr_box_stats produce.  8240 bytes, all 64-bit words."""
     _fields_ = [("count", ctypes.c_uint64), ("weight", ctypes.c_uint64), ("wsum", ctypes.c_uint64 * 4),
@@ -179,6 +184,14 @@ _SIGS = {
     "vr_morph": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, _vp]),
     "vr_brush_morph_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int]),
+    "vr_clone": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.POINTER(CloneMap), _vp]),
+    "vr_brush_clone_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(CloneMap), _vp, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int]),
+    "vr_stamp": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, ctypes.POINTER(Box), _vp]),
+    "vr_brush_stamp_apply": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.POINTER(Box), _vp, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int]),
+    "vr_stamp_box": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(Box), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    c_int_p, c_int_p]),
     "vr_brush_stats": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, _vp]),
     "vr_box_stats": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp, _vp]),
     "vr_brush_stats_host": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -15,6 +15,7 @@
 // renders in vr_rect.cpp.
 #include "vr_blur.h"
 #include "vr_brush.h"
+#include "vr_clone.h"
 #include "vr_ctx.h"
 #include "vr_morph.h"
 #include "vr_stats.h"
@@ -816,6 +817,80 @@ try {
     return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
 } catch (...) {
     return caught_exception("vr_morph");
+}
+
+// The brush of a validated vr_brush over the box o, e of the volume (PaintArgs but for value, which the brushes
+// below do not read); false when every strength is 0 -- nothing would be read or written.
+static bool source_brush_args(const Ctx* c, const vr_brush* b, PaintArgs& a)
+{
+    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    a.s = t.s;
+    for (int ax = 0; ax < 3; ++ax) {
+        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
+        a.k[ax] = t.k[ax];
+    }
+    a.op = b->op;
+    a.falloff = b->falloff;
+    bool any = false;
+    for (int ch = 0; ch < 4; ++ch) { a.strength[ch] = b->strength[ch]; any = any || b->strength[ch] != 0; }
+    return any;
+}
+
+// The clone brush on the device: every check first, then the host picks the path in integers (vr_clone.h direct).
+// Direct: one launch from the planes to the planes.  Staged: k_clone_stage to the blur's scratch (grown only when
+// the call needs more than is held), then the blur's commit launch.  Both end with what follows an edit of the box.
+vr_status vr_clone(void* p, const vr_brush* b, const vr_clone_map* m, void* stream)
+try {
+    if (!p || !b || !m) return fail(VR_ERR_INVALID, "vr_clone: null argument");
+    if (const char* why = vr::clone::invalid(b, m)) return fail(VR_ERR_INVALID, "vr_clone: %s", why);
+    Ctx* c = as_ctx(p);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_clone: no volume set");
+    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_clone: a procedural medium is enabled (it reads no volume)");
+    CloneArgs g{};
+    PaintArgs& a = g.p;
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
+    if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
+    for (int ax = 0; ax < 3; ++ax) { g.offset[ax] = m->offset[ax]; g.mirror[ax] = m->mirror[ax]; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (vr::clone::direct(m, a.o, a.e, c->nx, c->ny, c->nz)) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(launch_clone_direct(g, c->d_planar, c->d_mm, s));
+    } else {
+        if (vr_status st = ensure_blur(c, blur_stage_bytes(a))) return st;
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(launch_clone_stage(g, c->d_planar, c->d_blur, s));
+        HIP_TRY(launch_blur_commit(a, c->d_blur, c->d_planar, c->d_mm, s));
+    }
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+} catch (...) {
+    return caught_exception("vr_clone");
+}
+
+// The stamp brush on the device: every check first, then k_paint_stamp over the edited box (the clipped box
+// intersected with the placement) and what follows an edit of that box.
+vr_status vr_stamp(void* p, const vr_brush* b, const void* d_rgba8, const vr_box* placement, void* stream)
+try {
+    if (!p || !b || !d_rgba8 || !placement) return fail(VR_ERR_INVALID, "vr_stamp: null argument");
+    if (const char* why = vr::stamp::invalid(b, placement)) return fail(VR_ERR_INVALID, "vr_stamp: %s", why);
+    if ((reinterpret_cast<uintptr_t>(d_rgba8) & 3u) != 0u) return fail(VR_ERR_INVALID, "vr_stamp: d_rgba8 is not 4-byte aligned");
+    Ctx* c = as_ctx(p);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_stamp: no volume set");
+    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_stamp: a procedural medium is enabled (it reads no volume)");
+    StampArgs g{};
+    PaintArgs& a = g.p;
+    if (!vr::stamp::clip(b, placement, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // nothing under brush and stamp
+    if (!source_brush_args(c, b, a)) return VR_OK;                                     // every strength is 0
+    const long long p0[3] = {placement->x, placement->y, placement->z};
+    for (int ax = 0; ax < 3; ++ax) g.so[ax] = (int)((long long)a.o[ax] - p0[ax]);   // 0 <= so < the stamp's extent
+    g.sbx = placement->bx;
+    g.sby = placement->by;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(launch_paint_stamp(g, static_cast<const uint8_t*>(d_rgba8), c->d_planar, c->d_mm, s));
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+} catch (...) {
+    return caught_exception("vr_stamp");
 }
 
 // The statistics under a brush or in a box: every check first (a refused call writes nothing), then the buffer is

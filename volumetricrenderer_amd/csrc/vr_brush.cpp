@@ -5,7 +5,10 @@
 // vr_brush_morph_apply: the erode / dilate brush of vr_morph on the host
 // (sec. 5.2.9; the argument check and the extremum are vr_morph.h's);
 // vr_brush_stats_host, vr_box_stats_host and vr_stats_summary: the statistics
-// under a brush or in a box (sec. 5.2.8; the arithmetic is vr_stats.h's).
+// under a brush or in a box (sec. 5.2.8; the arithmetic is vr_stats.h's);
+// vr_brush_clone_apply, vr_brush_stamp_apply and vr_stamp_box: the brushes
+// whose value is a texel, on the host (sec. 5.2.10; the checks, the source
+// coordinate and the edited box are vr_clone.h's).
 //
 // Pure host code in integers: no context, no device, no HIP call.  The
 // arithmetic is vr_brush.h's, which the paint kernel (vr_volume.hip) includes
@@ -18,6 +21,7 @@
 
 #include "vr_blur.h"
 #include "vr_brush.h"
+#include "vr_clone.h"
 #include "vr_morph.h"
 #include "vr_stats.h"
 
@@ -246,6 +250,111 @@ vr_status vr_brush_morph_apply(const vr_brush* b, int op, int half_width, uint8_
                             for (int dx = -h; dx <= h; ++dx) m = vr::morph::pick(op, m, at(x + dx, y + dy, z + dz, c));
                     uint8_t* p = row + (size_t)x * 4 + c;
                     *p = (uint8_t)vr::brush::blend(VR_BRUSH_SET, *p, m, w * b->strength[c]);
+                }
+            }
+        }
+    }
+    return VR_OK;
+}
+
+// The clone brush on the host (include/vr.h): vr_brush_apply with the value of a texel read from the volume's own
+// texel at the mapped, clamped position, as it was BEFORE the call.  The source range of the clipped box (a box
+// inside the volume, no larger than the clipped box) is copied first and every value reads the copy (Jacobi).
+vr_status vr_brush_clone_apply(const vr_brush* b, const vr_clone_map* m, uint8_t* rgba8, int nx, int ny, int nz)
+{
+    if (!b || !m || !rgba8) return fail(VR_ERR_INVALID, "vr_brush_clone_apply: null argument");
+    if (const char* why = vr::clone::invalid(b, m)) return fail(VR_ERR_INVALID, "vr_brush_clone_apply: %s", why);
+    if (nx <= 0 || ny <= 0 || nz <= 0)
+        return fail(VR_ERR_INVALID, "vr_brush_clone_apply: bad extent %dx%dx%d", nx, ny, nz);
+    int o[3], e[3];
+    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
+    const int n[3] = {nx, ny, nz};
+    int lo[3], ext[3];   // what the box reads
+    for (int a = 0; a < 3; ++a) {
+        const int s0 = vr::clone::source(o[a], m->offset[a], m->mirror[a], n[a]);
+        const int s1 = vr::clone::source(o[a] + e[a] - 1, m->offset[a], m->mirror[a], n[a]);
+        lo[a] = s0 < s1 ? s0 : s1;
+        ext[a] = (s0 < s1 ? s1 : s0) - lo[a] + 1;
+    }
+    std::vector<uint8_t> before((size_t)ext[0] * (size_t)ext[1] * (size_t)ext[2] * 4);
+    for (int z = 0; z < ext[2]; ++z)
+        for (int y = 0; y < ext[1]; ++y) {
+            const uint8_t* src = rgba8 + (((size_t)(lo[2] + z) * (size_t)ny + (size_t)(lo[1] + y)) * (size_t)nx + (size_t)lo[0]) * 4;
+            uint8_t* dst = &before[((size_t)z * (size_t)ext[1] + (size_t)y) * (size_t)ext[0] * 4];
+            for (size_t i = 0; i < (size_t)ext[0] * 4; ++i) dst[i] = src[i];
+        }
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    for (int z = o[2]; z < o[2] + e[2]; ++z) {
+        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
+        const int sz = vr::clone::source(z, m->offset[2], m->mirror[2], nz);
+        for (int y = o[1]; y < o[1] + e[1]; ++y) {
+            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
+            if (qyz > t.s) continue;
+            const int sy = vr::clone::source(y, m->offset[1], m->mirror[1], ny);
+            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
+            const uint8_t* srow = &before[((size_t)(sz - lo[2]) * (size_t)ext[1] + (size_t)(sy - lo[1])) * (size_t)ext[0] * 4];
+            for (int x = o[0]; x < o[0] + e[0]; ++x) {
+                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
+                if (q > t.s) continue;
+                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
+                const int sx = vr::clone::source(x, m->offset[0], m->mirror[0], nx);
+                for (int c = 0; c < 4; ++c) {
+                    if (!b->strength[c]) continue;
+                    uint8_t* p = row + (size_t)x * 4 + c;
+                    *p = (uint8_t)vr::brush::blend(b->op, *p, srow[(size_t)(sx - lo[0]) * 4 + (size_t)c], w * b->strength[c]);
+                }
+            }
+        }
+    }
+    return VR_OK;
+}
+
+vr_status vr_stamp_box(const vr_brush* b, const vr_box* placement, int nx, int ny, int nz, int origin[3], int extent[3])
+{
+    if (!b || !placement || !origin || !extent) return fail(VR_ERR_INVALID, "vr_stamp_box: null argument");
+    if (const char* why = vr::stamp::invalid(b, placement)) return fail(VR_ERR_INVALID, "vr_stamp_box: %s", why);
+    if (nx <= 0 || ny <= 0 || nz <= 0) return fail(VR_ERR_INVALID, "vr_stamp_box: bad extent %dx%dx%d", nx, ny, nz);
+    (void)vr::stamp::clip(b, placement, nx, ny, nz, origin, extent);
+    return VR_OK;
+}
+
+// The stamp brush on the host (include/vr.h): vr_brush_apply over the edited box (vr_stamp_box) with the value of a
+// texel read from the stamp texel that lies on it.  The part of the stamp over the edited box is copied first.
+vr_status vr_brush_stamp_apply(const vr_brush* b, const uint8_t* stamp, const vr_box* placement, uint8_t* rgba8, int nx,
+                               int ny, int nz)
+{
+    if (!b || !stamp || !placement || !rgba8) return fail(VR_ERR_INVALID, "vr_brush_stamp_apply: null argument");
+    if (const char* why = vr::stamp::invalid(b, placement)) return fail(VR_ERR_INVALID, "vr_brush_stamp_apply: %s", why);
+    if (nx <= 0 || ny <= 0 || nz <= 0)
+        return fail(VR_ERR_INVALID, "vr_brush_stamp_apply: bad extent %dx%dx%d", nx, ny, nz);
+    int o[3], e[3];
+    if (!vr::stamp::clip(b, placement, nx, ny, nz, o, e)) return VR_OK;
+    // the edited box lies inside the placement: its first texel's position in the stamp is not negative
+    const size_t so[3] = {(size_t)((int64_t)o[0] - placement->x), (size_t)((int64_t)o[1] - placement->y),
+                          (size_t)((int64_t)o[2] - placement->z)};
+    std::vector<uint8_t> copy((size_t)e[0] * (size_t)e[1] * (size_t)e[2] * 4);
+    for (int z = 0; z < e[2]; ++z)
+        for (int y = 0; y < e[1]; ++y) {
+            const uint8_t* src = stamp + (((so[2] + (size_t)z) * (size_t)placement->by + so[1] + (size_t)y) * (size_t)placement->bx + so[0]) * 4;
+            uint8_t* dst = &copy[((size_t)z * (size_t)e[1] + (size_t)y) * (size_t)e[0] * 4];
+            for (size_t i = 0; i < (size_t)e[0] * 4; ++i) dst[i] = src[i];
+        }
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    for (int z = o[2]; z < o[2] + e[2]; ++z) {
+        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
+        for (int y = o[1]; y < o[1] + e[1]; ++y) {
+            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
+            if (qyz > t.s) continue;
+            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
+            const uint8_t* srow = &copy[((size_t)(z - o[2]) * (size_t)e[1] + (size_t)(y - o[1])) * (size_t)e[0] * 4];
+            for (int x = o[0]; x < o[0] + e[0]; ++x) {
+                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
+                if (q > t.s) continue;
+                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
+                for (int c = 0; c < 4; ++c) {
+                    if (!b->strength[c]) continue;
+                    uint8_t* p = row + (size_t)x * 4 + c;
+                    *p = (uint8_t)vr::brush::blend(b->op, *p, srow[(size_t)(x - o[0]) * 4 + (size_t)c], w * b->strength[c]);
                 }
             }
         }

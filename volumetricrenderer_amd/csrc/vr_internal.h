@@ -617,6 +617,25 @@ hipError_t launch_blur_commit(const PaintArgs& a, const uint8_t* d_stage, uint8_
 // maximum (VR_MORPH_DILATE) over the cube as the value; launch_blur_commit follows it.
 hipError_t launch_morph_stage(const PaintArgs& a, int op, int half_width, const uint8_t* d_planar, uint8_t* d_stage,
                               hipStream_t s);
+// vr_clone: the brush as for launch_paint_planar (value is not read) and the validated map.
+// launch_clone_direct goes from the planes to the planes in one launch and folds the new bytes into mm: only for a
+// map whose source range misses the clipped box on an axis (vr_clone.h direct).  launch_clone_stage has
+// launch_blur_stage's contract and slabs; launch_blur_commit follows it.
+struct CloneArgs {
+    PaintArgs p;
+    int offset[3], mirror[3];
+};
+hipError_t launch_clone_direct(const CloneArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+hipError_t launch_clone_stage(const CloneArgs& a, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s);
+// vr_stamp: p is the brush over the EDITED box (the clipped box intersected with the placement: o, e and d0 are that
+// box's; value is not read); so is the position of the edited box's first texel in the stamp (>= 0), sbx and sby the
+// stamp's row and slice pitch in texels.  d_stamp is 4-byte aligned.
+struct StampArgs {
+    PaintArgs p;
+    int so[3];
+    int sbx, sby;
+};
+hipError_t launch_paint_stamp(const StampArgs& a, const uint8_t* d_stamp, uint8_t* d_planar, unsigned* mm, hipStream_t s);
 // vr_brush_stats / vr_box_stats: a texel box inside the volume and, for a brush
 // (ellipsoid != 0), the ellipsoid as in PaintArgs; for a box d0, s and k are not read.
 struct StatsArgs {

@@ -12,6 +12,7 @@
 
 #include "vr_blur.h"
 #include "vr_brush.h"
+#include "vr_clone.h"
 #include "vr_internal.h"
 #include "vr_morph.h"
 #include "vr_noise.h"
@@ -621,6 +622,120 @@ __global__ __launch_bounds__(kBlock) void k_morph_stage(PaintArgs a, const uint8
         ++k;
         __syncthreads();   // the next channel rewrites the tile
     }
+}
+
+// vr_clone: k_paint_planar with the value of a texel
+// read from the volume's own texel at the mapped, clamped position
+// (vr_clone.h source).  Rows and lanes are k_paint_planar's.  The source row's
+// y and z belong to the box row -- wave-uniform, computed once per row; x is
+// per lane: consecutive lanes read consecutive bytes of ONE source row, rising
+// or (mirrored) falling, until the clamp pins them to its first or last byte.
+// A row or a texel outside the ellipsoid is left before any load.
+//
+// STAGE = false (k_clone_direct): `out` is the planes themselves.  The host has
+// checked (vr_clone.h direct) that no texel of the box is read, so the bytes
+// read are the bytes before the call whatever the order of the waves; a store
+// goes only where the byte changed and the new bytes are folded into lo / hi.
+// STAGE = true (k_clone_stage): the planes are read only and the new byte of
+// every inside texel and painted channel goes to the staging slabs, exactly as
+// k_blur_stage and k_morph_stage leave them; k_blur_commit follows.
+template <bool STAGE>
+__device__ __forceinline__ void clone_rows(const CloneArgs& g, const uint8_t* planes, uint8_t* out, unsigned (&lo)[4],
+                                           unsigned (&hi)[4])
+{
+    constexpr unsigned kWaves = kBlock / 64;
+    const PaintArgs& a = g.p;
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    const size_t slab = (size_t)a.e[0] * (size_t)a.e[1] * (size_t)a.e[2];
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned rows = (unsigned)a.e[1] * (unsigned)a.e[2];   // <= 511^2
+    for (unsigned r = blockIdx.x * kWaves + wave; r < rows; r += gridDim.x * kWaves) {
+        const int z = (int)(r / (unsigned)a.e[1]), y = (int)(r - (unsigned)z * (unsigned)a.e[1]);
+        const unsigned long long qyz = brush::axis_term(a.d0[1] + y, a.k[1]) + brush::axis_term(a.d0[2] + z, a.k[2]);
+        if (qyz > a.s) continue;
+        const int sy = clone::source(a.o[1] + y, g.offset[1], g.mirror[1], a.ny);
+        const int sz = clone::source(a.o[2] + z, g.offset[2], g.mirror[2], a.nz);
+        const long long drow = ((long long)(a.o[2] + z) * a.ny + (a.o[1] + y)) * a.nx + a.o[0];
+        const long long srow = ((long long)sz * a.ny + sy) * a.nx;
+        for (int x = lane; x < a.e[0]; x += 64) {
+            const unsigned long long q = qyz + brush::axis_term(a.d0[0] + x, a.k[0]);
+            if (q > a.s) continue;
+            const unsigned w = brush::weight(q, a.s, a.falloff);
+            const int sx = clone::source(a.o[0] + x, g.offset[0], g.mirror[0], a.nx);
+            int k = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (a.strength[c] == 0u) continue;
+                const uint8_t* pc = planes + c * plane;
+                const unsigned old = pc[drow + x];
+                const unsigned nw = brush::blend(a.op, old, pc[srow + sx], w * a.strength[c]);
+                if constexpr (STAGE) {
+                    out[(size_t)k * slab + (size_t)r * (size_t)a.e[0] + (size_t)x] = (uint8_t)nw;
+                    ++k;
+                } else {
+                    if (nw != old) out[c * plane + drow + x] = (uint8_t)nw;
+                    lo[c] = min(lo[c], nw);
+                    hi[c] = max(hi[c], nw);
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_clone_direct(CloneArgs g, uint8_t* planes, unsigned* __restrict__ mm)
+{
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    clone_rows<false>(g, planes, planes, lo, hi);
+    fold_minmax(lo, hi, mm);
+}
+
+__global__ __launch_bounds__(kBlock) void k_clone_stage(CloneArgs g, const uint8_t* __restrict__ src,
+                                                        uint8_t* __restrict__ stage)
+{
+    unsigned lo[4], hi[4];   // not used
+    clone_rows<true>(g, src, stage, lo, hi);
+}
+
+// vr_stamp: k_paint_planar over the EDITED box (the
+// clipped box intersected with the placement) with the value of a texel read
+// from the stamp texel that lies on it: one 4-byte load per inside lane,
+// consecutive lanes on consecutive texels of one stamp row.
+__global__ __launch_bounds__(kBlock) void k_paint_stamp(StampArgs g, const uint32_t* __restrict__ stamp,
+                                                        uint8_t* __restrict__ dst, unsigned* __restrict__ mm)
+{
+    constexpr unsigned kWaves = kBlock / 64;
+    const PaintArgs& a = g.p;
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned rows = (unsigned)a.e[1] * (unsigned)a.e[2];   // <= 511^2
+    for (unsigned r = blockIdx.x * kWaves + wave; r < rows; r += gridDim.x * kWaves) {
+        const int z = (int)(r / (unsigned)a.e[1]), y = (int)(r - (unsigned)z * (unsigned)a.e[1]);
+        const unsigned long long qyz = brush::axis_term(a.d0[1] + y, a.k[1]) + brush::axis_term(a.d0[2] + z, a.k[2]);
+        if (qyz > a.s) continue;
+        uint8_t* __restrict__ row = dst + ((long long)(a.o[2] + z) * a.ny + (a.o[1] + y)) * a.nx + a.o[0];
+        const uint32_t* __restrict__ srow =
+            stamp + (((size_t)g.so[2] + (size_t)z) * (size_t)g.sby + (size_t)g.so[1] + (size_t)y) * (size_t)g.sbx + (size_t)g.so[0];
+        for (int x = lane; x < a.e[0]; x += 64) {
+            const unsigned long long q = qyz + brush::axis_term(a.d0[0] + x, a.k[0]);
+            if (q > a.s) continue;
+            const unsigned w = brush::weight(q, a.s, a.falloff);
+            const uint32_t v = srow[x];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (a.strength[c] == 0u) continue;
+                uint8_t* p = row + x + c * plane;
+                const unsigned old = *p;
+                const unsigned nw = brush::blend(a.op, old, (v >> (8 * c)) & 255u, w * a.strength[c]);
+                if (nw != old) *p = (uint8_t)nw;
+                lo[c] = min(lo[c], nw);
+                hi[c] = max(hi[c], nw);
+            }
+        }
+    }
+    fold_minmax(lo, hi, mm);
 }
 
 // vr_brush_stats / vr_box_stats: the statistics of the
@@ -1353,6 +1468,34 @@ hipError_t launch_blur_commit(const PaintArgs& a, const uint8_t* d_stage, uint8_
 {
     const long long rows = (long long)a.e[1] * a.e[2];
     hipLaunchKernelGGL(k_blur_commit, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a, d_stage, d_planar, mm);
+    return hipGetLastError();
+}
+
+// vr_clone and vr_stamp: a wave per box row, as launch_paint_planar
+hipError_t launch_clone_direct(const CloneArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s)
+{
+    if (a.p.e[0] < 1 || a.p.e[1] < 1 || a.p.e[2] < 1 || !d_planar) return hipErrorInvalidValue;
+    const long long rows = (long long)a.p.e[1] * a.p.e[2];
+    hipLaunchKernelGGL(k_clone_direct, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a, d_planar, mm);
+    return hipGetLastError();
+}
+
+hipError_t launch_clone_stage(const CloneArgs& a, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s)
+{
+    if (a.p.e[0] < 1 || a.p.e[1] < 1 || a.p.e[2] < 1 || !d_planar || !d_stage) return hipErrorInvalidValue;
+    const long long rows = (long long)a.p.e[1] * a.p.e[2];
+    hipLaunchKernelGGL(k_clone_stage, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a, d_planar, d_stage);
+    return hipGetLastError();
+}
+
+hipError_t launch_paint_stamp(const StampArgs& a, const uint8_t* d_stamp, uint8_t* d_planar, unsigned* mm, hipStream_t s)
+{
+    if (a.p.e[0] < 1 || a.p.e[1] < 1 || a.p.e[2] < 1 || !d_planar || !d_stamp) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(d_stamp) & 3u) != 0u || a.so[0] < 0 || a.so[1] < 0 || a.so[2] < 0) return hipErrorInvalidValue;
+    if ((long long)a.so[0] + a.p.e[0] > a.sbx || (long long)a.so[1] + a.p.e[1] > a.sby) return hipErrorInvalidValue;
+    const long long rows = (long long)a.p.e[1] * a.p.e[2];
+    hipLaunchKernelGGL(k_paint_stamp, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a,
+                       reinterpret_cast<const uint32_t*>(d_stamp), d_planar, mm);
     return hipGetLastError();
 }
 

@@ -37,6 +37,7 @@ from ._lib import (BRUSH_ADD, BRUSH_SET, BRUSH_SUB, BYTES_PER_PIXEL, CHANNELS, F
                    FMT_RGBA8_UNORM, FMT_RGBA32F, Brush, GREY_OF, RAY_RECORD_WORDS, GlobalShaderData, MarchParams, ObjectShaderData, Procedural, RayRecord,
                    Rect, Target, VolumeRecipe, VR_MAX_RECTS, VRError, call)
 from ._lib import VOLUME_STATS_BYTES, StatsSummary, VolumeStats
+from ._lib import Box, CloneMap
 
 _lib.load()  # fail at import if the HIP library is missing
 
@@ -317,6 +318,72 @@ def brush_morph_apply(brush: Brush, op: int, half_width: int, rgba: np.ndarray) 
     return rgba
 
 
+def make_clone_map(offset=(0, 0, 0), mirror=(0, 0, 0)) -> CloneMap:
+    """A vr_clone_map: per axis the source of texel coordinate t is ``t + offset``,
+    or ``offset - t`` where `mirror` is 1, clamped to the volume.  A mirror about
+    the plane through x = cx is ``offset=(2 * cx, 0, 0), mirror=(1, 0, 0)``."""
+    m = CloneMap()
+    m.offset[:] = [int(v) for v in offset]
+    m.mirror[:] = [int(v) for v in mirror]
+    return m
+
+
+def _host_box(v) -> Box:
+    origin, extent = v
+    return Box(*(int(x) for x in origin), *(int(x) for x in extent))
+
+
+def brush_clone_apply(brush: Brush, clone_map: CloneMap, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_clone_apply: the clone brush applied to a host RGBA8 volume shaped
+    (nz, ny, nx, 4) (a contiguous uint8 array) -- `brush` blended as
+    :func:`brush_apply` blends it, with the value of each texel read from the
+    volume's own texel at the mapped position (:func:`make_clone_map`) as it
+    was before the call; `brush.value` is not read.  The CPU statement of what
+    :meth:`Renderer.clone` does on the device.  Writes `rgba` and returns it."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_clone_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    call("vr_brush_clone_apply", ctypes.byref(brush), ctypes.byref(clone_map), rgba.ctypes.data_as(ctypes.c_void_p),
+         nx, ny, nz)
+    return rgba
+
+
+def brush_stamp_apply(brush: Brush, stamp: np.ndarray, placement_origin, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_stamp_apply: the stamp brush applied to a host RGBA8 volume shaped
+    (nz, ny, nx, 4) -- `brush` blended as :func:`brush_apply` blends it, with
+    the value of each texel read from the texel of `stamp` (a contiguous uint8
+    array shaped (bz, by, bx, 4), its first texel on volume texel
+    `placement_origin` = (x, y, z)) that lies on it; texels the stamp does not
+    cover are left alone and `brush.value` is not read.  The CPU statement of
+    what :meth:`Renderer.stamp` does on the device.  Writes `rgba` and returns
+    it."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_stamp_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    if (not isinstance(stamp, np.ndarray) or stamp.dtype != np.uint8 or stamp.ndim != 4 or stamp.shape[3] != 4
+            or not stamp.flags.c_contiguous or stamp.size == 0):
+        raise ValueError("brush_stamp_apply: the stamp is a non-empty contiguous uint8 array shaped (bz, by, bx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    box = _host_box((placement_origin, stamp.shape[2::-1]))
+    call("vr_brush_stamp_apply", ctypes.byref(brush), stamp.ctypes.data_as(ctypes.c_void_p), ctypes.byref(box),
+         rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz)
+    return rgba
+
+
+def stamp_box(brush: Brush, placement, dims):
+    """vr_stamp_box: ``(origin, extent)`` of what a stamp edits in a volume of
+    `dims` = (nx, ny, nz) -- the brush's clipped box (:func:`brush_box`)
+    intersected with `placement` = ((x, y, z), (bx, by, bz)), the texels the
+    stamp covers -- or None when it is empty.  What
+    :meth:`Renderer.update_footprint` takes after :meth:`Renderer.stamp`."""
+    nx, ny, nz = (int(v) for v in dims)
+    box = _host_box(placement)
+    o, e = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+    call("vr_stamp_box", ctypes.byref(brush), ctypes.byref(box), nx, ny, nz, o, e)
+    return (tuple(o), tuple(e)) if e[0] > 0 else None
+
+
 def _brush_copy(b: Brush) -> Brush:
     c = Brush()
     ctypes.memmove(ctypes.byref(c), ctypes.byref(b), ctypes.sizeof(Brush))
@@ -567,6 +634,56 @@ class Renderer:
         if stream is None:
             torch.cuda.current_stream().synchronize()
         return brush_box(b, self.volume_dims())
+
+    def clone(self, centre, radius, offset, mirror=(0, 0, 0), op=BRUSH_SET, falloff: int = 0,
+              strength=(255, 255, 255, 255), stream=None):
+        """Paint the installed volume under an ellipsoidal brush with its own
+        texels from elsewhere, on the device (vr_clone): the brush is
+        :meth:`paint`'s, with the value of texel t read from the texel at
+        ``t + offset`` (per axis ``offset - t`` where `mirror` is 1), clamped to
+        the volume, as it was before the call -- a clone stamp for an offset
+        larger than the brush, a push for an offset of a texel, a mirror about
+        the plane x = cx for ``offset=(2 * cx, 0, 0), mirror=(1, 0, 0)``.  Bit
+        for bit what :func:`brush_clone_apply` gives on the host.  Returns
+        ``(origin, extent)`` of the clipped bounding box it rewrote, or None
+        when the brush misses the volume, and queues on `stream` as
+        :meth:`paint` does.  A source that does not meet the box costs one
+        launch and no scratch; one that does goes through :meth:`blur`'s
+        staging scratch (``blur_scratch_kib``), which grows by the same rule."""
+        b = make_brush(centre, radius, op, falloff, 0, strength)
+        m = make_clone_map(offset, mirror)
+        call("vr_clone", self._ctx, ctypes.byref(b), ctypes.byref(m), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return brush_box(b, self.volume_dims())
+
+    def stamp(self, stamp_tensor, placement_origin, centre, radius, op=BRUSH_SET, falloff: int = 0,
+              strength=(255, 255, 255, 255), stream=None):
+        """Paint the installed volume under an ellipsoidal brush with the texels
+        of a device box (vr_stamp): `stamp_tensor` is a contiguous CUDA uint8
+        tensor shaped (bz, by, bx, 4) -- what :meth:`get_volume_box` returns on
+        the device -- whose first texel lies on volume texel `placement_origin`
+        = (x, y, z); the brush is :meth:`paint`'s, with the value of a texel
+        read from the stamp texel on it, and texels the stamp does not cover
+        are left alone.  Bit for bit what :func:`brush_stamp_apply` gives on
+        the host.  Returns ``(origin, extent)`` of the box it edited
+        (:func:`stamp_box`), or None when that is empty.  One launch queued on
+        `stream` as :meth:`paint` is: no scratch, no host wait; the tensor must
+        be 4-byte aligned and stay alive until the launch has run."""
+        if (not isinstance(stamp_tensor, torch.Tensor) or not stamp_tensor.is_cuda
+                or stamp_tensor.device.index != self.device or stamp_tensor.dtype != torch.uint8
+                or stamp_tensor.dim() != 4 or stamp_tensor.shape[3] != 4 or not stamp_tensor.is_contiguous()):
+            raise ValueError(f"stamp: a contiguous uint8 tensor shaped (bz, by, bx, 4) on cuda:{self.device}")
+        bz, by, bx, _ = stamp_tensor.shape
+        b = make_brush(centre, radius, op, falloff, 0, strength)
+        placement = (placement_origin, (bx, by, bz))
+        box = _host_box(placement)
+        # an empty stamp has no buffer to hand over: the library refuses the extent either way
+        ptr = ctypes.c_void_p(stamp_tensor.data_ptr()) if stamp_tensor.numel() else ctypes.c_void_p(4)
+        call("vr_stamp", self._ctx, ctypes.byref(b), ptr, ctypes.byref(box), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return stamp_box(b, placement, self.volume_dims())
 
     def get_volume_box(self, origin, extent, out=None, stream=None):
         """The texel box `extent` = (bx, by, bz) at `origin` = (x0, y0, z0) of the
