@@ -616,6 +616,97 @@ typedef struct {              /* 112 bytes */
     int32_t  min[4], max[4], mean[4], wmean[4], median[4];
 } vr_volume_summary;
 vr_status vr_stats_summary(const vr_volume_stats* stats, vr_volume_summary* out);
+
+/* The lookup-table brush: the tone family of an editor
+ * -- levels, contrast, invert, threshold, posterise, equalise.  vr_remap is a
+ * SOURCE BRUSH in the sense of vr_clone above: the inside test, the clipped box
+ * (vr_brush_box), the weight w, a = w * strength[c], all three ops and their
+ * blends are vr_paint's; only value[c] is replaced, by a function of the
+ * texel's OWN byte,
+ *   v_c(t) = lut[c][ old_c(t) ]      new = blend(op, old, lut[c][old], a)
+ * brush->value is validated like the rest of the brush and never read.  A
+ * channel with strength 0 is neither read nor written, and its table is never
+ * read.  A texel's new byte depends on that texel's old byte alone: there is
+ * no Jacobi question, no scratch and no choice of path -- one launch, in
+ * place.  The identity table with VR_BRUSH_SET leaves every byte as it was (so
+ * it never breaks a uniform channel); ADD and SUB do not.
+ *
+ * Everything is in integers, so the host and the device agree bit for bit.  */
+typedef struct { uint8_t lut[4][256]; } vr_lut;      /* 1024 bytes; lut[c][v] = the value for byte v of channel c */
+typedef enum { VR_LUT_EQUALIZE = 0, VR_LUT_STRETCH = 1 } vr_lut_kind;
+/* Table builders: pure host code, no context, no device.  Each writes *out
+ * only on success; VR_ERR_INVALID for a null pointer, a bad kind, a mask
+ * outside 0..15 or a bad range.
+ *   vr_lut_identity  out[c][v] = v.
+ *   vr_lut_levels    for the channels of channel_mask (bit c = channel c; the
+ *     others keep what *out ALREADY holds, so calls stack per channel), with
+ *     0 <= in_lo < in_hi <= 255 and out_lo, out_hi in 0..255 in either order:
+ *     v <= in_lo gives out_lo, v >= in_hi gives out_hi, and between them
+ *       out_lo + floor((2 (v - in_lo)(out_hi - out_lo) + (in_hi - in_lo))
+ *                      / (2 (in_hi - in_lo)))
+ *     (floor also of a negative numerator, as in vr_brush_line).  Invert is
+ *     (0, 255, 255, 0); a threshold at T >= 1 is (T - 1, T, 0, 255).
+ *   vr_lut_compose   out[c][v] = then[c][ first[c][v] ]; out may alias either.
+ *   vr_stats_lut     a table from the histograms of a vr_volume_stats (only
+ *     hist is read); it overwrites all four channels.  A channel outside the
+ *     mask is the identity, and so is one whose bins sum to n = 0 or that has
+ *     a single non-empty bin.  For the others, with lo and hi the lowest and
+ *     highest non-empty bin, cum(v) = sum_{u<=v} hist[c][u] in 64 bits and
+ *     cmin = cum(lo) (integer division):
+ *       VR_LUT_STRETCH   v <= lo: 0;  v >= hi: 255;  else
+ *                        ((v - lo) 255 + (hi - lo) / 2) / (hi - lo)
+ *       VR_LUT_EQUALIZE  v < lo: 0;  else
+ *                        ((cum(v) - cmin) 255 + (n - cmin) / 2) / (n - cmin)
+ *     (bins are meant to be those of vr_brush_stats / vr_box_stats, below
+ *     2^47 in sum; sums wrap at 64 bits, a wrapped n - cmin of 0 gives the
+ *     identity, and the entry is the low byte of the quotient).              */
+vr_status vr_lut_identity(vr_lut* out);
+vr_status vr_lut_levels(vr_lut* out, int channel_mask, int in_lo, int in_hi, int out_lo, int out_hi);
+vr_status vr_lut_compose(const vr_lut* first, const vr_lut* then, vr_lut* out);
+vr_status vr_stats_lut(const vr_volume_stats* stats, int kind, int channel_mask, vr_lut* out);
+/* vr_remap: the brush on the installed volume with a HOST table.  The table is
+ * read DURING the call (its 1024 bytes travel by value in the kernel's
+ * arguments): the caller may overwrite it as soon as the call returns, queued
+ * calls never share a buffer, and the call can be captured in a graph.
+ * vr_remap_device: the table is a DEVICE vr_lut, 4-byte aligned, read WHEN THE
+ * KERNEL RUNS: a table written earlier on the same stream -- by
+ * vr_stats_lut_device or by a copy -- is the one applied; d_lut must stay
+ * valid until then.  Both follow vr_paint's contract: asynchronous on
+ * `stream`, nothing allocated, no host wait; afterwards the context renders,
+ * and vr_get_volume reads, bit for bit what vr_set_volume of the remapped
+ * volume would give.  One launch (the tables of the painted channels are
+ * staged into 1 KiB of LDS per workgroup, the lookup is an LDS byte read, a
+ * byte is stored only where it changed, the new bytes are folded into the
+ * channels' byte ranges), then the layout rebuild over the clipped box
+ * (vr_brush_box names it: what to hand to vr_update_footprint); cached
+ * launches, region lists and the uniform-channel read-back are treated exactly
+ * as after vr_paint.
+ * VR_ERR_INVALID: a null pointer, anything vr_paint refuses, a misaligned
+ * d_lut; VR_ERR_NO_VOLUME before an install and while a procedural medium is
+ * enabled.  A brush that misses the volume, or whose strengths are all 0, is
+ * VR_OK and launches nothing.  A refused call has launched nothing and leaves
+ * the volume untouched.                                                      */
+vr_status vr_remap(void* ctx, const vr_brush* brush, const vr_lut* lut /* HOST */, void* stream);
+vr_status vr_remap_device(void* ctx, const vr_brush* brush, const void* d_lut /* DEVICE vr_lut, 4-byte aligned */, void* stream);
+/* vr_stats_lut on the device: d_stats is a DEVICE vr_volume_stats (8-byte
+ * aligned) as vr_brush_stats / vr_box_stats leave it, d_lut a DEVICE vr_lut
+ * (4-byte aligned).  One launch on `stream` that writes all 1024 bytes of
+ * d_lut -- bit for bit vr_stats_lut's -- and nothing else, so
+ *   vr_brush_stats -> vr_stats_lut_device -> vr_remap_device
+ *     -> vr_update_footprint -> vr_render_rect
+ * queues on one stream with no host round trip.  It needs a context only for
+ * its device: no volume is needed, a procedural medium may be enabled, and
+ * nothing of the context is used or disturbed.
+ * VR_ERR_INVALID: a null pointer, a misaligned d_stats or d_lut, a bad kind or
+ * mask; a refused call has launched nothing and leaves d_lut untouched.      */
+vr_status vr_stats_lut_device(void* ctx, const void* d_stats /* DEVICE vr_volume_stats, 8-byte aligned */,
+                              int kind, int channel_mask, void* d_lut /* DEVICE vr_lut, 4-byte aligned */, void* stream);
+/* vr_remap on a HOST RGBA8 volume (x fastest): the CPU statement, which the
+ * device reproduces bit for bit.  In place -- safe, since a texel depends on
+ * itself only.  Pure host code.  VR_ERR_INVALID as above (no alignment is
+ * asked), and for a non-positive dimension; a refused call leaves the array as
+ * it was.                                                                    */
+vr_status vr_brush_remap_apply(const vr_brush* brush, const vr_lut* lut, uint8_t* rgba8, int nx, int ny, int nz);
 /* 1 if vr_set_volume / vr_set_volume_device accept an nx x ny x nz extent
  * (the device layouts index a plane with 32-bit offsets), else 0          */
 int       vr_volume_extent_ok(int nx, int ny, int nz);

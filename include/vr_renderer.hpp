@@ -102,6 +102,14 @@ inline bool StampBox(const vr_brush& brush, const vr_box& placement, int nx, int
     return extent[0] > 0;
 }
 
+// The lookup-table brush on a host RGBA8 volume (vr_brush_remap_apply): the CPU
+// statement of Renderer::Remap.  vr_lut_identity, vr_lut_levels, vr_lut_compose
+// and vr_stats_lut build the table.  Host code only.
+inline void BrushRemapApply(const vr_brush& brush, const vr_lut& lut, uint8_t* rgba, int nx, int ny, int nz)
+{
+    Check(vr_brush_remap_apply(&brush, &lut, rgba, nx, ny, nz), "vr_brush_remap_apply");
+}
+
 // The dabs of a drag from brush.centre to the texel `to`, at most `spacing`
 // texels apart (vr_brush_line): what Renderer::PaintStroke takes.  skip_first
 // omits the dab on the brush's own centre, the joint of two segments.  Host
@@ -186,6 +194,26 @@ public:
     void Stamp(const vr_brush& brush, const void* d_rgba, const vr_box& placement, void* stream = nullptr)
     {
         Check(vr_stamp(ctx_, &brush, d_rgba, &placement, stream), "vr_stamp");
+    }
+    // Paint under the brush with a function of each texel's own byte
+    // (vr_remap): the value of channel c is lut.lut[c][old byte] -- levels,
+    // invert, threshold, equalise.  The host table is copied during the call.
+    // Queued on `stream` as Paint is: one launch, no scratch.
+    void Remap(const vr_brush& brush, const vr_lut& lut, void* stream = nullptr)
+    {
+        Check(vr_remap(ctx_, &brush, &lut, stream), "vr_remap");
+    }
+    // The same with a DEVICE vr_lut (vr_remap_device; 4-byte aligned), read when
+    // the kernel runs: a table written earlier on `stream` is the one applied.
+    void RemapDevice(const vr_brush& brush, const void* d_lut, void* stream = nullptr)
+    {
+        Check(vr_remap_device(ctx_, &brush, d_lut, stream), "vr_remap_device");
+    }
+    // A device table from a device vr_volume_stats (vr_stats_lut_device): what
+    // BrushStats / BoxStats wrote -> what RemapDevice takes, on one stream.
+    void StatsLutDevice(const void* d_stats, int kind, int channel_mask, void* d_lut, void* stream = nullptr) const
+    {
+        Check(vr_stats_lut_device(ctx_, d_stats, kind, channel_mask, d_lut, stream), "vr_stats_lut_device");
     }
     // The read-back counterpart of UpdateVolume (vr_get_volume_box): save a
     // box, Paint, UpdateVolume the saved box -- undo.

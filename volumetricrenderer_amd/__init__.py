@@ -15,6 +15,8 @@ from ._lib import MORPH_DILATE, MORPH_ERODE, MORPH_MAX_HALF  # noqa: F401
 from .renderer import brush_morph_apply  # noqa: F401
 from ._lib import CloneMap  # noqa: F401
 from .renderer import brush_clone_apply, brush_stamp_apply, make_clone_map, stamp_box  # noqa: F401
+from ._lib import LUT_BYTES, LUT_EQUALIZE, LUT_STRETCH, Lut  # noqa: F401
+from .renderer import brush_remap_apply, lut_compose, lut_identity, lut_levels, stats_lut  # noqa: F401
 from .renderer import brush_apply, brush_blur_apply, brush_box, brush_line, coalesce_boxes, make_brush  # noqa: F401
 from .renderer import (RAY_RECORD_DTYPE, Renderer, band_rows_packed, coalesce_rects, march_defaults,  # noqa: F401
                        procedural_defaults, ray_records, reference_shader_data, scaled_recipe, shader_data_arrays,
@@ -30,6 +32,8 @@ __all__ = [
     "brush_line", "coalesce_boxes", "VR_MAX_DABS", "Box", "brush_blur_apply", "BLUR_MAX_HALF",
     "brush_morph_apply", "MORPH_ERODE", "MORPH_DILATE", "MORPH_MAX_HALF",
     "CloneMap", "make_clone_map", "brush_clone_apply", "brush_stamp_apply", "stamp_box",
+    "Lut", "LUT_BYTES", "LUT_EQUALIZE", "LUT_STRETCH", "lut_identity", "lut_levels", "lut_compose", "stats_lut",
+    "brush_remap_apply",
     "VolumeStats", "StatsSummary", "VOLUME_STATS_BYTES", "Stats", "Summary", "brush_stats_host", "box_stats_host",
     "stats_summary", "unpack_stats",
 ]

@@ -154,6 +154,15 @@ class StatsSummary(ctypes.Structure):
 
 VOLUME_STATS_BYTES = ctypes.sizeof(VolumeStats)   # 8240
 
+
+class Lut(ctypes.Structure):
+    """vr_lut: the tables of vr_remap -- lut[c][v] is the value for byte v of channel c.  1024 bytes."""
+    _fields_ = [("lut", (ctypes.c_uint8 * 256) * 4)]
+
+
+LUT_BYTES = ctypes.sizeof(Lut)               # 1024
+LUT_EQUALIZE, LUT_STRETCH = 0, 1             # vr.h vr_lut_kind
+
 RAY_RECORD_WORDS = ctypes.sizeof(RayRecord) // 4   # a record as int32 words: query_rect's last axis
 
 _vp = ctypes.c_void_p
@@ -192,6 +201,15 @@ _SIGS = {
                                             ctypes.c_int, ctypes.c_int]),
     "vr_stamp_box": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(Box), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     c_int_p, c_int_p]),
+    "vr_remap": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.POINTER(Lut), _vp]),
+    "vr_remap_device": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, _vp]),
+    "vr_stats_lut_device": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "vr_brush_remap_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(Lut), _vp, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int]),
+    "vr_lut_identity": (ctypes.c_int, [ctypes.POINTER(Lut)]),
+    "vr_lut_levels": (ctypes.c_int, [ctypes.POINTER(Lut)] + [ctypes.c_int] * 5),
+    "vr_lut_compose": (ctypes.c_int, [ctypes.POINTER(Lut), ctypes.POINTER(Lut), ctypes.POINTER(Lut)]),
+    "vr_stats_lut": (ctypes.c_int, [ctypes.POINTER(VolumeStats), ctypes.c_int, ctypes.c_int, ctypes.POINTER(Lut)]),
     "vr_brush_stats": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, _vp]),
     "vr_box_stats": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp, _vp]),
     "vr_brush_stats_host": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

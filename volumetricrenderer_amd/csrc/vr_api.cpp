@@ -18,6 +18,7 @@
 #include "vr_clone.h"
 #include "vr_ctx.h"
 #include "vr_morph.h"
+#include "vr_remap.h"
 #include "vr_stats.h"
 
 namespace vrapi {
@@ -891,6 +892,57 @@ try {
     return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
 } catch (...) {
     return caught_exception("vr_stamp");
+}
+
+// The lookup-table brush on the device: every check first, then k_remap over the clipped box -- with the host table
+// in the kernel's arguments (lut) or the caller's device table (d_lut) -- and what follows an edit of that box.
+static vr_status remap_brush(const char* fn, void* p, const vr_brush* b, const vr_lut* lut, const void* d_lut, void* stream)
+{
+    if (!p || !b || (!lut && !d_lut)) return fail(VR_ERR_INVALID, "%s: null argument", fn);
+    if (const char* why = vr::brush::invalid(b)) return fail(VR_ERR_INVALID, "%s: %s", fn, why);
+    if (!lut && (reinterpret_cast<uintptr_t>(d_lut) & 3u) != 0u) return fail(VR_ERR_INVALID, "%s: d_lut is not 4-byte aligned", fn);
+    Ctx* c = as_ctx(p);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "%s: no volume set", fn);
+    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "%s: a procedural medium is enabled (it reads no volume)", fn);
+    PaintArgs a{};
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
+    if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(launch_remap(a, lut, d_lut, c->d_planar, c->d_mm, s));
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+}
+
+vr_status vr_remap(void* p, const vr_brush* b, const vr_lut* lut, void* stream)
+try {
+    return remap_brush("vr_remap", p, b, lut, nullptr, stream);
+} catch (...) {
+    return caught_exception("vr_remap");
+}
+
+vr_status vr_remap_device(void* p, const vr_brush* b, const void* d_lut, void* stream)
+try {
+    return remap_brush("vr_remap_device", p, b, nullptr, d_lut, stream);
+} catch (...) {
+    return caught_exception("vr_remap_device");
+}
+
+// vr_stats_lut on the device: the context names the device and nothing else of it is used -- no volume is needed
+// and a procedural medium may be enabled.
+vr_status vr_stats_lut_device(void* p, const void* d_stats, int kind, int channel_mask, void* d_lut, void* stream)
+try {
+    if (!p || !d_stats || !d_lut) return fail(VR_ERR_INVALID, "vr_stats_lut_device: null argument");
+    if (const char* why = vr::remap::invalid_kind(kind)) return fail(VR_ERR_INVALID, "vr_stats_lut_device: %s", why);
+    if (const char* why = vr::remap::invalid_mask(channel_mask)) return fail(VR_ERR_INVALID, "vr_stats_lut_device: %s", why);
+    if ((reinterpret_cast<uintptr_t>(d_stats) & 7u) != 0u) return fail(VR_ERR_INVALID, "vr_stats_lut_device: d_stats is not 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_lut) & 3u) != 0u) return fail(VR_ERR_INVALID, "vr_stats_lut_device: d_lut is not 4-byte aligned");
+    const Ctx* c = as_ctx(p);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_stats_lut(static_cast<const vr_volume_stats*>(d_stats), kind, (unsigned)channel_mask,
+                             static_cast<vr_lut*>(d_lut), static_cast<hipStream_t>(stream)));
+    return VR_OK;
+} catch (...) {
+    return caught_exception("vr_stats_lut_device");
 }
 
 // The statistics under a brush or in a box: every check first (a refused call writes nothing), then the buffer is

@@ -8,7 +8,10 @@
 // under a brush or in a box (sec. 5.2.8; the arithmetic is vr_stats.h's);
 // vr_brush_clone_apply, vr_brush_stamp_apply and vr_stamp_box: the brushes
 // whose value is a texel, on the host (sec. 5.2.10; the checks, the source
-// coordinate and the edited box are vr_clone.h's).
+// coordinate and the edited box are vr_clone.h's); vr_brush_remap_apply,
+// vr_lut_identity, vr_lut_levels, vr_lut_compose and vr_stats_lut: the
+// lookup-table brush on the host and its table builders (sec. 5.2.11; the
+// checks and the entries of a table are vr_remap.h's).
 //
 // Pure host code in integers: no context, no device, no HIP call.  The
 // arithmetic is vr_brush.h's, which the paint kernel (vr_volume.hip) includes
@@ -23,6 +26,7 @@
 #include "vr_brush.h"
 #include "vr_clone.h"
 #include "vr_morph.h"
+#include "vr_remap.h"
 #include "vr_stats.h"
 
 #ifdef VR_BRUSH_STANDALONE
@@ -359,6 +363,77 @@ vr_status vr_brush_stamp_apply(const vr_brush* b, const uint8_t* stamp, const vr
             }
         }
     }
+    return VR_OK;
+}
+
+// The lookup-table brush on the host (include/vr.h): vr_brush_apply with the value of a texel read from the table at
+// the texel's own old byte.  In place: a texel's new byte depends on that texel alone.
+vr_status vr_brush_remap_apply(const vr_brush* b, const vr_lut* lut, uint8_t* rgba8, int nx, int ny, int nz)
+{
+    if (!lut || !rgba8) return fail(VR_ERR_INVALID, "vr_brush_remap_apply: null argument");
+    if (vr_status st = check("vr_brush_remap_apply", b, nx, ny, nz)) return st;
+    int o[3], e[3];
+    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    for (int z = o[2]; z < o[2] + e[2]; ++z) {
+        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
+        for (int y = o[1]; y < o[1] + e[1]; ++y) {
+            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
+            if (qyz > t.s) continue;
+            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
+            for (int x = o[0]; x < o[0] + e[0]; ++x) {
+                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
+                if (q > t.s) continue;
+                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
+                for (int c = 0; c < 4; ++c) {
+                    if (!b->strength[c]) continue;
+                    uint8_t* p = row + (size_t)x * 4 + c;
+                    *p = (uint8_t)vr::brush::blend(b->op, *p, lut->lut[c][*p], w * b->strength[c]);
+                }
+            }
+        }
+    }
+    return VR_OK;
+}
+
+vr_status vr_lut_identity(vr_lut* out)
+{
+    if (!out) return fail(VR_ERR_INVALID, "vr_lut_identity: null argument");
+    for (int c = 0; c < 4; ++c)
+        for (int v = 0; v < 256; ++v) out->lut[c][v] = (uint8_t)v;
+    return VR_OK;
+}
+
+vr_status vr_lut_levels(vr_lut* out, int channel_mask, int in_lo, int in_hi, int out_lo, int out_hi)
+{
+    if (!out) return fail(VR_ERR_INVALID, "vr_lut_levels: null argument");
+    if (const char* why = vr::remap::invalid_mask(channel_mask)) return fail(VR_ERR_INVALID, "vr_lut_levels: %s", why);
+    if (const char* why = vr::remap::invalid_levels(in_lo, in_hi, out_lo, out_hi))
+        return fail(VR_ERR_INVALID, "vr_lut_levels: %s", why);
+    for (int c = 0; c < 4; ++c) {
+        if (!(channel_mask >> c & 1)) continue;
+        for (int v = 0; v < 256; ++v) out->lut[c][v] = (uint8_t)vr::remap::levels_value(v, in_lo, in_hi, out_lo, out_hi);
+    }
+    return VR_OK;
+}
+
+// out may be first or then: the result is formed in a table of its own
+vr_status vr_lut_compose(const vr_lut* first, const vr_lut* then, vr_lut* out)
+{
+    if (!first || !then || !out) return fail(VR_ERR_INVALID, "vr_lut_compose: null argument");
+    vr_lut r;
+    for (int c = 0; c < 4; ++c)
+        for (int v = 0; v < 256; ++v) r.lut[c][v] = then->lut[c][first->lut[c][v]];
+    *out = r;
+    return VR_OK;
+}
+
+vr_status vr_stats_lut(const vr_volume_stats* stats, int kind, int channel_mask, vr_lut* out)
+{
+    if (!stats || !out) return fail(VR_ERR_INVALID, "vr_stats_lut: null argument");
+    if (const char* why = vr::remap::invalid_kind(kind)) return fail(VR_ERR_INVALID, "vr_stats_lut: %s", why);
+    if (const char* why = vr::remap::invalid_mask(channel_mask)) return fail(VR_ERR_INVALID, "vr_stats_lut: %s", why);
+    vr::remap::stats_lut(stats, kind, (unsigned)channel_mask, out);
     return VR_OK;
 }
 

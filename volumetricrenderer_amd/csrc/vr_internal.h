@@ -636,6 +636,15 @@ struct StampArgs {
     int sbx, sby;
 };
 hipError_t launch_paint_stamp(const StampArgs& a, const uint8_t* d_stamp, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+// vr_remap / vr_remap_device: the brush as for launch_paint_planar (value is not read) with
+// the value of a texel read from a table at the texel's old byte.  host_lut != null: the table is copied into the
+// kernel's arguments during the call (d_lut is not used); host_lut == null: d_lut, a 4-byte aligned DEVICE vr_lut, is
+// read when the kernel runs.  One launch, in place; the new bytes are folded into mm.
+hipError_t launch_remap(const PaintArgs& a, const vr_lut* host_lut, const void* d_lut, uint8_t* d_planar, unsigned* mm,
+                        hipStream_t s);
+// vr_stats_lut_device: vr_stats_lut of the DEVICE *d_stats into the DEVICE *d_lut (k_stats_lut, one workgroup); it
+// writes the table's 1024 bytes and nothing else
+hipError_t launch_stats_lut(const vr_volume_stats* d_stats, int kind, unsigned mask, vr_lut* d_lut, hipStream_t s);
 // vr_brush_stats / vr_box_stats: a texel box inside the volume and, for a brush
 // (ellipsoid != 0), the ellipsoid as in PaintArgs; for a box d0, s and k are not read.
 struct StatsArgs {

@@ -16,6 +16,7 @@
 #include "vr_internal.h"
 #include "vr_morph.h"
 #include "vr_noise.h"
+#include "vr_remap.h"
 #include "vr_stats.h"
 
 namespace vr {
@@ -736,6 +737,110 @@ __global__ __launch_bounds__(kBlock) void k_paint_stamp(StampArgs g, const uint3
         }
     }
     fold_minmax(lo, hi, mm);
+}
+
+// vr_remap / vr_remap_device: k_paint_planar with the
+// value of a texel read from a table at the texel's own old byte
+// (vr_remap.h).  Rows and lanes are k_paint_planar's.  At workgroup start the
+// tables of the painted channels go into 1 KiB of LDS as dwords: wave c stages
+// channel c (64 lanes x one dword = its 256 bytes) when strength[c] != 0 -- a
+// wave-uniform test, and a table that is not needed is never read.  The source
+// is the kernel's own arguments (DEVICE_LUT = false: the 1024 bytes travel by
+// value, so the host table is free again when the launch call returns) or the
+// caller's device table read when the kernel runs (DEVICE_LUT = true; 4-byte
+// aligned).  Every thread reaches the barrier after the stage and
+// fold_minmax's: a wave without a row falls through its loop, nothing returns
+// early.  The lookup is one LDS byte read per texel and channel; a store goes
+// only where the byte changed and the new bytes are folded into mm.
+template <bool DEVICE_LUT>
+struct RemapLut {
+    vr_lut t;
+};
+template <>
+struct RemapLut<true> {
+    const uint32_t* t;
+};
+
+template <bool DEVICE_LUT>
+__global__ __launch_bounds__(kBlock) void k_remap(PaintArgs a, RemapLut<DEVICE_LUT> lut, uint8_t* __restrict__ dst,
+                                                  unsigned* __restrict__ mm)
+{
+    constexpr unsigned kWaves = kBlock / 64;
+    static_assert(kWaves == 4 && sizeof(vr_lut) == 4 * 64 * sizeof(uint32_t), "a wave stages one channel's table");
+    __shared__ uint32_t table[4 * 64];
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (a.strength[wave] != 0u) {
+        const uint32_t* src;
+        if constexpr (DEVICE_LUT) src = lut.t;
+        else src = reinterpret_cast<const uint32_t*>(&lut.t);
+        table[wave * 64 + lane] = src[wave * 64 + lane];
+    }
+    __syncthreads();
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(table);
+    const unsigned rows = (unsigned)a.e[1] * (unsigned)a.e[2];   // <= 511^2
+    for (unsigned r = blockIdx.x * kWaves + wave; r < rows; r += gridDim.x * kWaves) {
+        const int z = (int)(r / (unsigned)a.e[1]), y = (int)(r - (unsigned)z * (unsigned)a.e[1]);
+        const unsigned long long qyz = brush::axis_term(a.d0[1] + y, a.k[1]) + brush::axis_term(a.d0[2] + z, a.k[2]);
+        if (qyz > a.s) continue;
+        uint8_t* __restrict__ row = dst + ((long long)(a.o[2] + z) * a.ny + (a.o[1] + y)) * a.nx + a.o[0];
+        for (int x = lane; x < a.e[0]; x += 64) {
+            const unsigned long long q = qyz + brush::axis_term(a.d0[0] + x, a.k[0]);
+            if (q > a.s) continue;
+            const unsigned w = brush::weight(q, a.s, a.falloff);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (a.strength[c] == 0u) continue;
+                uint8_t* p = row + x + c * plane;
+                const unsigned old = *p;
+                const unsigned nw = brush::blend(a.op, old, bytes[c * 256 + (int)old], w * a.strength[c]);
+                if (nw != old) *p = (uint8_t)nw;
+                lo[c] = min(lo[c], nw);
+                hi[c] = max(hi[c], nw);
+            }
+        }
+    }
+    fold_minmax(lo, hi, mm);
+}
+
+// vr_stats_lut_device: vr_stats_lut (vr_remap.h) in ONE
+// workgroup of 256 threads; thread v owns bin v.  Per channel: the bin goes to
+// LDS, an inclusive block scan (Hillis-Steele, 8 steps, 64-bit) leaves cum(v)
+// there, and lo / hi -- the lowest and highest non-empty bin -- come from LDS
+// min / max over the threads whose bin is not 0; n = cum(255), cmin = cum(lo).
+// Every thread then stores its byte of the channel's table: 1024 byte stores
+// in all, nothing else is written.  An unselected channel reads no bin.
+__global__ __launch_bounds__(256) void k_stats_lut(const vr_volume_stats* __restrict__ stats, int kind, unsigned mask,
+                                                   vr_lut* __restrict__ out)
+{
+    __shared__ unsigned long long cum[256];
+    __shared__ int ends[2];
+    const int v = threadIdx.x;
+    for (int c = 0; c < 4; ++c) {
+        const bool selected = (mask >> c & 1u) != 0u;   // workgroup-uniform
+        if (!selected) {
+            out->lut[c][v] = (uint8_t)v;
+            continue;
+        }
+        const unsigned long long h = stats->hist[c][v];
+        cum[v] = h;
+        if (v == 0) { ends[0] = 256; ends[1] = -1; }
+        __syncthreads();
+        if (h != 0ull) { atomicMin(&ends[0], v); atomicMax(&ends[1], v); }
+        for (int off = 1; off < 256; off <<= 1) {
+            const unsigned long long below = v >= off ? cum[v - off] : 0ull;
+            __syncthreads();
+            cum[v] += below;
+            __syncthreads();
+        }
+        remap::Range r{ends[0], ends[1], cum[255], 0ull};
+        if (r.lo <= 255) r.cmin = cum[r.lo];
+        const unsigned long long mine = cum[v];
+        __syncthreads();   // the next channel overwrites cum and ends
+        out->lut[c][v] = (uint8_t)(remap::mapped(kind, true, r) ? remap::stats_value(kind, v, mine, r) : (unsigned)v);
+    }
 }
 
 // vr_brush_stats / vr_box_stats: the statistics of the
@@ -1496,6 +1601,33 @@ hipError_t launch_paint_stamp(const StampArgs& a, const uint8_t* d_stamp, uint8_
     const long long rows = (long long)a.p.e[1] * a.p.e[2];
     hipLaunchKernelGGL(k_paint_stamp, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a,
                        reinterpret_cast<const uint32_t*>(d_stamp), d_planar, mm);
+    return hipGetLastError();
+}
+
+// vr_remap (host_lut: its 1024 bytes go into the kernel's arguments here, during the call) and vr_remap_device
+// (host_lut null: d_lut is read when the kernel runs): a wave per box row, as launch_paint_planar
+hipError_t launch_remap(const PaintArgs& a, const vr_lut* host_lut, const void* d_lut, uint8_t* d_planar, unsigned* mm,
+                        hipStream_t s)
+{
+    if (a.e[0] < 1 || a.e[1] < 1 || a.e[2] < 1 || !d_planar) return hipErrorInvalidValue;
+    const long long rows = (long long)a.e[1] * a.e[2];
+    if (host_lut) {
+        RemapLut<false> l;
+        l.t = *host_lut;
+        hipLaunchKernelGGL(k_remap<false>, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a, l, d_planar, mm);
+    } else {
+        if (!d_lut || (reinterpret_cast<uintptr_t>(d_lut) & 3u) != 0u) return hipErrorInvalidValue;
+        RemapLut<true> l;
+        l.t = static_cast<const uint32_t*>(d_lut);
+        hipLaunchKernelGGL(k_remap<true>, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a, l, d_planar, mm);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_stats_lut(const vr_volume_stats* d_stats, int kind, unsigned mask, vr_lut* d_lut, hipStream_t s)
+{
+    if (!d_stats || !d_lut || mask > 15u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_stats_lut, dim3(1), dim3(256), 0, s, d_stats, kind, mask, d_lut);
     return hipGetLastError();
 }
 

@@ -38,6 +38,7 @@ from ._lib import (BRUSH_ADD, BRUSH_SET, BRUSH_SUB, BYTES_PER_PIXEL, CHANNELS, F
                    Rect, Target, VolumeRecipe, VR_MAX_RECTS, VRError, call)
 from ._lib import VOLUME_STATS_BYTES, StatsSummary, VolumeStats
 from ._lib import Box, CloneMap
+from ._lib import LUT_BYTES, LUT_EQUALIZE, LUT_STRETCH, Lut  # noqa: F401
 
 _lib.load()  # fail at import if the HIP library is missing
 
@@ -384,6 +385,84 @@ def stamp_box(brush: Brush, placement, dims):
     return (tuple(o), tuple(e)) if e[0] > 0 else None
 
 
+def _lut_struct(fn: str, lut) -> Lut:
+    """The vr_lut of a (4, 256) uint8 array (or a Lut, as it is): a copy."""
+    if isinstance(lut, Lut):
+        return lut
+    if not isinstance(lut, np.ndarray) or lut.dtype != np.uint8 or lut.shape != (4, 256):
+        raise ValueError(f"{fn}: a table is a uint8 array shaped (4, 256)")
+    s = Lut()
+    ctypes.memmove(ctypes.byref(s), np.ascontiguousarray(lut).ctypes.data, LUT_BYTES)
+    return s
+
+
+def _lut_array(s: Lut) -> np.ndarray:
+    return np.frombuffer(bytes(s), np.uint8).reshape(4, 256).copy()
+
+
+def lut_identity() -> np.ndarray:
+    """vr_lut_identity: the table that maps every byte to itself, a (4, 256)
+    uint8 array -- ``lut[c, v]`` is the value for byte v of channel c, what
+    :meth:`Renderer.remap` and :func:`brush_remap_apply` take."""
+    s = Lut()
+    call("vr_lut_identity", ctypes.byref(s))
+    return _lut_array(s)
+
+
+def lut_levels(in_lo: int, in_hi: int, out_lo: int, out_hi: int, channels: int = 0xF, lut=None) -> np.ndarray:
+    """vr_lut_levels: a new table in which the channels of `channels` (bit c =
+    channel c) map ``v <= in_lo`` to `out_lo`, ``v >= in_hi`` to `out_hi` and
+    the bytes between them along the line through the two, rounded to the
+    nearest; the other channels keep what `lut` holds (default: the
+    identity), so calls stack per channel.  ``0 <= in_lo < in_hi <= 255``;
+    `out_lo` and `out_hi` in 0..255 in either order: ``(0, 255, 255, 0)``
+    inverts, ``(T - 1, T, 0, 255)`` is a threshold at T."""
+    s = Lut()
+    if lut is None:
+        call("vr_lut_identity", ctypes.byref(s))
+    else:
+        ctypes.memmove(ctypes.byref(s), ctypes.byref(_lut_struct("lut_levels", lut)), LUT_BYTES)
+    call("vr_lut_levels", ctypes.byref(s), int(channels), int(in_lo), int(in_hi), int(out_lo), int(out_hi))
+    return _lut_array(s)
+
+
+def lut_compose(first, then) -> np.ndarray:
+    """vr_lut_compose: the table of `first` followed by `then`,
+    ``out[c, v] = then[c, first[c, v]]``."""
+    a, b, out = _lut_struct("lut_compose", first), _lut_struct("lut_compose", then), Lut()
+    call("vr_lut_compose", ctypes.byref(a), ctypes.byref(b), ctypes.byref(out))
+    return _lut_array(out)
+
+
+def stats_lut(stats, kind: int, channels: int = 0xF) -> np.ndarray:
+    """vr_stats_lut: a table from the histograms of `stats` (a :class:`Stats`,
+    as :meth:`Renderer.brush_stats` returns it, a :class:`VolumeStats` or
+    whatever :func:`unpack_stats` takes).  `kind` LUT_STRETCH maps the lowest
+    non-empty bin to 0 and the highest to 255 linearly, LUT_EQUALIZE maps byte
+    v by the cumulative count up to v; a channel outside `channels`, an empty
+    one and one with a single non-empty bin get the identity.  The CPU
+    statement of :meth:`Renderer.stats_lut`."""
+    s, out = _pack_stats(stats), Lut()
+    call("vr_stats_lut", ctypes.byref(s), int(kind), int(channels), ctypes.byref(out))
+    return _lut_array(out)
+
+
+def brush_remap_apply(brush: Brush, lut, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_remap_apply: the lookup-table brush applied to a host RGBA8
+    volume shaped (nz, ny, nx, 4) (a contiguous uint8 array) -- `brush` blended
+    as :func:`brush_apply` blends it, with the value of each texel and channel
+    read from `lut` (a (4, 256) uint8 array) at the texel's own old byte;
+    `brush.value` is not read.  The CPU statement of what
+    :meth:`Renderer.remap` does on the device.  Writes `rgba` and returns it."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_remap_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    s = _lut_struct("brush_remap_apply", lut)
+    call("vr_brush_remap_apply", ctypes.byref(brush), ctypes.byref(s), rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz)
+    return rgba
+
+
 def _brush_copy(b: Brush) -> Brush:
     c = Brush()
     ctypes.memmove(ctypes.byref(c), ctypes.byref(b), ctypes.sizeof(Brush))
@@ -684,6 +763,60 @@ class Renderer:
         if stream is None:
             torch.cuda.current_stream().synchronize()
         return stamp_box(b, placement, self.volume_dims())
+
+    def remap(self, centre, radius, lut, op=BRUSH_SET, falloff: int = 0, strength=(255, 255, 255, 255), stream=None):
+        """Paint the installed volume under an ellipsoidal brush with a function
+        of each texel's own byte, on the device (vr_remap): the brush is
+        :meth:`paint`'s, with the value of a texel's channel c read from
+        ``lut[c, old byte]`` -- levels, invert, threshold, posterise
+        (:func:`lut_levels`, :func:`lut_compose`), stretch and equalise
+        (:func:`stats_lut`, :meth:`stats_lut`).  `lut` is a (4, 256) uint8 numpy
+        array, copied during the call (vr_remap: it may be overwritten as soon
+        as this returns), or a contiguous CUDA uint8 tensor of 1024 elements
+        (4-byte aligned), read when the kernel runs (vr_remap_device: a table
+        written earlier on `stream` is the one applied, and the tensor must
+        stay alive until then).  Bit for bit what :func:`brush_remap_apply`
+        gives on the host.  Returns ``(origin, extent)`` of the clipped
+        bounding box it rewrote, or None when the brush misses the volume, and
+        queues on `stream` as :meth:`paint` does: one launch, no scratch, no
+        host wait."""
+        b = make_brush(centre, radius, op, falloff, 0, strength)
+        if isinstance(lut, torch.Tensor):
+            if (not lut.is_cuda or lut.device.index != self.device or lut.dtype != torch.uint8
+                    or lut.numel() != LUT_BYTES or not lut.is_contiguous()):
+                raise ValueError(f"remap: a device table is a contiguous uint8 tensor of {LUT_BYTES} elements on cuda:{self.device}")
+            call("vr_remap_device", self._ctx, ctypes.byref(b), ctypes.c_void_p(lut.data_ptr()), _stream_handle(stream))
+        else:
+            s = _lut_struct("remap", lut)
+            call("vr_remap", self._ctx, ctypes.byref(b), ctypes.byref(s), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return brush_box(b, self.volume_dims())
+
+    def stats_lut(self, stats_tensor, kind: int, channels: int = 0xF, stream=None, out=None):
+        """A table from the histograms of a device vr_volume_stats, on the device
+        (vr_stats_lut_device): `stats_tensor` is what :meth:`brush_stats` /
+        :meth:`box_stats` wrote with `out` (a CUDA uint8 tensor of 8240 bytes,
+        8-byte aligned); the result -- bit for bit :func:`stats_lut`'s -- goes
+        to `out`, a contiguous CUDA uint8 tensor of 1024 elements (4-byte
+        aligned; default: a new one shaped (4, 256)), which is returned and is
+        what :meth:`remap` takes.  One launch queued on `stream`, nothing
+        waits: ``brush_stats -> stats_lut -> remap -> update_footprint ->
+        render_rect`` runs on one stream with no host round trip.  No volume
+        is needed."""
+        dev = torch.device("cuda", self.device)
+        if (not isinstance(stats_tensor, torch.Tensor) or not stats_tensor.is_cuda or stats_tensor.device.index != self.device
+                or stats_tensor.dtype != torch.uint8 or stats_tensor.numel() != VOLUME_STATS_BYTES
+                or not stats_tensor.is_contiguous()):
+            raise ValueError(f"stats_lut: stats must be a contiguous uint8 tensor of {VOLUME_STATS_BYTES} bytes on cuda:{self.device}")
+        if out is None:
+            out = torch.empty((4, 256), dtype=torch.uint8, device=dev)
+        elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != self.device
+                or out.dtype != torch.uint8 or out.numel() != LUT_BYTES or not out.is_contiguous()):
+            raise ValueError(f"stats_lut: out must be a contiguous uint8 tensor of {LUT_BYTES} elements on cuda:{self.device}")
+        call("vr_stats_lut_device", self._ctx, ctypes.c_void_p(stats_tensor.data_ptr()), int(kind), int(channels),
+             ctypes.c_void_p(out.data_ptr()), _stream_handle(stream))
+        return out
 
     def get_volume_box(self, origin, extent, out=None, stream=None):
         """The texel box `extent` = (bx, by, bz) at `origin` = (x0, y0, z0) of the
