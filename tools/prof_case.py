@@ -72,7 +72,7 @@ def main():
                 r.render(a.width, a.height, vr.FMT_RGBA8_UNORM, out=out)
         torch.cuda.synchronize()
         print("variant", r.kernel_variant, "schedule", r.get_option("schedule"), "pair_launches", r.get_option("pair_launches"),
-              "group_launches", r.get_option("group_launches"))
+              "group_launches", r.get_option("group_launches"), "quad_launches", r.get_option("quad_launches"))
 
 
 if __name__ == "__main__":

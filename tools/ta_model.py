@@ -7,7 +7,11 @@ line among the quad's active lanes.  Also: distinct lines per wave
 instruction (what an LDS-staged fill would have to fetch) and the 16-B chunks
 of a tile's per-step bounding box.
 
-    python tools/ta_model.py [--layout brick4832] [--quad 2x2|4x1|1x4] [--tiles K]
+    python tools/ta_model.py [--layout brick4832] [--quad 2x2|4x1|1x4|frames] [--tiles K]
+
+--quad frames is the QUAD kernels' map: a wave is one 4x4-pixel
+quadrant of a tile for four frames of one camera, lane l = frame l & 3 at the pixel
+((l >> 2) & 3, l >> 4), so the four lanes of a quad hold one ray.
 
 Geometry: frag.glsl:42-55 (step counts, box-normalised points), taps at
 scales 1/.8/.75/.7 (frag.glsl:66-69), padded base a = floor(P*s*N + .5).
@@ -101,6 +105,8 @@ def main():
         lx, ly = ((lane >> 2) & 3) * 2 + (lane & 1), (lane >> 4) * 2 + ((lane >> 1) & 1)
     elif args.quad == "4x1":
         lx, ly = lane & 7, lane >> 3
+    elif args.quad == "frames":   # 16 pixels x 4 equal frames; the quadrant is added below
+        lx, ly = (lane >> 2) & 3, lane >> 4
     else:  # 1x4: four rows of one column
         lx, ly = (lane >> 2) & 7, (lane >> 5) * 4 + (lane & 3)
     T = np.arange(tx8 * ty8)
@@ -108,6 +114,9 @@ def main():
         T = T[::args.tiles]
     X = (T % tx8)[:, None] * 8 + lx[None, :]
     Y = (T // tx8)[:, None] * 8 + ly[None, :]
+    if args.quad == "frames":   # the four waves of a workgroup: the tile's quadrants (w & 1, w >> 1)
+        X = np.concatenate([X + 4 * (w & 1) for w in range(4)])
+        Y = np.concatenate([Y + 4 * (w >> 1) for w in range(4)])
     ok = Y < H
     Y = np.minimum(Y, H - 1)
     nn = np.where(ok, n[Y, X], 0)
@@ -126,7 +135,7 @@ def main():
     else:
         off = brick_offset(args.layout)
         span = 8
-    look = insts = lines_w = steps = 0
+    look = insts = lines_w = steps = quads = 0
     bbox_chunks = 0
     for i in range(S):
         act = i < nn
@@ -153,6 +162,7 @@ def main():
                 q = np.sort(np.concatenate([ln.reshape(len(ln), 16, 4), ln2.reshape(len(ln), 16, 4)], -1), axis=-1)
                 new = np.concatenate([q[..., :1] >= 0, (q[..., 1:] != q[..., :-1]) & (q[..., 1:] >= 0)], -1)
                 look += new.sum()
+                quads += (ln.reshape(len(ln), 16, 4) >= 0).any(-1).sum()
                 w = np.sort(ln, axis=-1)
                 lines_w += (np.concatenate([w[:, :1] >= 0, (w[:, 1:] != w[:, :-1]) & (w[:, 1:] >= 0)], -1)).sum()
                 insts += len(ln)
@@ -167,6 +177,8 @@ def main():
           f"{insts * 64 / steps:.2f} lane loads/step (incl. idle lanes)")
     per_step = insts / (steps / 64) if steps else 0
     print(f"  L1 lookups per instruction {look / insts:.2f}, per wave-step {look / insts * (16 if args.b32 else 8):.1f}")
+    if quads:   # a quad whose rays have all ended costs no lookup: per instruction = this x the quads still marching
+        print(f"  L1 lookups per quad with an active lane {look / quads:.3f}, such quads per instruction {quads / insts:.2f}")
     print(f"  distinct 128-B lines per instruction (wave) {lines_w / insts:.2f}")
     print(f"  planar bbox 16-B chunks per tap-step {bbox_chunks / (insts / 2):.1f} "
           f"(= {bbox_chunks / (insts / 2) / 64:.2f} b128 wave loads)")

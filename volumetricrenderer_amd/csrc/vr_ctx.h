@@ -278,6 +278,9 @@ struct Ctx {
     int frame_group = 4;           // option "frame_group": frames per launch of that loop where frame_pairing is on, 2 or
                                    // 4 (measured)
     long long group_launches = 0;  // read-only option "group_launches": four-frame launches so far (vr_render_group)
+    int frame_quad = 1;            // option "frame_quad": a four-frame launch whose frames share one camera
+                                   // (frames_share_camera) takes the QUAD kernels; 0 = the kernel of every other group
+    long long quad_launches = 0;   // read-only option "quad_launches": QUAD launches so far
     uint2* d_lat = nullptr;
     size_t lat_cap = 0;            // bytes allocated
     long long lat_key[3] = {0, 0, -1};

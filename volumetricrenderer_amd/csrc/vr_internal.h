@@ -266,6 +266,17 @@ constexpr int u_kernel_channel(bool early, bool zero_offsets, int umask)
     return umask == 1 ? 0 : umask == 2 ? 1 : umask == 4 ? 2 : umask == 8 ? 3 : -1;
 }
 
+// The kernels with a QUAD instance (four frames of one camera in the lanes of a quad,
+// vr_march_kernels.h regions_frames_body): every multi-frame kernel but the general one of
+// COL48 / BRICK4832 with zero offsets and no early-out, whose QUAD instance needs 97 VGPRs
+// where the NF = 4 one needs 96 and so loses a wave per SIMD; its
+// launches keep the NF = 4 kernel until the trade is measured.
+constexpr bool quad_instance(int layout, bool early, bool zero_offsets, int umask)
+{
+    if (u_kernel_channel(early, zero_offsets, umask) >= 0) return true;   // the _u kernels
+    return !(is_b4_family(layout) && !early && zero_offsets);
+}
+
 // The part of MarchArgs that differs between the frames of one multi-frame launch
 // (vr_render_pair, vr_render_group): the camera (ray basis, r2 / r3, cam, tap_T), the
 // target buffer, the empty-tile fill and the step counter -- what vr_render.cpp's
@@ -315,6 +326,27 @@ struct FramesArgs {
     FrameArgs fr[NF];
 };
 using GroupArgs = FramesArgs<kGroupFrames>;
+// The frames of a four-frame launch share one camera: fr[1..3] equal fr[0] bit for bit in
+// every field but the target buffer and the step counter, so one ray serves a pixel of all
+// four (the QUAD kernels).  Every field is named in the bindings below: one added to
+// FrameArgs does not compile here until it is classified as compared or per-frame.
+inline bool frames_share_camera(const FrameArgs* fr, int n)
+{
+    if (n != kGroupFrames) return false;
+    const auto& [org0, o0, px0, py0, r20, r30, cam_mode0, cam0, tap_T0, empty_fill0, out0, step_counter0] = fr[0];
+    (void)out0; (void)step_counter0;   // per frame
+    for (int k = 1; k < n; ++k) {
+        const auto& [org, o, px, py, r2, r3, cam_mode, cam, tap_T, empty_fill, out, step_counter] = fr[k];
+        (void)out; (void)step_counter;   // per frame
+#define VR_SAME(A, B) (sizeof(A) == sizeof(B) && __builtin_memcmp(&(A), &(B), sizeof(A)) == 0)
+        if (!(VR_SAME(org, org0) && VR_SAME(o, o0) && VR_SAME(px, px0) && VR_SAME(py, py0) && VR_SAME(r2, r20) &&
+              VR_SAME(r3, r30) && VR_SAME(cam_mode, cam_mode0) && VR_SAME(cam, cam0) && VR_SAME(tap_T, tap_T0) &&
+              VR_SAME(empty_fill, empty_fill0)))
+            return false;
+#undef VR_SAME
+    }
+    return true;
+}
 static_assert(sizeof(FramesArgs<2>) + 64 <= 4096 && sizeof(GroupArgs) + 64 <= 4096,
               "one MarchArgs, the FrameArgs and the lists' pointers travel in the 4-KiB kernarg segment");
 
@@ -485,10 +517,12 @@ hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, co
 // regions schedule with one lane per ray (no split, no slab, 4-wave workgroups); deal
 // (nf = 2 only) 0 = the frame in the wave's parity, 1 = in the workgroup's (vr_march_kernels.h)
 constexpr bool pair_layout(int layout) { return list_has(FrameLayouts{}, layout); }
+// quad (nf = 4, frames_share_camera(fr, nf) and no step counter only): the kernels' QUAD
+// instance, the four frames in the lanes of a quad (vr_march_kernels.h regions_frames_body)
 hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
-                               int deal, hipStream_t s);
+                               int deal, bool quad, hipStream_t s);
 hipError_t launch_march_frames_cornerh(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc,
-                                       int deal, hipStream_t s);   // vr_march_c8.hip
+                                       int deal, bool quad, hipStream_t s);   // vr_march_c8.hip
 // per-plane byte min (mm[0..3]) and max (mm[4..7]) of the planar volume; mm
 // must hold 0xffffffff x 4 then 0 x 4 (atomicMin / atomicMax)
 hipError_t launch_plane_minmax(const uint8_t* d_planar, long long total, unsigned* mm, hipStream_t s);

@@ -136,13 +136,13 @@ hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, co
 }
 
 hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
-                               int deal, hipStream_t s)
+                               int deal, bool quad, hipStream_t s)
 {
     if (a.width <= 0 || a.out_rows <= 0) return hipSuccess;
     // a layout without a multi-frame kernel is an error: the caller renders the frames one by one
     return with_layout<FrameLayouts>(layout, [&](auto L) {
-        if constexpr (list_has(CornerLayouts{}, L)) return launch_march_frames_cornerh(a, fr, nf, early, sc, deal, s);   // vr_march_c8.hip
-        else return launch_frames_l<L, WRAP_CLAMP>(a, fr, nf, early, sc, deal, s);
+        if constexpr (list_has(CornerLayouts{}, L)) return launch_march_frames_cornerh(a, fr, nf, early, sc, deal, quad, s);   // vr_march_c8.hip
+        else return launch_frames_l<L, WRAP_CLAMP>(a, fr, nf, early, sc, deal, quad, s);
     });
 }
 

@@ -578,11 +578,21 @@ __global__ __launch_bounds__(kThreads) void march_regions_u(const MarchArgs a, c
 //                 entry waves x 2 frames, both readers on one CU (L1 and L2)
 //   NF 2, deal 1: f = the workgroup's parity on its XCD -- a workgroup keeps 4 consecutive
 //                 entry waves (the 2x2 supertile) of one frame; L2 only (option pair_deal)
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF>
+//   NF 4, QUAD:   frames whose cameras the host has proved equal (vr_internal.h
+//                 frames_share_camera).  The four waves of workgroup g
+//                 all take entry wave g's entries; wave w marches the 4x4-pixel quadrant
+//                 (w & 1, w >> 1) of the 8x8 tile, and lane l is frame l & 3 at the pixel
+//                 ((l >> 2) & 3, l >> 4) of it.  The four lanes of a quad -- the unit the
+//                 texture addresser looks a b64 load up by -- march one ray and present one
+//                 address, where four waves used to present it one after the other.  The ray
+//                 runs on the common arguments; a lane's own part is its target pointer.
+//                 Steps are not counted: the host sends a counted launch down the NF 4 path.
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false>
 __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, const unsigned* __restrict__ tiles,
                                                     const int* __restrict__ hdr, int nwx, int deal, unsigned* lds)
 {
     static_assert(NF == 2 || NF == 4, "a 4-wave workgroup is 4 / NF entry waves x NF frames");
+    static_assert(!QUAD || NF == 4, "a quad of lanes is four frames");
     const int xcd = blockIdx.x & 7, wg = (int)(blockIdx.x >> 3);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int fr = wave, first = wg, w = wg;   // the frame, the workgroup's first entry wave, this wave's
@@ -593,7 +603,7 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
     }
     const int begin = hdr[xcd], all = hdr[xcd + 1] - begin;
     const int marched = min(hdr[kRegionWork + xcd], all);
-    MarchArgs a = g.c;
+    MarchArgs a = g.c;   // this wave's frame (QUAD: the fill's wave = frame set only; the march's is q below)
     set_frame(&a, g.fr[fr]);
     const int count = a.empty_fill ? marched : all;
     if (a.empty_fill) fill_empty_tiles(a, tiles, begin, count, all, w, nwx);
@@ -601,9 +611,28 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
     for (int k = 1; k < NF; ++k) every = every && g.fr[k].empty_fill;
     if (first >= (every ? marched : all)) return;   // whole workgroup, before the barrier
     FastCtx f = fast_prologue<LAYOUT>(g.c, lds);   // volume and layout geometry: the frames' common part
+    const int lane = threadIdx.x & 63;
+    if constexpr (QUAD) {
+        // fr[0..3] equal the common part in all but the target and the counter: the ray and
+        // the prologue (CORNERH's oz too) are the common part's, in SGPRs
+        MarchArgs q = g.c;
+        const int fl = lane & 3;
+        void* out = g.fr[0].out;
+        for (int k = 1; k < NF; ++k) out = fl == k ? g.fr[k].out : out;
+        q.out = out;
+        const int qx = (wave & 1) * 4 + ((lane >> 2) & 3), qy = (wave >> 1) * 4 + (lane >> 4);
+        const int qcount = g.c.empty_fill ? marched : all;
+        // no step count: a launch with a step counter takes the other instance (render_frames),
+        // which keeps the two VGPRs of the per-lane sum out of this one
+        for (int k = wg; wg < nwx && k < qcount; k += nwx) {
+            const unsigned t = tiles[begin + k];
+            const int tx = (int)(t & 0xffffu), ty = (int)(t >> 16);
+            (void)march_pixel<LAYOUT, WRAP, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy);
+        }
+        return;
+    }
     if constexpr (LAYOUT == LAYOUT_CORNERH)   // the one per-frame part of the prologue
         for (int c = 0; c < 4; ++c) f.oz[c] = noise::in_vgpr(a.tap_T[c][2]);
-    const int lane = threadIdx.x & 63;
     unsigned long long steps = 0;
     for (int k = w; w < nwx && k < count; k += nwx) {
         const unsigned t = tiles[begin + k];
@@ -613,19 +642,19 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
     }
     if (a.step_counter) add_steps(a, steps);
 }
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF>
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF, bool QUAD = false>
 __global__ __launch_bounds__(kThreads) void march_regions_frames(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
                                                                 const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF, QUAD>(g, tiles, hdr, nwx, deal, lds);
 }
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF>
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false>
 __global__ __launch_bounds__(kThreads) void march_regions_frames_u(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
                                                                   const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF, QUAD>(g, tiles, hdr, nwx, deal, lds);
 }
 
 
@@ -900,10 +929,15 @@ hipError_t launch_lw(const MarchArgs& a, bool early, const Schedule& sc, hipStre
 // arguments (vr_render.cpp), that sc is a regions schedule without split, slab or wide
 // workgroups, and that L is one of FrameLayouts.  XCD x runs
 // sc.map.nwx entry waves, 4 / NF to a workgroup (regions_frames_body).
+// quad: the QUAD instance (nf = 4 only; the caller has proved frames_share_camera) -- the same grid.
 template <int L, int W>
-hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc, int deal, hipStream_t s)
+hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc, int deal, bool quad,
+                           hipStream_t s)
 {
-    return with_value<2, kGroupFrames>(nf, [&](auto NF) {
+    if (quad && (nf != kGroupFrames || !quad_instance(L, early, a.zero_offsets != 0, a.umask)))
+        return hipErrorInvalidValue;   // no such kernel
+    return with_value<2, kGroupFrames>(nf, [&](auto NF) { return with_bool(quad, [&](auto QD) {
+        constexpr bool Q = decltype(QD)::value && decltype(NF)::value == kGroupFrames;   // instantiated for NF = 4 only
         FramesArgs<NF> g;
         g.c = a;
         for (int k = 0; k < NF; ++k) g.fr[k] = fr[k];
@@ -916,14 +950,15 @@ hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool
         const dim3 grid((unsigned)(NF == 4 ? 8 * nwx : dl ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
         if (u_kernel_channel(early, a.zero_offsets, a.umask) >= 0)
             return with_value<1, 2, 4, 8>(a.umask, [&](auto U) {
-                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF, Q>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
                 return hipGetLastError();
             }, hipErrorInvalidValue);
         return with_bool(early, [&](auto E) { return with_bool(a.zero_offsets, [&](auto Z) {
-            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+            constexpr bool QG = Q && quad_instance(L, decltype(E)::value, decltype(Z)::value, 0);
+            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF, QG>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
             return hipGetLastError();
         }); });
-    }, hipErrorInvalidValue);   // no kernel for this many frames
+    }); }, hipErrorInvalidValue);   // no kernel for this many frames
 }
 
 }  // namespace

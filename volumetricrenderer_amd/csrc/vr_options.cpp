@@ -79,6 +79,11 @@ try {
         c->pair_deal = value;
         return VR_OK;
     }
+    if (n == "frame_quad") {   // four frames of one camera in the lanes of a quad (vr_render_group)
+        if (value < 0 || value > 1) return fail(VR_ERR_INVALID, "vr_set_option: frame_quad is 0 or 1");
+        c->frame_quad = value;
+        return VR_OK;
+    }
     if (n == "inject_throw") {   // test hook: the next vr_render throws in its host path
         if (value < 0 || value > 2)
             return fail(VR_ERR_INVALID, "vr_set_option: inject_throw is 0, 1 (std::runtime_error) or 2 (std::bad_alloc)");
@@ -274,6 +279,8 @@ try {
     if (n == "frame_group") return c->frame_group;
     if (n == "group_launches") return (int)std::min<long long>(c->group_launches, 0x7fffffff);
     if (n == "pair_launches") return (int)std::min<long long>(c->pair_launches, 0x7fffffff);
+    if (n == "frame_quad") return c->frame_quad;
+    if (n == "quad_launches") return (int)std::min<long long>(c->quad_launches, 0x7fffffff);
     if (n == "launch_cache_hits") return (int)std::min<long long>(c->lc_hits, 0x7fffffff);
     if (n == "experiments") return VR_EXPERIMENTS;   // read-only: the measured-slower variants are built
     if (n == "region_interval") return c->region_interval;

@@ -386,7 +386,15 @@ vr_status render_frames(void* p, const vr_target* t, int n, const vr_object_shad
     }
     Schedule sc = f[0].sc;
     if (f[0].a.empty_fill && !every) sc.map.nwx = std::max(1, rb.map.nwx);
-    HIP_TRY(launch_march_frames(f[0].a, fr, n, f[0].pl.layout, f[0].pl.early, sc, c->pair_deal, hs));
+    // four frames of one camera (the static-camera frame loop): the QUAD instance, one ray per
+    // pixel for all four; every other group launches the kernel it always did.  The QUAD
+    // instance counts no steps (the per-lane sum's registers would cost it a wave per SIMD),
+    // so a counted launch is one of those others
+    bool quad = c->frame_quad && frames_share_camera(fr, n) &&
+                quad_instance(f[0].pl.layout, f[0].pl.early, f[0].a.zero_offsets != 0, f[0].a.umask);
+    for (int k = 0; k < n; ++k) quad = quad && !fr[k].step_counter;
+    HIP_TRY(launch_march_frames(f[0].a, fr, n, f[0].pl.layout, f[0].pl.early, sc, c->pair_deal, quad, hs));
+    c->quad_launches += quad;
     c->group_launches += n == VR_MAX_GROUP;
     c->pair_launches += n / 2;   // (pairs of frames that shared a launch)
     c->renders_since_build += n - 1;   // the later renders with these lists (build_regions counted the first)
