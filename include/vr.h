@@ -458,6 +458,58 @@ vr_status vr_morph(void* ctx, const vr_brush* brush, int op, int half_width, voi
 vr_status vr_brush_morph_apply(const vr_brush* brush, int op, int half_width,
                                uint8_t* rgba8, int nx, int ny, int nz);
 
+/* The median / rank-filter brush: it removes speckle
+ * under the brush and leaves edges where they are.  vr_rank is a VR_BRUSH_SET
+ * brush whose value, per texel and channel, is the RANK-TH SMALLEST byte of
+ * that channel over the texel's neighbourhood AS IT WAS BEFORE THE CALL.  In
+ * integers, with h = half_width in 1..VR_RANK_MAX_HALF and N = (2h + 1)^3 (27,
+ * 125, 343): for a texel t inside the ellipsoid and the volume (the inside
+ * test and the weight w are the brush's, above) and a channel c with
+ * strength[c] != 0,
+ *   m   = the rank-th smallest (0-based) of the N bytes of channel c at
+ *         offsets -h..h per axis from t, coordinates clamped to the volume
+ *         (clamp-to-edge), so a clamped texel counts once for every offset
+ *         that lands on it; neighbours outside the brush's box are read like
+ *         any other.  Equivalently m is the largest byte v with
+ *         #{neighbours < v} <= rank, which is how it is computed (bisection
+ *         on the byte from bit 7 down, csrc/vr_rank.h): ties need no rule
+ *   new = (old (65280 - a) + m a + 32640) / 65280,  a = w * strength[c]
+ * -- the SET blend, unchanged.  rank is 0..N - 1, or VR_RANK_MEDIAN for
+ * (N - 1) / 2 = 13, 62, 171.  brush->op must be VR_BRUSH_SET; brush->value is
+ * not read; a channel with strength 0 is neither read nor written.  Every m is
+ * taken from the bytes before the call, whatever the order in which texels are
+ * processed (a Jacobi step), so the host statement and the device agree bit
+ * for bit.  Rank 0 is vr_morph's VR_MORPH_ERODE and rank N - 1 its
+ * VR_MORPH_DILATE, bit for bit.  A channel whose texels are all equal has
+ * m = old everywhere: vr_rank never breaks a uniform channel.
+ *
+ * Device path: vr_blur's and vr_morph's -- a stage launch from the planes to
+ * the context's staging scratch (a rank is not separable, so this stage
+ * selects over the whole cube), vr_blur's commit launch, the layout rebuild
+ * over the clipped box (vr_brush_box names it) and the uniform-channel re-arm.
+ * The scratch is the one vr_blur and vr_morph share: same need, same growth
+ * rule (device synchronisation, whole MiB, VR_ERR_OOM holds nothing and leaves
+ * the volume untouched), same option "blur_scratch_kib".  Every call within
+ * what is held allocates nothing and never waits on the host, so pick ->
+ * vr_rank -> vr_update_footprint -> vr_render_rect queue on one stream.  Calls
+ * of one ctx on DIFFERENT streams share the scratch: they are the caller's to
+ * order.
+ * VR_ERR_INVALID: a null pointer, anything vr_paint refuses, brush->op other
+ * than VR_BRUSH_SET, half_width outside 1..VR_RANK_MAX_HALF, rank outside
+ * 0..N - 1 and not VR_RANK_MEDIAN; VR_ERR_NO_VOLUME before an install and
+ * while a procedural medium is enabled.  A brush that misses the volume, or
+ * whose strengths are all 0, is VR_OK and launches nothing.  A refused call
+ * has launched nothing and leaves the volume untouched.                     */
+#define VR_RANK_MAX_HALF 3
+#define VR_RANK_MEDIAN (-1)
+vr_status vr_rank(void* ctx, const vr_brush* brush, int rank, int half_width, void* stream);
+/* The same on a HOST RGBA8 volume (x fastest): the CPU statement, which
+ * vr_rank reproduces bit for bit.  It works from a copy of the clipped box and
+ * its halo, never in place.  Pure host code.  VR_ERR_INVALID as above, and for
+ * a non-positive dimension; a refused call leaves the array as it was.      */
+vr_status vr_brush_rank_apply(const vr_brush* brush, int rank, int half_width,
+                              uint8_t* rgba8, int nx, int ny, int nz);
+
 /* Brushes whose value is read from texels: the clone
  * stamp, push / smudge, mirror (vr_clone) and the paste of a block with a soft
  * edge (vr_stamp).  A SOURCE BRUSH is a vr_brush used as vr_paint uses it: the

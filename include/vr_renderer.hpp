@@ -77,6 +77,13 @@ inline void BrushMorphApply(const vr_brush& brush, int op, int half_width, uint8
     Check(vr_brush_morph_apply(&brush, op, half_width, rgba, nx, ny, nz), "vr_brush_morph_apply");
 }
 
+// The median / rank-filter brush on a host RGBA8 volume (vr_brush_rank_apply):
+// the CPU statement of Renderer::Rank.  Host code only.
+inline void BrushRankApply(const vr_brush& brush, int rank, int half_width, uint8_t* rgba, int nx, int ny, int nz)
+{
+    Check(vr_brush_rank_apply(&brush, rank, half_width, rgba, nx, ny, nz), "vr_brush_rank_apply");
+}
+
 // The clone brush on a host RGBA8 volume (vr_brush_clone_apply): the CPU
 // statement of Renderer::Clone.  Host code only.
 inline void BrushCloneApply(const vr_brush& brush, const vr_clone_map& map, uint8_t* rgba, int nx, int ny, int nz)
@@ -176,6 +183,15 @@ public:
     void Morph(const vr_brush& brush, int op, int half_width = 1, void* stream = nullptr)
     {
         Check(vr_morph(ctx_, &brush, op, half_width, stream), "vr_morph");
+    }
+    // Remove speckle under the brush and keep edges where they are (vr_rank):
+    // a SET brush whose value is the rank-th smallest byte (VR_RANK_MEDIAN:
+    // the median) of each texel's (2 half_width + 1)^3 cube as it was before
+    // the call; brush.op must be VR_BRUSH_SET.  Queued on `stream` as Blur is,
+    // through the same staging scratch.
+    void Rank(const vr_brush& brush, int rank = VR_RANK_MEDIAN, int half_width = 1, void* stream = nullptr)
+    {
+        Check(vr_rank(ctx_, &brush, rank, half_width, stream), "vr_rank");
     }
     // Paint under the brush with the volume's own texels from elsewhere
     // (vr_clone): the value of texel t is the texel at t + map.offset (per

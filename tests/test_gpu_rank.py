@@ -1,0 +1,363 @@
+"""vr_rank on the GPU: the rank-filtered volume against the numpy restatement
+(tests/rank_spec.py), byte for byte, on both of its inputs; volumes that cut
+the stage kernel's tiles; ranks 0 and N - 1 against vr_morph; the edited
+context's frame against a fresh install of the specification's volume and
+against the CPU oracle, per layout; a median and a render_rect queued on one
+side stream; uniform channels; the staging scratch it shares with vr_blur and
+vr_morph; undo; refusals.  Everything is exact.
+
+The volumes are rank_spec's (37 x 22 x 45: the ramp with noise of the morph
+tests and a four-byte volume full of ties); frame, march and cameras are
+test_gpu_paint.py's: the reference camera at 64 x 64, 32 steps.
+"""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import blur_spec as bs  # noqa: E402
+import morph_spec as ms  # noqa: E402
+import paint_spec as ps  # noqa: E402
+import rank_spec as rs  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+if torch.cuda.is_available():
+    import volumetricrenderer_amd as vr
+from volumetricrenderer_amd import _lib  # noqa: E402
+from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
+
+NX, NY, NZ = ps.NX, ps.NY, ps.NZ
+W = H = 64
+STEPS = 32
+LAYOUTS = [(1, "planar"), (5, "corner8"), (12, "brick4832"), (14, "cornerh"), (15, "col48")]
+LAYOUT_IDS = [n for _, n in LAYOUTS]
+UNIFORM_LAYOUTS = [(12, "brick4832"), (14, "cornerh"), (15, "col48")]
+VOLUME_BRUSHES = ["interior", "texel", "corner", "outside_centre", "straddle", "whole", "max", "miss"]
+FULL = rs.FULL
+MEDIAN = rs.MEDIAN
+STRENGTHS = [(rs.STRENGTH, "mixed"), (FULL, "full")]
+INPUT_IDS = [n for n, _ in rs.INPUTS]
+
+_oracle_frames = {}
+
+
+def oracle_frame(oracle, vol, angles=(0.0, 0.0), density=1.0):
+    """The oracle's frame and executed steps for `vol`, computed once per (volume, camera, density)."""
+    osd, gsd = vr.reference_shader_data(1.0, *angles)
+    obj, glob = vr.shader_data_arrays(osd, gsd)
+    key = (hash(vol.tobytes()), angles, density)
+    if key not in _oracle_frames:
+        _oracle_frames[key] = oracle.render(vol, obj, glob, oracle.march(STEPS, density=density), W, H, FMT_RGBA32F)
+    return _oracle_frames[key]
+
+
+@pytest.fixture(scope="module")
+def inputs():
+    return {name: make() for name, make in rs.INPUTS}
+
+
+@pytest.fixture(scope="module")
+def base(inputs):
+    return inputs["ramp"]
+
+
+@pytest.fixture(scope="module")
+def r():
+    with vr.Renderer(0) as rr:
+        yield rr
+        rr.set_layout_preference(0)
+
+
+@pytest.fixture(scope="module")
+def fresh():
+    with vr.Renderer(0) as rr:
+        yield rr
+
+
+def setup(rr, pref, vol, angles=(0.0, 0.0), density=1.0):
+    rr.set_option("uniform_skip", 1)
+    rr.set_layout_preference(pref)
+    rr.set_volume(vol)
+    rr.set_shader_data(*vr.reference_shader_data(1.0, *angles))
+    rr.set_march(vr.march_defaults(max_steps=STEPS, density=density))
+
+
+def frame(rr, stream=None):
+    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+    img = rr.render(W, H, FMT_RGBA32F, step_counter=cnt, stream=stream)
+    torch.cuda.synchronize()
+    return img.cpu().numpy(), int(cnt.item())
+
+
+def assert_marches(rr, name):
+    """The intended layout really marches: a silent planar fallback must not pass."""
+    assert rr.kernel_variant.startswith(f"grid_{name}_clamp"), rr.kernel_variant
+
+
+def assert_exact(img, ref):
+    assert img.shape == ref.shape
+    bad = np.argwhere(img != ref)
+    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
+
+
+def rank(rr, name, k, h, falloff, strength=rs.STRENGTH, stream=None):
+    centre, radius = ps.BRUSHES[name]
+    return rr.rank(centre, radius, k, h, falloff, strength, stream=stream)
+
+
+# ---- 1. the edited volume is the specification's ----------------------------------------------
+@pytest.mark.parametrize("iname", INPUT_IDS)
+@pytest.mark.parametrize("strength,sname", STRENGTHS, ids=[n for _, n in STRENGTHS])
+@pytest.mark.parametrize("falloff,fname", ps.FALLOFFS, ids=[n for _, n in ps.FALLOFFS])
+@pytest.mark.parametrize("h", rs.HALF_WIDTHS)
+@pytest.mark.parametrize("name", VOLUME_BRUSHES)
+def test_ranked_volume_equals_the_specification(r, inputs, name, h, falloff, fname, strength, sname, iname):
+    vol = inputs[iname]
+    r.set_layout_preference(14)
+    centre, radius = ps.BRUSHES[name]
+    for k in (MEDIAN, 0, rs.window(h) - 1):
+        r.set_volume(vol)
+        assert r.rank(centre, radius, k, h, falloff, strength) == ps.spec_box(centre, radius)
+        want = rs.spec_rank(vol, centre, radius, k, h, falloff, strength)
+        if name == "miss":
+            assert (want == vol).all()
+        elif name != "texel":   # one texel may hold its own rank-th byte
+            assert (want != vol).any()
+        assert_exact(r.get_volume(), want)
+    if iname == "ramp" and strength is FULL:   # the host statement once per brush, half width and falloff
+        assert_exact(vr.brush_rank_apply(vr.make_brush(centre, radius, 0, falloff, 0, strength), MEDIAN, h, vol.copy()),
+                     rs.spec_rank(vol, centre, radius, MEDIAN, h, falloff, strength))
+
+
+# ---- 2. volumes that cut the stage kernel's tiles ----------------------------------------------
+@pytest.mark.parametrize("where", ["whole", "corner"])
+@pytest.mark.parametrize("dims", [(150, 9, 7), (5, 4, 2), (33, 17, 9)], ids=["150x9x7", "5x4x2", "33x17x9"])
+def test_tile_edges(r, dims, where):
+    """Rows longer than four 32-texel tiles with y and z smaller than a tile; a volume smaller than the window on
+    every axis; one texel more than the 32 x 8 x 8 tile on every axis.  The largest brush covers each whole, and
+    one centred on the far corner leaves tiles partly and wholly outside the ellipsoid; h = 3, the median."""
+    nx, ny, nz = dims
+    rng = np.random.default_rng(nx * 1000 + ny)
+    z, y, x, c = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), np.arange(4), indexing="ij")
+    vol = (((5 * x + 7 * y + 11 * z + 50 * c) % 200) + rng.integers(0, 56, size=(nz, ny, nx, 4))).astype(np.uint8)
+    if where == "whole":
+        centre, radius = (nx // 2, ny // 2, nz // 2), (255, 255, 255)
+    else:
+        centre, radius = (nx - 1, ny - 1, nz - 1), (max(2, (2 * nx) // 3), max(2, ny - 2), max(2, nz - 2))
+    inside, _ = ps.spec_weights(vol.shape[:3], centre, radius, 0)
+    assert inside.all() if where == "whole" else (inside.any() and not inside.all())
+    for falloff in (0, 1):
+        r.set_layout_preference(0)
+        r.set_volume(vol)
+        assert r.rank(centre, radius, MEDIAN, 3, falloff, FULL) == ps.spec_box(centre, radius, dims)
+        want = rs.spec_rank(vol, centre, radius, MEDIAN, 3, falloff, FULL)
+        assert (want != vol)[inside].mean() > (0.0 if falloff else 0.5)   # a smooth rim may round to the old byte
+        assert_exact(r.get_volume(), want)
+
+
+@pytest.mark.parametrize("h", rs.HALF_WIDTHS)
+def test_tiles_outside_the_ellipsoid(r, base, h):
+    """An ellipsoid inscribed in the volume: its box is the volume, 2 x 3 x 6 tiles, and the corner tiles hold no
+    texel inside -- they leave before any load -- while their neighbours are cut by the rim."""
+    centre, radius = (18, 11, 22), (18, 11, 22)
+    inside, _ = ps.spec_weights(base.shape[:3], centre, radius, 0)
+    assert not inside[40:, 16:, 32:].any() and not inside[:8, :8, 32:].any() and inside[:8, :8, :32].any()
+    for falloff in (0, 1):
+        r.set_layout_preference(0)
+        r.set_volume(base)
+        assert r.rank(centre, radius, MEDIAN, h, falloff, FULL) == ((0, 0, 0), (NX, NY, NZ))
+        assert_exact(r.get_volume(), rs.spec_rank(base, centre, radius, MEDIAN, h, falloff, FULL))
+
+
+# ---- 3. the first and the last rank are the morph's erode and dilate ---------------------------
+@pytest.mark.parametrize("h", rs.HALF_WIDTHS)
+def test_first_and_last_rank_are_erode_and_dilate(r, base, h):
+    r.set_layout_preference(0)
+    for name, falloff in (("straddle", 1), ("corner", 0)):
+        for k, op in ((0, ms.ERODE), (rs.window(h) - 1, ms.DILATE)):
+            r.set_volume(base)
+            box = r.morph(*ps.BRUSHES[name], op, h, falloff, rs.STRENGTH)
+            morphed = r.get_volume()
+            assert (morphed != base).any()
+            r.set_volume(base)
+            assert rank(r, name, k, h, falloff) == box
+            assert_exact(r.get_volume(), morphed)
+
+
+# ---- 4. the edited context renders what a fresh install of the specification's volume renders --
+@pytest.mark.parametrize("pref,lname", LAYOUTS, ids=LAYOUT_IDS)
+def test_ranked_render_equals_fresh_install(r, fresh, oracle, base, pref, lname):
+    setup(r, pref, base)
+    assert_marches(r, lname)
+    vol = base
+    for name, k, h in (("straddle", MEDIAN, 2), ("whole", 5, 1)):
+        centre, radius = ps.BRUSHES[name]
+        before, _ = oracle_frame(oracle, vol)
+        vol = rs.spec_rank(vol, centre, radius, k, h, 1)
+        ref, ref_steps = oracle_frame(oracle, vol)
+        assert (ref != before).any(), "the rank filter does not change the oracle's frame"
+        rank(r, name, k, h, 1)
+        assert_marches(r, lname)
+        img, steps = frame(r)
+        assert_exact(img, ref)
+        assert steps == ref_steps
+        assert_exact(r.get_volume(), vol)
+        setup(fresh, pref, vol)
+        assert_marches(fresh, lname)
+        img2, steps2 = frame(fresh)
+        assert_exact(img, img2)
+        assert steps == steps2
+
+
+# ---- 5. one stream, no host wait ---------------------------------------------------------------
+@pytest.mark.parametrize("pref,lname", LAYOUTS, ids=LAYOUT_IDS)
+def test_a_median_then_render_rect_on_a_side_stream(r, oracle, base, pref, lname):
+    """A median of `straddle`, its footprint and the re-render of that rectangle queue on one side stream with one
+    synchronise at the end."""
+    setup(r, pref, base)
+    assert_marches(r, lname)
+    buf = r.render(W, H, FMT_RGBA32F)
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    origin, extent = rank(r, "straddle", MEDIAN, 2, 1, FULL, stream=s)
+    rect = r.update_footprint(origin, extent, W, H)
+    r.render_rect(buf, rect, FMT_RGBA32F, stream=s)
+    s.synchronize()
+    once = rs.spec_rank(base, *ps.BRUSHES["straddle"], MEDIAN, 2, 1, FULL)
+    assert_exact(r.get_volume(), once)
+    want, want_steps = oracle_frame(oracle, once)
+    assert (want != oracle_frame(oracle, base)[0]).any()
+    assert_exact(buf.cpu().numpy(), want)
+    img, steps = frame(r)
+    assert_exact(img, want)
+    assert steps == want_steps
+
+
+# ---- 6. uniform channels on the recipe volume --------------------------------------------------
+@pytest.fixture(scope="module")
+def recipe_volume():
+    with vr.Renderer(0) as rr:
+        rr.generate_volume(vr.volume_recipe_defaults(size=32))
+        vol = rr.get_volume()
+    g = int(vol[0, 0, 0, 1])
+    assert (vol[..., 1] == g).all(), "the recipe's G is not uniform"
+    assert all(len(np.unique(vol[..., c])) > 1 for c in (0, 2, 3))
+    return vol, g
+
+
+@pytest.mark.parametrize("pref,lname", UNIFORM_LAYOUTS, ids=[n for _, n in UNIFORM_LAYOUTS])
+def test_uniform_channel(r, fresh, oracle, recipe_volume, pref, lname):
+    vol, g = recipe_volume
+    centre, radius = (15, 17, 14), (12, 10, 13)
+    setup(r, pref, vol)
+    assert r.get_option("uniform_mask") & 2 and r.kernel_variant.endswith("_uG")
+    r.rank(centre, radius, MEDIAN, 2, 1, FULL)          # a median of all four channels cannot break G
+    ranked = rs.spec_rank(vol, centre, radius, MEDIAN, 2, 1, FULL)
+    assert (ranked != vol).any() and (ranked[..., 1] == g).all()
+    assert r.get_option("uniform_mask") & 2 and r.kernel_variant.endswith("_uG")
+    img, steps = frame(r)
+    ref, ref_steps = oracle_frame(oracle, ranked)
+    assert_exact(img, ref)
+    assert steps == ref_steps
+    assert_exact(r.get_volume(), ranked)
+    setup(fresh, pref, ranked)
+    assert fresh.kernel_variant.endswith("_uG")
+    img2, steps2 = frame(fresh)
+    assert_exact(img, img2)
+    assert steps == steps2
+
+
+# ---- 7. the staging scratch is the blur's ------------------------------------------------------
+def test_scratch_is_shared_with_blur_and_morph(base):
+    with vr.Renderer(0) as rr:
+        assert rr.get_option("blur_scratch_kib") == 0
+        rr.set_volume(base)
+        assert rank(rr, "miss", MEDIAN, 1, 0) is None
+        assert rr.rank(*ps.BRUSHES["straddle"], MEDIAN, 1, 0, (0, 0, 0, 0)) is not None
+        assert rr.get_option("blur_scratch_kib") == 0            # no launch, no scratch
+        assert_exact(rr.get_volume(), base)
+        box = rank(rr, "straddle", MEDIAN, 1, 0)                 # 33 x 9 x 5 texels x 3 channels
+        need = 3 * box[1][0] * box[1][1] * box[1][2]
+        assert rr.get_option("blur_scratch_kib") == 1024 >= (need + 1023) // 1024   # rounded up to 1 MiB
+        once = rs.spec_rank(base, *ps.BRUSHES["straddle"], MEDIAN, 1, 0)
+        assert_exact(rr.get_volume(), once)
+        rr.blur(*ps.BRUSHES["whole"], 2, 1, FULL)                # a blur within what the rank call left
+        assert rr.get_option("blur_scratch_kib") == 1024
+        twice = bs.spec_blur(once, *ps.BRUSHES["whole"], 2, 1, FULL)
+        assert_exact(rr.get_volume(), twice)
+        rank(rr, "whole", 7, 3, 1, FULL)                         # and a rank call after the blur
+        assert rr.get_option("blur_scratch_kib") == 1024
+        assert_exact(rr.get_volume(), rs.spec_rank(twice, *ps.BRUSHES["whole"], 7, 3, 1, FULL))
+        rr.set_option("blur_scratch_kib", 0)
+        assert rr.get_option("blur_scratch_kib") == 0
+        rr.set_option("blur_scratch_kib", 2000)                  # one reservation serves blur, morph and rank
+        assert rr.get_option("blur_scratch_kib") == 2048
+        rr.set_volume(base)
+        rr.blur(*ps.BRUSHES["max"], 1, 0, FULL)
+        rr.set_volume(base)
+        rank(rr, "max", MEDIAN, 2, 0, FULL)                      # the same box: no growth
+        assert rr.get_option("blur_scratch_kib") == 2048
+        assert_exact(rr.get_volume(), rs.spec_rank(base, *ps.BRUSHES["max"], MEDIAN, 2, 0, FULL))
+
+
+# ---- 8. undo and refusals ----------------------------------------------------------------------
+def test_undo(r, base):
+    r.set_layout_preference(0)
+    r.set_volume(base)
+    centre, radius = ps.BRUSHES["straddle"]
+    origin, extent = vr.brush_box(vr.make_brush(centre, radius), (NX, NY, NZ))
+    saved = r.get_volume_box(origin, extent, stream=torch.cuda.current_stream())   # a device tensor
+    assert rank(r, "straddle", MEDIAN, 3, 1) == (origin, extent)
+    assert (r.get_volume() != base).any()
+    # the saved box stamped back under a hard, full brush that covers it
+    assert r.stamp(saved, origin, centre, (255, 255, 255), ps.SET, 0, FULL) == (origin, extent)
+    assert_exact(r.get_volume(), base)
+
+
+def test_refusals(r, base):
+    setup(r, 0, base)
+    good = dict(centre=(17, 11, 23), radius=(3, 2, 4))
+    bad = [dict(good, half_width=0), dict(good, half_width=4), dict(good, half_width=-1), dict(good, falloff=2),
+           dict(good, rank=27), dict(good, rank=125, half_width=2), dict(good, rank=343, half_width=3),
+           dict(good, rank=-2), dict(good, rank=2**31 - 1), dict(good, rank=-2**31),
+           dict(good, radius=(3, 256, 4)), dict(good, radius=(-1, 2, 4))]
+    for kw in bad:
+        with pytest.raises(vr.VRError) as e:
+            r.rank(**kw)
+        assert e.value.status == 1 and "vr_rank" in str(e.value), kw   # VR_ERR_INVALID
+        assert np.array_equal(r.get_volume(), base)
+    for bop in (ps.ADD, ps.SUB, 3, -1):
+        b = vr.make_brush(op=bop, **good)
+        with pytest.raises(vr.VRError) as e:
+            _lib.call("vr_rank", r._ctx, ctypes.byref(b), MEDIAN, 1, None)
+        assert e.value.status == 1 and "vr_rank" in str(e.value), bop
+        assert np.array_equal(r.get_volume(), base)
+    b = vr.make_brush(**good)
+    b.reserved[1] = 7
+    with pytest.raises(vr.VRError) as e:
+        _lib.call("vr_rank", r._ctx, ctypes.byref(b), MEDIAN, 1, None)
+    assert e.value.status == 1
+    with pytest.raises(vr.VRError) as e:
+        _lib.call("vr_rank", r._ctx, None, MEDIAN, 1, None)
+    assert e.value.status == 1
+    assert r.rank((-10, -10, -10), (4, 4, 4)) is None              # a miss is VR_OK
+    assert r.rank(strength=(0, 0, 0, 0), **good) is not None       # nothing to do is VR_OK too
+    assert np.array_equal(r.get_volume(), base)
+    with vr.Renderer(0) as empty:                                  # no volume installed
+        with pytest.raises(vr.VRError) as e:
+            empty.rank(**good)
+        assert e.value.status == 3                                 # VR_ERR_NO_VOLUME
+        assert empty.get_option("blur_scratch_kib") == 0
+    r.set_procedural()                                             # a procedural medium reads no volume
+    try:
+        with pytest.raises(vr.VRError) as e:
+            r.rank(**good)
+        assert e.value.status == 3
+    finally:
+        r.set_procedural(vr.procedural_defaults(enabled=0))
+    assert np.array_equal(r.get_volume(), base)

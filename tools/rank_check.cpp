@@ -1,0 +1,183 @@
+// rank_check -- stand-alone host check of vr_brush_rank_apply
+// (volumetricrenderer_amd/csrc/vr_brush.cpp), built with
+// -fsanitize=address,undefined and run on the CPU (`make check-rank` builds
+// and runs it).  It links the brush's translation unit only: no libvr.so, no
+// HIP, no device.
+//
+// Every volume is allocated exactly, so a read or write outside it trips the
+// address sanitizer: volumes with an edge shorter than the window (1 x 1 x 1,
+// 2 x 3 x 1 and 5 x 1 x 2 at every half width), centres at INT32_MAX /
+// INT32_MIN, radius 0 and 255, both falloffs, all three half widths, ranks 0,
+// 1, the median, N - 2 and N - 1.  Each result is compared with a naive
+// restatement of vr.h that shares no selection with the library: the N
+// clamped neighbours of a texel are copied out and std::nth_element picks the
+// rank-th, with the ellipsoid in unsigned __int128.  Ranks 0 and N - 1 are also
+// compared with vr_brush_morph_apply.  Half the volumes are ramps with noise,
+// half hold four distinct bytes, so that windows are full of ties.
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+#include <cstdio>
+#include <random>
+#include <vector>
+
+#include "vr.h"
+
+namespace {
+
+typedef unsigned __int128 u128;
+
+// include/vr.h, literally, from a copy of the volume before the call
+void restate(const vr_brush& b, int rank, int h, std::vector<uint8_t>& v, int nx, int ny, int nz)
+{
+    const std::vector<uint8_t> before = v;
+    auto cl = [](int i, int n) { return i < 0 ? 0 : i > n - 1 ? n - 1 : i; };
+    const int w = 2 * h + 1, count = w * w * w;
+    if (rank == VR_RANK_MEDIAN) rank = (count - 1) / 2;
+    std::vector<uint8_t> cube((size_t)count);
+    u128 D2[3];
+    for (int a = 0; a < 3; ++a) D2[a] = (u128)(2 * b.radius[a] + 1) * (u128)(2 * b.radius[a] + 1);
+    const u128 S = D2[0] * D2[1] * D2[2];
+    for (int z = 0; z < nz; ++z)
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) {
+                const long long d[3] = {(long long)x - b.centre[0], (long long)y - b.centre[1], (long long)z - b.centre[2]};
+                bool in = true;
+                for (int a = 0; a < 3; ++a) in = in && d[a] >= -(long long)b.radius[a] && d[a] <= (long long)b.radius[a];
+                if (!in) continue;
+                const u128 Q = (u128)(4 * d[0] * d[0]) * D2[1] * D2[2] + (u128)(4 * d[1] * d[1]) * D2[0] * D2[2] +
+                               (u128)(4 * d[2] * d[2]) * D2[0] * D2[1];
+                if (Q > S) continue;
+                const unsigned wt = b.falloff ? 256u - (unsigned)((256 * Q) / (S + 1)) : 256u;
+                uint8_t* p = &v[(((size_t)z * ny + y) * nx + x) * 4];
+                for (int c = 0; c < 4; ++c) {
+                    if (!b.strength[c]) continue;
+                    size_t i = 0;
+                    for (int dz = -h; dz <= h; ++dz)
+                        for (int dy = -h; dy <= h; ++dy)
+                            for (int dx = -h; dx <= h; ++dx)
+                                cube[i++] = before[(((size_t)cl(z + dz, nz) * ny + cl(y + dy, ny)) * nx + cl(x + dx, nx)) * 4 + c];
+                    std::nth_element(cube.begin(), cube.begin() + rank, cube.end());
+                    const long long m = cube[(size_t)rank];
+                    const long long a = (long long)wt * b.strength[c], old = p[c];
+                    p[c] = (uint8_t)((old * (65280 - a) + m * a + 32640) / 65280);
+                }
+            }
+}
+
+long failures = 0;
+
+void expect(bool ok, const char* what, int it)
+{
+    if (!ok && ++failures <= 10) std::fprintf(stderr, "rank_check: %s (case %d)\n", what, it);
+}
+
+}  // namespace
+
+int main()
+{
+    std::mt19937_64 rng(20240917);
+    auto pick = [&](int a, int b) { return std::uniform_int_distribution<int>(a, b)(rng); };
+    long applied = 0, missed = 0, refused = 0, changed = 0;
+    const int far[] = {INT32_MAX, INT32_MIN, INT32_MAX - 255, INT32_MIN + 255, 1 << 30, -(1 << 30)};
+    const uint8_t four[] = {0, 1, 128, 255};
+    for (int it = 0; it < 1800; ++it) {
+        // kind, half width, falloff / edge radius and which rank run through every combination: 6 x 3 x 2 x 5 = 180
+        const int kind = it % 6, h = 1 + it / 6 % 3, flip = it / 18 % 2, which = it / 36 % 5;
+        const int count = (2 * h + 1) * (2 * h + 1) * (2 * h + 1);
+        const int rank = which == 0 ? 0 : which == 1 ? 1 : which == 2 ? VR_RANK_MEDIAN : which == 3 ? count - 2 : count - 1;
+        int nx = pick(1, 12), ny = pick(1, 12), nz = pick(1, 12);
+        if (kind == 1) nx = ny = nz = 1;            // an edge shorter than any window
+        if (kind == 2) { nx = 2; ny = 3; nz = 1; }
+        if (kind == 5) { nx = 5; ny = 1; nz = 2; }
+        vr_brush b{};
+        for (int a = 0; a < 3; ++a) {
+            const int n = a == 0 ? nx : a == 1 ? ny : nz;
+            b.centre[a] = pick(-3, n + 2);
+            b.radius[a] = pick(0, 6);
+        }
+        if (kind == 1 || kind == 2 || kind == 5)
+            for (int a = 0; a < 3; ++a) { b.radius[a] = flip ? VR_BRUSH_MAX_RADIUS : 0; b.centre[a] = pick(0, 1); }
+        if (kind == 3)   // the largest radius around a centre up to a radius away
+            for (int a = 0; a < 3; ++a) { b.radius[a] = VR_BRUSH_MAX_RADIUS; b.centre[a] = pick(-260, 270); }
+        if (kind == 4)   // one or more axes at the ends of int32
+            for (int a = 0; a < 3; ++a)
+                if (a == it / 6 % 3 || pick(0, 2) == 0) { b.centre[a] = far[pick(0, 5)]; b.radius[a] = pick(0, 1) ? 255 : 0; }
+        b.op = VR_BRUSH_SET;
+        b.falloff = flip;
+        for (int c = 0; c < 4; ++c) { b.value[c] = (uint8_t)pick(0, 255); b.strength[c] = (uint8_t)(pick(0, 3) ? pick(0, 255) : pick(0, 1) * 255); }
+        std::vector<uint8_t> vol((size_t)nx * ny * nz * 4);
+        for (size_t i = 0; i < vol.size(); ++i) {
+            const size_t t = i / 4, x = t % nx, y = t / nx % ny, z = t / nx / ny;
+            vol[i] = it / 180 % 2 ? four[pick(0, 3)] : (uint8_t)((9 * x + 13 * y + 17 * z + 40 * (i % 4)) % 200 + pick(0, 55));
+        }
+        const std::vector<uint8_t> before = vol;
+        std::vector<uint8_t> want = vol;
+        restate(b, rank, h, want, nx, ny, nz);
+        int o[3], e[3];
+        expect(vr_brush_box(&b, nx, ny, nz, o, e) == VR_OK, "vr_brush_box refused a valid brush", it);
+        expect(vr_brush_rank_apply(&b, rank, h, vol.data(), nx, ny, nz) == VR_OK, "vr_brush_rank_apply refused a valid brush", it);
+        expect(vol == want, "vr_brush_rank_apply differs from the restatement", it);
+        if (e[0] == 0) expect(vol == before, "a brush that misses the volume changed it", it);
+        if (kind == 1) expect(vol == before, "a 1 x 1 x 1 volume changed", it);
+        if (which == 2) {   // the median by its number
+            std::vector<uint8_t> again = before;
+            expect(vr_brush_rank_apply(&b, (count - 1) / 2, h, again.data(), nx, ny, nz) == VR_OK && again == vol,
+                   "VR_RANK_MEDIAN is not rank (N - 1) / 2", it);
+        }
+        if (which == 0 || which == 4) {   // the ends of the family are the morph's
+            std::vector<uint8_t> morphed = before;
+            expect(vr_brush_morph_apply(&b, which == 0 ? VR_MORPH_ERODE : VR_MORPH_DILATE, h, morphed.data(), nx, ny, nz) == VR_OK,
+                   "vr_brush_morph_apply refused a valid brush", it);
+            expect(morphed == vol, "rank 0 / N - 1 differs from erode / dilate", it);
+        }
+        ++(e[0] > 0 ? applied : missed);
+        changed += vol != before;
+        // refusals: nothing written
+        vr_brush bad = b;
+        int bad_h = h, bad_rank = rank;
+        switch (it % 8) {
+        case 0: bad.op = VR_BRUSH_ADD; break;
+        case 1: bad.op = VR_BRUSH_SUB; break;
+        case 2: bad_h = 0; break;
+        case 3: bad_h = VR_RANK_MAX_HALF + 1; break;
+        case 4: bad.radius[it % 3] = 256; break;
+        case 5: bad_rank = count; break;
+        case 6: bad_rank = -2; break;
+        default: bad.reserved[it % 2] = 1; break;
+        }
+        std::vector<uint8_t> keep = vol;
+        expect(vr_brush_rank_apply(&bad, bad_rank, bad_h, vol.data(), nx, ny, nz) == VR_ERR_INVALID && vol == keep, "a bad call was applied", it);
+        expect(vr_brush_rank_apply(&b, rank, h, vol.data(), it % 2 ? 0 : nx, ny, it % 2 ? nz : -1) == VR_ERR_INVALID && vol == keep,
+               "bad dimensions were accepted", it);
+        expect(vr_brush_rank_apply(nullptr, rank, h, vol.data(), nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_brush_rank_apply(&b, rank, h, nullptr, nx, ny, nz) == VR_ERR_INVALID,
+               "a null pointer was accepted", it);
+        expect(vr_brush_rank_apply(&b, rank, INT32_MIN, vol.data(), nx, ny, nz) == VR_ERR_INVALID && vol == keep, "half width INT32_MIN", it);
+        expect(vr_brush_rank_apply(&b, it % 2 ? INT32_MIN : INT32_MAX, h, vol.data(), nx, ny, nz) == VR_ERR_INVALID && vol == keep,
+               "rank at the ends of int", it);
+        refused += 6;
+    }
+    // a constant channel stays constant, whatever the other channels hold and whatever the rank
+    for (int k = 0; k < 5 * VR_RANK_MAX_HALF; ++k) {
+        const int h = 1 + k / 5, count = (2 * h + 1) * (2 * h + 1) * (2 * h + 1);
+        const int ranks[5] = {0, 1, VR_RANK_MEDIAN, count - 2, count - 1};
+        const int nx = 9, ny = 5, nz = 7;
+        std::vector<uint8_t> vol((size_t)nx * ny * nz * 4);
+        for (size_t i = 0; i < vol.size(); ++i) vol[i] = i % 4 == 2 ? 131 : (uint8_t)pick(0, 255);
+        vr_brush b{};
+        b.centre[0] = 4; b.centre[1] = 2; b.centre[2] = 3;
+        for (int a = 0; a < 3; ++a) b.radius[a] = 9;
+        b.falloff = 1;
+        for (int c = 0; c < 4; ++c) b.strength[c] = 255;
+        expect(vr_brush_rank_apply(&b, ranks[k % 5], h, vol.data(), nx, ny, nz) == VR_OK, "the constant-channel case was refused", k);
+        bool constant = true;
+        for (size_t i = 2; i < vol.size(); i += 4) constant = constant && vol[i] == 131;
+        expect(constant, "a constant channel changed", k);
+        ++applied;
+    }
+    expect(changed > 600, "too few cases changed a byte", (int)changed);
+    std::printf("rank_check: %ld applied (%ld changed bytes), %ld missed, %ld refused, %ld failures\n", applied, changed, missed,
+                refused, failures);
+    return failures ? 1 : 0;
+}

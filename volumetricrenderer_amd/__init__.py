@@ -13,6 +13,8 @@ from ._lib import VOLUME_STATS_BYTES, StatsSummary, VolumeStats  # noqa: F401
 from .renderer import Stats, Summary, box_stats_host, brush_stats_host, stats_summary, unpack_stats  # noqa: F401
 from ._lib import MORPH_DILATE, MORPH_ERODE, MORPH_MAX_HALF  # noqa: F401
 from .renderer import brush_morph_apply  # noqa: F401
+from ._lib import RANK_MAX_HALF, RANK_MEDIAN  # noqa: F401
+from .renderer import brush_rank_apply  # noqa: F401
 from ._lib import CloneMap  # noqa: F401
 from .renderer import brush_clone_apply, brush_stamp_apply, make_clone_map, stamp_box  # noqa: F401
 from ._lib import LUT_BYTES, LUT_EQUALIZE, LUT_STRETCH, Lut  # noqa: F401
@@ -31,6 +33,7 @@ __all__ = [
     "Brush", "BRUSH_SET", "BRUSH_ADD", "BRUSH_SUB", "BRUSH_MAX_RADIUS", "make_brush", "brush_box", "brush_apply",
     "brush_line", "coalesce_boxes", "VR_MAX_DABS", "Box", "brush_blur_apply", "BLUR_MAX_HALF",
     "brush_morph_apply", "MORPH_ERODE", "MORPH_DILATE", "MORPH_MAX_HALF",
+    "brush_rank_apply", "RANK_MEDIAN", "RANK_MAX_HALF",
     "CloneMap", "make_clone_map", "brush_clone_apply", "brush_stamp_apply", "stamp_box",
     "Lut", "LUT_BYTES", "LUT_EQUALIZE", "LUT_STRETCH", "lut_identity", "lut_levels", "lut_compose", "stats_lut",
     "brush_remap_apply",

@@ -128,6 +128,8 @@ VR_MAX_DABS = 64                            # vr.h: the longest list vr_paint_st
 BLUR_MAX_HALF = 3                           # vr.h VR_BLUR_MAX_HALF: the widest box filter of vr_blur (7 texels)
 MORPH_ERODE, MORPH_DILATE = 0, 1            # vr.h vr_morph_op
 MORPH_MAX_HALF = 3                          # vr.h VR_MORPH_MAX_HALF: the widest cube of vr_morph (7 texels)
+RANK_MEDIAN = -1                            # vr.h VR_RANK_MEDIAN: the middle rank of vr_rank's window
+RANK_MAX_HALF = 3                           # vr.h VR_RANK_MAX_HALF: the widest cube of vr_rank (7 texels)
 
 
 class Box(ctypes.Structure):
@@ -210,6 +212,9 @@ _SIGS = {
     "vr_lut_levels": (ctypes.c_int, [ctypes.POINTER(Lut)] + [ctypes.c_int] * 5),
     "vr_lut_compose": (ctypes.c_int, [ctypes.POINTER(Lut), ctypes.POINTER(Lut), ctypes.POINTER(Lut)]),
     "vr_stats_lut": (ctypes.c_int, [ctypes.POINTER(VolumeStats), ctypes.c_int, ctypes.c_int, ctypes.POINTER(Lut)]),
+    "vr_rank": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, _vp]),
+    "vr_brush_rank_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int]),
     "vr_brush_stats": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, _vp]),
     "vr_box_stats": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp, _vp]),
     "vr_brush_stats_host": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

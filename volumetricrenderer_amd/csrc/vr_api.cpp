@@ -18,6 +18,7 @@
 #include "vr_clone.h"
 #include "vr_ctx.h"
 #include "vr_morph.h"
+#include "vr_rank.h"
 #include "vr_remap.h"
 #include "vr_stats.h"
 
@@ -836,6 +837,28 @@ static bool source_brush_args(const Ctx* c, const vr_brush* b, PaintArgs& a)
     bool any = false;
     for (int ch = 0; ch < 4; ++ch) { a.strength[ch] = b->strength[ch]; any = any || b->strength[ch] != 0; }
     return any;
+}
+
+// The median / rank-filter brush on the device: vr_morph's sequence with k_rank_stage as the first launch.  The
+// staging scratch is the blur's (same need, same growth rule, same option).
+vr_status vr_rank(void* p, const vr_brush* b, int rank, int half_width, void* stream)
+try {
+    if (!p || !b) return fail(VR_ERR_INVALID, "vr_rank: null argument");
+    if (const char* why = vr::rank::invalid(b, rank, half_width)) return fail(VR_ERR_INVALID, "vr_rank: %s", why);
+    Ctx* c = as_ctx(p);
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_rank: no volume set");
+    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_rank: a procedural medium is enabled (it reads no volume)");
+    PaintArgs a{};
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
+    if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
+    if (vr_status st = ensure_blur(c, blur_stage_bytes(a))) return st;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(launch_rank_stage(a, vr::rank::resolve(rank, half_width), half_width, c->d_planar, c->d_blur, s));
+    HIP_TRY(launch_blur_commit(a, c->d_blur, c->d_planar, c->d_mm, s));
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+} catch (...) {
+    return caught_exception("vr_rank");
 }
 
 // The clone brush on the device: every check first, then the host picks the path in integers (vr_clone.h direct).

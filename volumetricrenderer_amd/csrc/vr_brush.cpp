@@ -4,6 +4,8 @@
 // brush of vr_blur on the host (sec. 5.2.7; the mean is vr_blur.h's);
 // vr_brush_morph_apply: the erode / dilate brush of vr_morph on the host
 // (sec. 5.2.9; the argument check and the extremum are vr_morph.h's);
+// vr_brush_rank_apply: the median / rank-filter brush of vr_rank on the host
+// (sec. 5.2.12; the argument check and the selection are vr_rank.h's);
 // vr_brush_stats_host, vr_box_stats_host and vr_stats_summary: the statistics
 // under a brush or in a box (sec. 5.2.8; the arithmetic is vr_stats.h's);
 // vr_brush_clone_apply, vr_brush_stamp_apply and vr_stamp_box: the brushes
@@ -26,6 +28,7 @@
 #include "vr_brush.h"
 #include "vr_clone.h"
 #include "vr_morph.h"
+#include "vr_rank.h"
 #include "vr_remap.h"
 #include "vr_stats.h"
 
@@ -434,6 +437,75 @@ vr_status vr_stats_lut(const vr_volume_stats* stats, int kind, int channel_mask,
     if (const char* why = vr::remap::invalid_kind(kind)) return fail(VR_ERR_INVALID, "vr_stats_lut: %s", why);
     if (const char* why = vr::remap::invalid_mask(channel_mask)) return fail(VR_ERR_INVALID, "vr_stats_lut: %s", why);
     vr::remap::stats_lut(stats, kind, (unsigned)channel_mask, out);
+    return VR_OK;
+}
+
+// The median / rank-filter brush on the host (include/vr.h): a SET brush whose value, per texel and channel, is the
+// rank-th smallest byte of the texel's (2 half_width + 1)^3 cube of the bytes BEFORE the call.  As for the blur and
+// the morph, the clipped box and its halo (inside the volume) are copied first and every selection reads the copy
+// (Jacobi); the selection is vr_rank.h's bisection, each count a plain loop over the cube.
+vr_status vr_brush_rank_apply(const vr_brush* b, int rank, int half_width, uint8_t* rgba8, int nx, int ny, int nz)
+{
+    if (!b || !rgba8) return fail(VR_ERR_INVALID, "vr_brush_rank_apply: null argument");
+    if (const char* why = vr::rank::invalid(b, rank, half_width))
+        return fail(VR_ERR_INVALID, "vr_brush_rank_apply: %s", why);
+    if (nx <= 0 || ny <= 0 || nz <= 0)
+        return fail(VR_ERR_INVALID, "vr_brush_rank_apply: bad extent %dx%dx%d", nx, ny, nz);
+    int o[3], e[3];
+    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
+    const int h = half_width, n[3] = {nx, ny, nz};
+    const unsigned k = (unsigned)vr::rank::resolve(rank, h);
+    int lo[3], ext[3];   // the box and its halo, inside the volume
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = o[a] - h < 0 ? 0 : o[a] - h;
+        const int hi = o[a] + e[a] - 1 + h > n[a] - 1 ? n[a] - 1 : o[a] + e[a] - 1 + h;
+        ext[a] = hi - lo[a] + 1;
+    }
+    std::vector<uint8_t> before((size_t)ext[0] * (size_t)ext[1] * (size_t)ext[2] * 4);
+    for (int z = 0; z < ext[2]; ++z)
+        for (int y = 0; y < ext[1]; ++y) {
+            const uint8_t* src = rgba8 + (((size_t)(lo[2] + z) * (size_t)ny + (size_t)(lo[1] + y)) * (size_t)nx + (size_t)lo[0]) * 4;
+            uint8_t* dst = &before[((size_t)z * (size_t)ext[1] + (size_t)y) * (size_t)ext[0] * 4];
+            for (size_t i = 0; i < (size_t)ext[0] * 4; ++i) dst[i] = src[i];
+        }
+    // a texel of the volume, clamped to it: inside the copy for every neighbour of a texel of the box
+    auto at = [&](int x, int y, int z, int c) -> unsigned {
+        x = x < 0 ? 0 : x > nx - 1 ? nx - 1 : x;
+        y = y < 0 ? 0 : y > ny - 1 ? ny - 1 : y;
+        z = z < 0 ? 0 : z > nz - 1 ? nz - 1 : z;
+        return before[(((size_t)(z - lo[2]) * (size_t)ext[1] + (size_t)(y - lo[1])) * (size_t)ext[0] + (size_t)(x - lo[0])) * 4 + (size_t)c];
+    };
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    unsigned cube[7 * 7 * 7];   // the neighbours of one texel and channel
+    static_assert(VR_RANK_MAX_HALF == 3, "the cube holds the widest window");
+    const int count = vr::rank::window(h);
+    for (int z = o[2]; z < o[2] + e[2]; ++z) {
+        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
+        for (int y = o[1]; y < o[1] + e[1]; ++y) {
+            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
+            if (qyz > t.s) continue;
+            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
+            for (int x = o[0]; x < o[0] + e[0]; ++x) {
+                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
+                if (q > t.s) continue;
+                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
+                for (int c = 0; c < 4; ++c) {
+                    if (!b->strength[c]) continue;
+                    int i = 0;
+                    for (int dz = -h; dz <= h; ++dz)
+                        for (int dy = -h; dy <= h; ++dy)
+                            for (int dx = -h; dx <= h; ++dx) cube[i++] = at(x + dx, y + dy, z + dz, c);
+                    const unsigned m = vr::rank::select(k, [&](unsigned cand) {
+                        unsigned below = 0u;
+                        for (int j = 0; j < count; ++j) below += vr::rank::below(cube[j], cand);
+                        return below;
+                    });
+                    uint8_t* p = row + (size_t)x * 4 + c;
+                    *p = (uint8_t)vr::brush::blend(VR_BRUSH_SET, *p, m, w * b->strength[c]);
+                }
+            }
+        }
+    }
     return VR_OK;
 }
 

@@ -651,6 +651,10 @@ hipError_t launch_blur_commit(const PaintArgs& a, const uint8_t* d_stage, uint8_
 // maximum (VR_MORPH_DILATE) over the cube as the value; launch_blur_commit follows it.
 hipError_t launch_morph_stage(const PaintArgs& a, int op, int half_width, const uint8_t* d_planar, uint8_t* d_stage,
                               hipStream_t s);
+// vr_rank: launch_blur_stage's contract and slabs with the rank-th smallest byte of the cube
+// as the value, rank already resolved to 0..(2 half_width + 1)^3 - 1; launch_blur_commit follows it.
+hipError_t launch_rank_stage(const PaintArgs& a, int rank, int half_width, const uint8_t* d_planar, uint8_t* d_stage,
+                             hipStream_t s);
 // vr_clone: the brush as for launch_paint_planar (value is not read) and the validated map.
 // launch_clone_direct goes from the planes to the planes in one launch and folds the new bytes into mm: only for a
 // map whose source range misses the clipped box on an axis (vr_clone.h direct).  launch_clone_stage has

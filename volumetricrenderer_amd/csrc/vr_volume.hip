@@ -16,6 +16,7 @@
 #include "vr_internal.h"
 #include "vr_morph.h"
 #include "vr_noise.h"
+#include "vr_rank.h"
 #include "vr_remap.h"
 #include "vr_stats.h"
 
@@ -608,6 +609,187 @@ __global__ __launch_bounds__(kBlock) void k_morph_stage(PaintArgs a, const uint8
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     nw |= brush::blend(VR_BRUSH_SET, (old[i] >> (8 * j)) & 255u, (m >> (8 * j)) & 255u, wgt[i][j] * a.strength[c])
+                          << (8 * j);
+                uint8_t* __restrict__ o8 =
+                    stage + (size_t)k * slab + ((size_t)(z + i) * (size_t)a.e[1] + (size_t)y) * (size_t)a.e[0] + (size_t)x;
+                if (wgt[i][0] && wgt[i][1] && wgt[i][2] && wgt[i][3] && (reinterpret_cast<uintptr_t>(o8) & 3u) == 0u) {
+                    *reinterpret_cast<uint32_t*>(o8) = nw;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (wgt[i][j]) o8[j] = (uint8_t)(nw >> (8 * j));
+                }
+            }
+        }
+        ++k;
+        __syncthreads();   // the next channel rewrites the tile
+    }
+}
+
+// vr_rank, first launch: k_blur_stage's contract -- the
+// planes read only, the new byte of every inside texel to the staging slabs in
+// the same shape, so k_blur_commit follows unchanged -- with the rank-th
+// smallest byte of the (2H + 1)^3 cube as the value.  A rank is not separable:
+// the selection runs over the whole cube, by vr_rank.h's bisection on the byte,
+// eight rounds of "how many neighbours lie below the candidate".
+//
+// The tile is the morph's, 32 x 8 x 8; thread t owns the four x of dword t % 8
+// at the two z of pair t / 8 % 4 in row t / 32.  The two z share 2H of their
+// 2H + 2 slices, so a staged row is read once per round for both.  A tile with
+// no texel inside leaves before any load.  Per painted channel:
+//  1. tile and halo, coordinates clamped to the volume, from the plane to LDS,
+//     as step 1 of k_morph_stage;
+//  2. every lane with an inside texel runs the eight rounds.  Per round and
+//     staged row of its windows it reads the NW dwords that hold the 4 + 2H
+//     bytes of its four windows and splits them into pairs of even and of odd
+//     bytes two apart in 16-bit halves (the morph's pe / po): pair n of one
+//     parity is byte n of the windows of texels 0 and 2, or of 1 and 3.  The
+//     candidates of those two texels sit in the halves of one register, and
+//     (pair - candidates) has bit 15 of a half set exactly when that byte is
+//     below that candidate (vr_rank.h below), so a packed subtract, a packed
+//     shift and a packed add count two comparisons: 2 (2H + 1) triples per
+//     row and quad.  A count is at most 343 and fits its half.  After the
+//     last row vr_rank.h advance decides the round's bit per texel;
+//  3. the SET blend and the store of step 4 of k_morph_stage.
+// A lane none of whose eight texels is inside does no selection; a quad none
+// of whose four is inside is skipped.  A texel outside that shares a quad with
+// one inside rides along in the packed halves at no cost and is not stored.
+// The 32 lanes of an LDS read group are 8 dwords x 4 z pairs of one row: the z
+// pitch is padded until twice the pitch is 8 or 24 mod 32 dwords, which puts
+// the four pairs on disjoint banks.
+constexpr int rank_z_pitch(int dwords)
+{
+    while (dwords % 16 != 4 && dwords % 16 != 12) ++dwords;
+    return dwords;
+}
+
+template <int H>
+__global__ __launch_bounds__(kBlock) void k_rank_stage(PaintArgs a, unsigned rank, const uint8_t* __restrict__ src,
+                                                       uint8_t* __restrict__ stage)
+{
+    constexpr int W = 2 * H + 1;
+    constexpr int XH = kMorphTX + 2 * H, YH = kMorphTY + 2 * H, ZH = kMorphTZ + 2 * H;
+    constexpr int XPW = (XH + 3) / 4;        // dwords of a staged row
+    constexpr int NW = (H + 1) / 2 + 1;      // dwords that hold the 4 + 2H bytes of four adjacent windows
+    constexpr int ZP = rank_z_pitch(YH * XPW);   // z pitch of the staged tile, in dwords
+    static_assert(kMorphQ - 1 + NW <= XPW, "step 2 reads inside its row");
+    static_assert(kMorphQ * (kMorphTZ / 2) * kMorphTY == kBlock, "a thread per dword and z pair of the tile");
+    static_assert(W * W * W < 32768, "a count fits 15 bits of its half");
+    __shared__ uint32_t raw32[ZH * ZP];
+
+    const int tid = threadIdx.x, xq = tid % kMorphQ, zp = tid / kMorphQ % (kMorphTZ / 2), ly = tid / (kMorphQ * (kMorphTZ / 2));
+    const int ntx = (a.e[0] + kMorphTX - 1) / kMorphTX, nty = (a.e[1] + kMorphTY - 1) / kMorphTY;
+    const int bt = blockIdx.x;
+    const int tx0 = (bt % ntx) * kMorphTX, ty0 = (bt / ntx % nty) * kMorphTY, tz0 = (bt / (ntx * nty)) * kMorphTZ;
+    const int x = tx0 + 4 * xq, y = ty0 + ly, z = tz0 + 2 * zp;   // the first owned texel, in the box
+
+    // the weights of the owned texels: 0 outside the ellipsoid or the box (an inside texel's is at least 1)
+    unsigned wgt[2][4];
+    const unsigned long long qy = y < a.e[1] ? brush::axis_term(a.d0[1] + y, a.k[1]) : 0ull;
+    bool act[2];   // the quad at z + i has a texel inside
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        act[i] = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            wgt[i][j] = 0u;
+            if (y < a.e[1] && z + i < a.e[2] && x + j < a.e[0]) {
+                const unsigned long long q =
+                    qy + brush::axis_term(a.d0[0] + x + j, a.k[0]) + brush::axis_term(a.d0[2] + z + i, a.k[2]);
+                if (q <= a.s) wgt[i][j] = brush::weight(q, a.s, a.falloff);
+            }
+            act[i] = act[i] || wgt[i][j] != 0u;
+        }
+    }
+    if (!__syncthreads_or(act[0] || act[1] ? 1 : 0)) return;
+
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    const size_t slab = (size_t)a.e[0] * (size_t)a.e[1] * (size_t)a.e[2];
+    int k = 0;   // the channel's slab
+#pragma unroll 1
+    for (int c = 0; c < 4; ++c) {
+        if (a.strength[c] == 0u) continue;
+        const uint8_t* __restrict__ p = src + c * plane;
+        for (int i = tid; i < ZH * YH * XPW; i += kBlock) {
+            const int xw = i % XPW, t = i / XPW, yi = t % YH, zi = t / YH;
+            const int gy = clampi(a.o[1] + ty0 - H + yi, 0, a.ny - 1), gz = clampi(a.o[2] + tz0 - H + zi, 0, a.nz - 1);
+            const uint8_t* __restrict__ row = p + ((long long)gz * a.ny + gy) * a.nx;
+            const int gx = a.o[0] + tx0 - H + 4 * xw;
+            uint32_t v = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v |= (uint32_t)row[clampi(gx + j, 0, a.nx - 1)] << (8 * j);
+            raw32[zi * ZP + yi * XPW + xw] = v;
+        }
+        __syncthreads();
+        if (act[0] || act[1]) {
+            // lo02[i], lo13[i]: the bits found so far of texels 0 and 2, and 1 and 3, of the quad at z + i, in halves
+            uint32_t lo02[2] = {0u, 0u}, lo13[2] = {0u, 0u};
+#pragma unroll 1
+            for (unsigned bit = 128u; bit != 0u; bit >>= 1) {
+                morph_u16x2 c02[2], c13[2], n02[2], n13[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    c02[i] = __builtin_bit_cast(morph_u16x2, lo02[i] | bit * 0x00010001u);
+                    c13[i] = __builtin_bit_cast(morph_u16x2, lo13[i] | bit * 0x00010001u);
+                    n02[i] = n13[i] = morph_u16x2{0, 0};
+                }
+#pragma unroll 1
+                for (int zi = 0; zi < W + 1; ++zi) {
+                    const bool use[2] = {act[0] && zi < W, act[1] && zi > 0};   // slice zi lies in the window of z + i
+                    const uint32_t* rows = raw32 + (2 * zp + zi) * ZP + ly * XPW + xq;
+#pragma unroll
+                    for (int dy = 0; dy < W; ++dy) {
+                        const uint32_t* w32 = rows + dy * XPW;
+                        uint32_t ev[NW], od[NW];
+#pragma unroll
+                        for (int j = 0; j < NW; ++j) {
+                            const uint32_t v = w32[j];
+                            ev[j] = v & 0x00ff00ffu;
+                            od[j] = (v >> 8) & 0x00ff00ffu;
+                        }
+                        // pe[n] = bytes (2n, 2n + 2), po[n] = bytes (2n + 1, 2n + 3) of the row from the dword's first byte on
+                        morph_u16x2 pe[H + 1], po[H + 1];
+#pragma unroll
+                        for (int n = 0; n <= H; ++n) {
+                            pe[n] = __builtin_bit_cast(morph_u16x2, n % 2 ? (ev[n / 2] >> 16) | (ev[n / 2 + 1] << 16) : ev[n / 2]);
+                            po[n] = __builtin_bit_cast(morph_u16x2, n % 2 ? (od[n / 2] >> 16) | (od[n / 2 + 1] << 16) : od[n / 2]);
+                        }
+                        // texels 0 and 2 see bytes 0..2H and 2..2H + 2: pe[0..H] and po[0..H - 1]; texels 1 and 3: po[0..H], pe[1..H]
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+                            if (!use[i]) continue;
+#pragma unroll
+                            for (int n = 0; n <= H; ++n) {
+                                n02[i] += (pe[n] - c02[i]) >> 15;
+                                n13[i] += (po[n] - c13[i]) >> 15;
+                            }
+#pragma unroll
+                            for (int n = 0; n < H; ++n) {
+                                n02[i] += (po[n] - c02[i]) >> 15;
+                                n13[i] += (pe[n + 1] - c13[i]) >> 15;
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const uint32_t m02 = __builtin_bit_cast(uint32_t, n02[i]), m13 = __builtin_bit_cast(uint32_t, n13[i]);
+                    lo02[i] = rank::advance(lo02[i] & 0xffffu, bit, m02 & 0xffffu, rank) |
+                              rank::advance(lo02[i] >> 16, bit, m02 >> 16, rank) << 16;
+                    lo13[i] = rank::advance(lo13[i] & 0xffffu, bit, m13 & 0xffffu, rank) |
+                              rank::advance(lo13[i] >> 16, bit, m13 >> 16, rank) << 16;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if (!act[i]) continue;
+                const uint32_t* w32 = raw32 + (2 * zp + i + H) * ZP + (ly + H) * XPW + xq;
+                const uint32_t old = (uint32_t)((((unsigned long long)w32[1] << 32) | w32[0]) >> (8 * H));
+                const uint32_t m = lo02[i] | (lo13[i] << 8);
+                uint32_t nw = 0u;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    nw |= brush::blend(VR_BRUSH_SET, (old >> (8 * j)) & 255u, (m >> (8 * j)) & 255u, wgt[i][j] * a.strength[c])
                           << (8 * j);
                 uint8_t* __restrict__ o8 =
                     stage + (size_t)k * slab + ((size_t)(z + i) * (size_t)a.e[1] + (size_t)y) * (size_t)a.e[0] + (size_t)x;
@@ -1563,6 +1745,25 @@ hipError_t launch_morph_stage(const PaintArgs& a, int op, int half_width, const 
     case 5: hipLaunchKernelGGL((k_morph_stage<2, true>), g, b, 0, s, a, d_planar, d_stage); break;
     case 6: hipLaunchKernelGGL((k_morph_stage<3, false>), g, b, 0, s, a, d_planar, d_stage); break;
     case 7: hipLaunchKernelGGL((k_morph_stage<3, true>), g, b, 0, s, a, d_planar, d_stage); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// the morph's grid and tile, one instantiation per half width; rank is 0..(2 half_width + 1)^3 - 1 (vr_rank.h resolve)
+hipError_t launch_rank_stage(const PaintArgs& a, int rank, int half_width, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s)
+{
+    if (a.e[0] < 1 || a.e[1] < 1 || a.e[2] < 1 || !d_stage) return hipErrorInvalidValue;
+    if (half_width < 1 || half_width > VR_RANK_MAX_HALF || rank < 0 || rank > rank::window(half_width) - 1)
+        return hipErrorInvalidValue;
+    const long long tiles = (long long)((a.e[0] + kMorphTX - 1) / kMorphTX) * ((a.e[1] + kMorphTY - 1) / kMorphTY) *
+                            ((a.e[2] + kMorphTZ - 1) / kMorphTZ);
+    if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+    const dim3 g((unsigned)tiles), b(kBlock);
+    switch (half_width) {
+    case 1: hipLaunchKernelGGL(k_rank_stage<1>, g, b, 0, s, a, (unsigned)rank, d_planar, d_stage); break;
+    case 2: hipLaunchKernelGGL(k_rank_stage<2>, g, b, 0, s, a, (unsigned)rank, d_planar, d_stage); break;
+    case 3: hipLaunchKernelGGL(k_rank_stage<3>, g, b, 0, s, a, (unsigned)rank, d_planar, d_stage); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

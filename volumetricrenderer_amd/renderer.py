@@ -38,6 +38,7 @@ from ._lib import (BRUSH_ADD, BRUSH_SET, BRUSH_SUB, BYTES_PER_PIXEL, CHANNELS, F
                    Rect, Target, VolumeRecipe, VR_MAX_RECTS, VRError, call)
 from ._lib import VOLUME_STATS_BYTES, StatsSummary, VolumeStats
 from ._lib import Box, CloneMap
+from ._lib import RANK_MEDIAN
 from ._lib import LUT_BYTES, LUT_EQUALIZE, LUT_STRETCH, Lut  # noqa: F401
 
 _lib.load()  # fail at import if the HIP library is missing
@@ -315,6 +316,23 @@ def brush_morph_apply(brush: Brush, op: int, half_width: int, rgba: np.ndarray) 
         raise ValueError("brush_morph_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
     nz, ny, nx, _ = rgba.shape
     call("vr_brush_morph_apply", ctypes.byref(brush), int(op), int(half_width), rgba.ctypes.data_as(ctypes.c_void_p),
+         nx, ny, nz)
+    return rgba
+
+
+def brush_rank_apply(brush: Brush, rank: int, half_width: int, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_rank_apply: the median / rank-filter brush applied to a host
+    RGBA8 volume shaped (nz, ny, nx, 4) (a contiguous uint8 array) -- under the
+    brush, each channel with a non-zero strength is SET towards the `rank`-th
+    smallest byte (0-based; RANK_MEDIAN: the middle one) of its
+    (2 half_width + 1)^3 cube as it was before the call.  The CPU statement of
+    what :meth:`Renderer.rank` does on the device; `brush.op` must be BRUSH_SET
+    and `brush.value` is not read.  Writes `rgba` and returns it."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_rank_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    call("vr_brush_rank_apply", ctypes.byref(brush), int(rank), int(half_width), rgba.ctypes.data_as(ctypes.c_void_p),
          nx, ny, nz)
     return rgba
 
@@ -710,6 +728,25 @@ class Renderer:
         (``blur_scratch_kib``) and grows by the same rule."""
         b = make_brush(centre, radius, BRUSH_SET, falloff, 0, strength)
         call("vr_morph", self._ctx, ctypes.byref(b), int(op), int(half_width), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return brush_box(b, self.volume_dims())
+
+    def rank(self, centre, radius, rank: int = RANK_MEDIAN, half_width: int = 1, falloff: int = 0,
+             strength=(255, 255, 255, 255), stream=None):
+        """Remove speckle under an ellipsoidal brush on the device and leave
+        edges where they are (vr_rank): each channel with a non-zero strength
+        is SET towards the `rank`-th smallest byte (0-based; RANK_MEDIAN, the
+        default, is the median; 0 is :meth:`morph`'s erode and the last rank
+        its dilate) of its (2 half_width + 1)^3 cube (half_width 1..3,
+        clamp-to-edge) as it was before the call, weighted as :meth:`paint`
+        weights a SET brush -- bit for bit what :func:`brush_rank_apply` gives
+        on the host.  Returns ``(origin, extent)`` of the clipped bounding box
+        it rewrote, or None when the brush misses the volume, and queues on
+        `stream` as :meth:`paint` does.  The staging scratch is :meth:`blur`'s
+        (``blur_scratch_kib``) and grows by the same rule."""
+        b = make_brush(centre, radius, BRUSH_SET, falloff, 0, strength)
+        call("vr_rank", self._ctx, ctypes.byref(b), int(rank), int(half_width), _stream_handle(stream))
         if stream is None:
             torch.cuda.current_stream().synchronize()
         return brush_box(b, self.volume_dims())
