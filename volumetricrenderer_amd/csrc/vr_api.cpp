@@ -596,6 +596,59 @@ vr_status ensure_blur(Ctx* c, size_t need)
     return VR_OK;
 }
 
+// What a brush or the statistics need of the context: an installed volume that the frames read.
+static vr_status check_target(const char* fn, const Ctx* c)
+{
+    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "%s: no volume set", fn);
+    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "%s: a procedural medium is enabled (it reads no volume)", fn);
+    return VR_OK;
+}
+
+// The ellipsoid of a validated vr_brush over the box a.o, a.e of the volume: the fields PaintArgs and StatsArgs share.
+template <class Args>
+static void brush_geometry(const Ctx* c, const vr_brush* b, Args& a)
+{
+    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    a.s = t.s;
+    for (int ax = 0; ax < 3; ++ax) {
+        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
+        a.k[ax] = t.k[ax];
+    }
+    a.falloff = b->falloff;
+}
+
+// The brush of a validated vr_brush over the box a.o, a.e of the volume; false when every strength is 0 -- nothing
+// would be read or written.
+static bool source_brush_args(const Ctx* c, const vr_brush* b, PaintArgs& a)
+{
+    brush_geometry(c, b, a);
+    a.op = b->op;
+    bool any = false;
+    for (int ch = 0; ch < 4; ++ch) {
+        a.value[ch] = b->value[ch];
+        a.strength[ch] = b->strength[ch];
+        any = any || b->strength[ch] != 0;
+    }
+    return any;
+}
+
+// The staged brushes (blur, morph, rank, and the clone whose source overlaps its box): the scratch (grown only when
+// the call needs more than is held), the caller's stage launch from the planes to the scratch, k_blur_commit from
+// the scratch to the planes, and what follows an edit of the clipped box.  Some strength of `a` is not 0.
+// stage_name is the launcher stage() calls, for the text of a failed launch.
+template <class Stage>
+static vr_status staged_brush(Ctx* c, const PaintArgs& a, hipStream_t s, const char* stage_name, Stage stage)
+{
+    if (vr_status st = ensure_blur(c, blur_stage_bytes(a))) return st;
+    HIP_TRY(hipSetDevice(c->device));
+    if (const hipError_t e = stage())
+        return fail(e == hipErrorOutOfMemory ? VR_ERR_OOM : VR_ERR_HIP, "%s: %s (%s:%d)", stage_name, hipGetErrorString(e),
+                    __FILE__, __LINE__);
+    HIP_TRY(launch_blur_commit(a, c->d_blur, c->d_planar, c->d_mm, s));
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+}
+
 }  // namespace vrapi
 
 extern "C" {
@@ -692,25 +745,16 @@ try {
 }
 
 // The brush on the device: k_paint_planar over the clipped bounding box, then what follows an update of that box.
+// A brush whose strengths are all 0 launches too: the kernel stores nothing, and the box counts as edited.
 vr_status vr_paint(void* p, const vr_brush* b, void* stream)
 try {
     if (!p || !b) return fail(VR_ERR_INVALID, "vr_paint: null argument");
     if (const char* why = vr::brush::invalid(b)) return fail(VR_ERR_INVALID, "vr_paint: %s", why);
     Ctx* c = as_ctx(p);
-    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_paint: no volume set");
-    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_paint: a procedural medium is enabled (it reads no volume)");
+    if (vr_status st = check_target("vr_paint", c)) return st;
     PaintArgs a{};
     if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    a.s = t.s;
-    for (int ax = 0; ax < 3; ++ax) {
-        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
-        a.k[ax] = t.k[ax];
-    }
-    a.op = b->op;
-    a.falloff = b->falloff;
-    for (int ch = 0; ch < 4; ++ch) { a.value[ch] = b->value[ch]; a.strength[ch] = b->strength[ch]; }
+    (void)source_brush_args(c, b, a);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(launch_paint_planar(a, c->d_planar, c->d_mm, s));
@@ -731,9 +775,7 @@ try {
     for (int i = 0; i < count; ++i)
         if (const char* why = vr::brush::invalid(&dabs[i])) return fail(VR_ERR_INVALID, "vr_paint_stroke: dab %d: %s", i, why);
     Ctx* c = as_ctx(p);
-    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_paint_stroke: no volume set");
-    if (c->proc.enabled)
-        return fail(VR_ERR_NO_VOLUME, "vr_paint_stroke: a procedural medium is enabled (it reads no volume)");
+    if (vr_status st = check_target("vr_paint_stroke", c)) return st;
     StrokeArgs a{};
     vr_box boxes[VR_MAX_DABS];
     a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
@@ -754,36 +796,20 @@ try {
     return caught_exception("vr_paint_stroke");
 }
 
-// The smoothing brush on the device: every check first, the scratch (grown only when the call needs more than is
-// held), k_blur_stage from the planes to the scratch, k_blur_commit from the scratch to the planes, and what
-// follows an edit of the clipped box.
+// The smoothing brush on the device: every check first, then the staged sequence with k_blur_stage as its first
+// launch.
 vr_status vr_blur(void* p, const vr_brush* b, int half_width, void* stream)
 try {
     if (!p || !b) return fail(VR_ERR_INVALID, "vr_blur: null argument");
     if (const char* why = vr::blur::invalid(b, half_width)) return fail(VR_ERR_INVALID, "vr_blur: %s", why);
     Ctx* c = as_ctx(p);
-    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_blur: no volume set");
-    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_blur: a procedural medium is enabled (it reads no volume)");
+    if (vr_status st = check_target("vr_blur", c)) return st;
     PaintArgs a{};
     if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    a.s = t.s;
-    for (int ax = 0; ax < 3; ++ax) {
-        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
-        a.k[ax] = t.k[ax];
-    }
+    if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
     a.op = VR_BRUSH_SET;
-    a.falloff = b->falloff;
-    for (int ch = 0; ch < 4; ++ch) a.strength[ch] = b->strength[ch];   // value is not read
-    const size_t need = blur_stage_bytes(a);
-    if (need == 0) return VR_OK;   // every strength is 0: nothing is read or written
-    if (vr_status st = ensure_blur(c, need)) return st;
-    HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(launch_blur_stage(a, half_width, c->d_planar, c->d_blur, s));
-    HIP_TRY(launch_blur_commit(a, c->d_blur, c->d_planar, c->d_mm, s));
-    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+    return staged_brush(c, a, s, "launch_blur_stage", [&] { return launch_blur_stage(a, half_width, c->d_planar, c->d_blur, s); });
 } catch (...) {
     return caught_exception("vr_blur");
 }
@@ -795,48 +821,15 @@ try {
     if (!p || !b) return fail(VR_ERR_INVALID, "vr_morph: null argument");
     if (const char* why = vr::morph::invalid(b, op, half_width)) return fail(VR_ERR_INVALID, "vr_morph: %s", why);
     Ctx* c = as_ctx(p);
-    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_morph: no volume set");
-    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_morph: a procedural medium is enabled (it reads no volume)");
+    if (vr_status st = check_target("vr_morph", c)) return st;
     PaintArgs a{};
     if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    a.s = t.s;
-    for (int ax = 0; ax < 3; ++ax) {
-        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
-        a.k[ax] = t.k[ax];
-    }
+    if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
     a.op = VR_BRUSH_SET;
-    a.falloff = b->falloff;
-    for (int ch = 0; ch < 4; ++ch) a.strength[ch] = b->strength[ch];   // value is not read
-    const size_t need = blur_stage_bytes(a);
-    if (need == 0) return VR_OK;   // every strength is 0: nothing is read or written
-    if (vr_status st = ensure_blur(c, need)) return st;
-    HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(launch_morph_stage(a, op, half_width, c->d_planar, c->d_blur, s));
-    HIP_TRY(launch_blur_commit(a, c->d_blur, c->d_planar, c->d_mm, s));
-    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+    return staged_brush(c, a, s, "launch_morph_stage", [&] { return launch_morph_stage(a, op, half_width, c->d_planar, c->d_blur, s); });
 } catch (...) {
     return caught_exception("vr_morph");
-}
-
-// The brush of a validated vr_brush over the box o, e of the volume (PaintArgs but for value, which the brushes
-// below do not read); false when every strength is 0 -- nothing would be read or written.
-static bool source_brush_args(const Ctx* c, const vr_brush* b, PaintArgs& a)
-{
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    a.s = t.s;
-    for (int ax = 0; ax < 3; ++ax) {
-        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
-        a.k[ax] = t.k[ax];
-    }
-    a.op = b->op;
-    a.falloff = b->falloff;
-    bool any = false;
-    for (int ch = 0; ch < 4; ++ch) { a.strength[ch] = b->strength[ch]; any = any || b->strength[ch] != 0; }
-    return any;
 }
 
 // The median / rank-filter brush on the device: vr_morph's sequence with k_rank_stage as the first launch.  The
@@ -846,46 +839,37 @@ try {
     if (!p || !b) return fail(VR_ERR_INVALID, "vr_rank: null argument");
     if (const char* why = vr::rank::invalid(b, rank, half_width)) return fail(VR_ERR_INVALID, "vr_rank: %s", why);
     Ctx* c = as_ctx(p);
-    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_rank: no volume set");
-    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_rank: a procedural medium is enabled (it reads no volume)");
+    if (vr_status st = check_target("vr_rank", c)) return st;
     PaintArgs a{};
     if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
     if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
-    if (vr_status st = ensure_blur(c, blur_stage_bytes(a))) return st;
-    HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(launch_rank_stage(a, vr::rank::resolve(rank, half_width), half_width, c->d_planar, c->d_blur, s));
-    HIP_TRY(launch_blur_commit(a, c->d_blur, c->d_planar, c->d_mm, s));
-    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+    return staged_brush(c, a, s, "launch_rank_stage", [&] {
+        return launch_rank_stage(a, vr::rank::resolve(rank, half_width), half_width, c->d_planar, c->d_blur, s);
+    });
 } catch (...) {
     return caught_exception("vr_rank");
 }
 
 // The clone brush on the device: every check first, then the host picks the path in integers (vr_clone.h direct).
-// Direct: one launch from the planes to the planes.  Staged: k_clone_stage to the blur's scratch (grown only when
-// the call needs more than is held), then the blur's commit launch.  Both end with what follows an edit of the box.
+// Direct: one launch from the planes to the planes, then what follows an edit of the box.  Staged: the staged
+// sequence with k_clone_stage as its first launch.
 vr_status vr_clone(void* p, const vr_brush* b, const vr_clone_map* m, void* stream)
 try {
     if (!p || !b || !m) return fail(VR_ERR_INVALID, "vr_clone: null argument");
     if (const char* why = vr::clone::invalid(b, m)) return fail(VR_ERR_INVALID, "vr_clone: %s", why);
     Ctx* c = as_ctx(p);
-    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_clone: no volume set");
-    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_clone: a procedural medium is enabled (it reads no volume)");
+    if (vr_status st = check_target("vr_clone", c)) return st;
     CloneArgs g{};
     PaintArgs& a = g.p;
     if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
     if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
     for (int ax = 0; ax < 3; ++ax) { g.offset[ax] = m->offset[ax]; g.mirror[ax] = m->mirror[ax]; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vr::clone::direct(m, a.o, a.e, c->nx, c->ny, c->nz)) {
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(launch_clone_direct(g, c->d_planar, c->d_mm, s));
-    } else {
-        if (vr_status st = ensure_blur(c, blur_stage_bytes(a))) return st;
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(launch_clone_stage(g, c->d_planar, c->d_blur, s));
-        HIP_TRY(launch_blur_commit(a, c->d_blur, c->d_planar, c->d_mm, s));
-    }
+    if (!vr::clone::direct(m, a.o, a.e, c->nx, c->ny, c->nz))
+        return staged_brush(c, a, s, "launch_clone_stage", [&] { return launch_clone_stage(g, c->d_planar, c->d_blur, s); });
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_clone_direct(g, c->d_planar, c->d_mm, s));
     return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
 } catch (...) {
     return caught_exception("vr_clone");
@@ -899,8 +883,7 @@ try {
     if (const char* why = vr::stamp::invalid(b, placement)) return fail(VR_ERR_INVALID, "vr_stamp: %s", why);
     if ((reinterpret_cast<uintptr_t>(d_rgba8) & 3u) != 0u) return fail(VR_ERR_INVALID, "vr_stamp: d_rgba8 is not 4-byte aligned");
     Ctx* c = as_ctx(p);
-    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "vr_stamp: no volume set");
-    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "vr_stamp: a procedural medium is enabled (it reads no volume)");
+    if (vr_status st = check_target("vr_stamp", c)) return st;
     StampArgs g{};
     PaintArgs& a = g.p;
     if (!vr::stamp::clip(b, placement, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // nothing under brush and stamp
@@ -925,8 +908,7 @@ static vr_status remap_brush(const char* fn, void* p, const vr_brush* b, const v
     if (const char* why = vr::brush::invalid(b)) return fail(VR_ERR_INVALID, "%s: %s", fn, why);
     if (!lut && (reinterpret_cast<uintptr_t>(d_lut) & 3u) != 0u) return fail(VR_ERR_INVALID, "%s: d_lut is not 4-byte aligned", fn);
     Ctx* c = as_ctx(p);
-    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "%s: no volume set", fn);
-    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "%s: a procedural medium is enabled (it reads no volume)", fn);
+    if (vr_status st = check_target(fn, c)) return st;
     PaintArgs a{};
     if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
     if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
@@ -973,9 +955,7 @@ try {
 static vr_status stats_target(const char* fn, const Ctx* c, const void* d_stats)
 {
     if (((uintptr_t)d_stats & 7u) != 0) return fail(VR_ERR_INVALID, "%s: d_stats is not 8-byte aligned", fn);
-    if (!c->d_planar) return fail(VR_ERR_NO_VOLUME, "%s: no volume set", fn);
-    if (c->proc.enabled) return fail(VR_ERR_NO_VOLUME, "%s: a procedural medium is enabled (it reads no volume)", fn);
-    return VR_OK;
+    return check_target(fn, c);
 }
 
 vr_status vr_brush_stats(void* p, const vr_brush* b, void* d_stats, void* stream)
@@ -989,15 +969,8 @@ try {
     HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(vr_volume_stats), s));
     StatsArgs a{};
     if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume: all zero
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    a.s = t.s;
-    for (int ax = 0; ax < 3; ++ax) {
-        a.d0[ax] = (int)((long long)a.o[ax] - b->centre[ax]);   // within the radius of 0
-        a.k[ax] = t.k[ax];
-    }
+    brush_geometry(c, b, a);
     a.ellipsoid = 1;
-    a.falloff = b->falloff;
     a.mask = vr::stats::brush_mask(b->strength);
     HIP_TRY(launch_stats(a, c->d_planar, static_cast<vr_volume_stats*>(d_stats), s));
     return VR_OK;

@@ -2,7 +2,7 @@
 // DESIGN.md sec. 5.2.7), stated once: the filter's argument check, its texel
 // count and the rounded mean.  Plain integer C++ in the manner of vr_brush.h,
 // which supplies everything else of the brush (inside test, weight, blend):
-// the blur kernels (vr_volume.hip), the host statement (vr_brush.cpp) and the
+// the blur kernels (vr_paint.hip), the host statement (vr_brush.cpp) and the
 // stand-alone check (tools/blur_check.cpp) include this file, so they cannot
 // diverge.
 //

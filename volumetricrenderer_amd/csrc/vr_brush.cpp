@@ -16,12 +16,15 @@
 // checks and the entries of a table are vr_remap.h's).
 //
 // Pure host code in integers: no context, no device, no HIP call.  The
-// arithmetic is vr_brush.h's, which the paint kernel (vr_volume.hip) includes
+// arithmetic is vr_brush.h's, which the paint kernel (vr_paint.hip) includes
 // too; vr_brush_apply is its CPU statement, what vr_paint must reproduce bit
-// for bit.  tools/brush_check.cpp compiles this file alone
-// (-DVR_BRUSH_STANDALONE, which only drops the vr_last_error text) under the
-// address and undefined-behaviour sanitizers.
+// for bit.  Every statement is one walk over the clipped box (walk), the
+// brushes through paint with their own value of a texel, and what a brush reads
+// of the bytes before the call is a Snapshot.  tools/brush_check.cpp compiles
+// this file alone (-DVR_BRUSH_STANDALONE, which only drops the vr_last_error
+// text) under the address and undefined-behaviour sanitizers.
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "vr_blur.h"
@@ -51,6 +54,120 @@ vr_status check(const char* fn, const vr_brush* b, int nx, int ny, int nz)
     return VR_OK;
 }
 
+// The same for a brush with a check of its own (vr_blur.h, vr_morph.h, ...): all_set = no pointer is null, and
+// invalid() -- which may then read them -- is nullptr or what is wrong.
+template <class Invalid>
+vr_status check(const char* fn, bool all_set, Invalid invalid, int nx, int ny, int nz)
+{
+    if (!all_set) return fail(VR_ERR_INVALID, "%s: null argument", fn);
+    if (const char* why = invalid()) return fail(VR_ERR_INVALID, "%s: %s", fn, why);
+    if (nx <= 0 || ny <= 0 || nz <= 0) return fail(VR_ERR_INVALID, "%s: bad extent %dx%dx%d", fn, nx, ny, nz);
+    return VR_OK;
+}
+
+// The walk of every statement below: the box o, e (a brush's clipped box or a part of it, so every offset is
+// within the radius: at most 255 in magnitude) in ascending z, y, x.  rw = row(y, z) once per row that the y and z
+// terms of Q leave inside the ellipsoid S = t.s, then texel(rw, x, y, z, q) for every texel of that row with its Q:
+// what q > S means is the caller's rule.
+template <class Row, class Texel>
+void walk(const vr_brush* b, const vr::brush::Terms& t, const int o[3], const int e[3], Row row, Texel texel)
+{
+    for (int z = o[2]; z < o[2] + e[2]; ++z) {
+        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
+        for (int y = o[1]; y < o[1] + e[1]; ++y) {
+            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
+            if (qyz > t.s) continue;
+            const auto rw = row(y, z);
+            for (int x = o[0]; x < o[0] + e[0]; ++x)
+                texel(rw, x, y, z, qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]));
+        }
+    }
+}
+
+// The brush over the box o, e of the volume, in place: the walk, a texel outside the ellipsoid left alone, and per
+// channel with strength != 0 the blend of the old byte with value(c, old), where value = texel(rw, x, y, z) is
+// made once per inside texel and holds by value what that texel's channels share.
+template <class Row, class Texel>
+void paint(const vr_brush* b, int op, const int o[3], const int e[3], uint8_t* rgba8, int nx, int ny, Row row, Texel texel)
+{
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    const int falloff = b->falloff;
+    const unsigned strength[4] = {b->strength[0], b->strength[1], b->strength[2], b->strength[3]};
+    walk(b, t, o, e, row, [&](const auto& rw, int x, int y, int z, uint64_t q) {
+        if (q > t.s) return;
+        const unsigned w = vr::brush::weight(q, t.s, falloff);
+        uint8_t* p = rgba8 + ((((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) + (size_t)x) * 4;
+        const auto value = texel(rw, x, y, z);
+        for (int c = 0; c < 4; ++c) {
+            if (!strength[c]) continue;
+            p[c] = (uint8_t)vr::brush::blend(op, p[c], value(c, (unsigned)p[c]), w * strength[c]);
+        }
+    });
+}
+
+const auto no_row = [](int, int) { return 0; };
+
+// The bytes before the call: a copy of the box lo, ext (inside it) of an nx x ny x nz RGBA8 array, addressed by
+// the array's coordinates.
+struct Snapshot {
+    int n[3], lo[3], ext[3];
+    std::vector<uint8_t> bytes;
+
+    Snapshot(const uint8_t* rgba8, int nx, int ny, int nz, const int lo_[3], const int ext_[3])
+        : n{nx, ny, nz}, lo{lo_[0], lo_[1], lo_[2]}, ext{ext_[0], ext_[1], ext_[2]},
+          bytes((size_t)ext_[0] * (size_t)ext_[1] * (size_t)ext_[2] * 4)
+    {
+        // byte stores may alias the members: the row length and the pointers are locals
+        const size_t row_bytes = (size_t)ext_[0] * 4;
+        uint8_t* dst = bytes.data();
+        for (int z = 0; z < ext_[2]; ++z)
+            for (int y = 0; y < ext_[1]; ++y, dst += row_bytes) {
+                const uint8_t* src = rgba8 + (((size_t)(lo_[2] + z) * (size_t)ny + (size_t)(lo_[1] + y)) * (size_t)nx + (size_t)lo_[0]) * 4;
+                for (size_t i = 0; i < row_bytes; ++i) dst[i] = src[i];
+            }
+    }
+    // the copied part of the array's row (y, z): texel lo[0] first
+    const uint8_t* row(int y, int z) const
+    {
+        return &bytes[((size_t)(z - lo[2]) * (size_t)ext[1] + (size_t)(y - lo[1])) * (size_t)ext[0] * 4];
+    }
+    // a texel of the array, clamped to it: inside the copy for every neighbour of a texel of a box whose halo it holds
+    unsigned at(int x, int y, int z, int c) const
+    {
+        x = x < 0 ? 0 : x > n[0] - 1 ? n[0] - 1 : x;
+        y = y < 0 ? 0 : y > n[1] - 1 ? n[1] - 1 : y;
+        z = z < 0 ? 0 : z > n[2] - 1 ? n[2] - 1 : z;
+        return row(y, z)[(size_t)(x - lo[0]) * 4 + (size_t)c];
+    }
+};
+
+// the box o, e and its halo of h texels, inside the volume
+void halo_box(const int o[3], const int e[3], int h, int nx, int ny, int nz, int lo[3], int ext[3])
+{
+    const int n[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = o[a] - h < 0 ? 0 : o[a] - h;
+        const int hi = o[a] + e[a] - 1 + h > n[a] - 1 ? n[a] - 1 : o[a] + e[a] - 1 + h;
+        ext[a] = hi - lo[a] + 1;
+    }
+}
+
+// The neighbourhood brushes (blur, morph, rank) on checked arguments: a SET brush whose value, per texel and
+// channel, is f(before, x, y, z, c) of the bytes BEFORE the call.  The clipped box and its halo of h texels are
+// copied first and f reads the copy, so no value sees a byte this call wrote (Jacobi).
+template <class F>
+vr_status neighbourhood_apply(const vr_brush* b, int h, uint8_t* rgba8, int nx, int ny, int nz, F f)
+{
+    int o[3], e[3], lo[3], ext[3];
+    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
+    halo_box(o, e, h, nx, ny, nz, lo, ext);
+    const Snapshot before(rgba8, nx, ny, nz, lo, ext);
+    paint(b, VR_BRUSH_SET, o, e, rgba8, nx, ny, no_row, [&](int, int x, int y, int z) {
+        return [f, &before, x, y, z](int c, unsigned) { return f(before, x, y, z, c); };
+    });
+    return VR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -69,26 +186,9 @@ vr_status vr_brush_apply(const vr_brush* b, uint8_t* rgba8, int nx, int ny, int 
     if (vr_status st = check("vr_brush_apply", b, nx, ny, nz)) return st;
     int o[3], e[3];
     if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    // inside the clipped box every offset is within the radius: at most 255 in magnitude
-    for (int z = o[2]; z < o[2] + e[2]; ++z) {
-        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
-        for (int y = o[1]; y < o[1] + e[1]; ++y) {
-            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
-            if (qyz > t.s) continue;
-            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
-            for (int x = o[0]; x < o[0] + e[0]; ++x) {
-                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
-                if (q > t.s) continue;
-                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
-                for (int c = 0; c < 4; ++c) {
-                    if (!b->strength[c]) continue;
-                    uint8_t* p = row + (size_t)x * 4 + c;
-                    *p = (uint8_t)vr::brush::blend(b->op, *p, b->value[c], w * b->strength[c]);
-                }
-            }
-        }
-    }
+    const unsigned value[4] = {b->value[0], b->value[1], b->value[2], b->value[3]};
+    paint(b, b->op, o, e, rgba8, nx, ny, no_row,
+          [&](int, int, int, int) { return [&value](int c, unsigned) { return value[c]; }; });
     return VR_OK;
 }
 
@@ -97,57 +197,16 @@ vr_status vr_brush_apply(const vr_brush* b, uint8_t* rgba8, int nx, int ny, int 
 // copied first and every sum reads the copy, so no mean sees a byte this call wrote (Jacobi).
 vr_status vr_brush_blur_apply(const vr_brush* b, int half_width, uint8_t* rgba8, int nx, int ny, int nz)
 {
-    if (!b || !rgba8) return fail(VR_ERR_INVALID, "vr_brush_blur_apply: null argument");
-    if (const char* why = vr::blur::invalid(b, half_width)) return fail(VR_ERR_INVALID, "vr_brush_blur_apply: %s", why);
-    if (nx <= 0 || ny <= 0 || nz <= 0)
-        return fail(VR_ERR_INVALID, "vr_brush_blur_apply: bad extent %dx%dx%d", nx, ny, nz);
-    int o[3], e[3];
-    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
-    const int h = half_width, n[3] = {nx, ny, nz};
-    int lo[3], ext[3];   // the box and its halo, inside the volume
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = o[a] - h < 0 ? 0 : o[a] - h;
-        const int hi = o[a] + e[a] - 1 + h > n[a] - 1 ? n[a] - 1 : o[a] + e[a] - 1 + h;
-        ext[a] = hi - lo[a] + 1;
-    }
-    std::vector<uint8_t> before((size_t)ext[0] * (size_t)ext[1] * (size_t)ext[2] * 4);
-    for (int z = 0; z < ext[2]; ++z)
-        for (int y = 0; y < ext[1]; ++y) {
-            const uint8_t* src = rgba8 + (((size_t)(lo[2] + z) * (size_t)ny + (size_t)(lo[1] + y)) * (size_t)nx + (size_t)lo[0]) * 4;
-            uint8_t* dst = &before[((size_t)z * (size_t)ext[1] + (size_t)y) * (size_t)ext[0] * 4];
-            for (size_t i = 0; i < (size_t)ext[0] * 4; ++i) dst[i] = src[i];
-        }
-    // a texel of the volume, clamped to it: inside the copy for every neighbour of a texel of the box
-    auto at = [&](int x, int y, int z, int c) -> unsigned {
-        x = x < 0 ? 0 : x > nx - 1 ? nx - 1 : x;
-        y = y < 0 ? 0 : y > ny - 1 ? ny - 1 : y;
-        z = z < 0 ? 0 : z > nz - 1 ? nz - 1 : z;
-        return before[(((size_t)(z - lo[2]) * (size_t)ext[1] + (size_t)(y - lo[1])) * (size_t)ext[0] + (size_t)(x - lo[0])) * 4 + (size_t)c];
-    };
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    for (int z = o[2]; z < o[2] + e[2]; ++z) {
-        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
-        for (int y = o[1]; y < o[1] + e[1]; ++y) {
-            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
-            if (qyz > t.s) continue;
-            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
-            for (int x = o[0]; x < o[0] + e[0]; ++x) {
-                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
-                if (q > t.s) continue;
-                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
-                for (int c = 0; c < 4; ++c) {
-                    if (!b->strength[c]) continue;
-                    unsigned sum = 0;
-                    for (int dz = -h; dz <= h; ++dz)
-                        for (int dy = -h; dy <= h; ++dy)
-                            for (int dx = -h; dx <= h; ++dx) sum += at(x + dx, y + dy, z + dz, c);
-                    uint8_t* p = row + (size_t)x * 4 + c;
-                    *p = (uint8_t)vr::brush::blend(VR_BRUSH_SET, *p, vr::blur::mean(sum, h), w * b->strength[c]);
-                }
-            }
-        }
-    }
-    return VR_OK;
+    if (vr_status st = check("vr_brush_blur_apply", b && rgba8, [&] { return vr::blur::invalid(b, half_width); }, nx, ny, nz))
+        return st;
+    const int h = half_width;
+    return neighbourhood_apply(b, h, rgba8, nx, ny, nz, [h](const Snapshot& before, int x, int y, int z, int c) {
+        unsigned sum = 0;
+        for (int dz = -h; dz <= h; ++dz)
+            for (int dy = -h; dy <= h; ++dy)
+                for (int dx = -h; dx <= h; ++dx) sum += before.at(x + dx, y + dy, z + dz, c);
+        return vr::blur::mean(sum, h);
+    });
 }
 
 // The statistics under the brush on the host (include/vr.h): vr_brush_apply's walk with vr_stats.h's sums in place
@@ -161,19 +220,10 @@ vr_status vr_brush_stats_host(const vr_brush* b, const uint8_t* rgba8, int nx, i
     if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
     const vr::brush::Terms t = vr::brush::terms(b->radius);
     const unsigned mask = vr::stats::brush_mask(b->strength);
-    for (int z = o[2]; z < o[2] + e[2]; ++z) {
-        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
-        for (int y = o[1]; y < o[1] + e[1]; ++y) {
-            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
-            if (qyz > t.s) continue;
-            const uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
-            for (int x = o[0]; x < o[0] + e[0]; ++x) {
-                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
-                const unsigned w = vr::stats::texel_weight(1, q, t.s, b->falloff);
-                if (w) vr::stats::add_texel(out, mask, w, row + (size_t)x * 4);
-            }
-        }
-    }
+    walk(b, t, o, e, no_row, [&](int, int x, int y, int z, uint64_t q) {
+        const unsigned w = vr::stats::texel_weight(1, q, t.s, b->falloff);
+        if (w) vr::stats::add_texel(out, mask, w, rgba8 + ((((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) + (size_t)x) * 4);
+    });
     return VR_OK;
 }
 
@@ -210,58 +260,21 @@ vr_status vr_stats_summary(const vr_volume_stats* s, vr_volume_summary* out)
 // clipped box and its halo (inside the volume) are copied first and every extremum reads the copy (Jacobi).
 vr_status vr_brush_morph_apply(const vr_brush* b, int op, int half_width, uint8_t* rgba8, int nx, int ny, int nz)
 {
-    if (!b || !rgba8) return fail(VR_ERR_INVALID, "vr_brush_morph_apply: null argument");
-    if (const char* why = vr::morph::invalid(b, op, half_width))
-        return fail(VR_ERR_INVALID, "vr_brush_morph_apply: %s", why);
-    if (nx <= 0 || ny <= 0 || nz <= 0)
-        return fail(VR_ERR_INVALID, "vr_brush_morph_apply: bad extent %dx%dx%d", nx, ny, nz);
-    int o[3], e[3];
-    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
-    const int h = half_width, n[3] = {nx, ny, nz};
-    int lo[3], ext[3];   // the box and its halo, inside the volume
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = o[a] - h < 0 ? 0 : o[a] - h;
-        const int hi = o[a] + e[a] - 1 + h > n[a] - 1 ? n[a] - 1 : o[a] + e[a] - 1 + h;
-        ext[a] = hi - lo[a] + 1;
-    }
-    std::vector<uint8_t> before((size_t)ext[0] * (size_t)ext[1] * (size_t)ext[2] * 4);
-    for (int z = 0; z < ext[2]; ++z)
-        for (int y = 0; y < ext[1]; ++y) {
-            const uint8_t* src = rgba8 + (((size_t)(lo[2] + z) * (size_t)ny + (size_t)(lo[1] + y)) * (size_t)nx + (size_t)lo[0]) * 4;
-            uint8_t* dst = &before[((size_t)z * (size_t)ext[1] + (size_t)y) * (size_t)ext[0] * 4];
-            for (size_t i = 0; i < (size_t)ext[0] * 4; ++i) dst[i] = src[i];
-        }
-    // a texel of the volume, clamped to it: inside the copy for every neighbour of a texel of the box
-    auto at = [&](int x, int y, int z, int c) -> unsigned {
-        x = x < 0 ? 0 : x > nx - 1 ? nx - 1 : x;
-        y = y < 0 ? 0 : y > ny - 1 ? ny - 1 : y;
-        z = z < 0 ? 0 : z > nz - 1 ? nz - 1 : z;
-        return before[(((size_t)(z - lo[2]) * (size_t)ext[1] + (size_t)(y - lo[1])) * (size_t)ext[0] + (size_t)(x - lo[0])) * 4 + (size_t)c];
+    if (vr_status st = check("vr_brush_morph_apply", b && rgba8, [&] { return vr::morph::invalid(b, op, half_width); }, nx, ny, nz))
+        return st;
+    const int h = half_width;
+    // the extremum is chosen once, outside the loops: op is a constant in each instance
+    const auto apply = [&](auto op_c) {
+        return neighbourhood_apply(b, h, rgba8, nx, ny, nz, [h, op_c](const Snapshot& before, int x, int y, int z, int c) {
+            unsigned m = before.at(x, y, z, c);
+            for (int dz = -h; dz <= h; ++dz)
+                for (int dy = -h; dy <= h; ++dy)
+                    for (int dx = -h; dx <= h; ++dx) m = vr::morph::pick(op_c(), m, before.at(x + dx, y + dy, z + dz, c));
+            return m;
+        });
     };
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    for (int z = o[2]; z < o[2] + e[2]; ++z) {
-        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
-        for (int y = o[1]; y < o[1] + e[1]; ++y) {
-            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
-            if (qyz > t.s) continue;
-            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
-            for (int x = o[0]; x < o[0] + e[0]; ++x) {
-                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
-                if (q > t.s) continue;
-                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
-                for (int c = 0; c < 4; ++c) {
-                    if (!b->strength[c]) continue;
-                    unsigned m = at(x, y, z, c);
-                    for (int dz = -h; dz <= h; ++dz)
-                        for (int dy = -h; dy <= h; ++dy)
-                            for (int dx = -h; dx <= h; ++dx) m = vr::morph::pick(op, m, at(x + dx, y + dy, z + dz, c));
-                    uint8_t* p = row + (size_t)x * 4 + c;
-                    *p = (uint8_t)vr::brush::blend(VR_BRUSH_SET, *p, m, w * b->strength[c]);
-                }
-            }
-        }
-    }
-    return VR_OK;
+    return op == VR_MORPH_DILATE ? apply(std::integral_constant<int, VR_MORPH_DILATE>{})
+                                 : apply(std::integral_constant<int, VR_MORPH_ERODE>{});
 }
 
 // The clone brush on the host (include/vr.h): vr_brush_apply with the value of a texel read from the volume's own
@@ -269,10 +282,8 @@ vr_status vr_brush_morph_apply(const vr_brush* b, int op, int half_width, uint8_
 // inside the volume, no larger than the clipped box) is copied first and every value reads the copy (Jacobi).
 vr_status vr_brush_clone_apply(const vr_brush* b, const vr_clone_map* m, uint8_t* rgba8, int nx, int ny, int nz)
 {
-    if (!b || !m || !rgba8) return fail(VR_ERR_INVALID, "vr_brush_clone_apply: null argument");
-    if (const char* why = vr::clone::invalid(b, m)) return fail(VR_ERR_INVALID, "vr_brush_clone_apply: %s", why);
-    if (nx <= 0 || ny <= 0 || nz <= 0)
-        return fail(VR_ERR_INVALID, "vr_brush_clone_apply: bad extent %dx%dx%d", nx, ny, nz);
+    if (vr_status st = check("vr_brush_clone_apply", b && m && rgba8, [&] { return vr::clone::invalid(b, m); }, nx, ny, nz))
+        return st;
     int o[3], e[3];
     if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
     const int n[3] = {nx, ny, nz};
@@ -283,44 +294,24 @@ vr_status vr_brush_clone_apply(const vr_brush* b, const vr_clone_map* m, uint8_t
         lo[a] = s0 < s1 ? s0 : s1;
         ext[a] = (s0 < s1 ? s1 : s0) - lo[a] + 1;
     }
-    std::vector<uint8_t> before((size_t)ext[0] * (size_t)ext[1] * (size_t)ext[2] * 4);
-    for (int z = 0; z < ext[2]; ++z)
-        for (int y = 0; y < ext[1]; ++y) {
-            const uint8_t* src = rgba8 + (((size_t)(lo[2] + z) * (size_t)ny + (size_t)(lo[1] + y)) * (size_t)nx + (size_t)lo[0]) * 4;
-            uint8_t* dst = &before[((size_t)z * (size_t)ext[1] + (size_t)y) * (size_t)ext[0] * 4];
-            for (size_t i = 0; i < (size_t)ext[0] * 4; ++i) dst[i] = src[i];
-        }
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    for (int z = o[2]; z < o[2] + e[2]; ++z) {
-        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
-        const int sz = vr::clone::source(z, m->offset[2], m->mirror[2], nz);
-        for (int y = o[1]; y < o[1] + e[1]; ++y) {
-            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
-            if (qyz > t.s) continue;
-            const int sy = vr::clone::source(y, m->offset[1], m->mirror[1], ny);
-            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
-            const uint8_t* srow = &before[((size_t)(sz - lo[2]) * (size_t)ext[1] + (size_t)(sy - lo[1])) * (size_t)ext[0] * 4];
-            for (int x = o[0]; x < o[0] + e[0]; ++x) {
-                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
-                if (q > t.s) continue;
-                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
-                const int sx = vr::clone::source(x, m->offset[0], m->mirror[0], nx);
-                for (int c = 0; c < 4; ++c) {
-                    if (!b->strength[c]) continue;
-                    uint8_t* p = row + (size_t)x * 4 + c;
-                    *p = (uint8_t)vr::brush::blend(b->op, *p, srow[(size_t)(sx - lo[0]) * 4 + (size_t)c], w * b->strength[c]);
-                }
-            }
-        }
-    }
+    const Snapshot before(rgba8, nx, ny, nz, lo, ext);
+    const int off0 = m->offset[0], mir0 = m->mirror[0], lo0 = lo[0];
+    paint(b, b->op, o, e, rgba8, nx, ny,
+          [&](int y, int z) {   // the source row of the box row
+              return before.row(vr::clone::source(y, m->offset[1], m->mirror[1], ny),
+                                vr::clone::source(z, m->offset[2], m->mirror[2], nz));
+          },
+          [=](const uint8_t* srow, int x, int, int) {   // the source texel
+              const uint8_t* s = srow + (size_t)(vr::clone::source(x, off0, mir0, nx) - lo0) * 4;
+              return [s](int c, unsigned) -> unsigned { return s[c]; };
+          });
     return VR_OK;
 }
 
 vr_status vr_stamp_box(const vr_brush* b, const vr_box* placement, int nx, int ny, int nz, int origin[3], int extent[3])
 {
-    if (!b || !placement || !origin || !extent) return fail(VR_ERR_INVALID, "vr_stamp_box: null argument");
-    if (const char* why = vr::stamp::invalid(b, placement)) return fail(VR_ERR_INVALID, "vr_stamp_box: %s", why);
-    if (nx <= 0 || ny <= 0 || nz <= 0) return fail(VR_ERR_INVALID, "vr_stamp_box: bad extent %dx%dx%d", nx, ny, nz);
+    if (vr_status st = check("vr_stamp_box", b && placement && origin && extent, [&] { return vr::stamp::invalid(b, placement); }, nx, ny, nz))
+        return st;
     (void)vr::stamp::clip(b, placement, nx, ny, nz, origin, extent);
     return VR_OK;
 }
@@ -330,42 +321,21 @@ vr_status vr_stamp_box(const vr_brush* b, const vr_box* placement, int nx, int n
 vr_status vr_brush_stamp_apply(const vr_brush* b, const uint8_t* stamp, const vr_box* placement, uint8_t* rgba8, int nx,
                                int ny, int nz)
 {
-    if (!b || !stamp || !placement || !rgba8) return fail(VR_ERR_INVALID, "vr_brush_stamp_apply: null argument");
-    if (const char* why = vr::stamp::invalid(b, placement)) return fail(VR_ERR_INVALID, "vr_brush_stamp_apply: %s", why);
-    if (nx <= 0 || ny <= 0 || nz <= 0)
-        return fail(VR_ERR_INVALID, "vr_brush_stamp_apply: bad extent %dx%dx%d", nx, ny, nz);
+    if (vr_status st = check("vr_brush_stamp_apply", b && stamp && placement && rgba8, [&] { return vr::stamp::invalid(b, placement); }, nx, ny, nz))
+        return st;
     int o[3], e[3];
     if (!vr::stamp::clip(b, placement, nx, ny, nz, o, e)) return VR_OK;
     // the edited box lies inside the placement: its first texel's position in the stamp is not negative
-    const size_t so[3] = {(size_t)((int64_t)o[0] - placement->x), (size_t)((int64_t)o[1] - placement->y),
-                          (size_t)((int64_t)o[2] - placement->z)};
-    std::vector<uint8_t> copy((size_t)e[0] * (size_t)e[1] * (size_t)e[2] * 4);
-    for (int z = 0; z < e[2]; ++z)
-        for (int y = 0; y < e[1]; ++y) {
-            const uint8_t* src = stamp + (((so[2] + (size_t)z) * (size_t)placement->by + so[1] + (size_t)y) * (size_t)placement->bx + so[0]) * 4;
-            uint8_t* dst = &copy[((size_t)z * (size_t)e[1] + (size_t)y) * (size_t)e[0] * 4];
-            for (size_t i = 0; i < (size_t)e[0] * 4; ++i) dst[i] = src[i];
-        }
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    for (int z = o[2]; z < o[2] + e[2]; ++z) {
-        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
-        for (int y = o[1]; y < o[1] + e[1]; ++y) {
-            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
-            if (qyz > t.s) continue;
-            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
-            const uint8_t* srow = &copy[((size_t)(z - o[2]) * (size_t)e[1] + (size_t)(y - o[1])) * (size_t)e[0] * 4];
-            for (int x = o[0]; x < o[0] + e[0]; ++x) {
-                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
-                if (q > t.s) continue;
-                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
-                for (int c = 0; c < 4; ++c) {
-                    if (!b->strength[c]) continue;
-                    uint8_t* p = row + (size_t)x * 4 + c;
-                    *p = (uint8_t)vr::brush::blend(b->op, *p, srow[(size_t)(x - o[0]) * 4 + (size_t)c], w * b->strength[c]);
-                }
-            }
-        }
-    }
+    const int so[3] = {(int)((int64_t)o[0] - placement->x), (int)((int64_t)o[1] - placement->y),
+                       (int)((int64_t)o[2] - placement->z)};
+    const Snapshot copy(stamp, placement->bx, placement->by, placement->bz, so, e);
+    const int o0 = o[0];
+    paint(b, b->op, o, e, rgba8, nx, ny,
+          [&](int y, int z) { return copy.row(so[1] + (y - o[1]), so[2] + (z - o[2])); },   // the stamp row on the box row
+          [=](const uint8_t* srow, int x, int, int) {
+              const uint8_t* s = srow + (size_t)(x - o0) * 4;
+              return [s](int c, unsigned) -> unsigned { return s[c]; };
+          });
     return VR_OK;
 }
 
@@ -377,25 +347,8 @@ vr_status vr_brush_remap_apply(const vr_brush* b, const vr_lut* lut, uint8_t* rg
     if (vr_status st = check("vr_brush_remap_apply", b, nx, ny, nz)) return st;
     int o[3], e[3];
     if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
-    for (int z = o[2]; z < o[2] + e[2]; ++z) {
-        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
-        for (int y = o[1]; y < o[1] + e[1]; ++y) {
-            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
-            if (qyz > t.s) continue;
-            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
-            for (int x = o[0]; x < o[0] + e[0]; ++x) {
-                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
-                if (q > t.s) continue;
-                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
-                for (int c = 0; c < 4; ++c) {
-                    if (!b->strength[c]) continue;
-                    uint8_t* p = row + (size_t)x * 4 + c;
-                    *p = (uint8_t)vr::brush::blend(b->op, *p, lut->lut[c][*p], w * b->strength[c]);
-                }
-            }
-        }
-    }
+    paint(b, b->op, o, e, rgba8, nx, ny, no_row,
+          [lut](int, int, int, int) { return [lut](int c, unsigned old) -> unsigned { return lut->lut[c][old]; }; });
     return VR_OK;
 }
 
@@ -446,67 +399,23 @@ vr_status vr_stats_lut(const vr_volume_stats* stats, int kind, int channel_mask,
 // (Jacobi); the selection is vr_rank.h's bisection, each count a plain loop over the cube.
 vr_status vr_brush_rank_apply(const vr_brush* b, int rank, int half_width, uint8_t* rgba8, int nx, int ny, int nz)
 {
-    if (!b || !rgba8) return fail(VR_ERR_INVALID, "vr_brush_rank_apply: null argument");
-    if (const char* why = vr::rank::invalid(b, rank, half_width))
-        return fail(VR_ERR_INVALID, "vr_brush_rank_apply: %s", why);
-    if (nx <= 0 || ny <= 0 || nz <= 0)
-        return fail(VR_ERR_INVALID, "vr_brush_rank_apply: bad extent %dx%dx%d", nx, ny, nz);
-    int o[3], e[3];
-    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
-    const int h = half_width, n[3] = {nx, ny, nz};
+    if (vr_status st = check("vr_brush_rank_apply", b && rgba8, [&] { return vr::rank::invalid(b, rank, half_width); }, nx, ny, nz))
+        return st;
+    const int h = half_width, count = vr::rank::window(h);
     const unsigned k = (unsigned)vr::rank::resolve(rank, h);
-    int lo[3], ext[3];   // the box and its halo, inside the volume
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = o[a] - h < 0 ? 0 : o[a] - h;
-        const int hi = o[a] + e[a] - 1 + h > n[a] - 1 ? n[a] - 1 : o[a] + e[a] - 1 + h;
-        ext[a] = hi - lo[a] + 1;
-    }
-    std::vector<uint8_t> before((size_t)ext[0] * (size_t)ext[1] * (size_t)ext[2] * 4);
-    for (int z = 0; z < ext[2]; ++z)
-        for (int y = 0; y < ext[1]; ++y) {
-            const uint8_t* src = rgba8 + (((size_t)(lo[2] + z) * (size_t)ny + (size_t)(lo[1] + y)) * (size_t)nx + (size_t)lo[0]) * 4;
-            uint8_t* dst = &before[((size_t)z * (size_t)ext[1] + (size_t)y) * (size_t)ext[0] * 4];
-            for (size_t i = 0; i < (size_t)ext[0] * 4; ++i) dst[i] = src[i];
-        }
-    // a texel of the volume, clamped to it: inside the copy for every neighbour of a texel of the box
-    auto at = [&](int x, int y, int z, int c) -> unsigned {
-        x = x < 0 ? 0 : x > nx - 1 ? nx - 1 : x;
-        y = y < 0 ? 0 : y > ny - 1 ? ny - 1 : y;
-        z = z < 0 ? 0 : z > nz - 1 ? nz - 1 : z;
-        return before[(((size_t)(z - lo[2]) * (size_t)ext[1] + (size_t)(y - lo[1])) * (size_t)ext[0] + (size_t)(x - lo[0])) * 4 + (size_t)c];
-    };
-    const vr::brush::Terms t = vr::brush::terms(b->radius);
     unsigned cube[7 * 7 * 7];   // the neighbours of one texel and channel
     static_assert(VR_RANK_MAX_HALF == 3, "the cube holds the widest window");
-    const int count = vr::rank::window(h);
-    for (int z = o[2]; z < o[2] + e[2]; ++z) {
-        const uint64_t qz = vr::brush::axis_term((int)((int64_t)z - b->centre[2]), t.k[2]);
-        for (int y = o[1]; y < o[1] + e[1]; ++y) {
-            const uint64_t qyz = qz + vr::brush::axis_term((int)((int64_t)y - b->centre[1]), t.k[1]);
-            if (qyz > t.s) continue;
-            uint8_t* row = rgba8 + (((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) * 4;
-            for (int x = o[0]; x < o[0] + e[0]; ++x) {
-                const uint64_t q = qyz + vr::brush::axis_term((int)((int64_t)x - b->centre[0]), t.k[0]);
-                if (q > t.s) continue;
-                const unsigned w = vr::brush::weight(q, t.s, b->falloff);
-                for (int c = 0; c < 4; ++c) {
-                    if (!b->strength[c]) continue;
-                    int i = 0;
-                    for (int dz = -h; dz <= h; ++dz)
-                        for (int dy = -h; dy <= h; ++dy)
-                            for (int dx = -h; dx <= h; ++dx) cube[i++] = at(x + dx, y + dy, z + dz, c);
-                    const unsigned m = vr::rank::select(k, [&](unsigned cand) {
-                        unsigned below = 0u;
-                        for (int j = 0; j < count; ++j) below += vr::rank::below(cube[j], cand);
-                        return below;
-                    });
-                    uint8_t* p = row + (size_t)x * 4 + c;
-                    *p = (uint8_t)vr::brush::blend(VR_BRUSH_SET, *p, m, w * b->strength[c]);
-                }
-            }
-        }
-    }
-    return VR_OK;
+    return neighbourhood_apply(b, h, rgba8, nx, ny, nz, [&](const Snapshot& before, int x, int y, int z, int c) {
+        int i = 0;
+        for (int dz = -h; dz <= h; ++dz)
+            for (int dy = -h; dy <= h; ++dy)
+                for (int dx = -h; dx <= h; ++dx) cube[i++] = before.at(x + dx, y + dy, z + dz, c);
+        return vr::rank::select(k, [&](unsigned cand) {
+            unsigned below = 0u;
+            for (int j = 0; j < count; ++j) below += vr::rank::below(cube[j], cand);
+            return below;
+        });
+    });
 }
 
 // The dabs of a drag (include/vr.h): n segments of at most `spacing` texels on the longest axis, dab i at the

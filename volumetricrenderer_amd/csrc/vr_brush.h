@@ -2,7 +2,7 @@
 // sec. 5.2.5), stated once: the argument check, the clipped bounding box, the
 // ellipsoid weight and the per-channel blend.  Plain integer C++, host and
 // device under hipcc and compilable as plain C++: the paint kernel
-// (vr_volume.hip), the host statement (vr_brush.cpp) and the stand-alone check
+// (vr_paint.hip), the host statement (vr_brush.cpp) and the stand-alone check
 // (tools/brush_check.cpp) include this file, so they cannot diverge.
 //
 // Offsets d = texel - centre, D_a = 2 radius[a] + 1, all in unsigned 64 bits:

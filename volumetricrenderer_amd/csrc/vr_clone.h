@@ -4,7 +4,7 @@
 // cloned texel, the rule that picks the clone's device path, and the edited
 // box of a stamp.  Plain integer C++ in the manner of vr_blur.h and vr_morph.h;
 // vr_brush.h supplies everything else of the brush (inside test, weight,
-// blend): the kernels (vr_volume.hip), the host statements (vr_brush.cpp) and
+// blend): the kernels (vr_paint.hip), the host statements (vr_brush.cpp) and
 // the stand-alone check (tools/clone_check.cpp) include this file, so they
 // cannot diverge.
 //

@@ -509,7 +509,7 @@ struct ShadowDefer {
 };
 constexpr unsigned kDeferInPlace = 0xffffffffu;
 
-// launchers (vr_march.hip / vr_volume.hip); return hipError_t
+// launchers (vr_march.hip / vr_volume.hip / vr_paint.hip); return hipError_t
 hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, const Schedule& sc, hipStream_t s);
 // nf (2 or 4) frames in one regions launch (march_regions_frames; vr_render_pair,
 // vr_render_group): the layouts with such a kernel, and the launch -- a is frame 0's

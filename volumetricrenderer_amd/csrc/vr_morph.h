@@ -2,7 +2,7 @@
 // (include/vr.h), stated once: the argument check and
 // the extremum of two bytes.  Plain integer C++ in the manner of vr_blur.h;
 // vr_brush.h supplies everything else of the brush (inside test, weight,
-// blend): the stage kernel (vr_volume.hip), the host statement (vr_brush.cpp)
+// blend): the stage kernel (vr_paint.hip), the host statement (vr_brush.cpp)
 // and the stand-alone check (tools/morph_check.cpp) include this file, so they
 // cannot diverge.
 //

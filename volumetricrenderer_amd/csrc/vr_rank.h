@@ -2,7 +2,7 @@
 // (include/vr.h), stated once: the argument check, the
 // rank a call means, and the selection rule.  Plain integer C++ in the manner
 // of vr_morph.h; vr_brush.h supplies everything else of the brush (inside
-// test, weight, blend): the stage kernel (vr_volume.hip), the host statement
+// test, weight, blend): the stage kernel (vr_paint.hip), the host statement
 // (vr_brush.cpp) and the stand-alone check (tools/rank_check.cpp) include this
 // file, so they cannot diverge.
 //

@@ -5,7 +5,7 @@
 // levels table, and one entry of a table built from a histogram.  Plain
 // integer C++ in the manner of vr_clone.h and vr_stats.h; vr_brush.h supplies
 // everything else of the brush (inside test, weight, blend): the kernels
-// (vr_volume.hip), the host statements (vr_brush.cpp) and the stand-alone
+// (vr_paint.hip), the host statements (vr_brush.cpp) and the stand-alone
 // check (tools/remap_check.cpp) include this file, so they cannot diverge.
 //
 // The remap brush is a source brush (sec. 5.2.10) whose per-texel value is

@@ -2,7 +2,7 @@
 // DESIGN.md sec. 5.2.8), stated once: which texels count and with what weight,
 // which channels are selected, what a texel adds to which field, and the
 // summary's rounding.  Plain integer C++ in the manner of vr_brush.h, which
-// supplies the ellipsoid: the kernel k_stats (vr_volume.hip), the host
+// supplies the ellipsoid: the kernel k_stats (vr_paint.hip), the host
 // statements (vr_brush.cpp) and the stand-alone check (tools/stats_check.cpp)
 // include this file, so they cannot diverge.
 //
