@@ -281,6 +281,9 @@ struct Ctx {
     int frame_quad = 1;            // option "frame_quad": a four-frame launch whose frames share one camera
                                    // (frames_share_camera) takes the QUAD kernels; 0 = the kernel of every other group
     long long quad_launches = 0;   // read-only option "quad_launches": QUAD launches so far
+    int quad_split = 1;            // option "quad_split": a QUAD launch of COL48 / BRICK4832 splits each tap's loads
+                                   // between the lanes of a quad; 0 = every lane loads all
+    long long quad_split_launches = 0;   // read-only option "quad_split_launches": those launches so far
     uint2* d_lat = nullptr;
     size_t lat_cap = 0;            // bytes allocated
     long long lat_key[3] = {0, 0, -1};

@@ -277,6 +277,13 @@ constexpr bool quad_instance(int layout, bool early, bool zero_offsets, int umas
     return !(is_b4_family(layout) && !early && zero_offsets);
 }
 
+// How a four-frame launch uses the lanes of a quad (launch_march_frames): not at all (wave =
+// frame), the QUAD instance, or the QUAD instance whose lanes split each tap's loads between
+// them (option quad_split; vr_march_kernels.h march_pixel_quad_split).  The split fetch is
+// built for the layouts whose footprint slice packs into one dword, 32 bytes apart in z.
+enum QuadMode : int { QUAD_NONE = 0, QUAD_FRAMES = 1, QUAD_SPLIT = 2 };
+constexpr bool quad_split_layout(int layout) { return layout == LAYOUT_COL48 || layout == LAYOUT_BRICK4832; }
+
 // The part of MarchArgs that differs between the frames of one multi-frame launch
 // (vr_render_pair, vr_render_group): the camera (ray basis, r2 / r3, cam, tap_T), the
 // target buffer, the empty-tile fill and the step counter -- what vr_render.cpp's
@@ -517,12 +524,13 @@ hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, co
 // regions schedule with one lane per ray (no split, no slab, 4-wave workgroups); deal
 // (nf = 2 only) 0 = the frame in the wave's parity, 1 = in the workgroup's (vr_march_kernels.h)
 constexpr bool pair_layout(int layout) { return list_has(FrameLayouts{}, layout); }
-// quad (nf = 4, frames_share_camera(fr, nf) and no step counter only): the kernels' QUAD
-// instance, the four frames in the lanes of a quad (vr_march_kernels.h regions_frames_body)
+// quad (a QuadMode; other than QUAD_NONE for nf = 4, frames_share_camera(fr, nf) and no step
+// counter only): the kernels' QUAD instance, the four frames in the lanes of a quad
+// (vr_march_kernels.h regions_frames_body); QUAD_SPLIT for a quad_split_layout only
 hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
-                               int deal, bool quad, hipStream_t s);
+                               int deal, int quad, hipStream_t s);
 hipError_t launch_march_frames_cornerh(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc,
-                                       int deal, bool quad, hipStream_t s);   // vr_march_c8.hip
+                                       int deal, int quad, hipStream_t s);   // vr_march_c8.hip
 // per-plane byte min (mm[0..3]) and max (mm[4..7]) of the planar volume; mm
 // must hold 0xffffffff x 4 then 0 x 4 (atomicMin / atomicMax)
 hipError_t launch_plane_minmax(const uint8_t* d_planar, long long total, unsigned* mm, hipStream_t s);

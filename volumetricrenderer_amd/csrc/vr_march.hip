@@ -136,7 +136,7 @@ hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, co
 }
 
 hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
-                               int deal, bool quad, hipStream_t s)
+                               int deal, int quad, hipStream_t s)
 {
     if (a.width <= 0 || a.out_rows <= 0) return hipSuccess;
     // a layout without a multi-frame kernel is an error: the caller renders the frames one by one

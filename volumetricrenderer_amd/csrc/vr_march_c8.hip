@@ -15,7 +15,7 @@ hipError_t launch_march_corner8(const MarchArgs& a, int layout, bool early, cons
 }
 
 hipError_t launch_march_frames_cornerh(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc,
-                                       int deal, bool quad, hipStream_t s)
+                                       int deal, int quad, hipStream_t s)
 {
     return launch_frames_l<LAYOUT_CORNERH, WRAP_CLAMP>(a, fr, nf, early, sc, deal, quad, s);
 }

@@ -370,6 +370,142 @@ __device__ __forceinline__ unsigned march_pixel(const MarchArgs& a, const FastCt
     return r.n > 0 ? (unsigned)i : 0u;
 }
 
+// ---- the QUAD kernels' split fetch (option quad_split) ----
+// In a QUAD kernel the four lanes of a quad hold one ray (regions_frames_body), so a
+// tap_fetch there loads the same two 8-byte slices four times over.  Here the march runs
+// in pairs of steps and the quad splits a pair's fetch: quad lane fl loads z-slice fl & 1
+// (+ (fl & 1) * kZ) of step a + (fl >> 1) -- one b64 instruction per tap and pair where
+// tap_fetch issues four, all in the tap's own channel plane, so the descriptor and its
+// range check are tap_fetch's.  The loading lane shifts its slice down by its own off & 3
+// and packs the four footprint texels into one dword: bytes 0, 1 = row y at x, x + 1,
+// bytes 2, 3 = row y + 1.  A consumer reads byte K of quad lane J's dword through DPP
+// quad_perm [J, J, J, J]: no LDS, no further memory instruction.
+//
+// Every lane still marches its own ray: it advances the point by the same repeated adds
+// as march_pixel, computes the weights of both steps from it, blends both and updates acc
+// in march_pixel's order: step a + 1's term is added only where the ray has that step and
+// step a's sum did not pass acc_limit, so acc takes march_pixel's values one after the
+// other.  Only the lane's own step goes through cvt_flr, the offset tables and the load.
+//
+// The exchange needs every lane of a quad active wherever one is.  That holds because the
+// lanes of a quad share the ray: r.n, the early-out and the edge-of-frame case are the
+// same in all four, so a quad takes every branch below as one.
+template <int J>
+__device__ __forceinline__ unsigned quad_lane(unsigned v)
+{
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, J * 0x55, 0xf, 0xf, true);
+}
+// byte K of v as float.  Not ubyte<K>(): the compiler folds quad_lane's DPP move into
+// this v_cvt_f32_ubyteK, which it cannot do through an asm statement, and it keeps the
+// wait states between the pack and the DPP read
+template <int K>
+__device__ __forceinline__ float ubyte_of(unsigned v) { return (float)((v >> (8 * K)) & 0xffu); }
+
+constexpr unsigned kSplitZ = 32;   // bytes between the z-slices of COL48 / BRICK4832 (tap_fetch's kZ)
+
+// one lane's part of a step pair's fetch of one tap: its slice, and the offset whose low bits shift it
+struct SliceRaw {
+    unsigned s0, s1, off;
+};
+template <int UM, int T, bool ZO>
+__device__ __forceinline__ SliceRaw split_fetch(const MarchArgs& a, const FastCtx& f, f2 pxy, float pz, unsigned zoff)
+{
+    if constexpr ((UM >> T) & 1) {
+        return SliceRaw{};
+    } else {
+        const f2 Tt = ZO ? f2{0.5f, 0.5f} : f2{a.tap_T[T][0], a.tap_T[T][1]};
+        const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[T][0], a.tap_S[T][1]}, Tt);
+        const float gz = fmaf(pz, a.tap_S[T][2], ZO ? 0.5f : a.tap_T[T][2]);
+        const unsigned off = f.tx[cvt_flr(gxy.x)] + f.ty[cvt_flr(gxy.y)] + f.tz[cvt_flr(gz)];
+        const auto s = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], (off & ~3u) + zoff, 0, 0);
+        return SliceRaw{s[0], s[1], off};
+    }
+}
+__device__ __forceinline__ unsigned split_pack(const SliceRaw& r)
+{
+    const unsigned q0 = __builtin_amdgcn_alignbyte(r.s1, r.s0, r.off);   // bytes 0, 1: row y at x, x + 1
+    const unsigned q1 = __builtin_amdgcn_alignbyte(r.s1, r.s1, r.off);   // row y + 1
+    return __builtin_amdgcn_perm(q1, q0, 0x05040100u);
+}
+// tap T of the pair's step H (0, 1) at the ray point (pxy, pz): the slices are quad lanes 2H and 2H + 1's
+template <int UM, int T, int H, bool ZO>
+__device__ __forceinline__ float split_blend(const MarchArgs& a, unsigned pk, f2 pxy, float pz, const float* uv)
+{
+    if constexpr ((UM >> T) & 1) {
+        return uv[T];
+    } else {
+        const f2 Tt = ZO ? f2{0.5f, 0.5f} : f2{a.tap_T[T][0], a.tap_T[T][1]};
+        const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[T][0], a.tap_S[T][1]}, Tt);
+        const float gz = fmaf(pz, a.tap_S[T][2], ZO ? 0.5f : a.tap_T[T][2]);
+        const unsigned z0 = quad_lane<2 * H>(pk), z1 = quad_lane<2 * H + 1>(pk);
+        return blend(f2{ubyte_of<0>(z0), ubyte_of<0>(z1)}, f2{ubyte_of<1>(z0), ubyte_of<1>(z1)},
+                     f2{ubyte_of<2>(z0), ubyte_of<2>(z1)}, f2{ubyte_of<3>(z0), ubyte_of<3>(z1)},
+                     fract_(gxy.x), fract_(gxy.y), fract_(gz));
+    }
+}
+// march_pixel for quad lane fl of a QUAD kernel (COL48 / BRICK4832).  Software-pipelined
+// like march_pixel, by pairs: the loads of steps i + 2, i + 3 are issued before steps i,
+// i + 1 are blended.  A lane whose own step lies past the ray's last one loads the pair's
+// first point again, which is in the box: no load names a point outside it.
+template <int LAYOUT, bool EARLY, bool ZO, int UM>
+__device__ __forceinline__ void march_pixel_quad_split(const MarchArgs& a, const FastCtx& f, int x, int orow, int fl)
+{
+    static_assert(quad_split_layout(LAYOUT), "the packed slice is the b4 family's with 32-byte z-slices");
+    const Ray r = setup_ray(a, x, orow);
+    float uv[4] = {};
+    if constexpr (UM != 0)
+        for (int t = 0; t < 4; ++t)
+            if ((UM >> t) & 1) uv[t] = noise::in_vgpr(a.uval[t]);
+    float acc = 0.0f;
+    if (r.n > 0) {
+        const bool hi = (fl & 2) != 0;             // this lane loads for the pair's second step
+        const unsigned zoff = (fl & 1) * kSplitZ;   // and this z-slice of it
+        f2 axy = r.pxy, bxy = r.pxy + r.sxy;        // the points of steps i and i + 1       // :74
+        float az = r.pz, bz = r.pz + r.sz;
+        bool mine = hi && 1 < r.n;
+        f2 qxy = mine ? bxy : axy;
+        float qz = mine ? bz : az;
+        SliceRaw c0 = split_fetch<UM, 0, ZO>(a, f, qxy, qz, zoff), c1 = split_fetch<UM, 1, ZO>(a, f, qxy, qz, zoff);
+        SliceRaw c2 = split_fetch<UM, 2, ZO>(a, f, qxy, qz, zoff), c3 = split_fetch<UM, 3, ZO>(a, f, qxy, qz, zoff);
+        for (int i = 0;;) {
+            const f2 cxy = bxy + r.sxy, dxy = cxy + r.sxy;   // steps i + 2 and i + 3
+            const float cz = bz + r.sz, dz = cz + r.sz;
+            mine = i + 2 + (hi ? 1 : 0) < r.n;
+            qxy = mine ? (hi ? dxy : cxy) : axy;
+            qz = mine ? (hi ? dz : cz) : az;
+            const SliceRaw n0 = split_fetch<UM, 0, ZO>(a, f, qxy, qz, zoff), n1 = split_fetch<UM, 1, ZO>(a, f, qxy, qz, zoff);
+            const SliceRaw n2 = split_fetch<UM, 2, ZO>(a, f, qxy, qz, zoff), n3 = split_fetch<UM, 3, ZO>(a, f, qxy, qz, zoff);
+            const unsigned p0 = split_pack(c0), p1 = split_pack(c1), p2 = split_pack(c2), p3 = split_pack(c3);
+            bool stop = false;
+            {
+                const float t0 = split_blend<UM, 0, 0, ZO>(a, p0, axy, az, uv), t1 = split_blend<UM, 1, 0, ZO>(a, p1, axy, az, uv);
+                const float t2 = split_blend<UM, 2, 0, ZO>(a, p2, axy, az, uv), t3 = split_blend<UM, 3, 0, ZO>(a, p3, axy, az, uv);
+                acc = acc + ((t0 * t1) * (t2 + t3)) * a.scale;                           // :71-73
+                if constexpr (EARLY) stop = acc > a.acc_limit;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            {
+                // the pair's second step counts where the ray has it and the first did not end the
+                // march; its term is formed either way, so a pair is one block with its loads on top
+                const float t0 = split_blend<UM, 0, 1, ZO>(a, p0, bxy, bz, uv), t1 = split_blend<UM, 1, 1, ZO>(a, p1, bxy, bz, uv);
+                const float t2 = split_blend<UM, 2, 1, ZO>(a, p2, bxy, bz, uv), t3 = split_blend<UM, 3, 1, ZO>(a, p3, bxy, bz, uv);
+                const float both = acc + ((t0 * t1) * (t2 + t3)) * a.scale;
+                acc = i + 1 < r.n && !stop ? both : acc;
+                if constexpr (EARLY) stop = acc > a.acc_limit;
+            }
+            i += 2;
+            if (stop || i >= r.n) break;
+            c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+            axy = cxy; az = cz;
+            bxy = dxy; bz = dz;
+        }
+    }
+    if (r.live) {
+        const float at = acc * a.step_size;
+        store_pixel(a, x, orow, r.n >= 0, 1.0f - spec_expf(a.density * fminf(-at, 0.0f)));
+    }
+}
+
 // Kernel prologue for the fast layouts: buffer descriptors (wave-uniform,
 // from kernargs only) and the per-axis offset tables, built in LDS by the
 // whole workgroup.  The tables are the only LDS use and are read-only after
@@ -587,12 +723,16 @@ __global__ __launch_bounds__(kThreads) void march_regions_u(const MarchArgs a, c
 //                 address, where four waves used to present it one after the other.  The ray
 //                 runs on the common arguments; a lane's own part is its target pointer.
 //                 Steps are not counted: the host sends a counted launch down the NF 4 path.
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false>
+//   QUAD, SPLIT:  COL48 / BRICK4832 only (option quad_split): the same
+//                 mapping, and the quad's lanes split the loads of two steps between them
+//                 (march_pixel_quad_split) instead of each issuing all of them.
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false>
 __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, const unsigned* __restrict__ tiles,
                                                     const int* __restrict__ hdr, int nwx, int deal, unsigned* lds)
 {
     static_assert(NF == 2 || NF == 4, "a 4-wave workgroup is 4 / NF entry waves x NF frames");
     static_assert(!QUAD || NF == 4, "a quad of lanes is four frames");
+    static_assert(!SPLIT || QUAD, "the lanes of a quad split a fetch only where they hold one ray");
     const int xcd = blockIdx.x & 7, wg = (int)(blockIdx.x >> 3);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int fr = wave, first = wg, w = wg;   // the frame, the workgroup's first entry wave, this wave's
@@ -627,7 +767,8 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
         for (int k = wg; wg < nwx && k < qcount; k += nwx) {
             const unsigned t = tiles[begin + k];
             const int tx = (int)(t & 0xffffu), ty = (int)(t >> 16);
-            (void)march_pixel<LAYOUT, WRAP, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy);
+            if constexpr (SPLIT) march_pixel_quad_split<LAYOUT, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
+            else (void)march_pixel<LAYOUT, WRAP, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy);
         }
         return;
     }
@@ -642,20 +783,26 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
     }
     if (a.step_counter) add_steps(a, steps);
 }
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF, bool QUAD = false>
-__global__ __launch_bounds__(kThreads) void march_regions_frames(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
+// The split-fetch instances are built for 5 or more waves per SIMD: left to itself the
+// scheduler spreads a pair's six blends over 102 VGPRs (4 waves), with the floor it needs 75
+// and no scratch.  1 is the floor a kernel of 4-wave workgroups has without the attribute, so
+// every other instance is compiled as before.
+#define VR_SPLIT_WAVES __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : 1)))
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF, bool QUAD = false, bool SPLIT = false>
+__global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES void march_regions_frames(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
                                                                 const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF, QUAD>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF, QUAD, SPLIT>(g, tiles, hdr, nwx, deal, lds);
 }
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false>
-__global__ __launch_bounds__(kThreads) void march_regions_frames_u(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false>
+__global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES void march_regions_frames_u(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
                                                                   const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF, QUAD>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF, QUAD, SPLIT>(g, tiles, hdr, nwx, deal, lds);
 }
+#undef VR_SPLIT_WAVES
 
 
 // ---- step-split rays (regions schedule) ----
@@ -929,15 +1076,18 @@ hipError_t launch_lw(const MarchArgs& a, bool early, const Schedule& sc, hipStre
 // arguments (vr_render.cpp), that sc is a regions schedule without split, slab or wide
 // workgroups, and that L is one of FrameLayouts.  XCD x runs
 // sc.map.nwx entry waves, 4 / NF to a workgroup (regions_frames_body).
-// quad: the QUAD instance (nf = 4 only; the caller has proved frames_share_camera) -- the same grid.
+// quad (QuadMode): the QUAD instance (nf = 4 only; the caller has proved frames_share_camera), with
+// the split fetch or without -- the same grid.
 template <int L, int W>
-hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc, int deal, bool quad,
+hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc, int deal, int quad,
                            hipStream_t s)
 {
-    if (quad && (nf != kGroupFrames || !quad_instance(L, early, a.zero_offsets != 0, a.umask)))
+    if (quad != QUAD_NONE && (nf != kGroupFrames || !quad_instance(L, early, a.zero_offsets != 0, a.umask)))
         return hipErrorInvalidValue;   // no such kernel
-    return with_value<2, kGroupFrames>(nf, [&](auto NF) { return with_bool(quad, [&](auto QD) {
-        constexpr bool Q = decltype(QD)::value && decltype(NF)::value == kGroupFrames;   // instantiated for NF = 4 only
+    if (quad == QUAD_SPLIT && !quad_split_layout(L)) return hipErrorInvalidValue;
+    return with_value<2, kGroupFrames>(nf, [&](auto NF) { return with_value<QUAD_NONE, QUAD_FRAMES, QUAD_SPLIT>(quad, [&](auto QD) {
+        constexpr bool Q = decltype(QD)::value != QUAD_NONE && decltype(NF)::value == kGroupFrames;   // instantiated for NF = 4 only
+        constexpr bool SP = Q && decltype(QD)::value == QUAD_SPLIT && quad_split_layout(L);
         FramesArgs<NF> g;
         g.c = a;
         for (int k = 0; k < NF; ++k) g.fr[k] = fr[k];
@@ -950,15 +1100,15 @@ hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool
         const dim3 grid((unsigned)(NF == 4 ? 8 * nwx : dl ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
         if (u_kernel_channel(early, a.zero_offsets, a.umask) >= 0)
             return with_value<1, 2, 4, 8>(a.umask, [&](auto U) {
-                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF, Q>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF, Q, SP>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
                 return hipGetLastError();
             }, hipErrorInvalidValue);
         return with_bool(early, [&](auto E) { return with_bool(a.zero_offsets, [&](auto Z) {
             constexpr bool QG = Q && quad_instance(L, decltype(E)::value, decltype(Z)::value, 0);
-            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF, QG>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF, QG, QG && SP>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
             return hipGetLastError();
         }); });
-    }); }, hipErrorInvalidValue);   // no kernel for this many frames
+    }, hipErrorInvalidValue); }, hipErrorInvalidValue);   // no kernel for this many frames or this mode
 }
 
 }  // namespace

@@ -84,6 +84,11 @@ try {
         c->frame_quad = value;
         return VR_OK;
     }
+    if (n == "quad_split") {   // a QUAD launch's lanes split each tap's loads between them
+        if (value < 0 || value > 1) return fail(VR_ERR_INVALID, "vr_set_option: quad_split is 0 or 1");
+        c->quad_split = value;
+        return VR_OK;
+    }
     if (n == "inject_throw") {   // test hook: the next vr_render throws in its host path
         if (value < 0 || value > 2)
             return fail(VR_ERR_INVALID, "vr_set_option: inject_throw is 0, 1 (std::runtime_error) or 2 (std::bad_alloc)");
@@ -280,6 +285,8 @@ try {
     if (n == "group_launches") return (int)std::min<long long>(c->group_launches, 0x7fffffff);
     if (n == "pair_launches") return (int)std::min<long long>(c->pair_launches, 0x7fffffff);
     if (n == "frame_quad") return c->frame_quad;
+    if (n == "quad_split") return c->quad_split;
+    if (n == "quad_split_launches") return (int)std::min<long long>(c->quad_split_launches, 0x7fffffff);
     if (n == "quad_launches") return (int)std::min<long long>(c->quad_launches, 0x7fffffff);
     if (n == "launch_cache_hits") return (int)std::min<long long>(c->lc_hits, 0x7fffffff);
     if (n == "experiments") return VR_EXPERIMENTS;   // read-only: the measured-slower variants are built
