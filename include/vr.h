@@ -597,6 +597,97 @@ vr_status vr_brush_stamp_apply(const vr_brush* brush, const uint8_t* stamp_rgba8
 vr_status vr_stamp_box(const vr_brush* brush, const vr_box* placement, int nx, int ny, int nz,
                        int origin[3], int extent[3]);
 
+/* Transform paste: vr_stamp and vr_clone with an
+ * affine map from destination texels to source POSITIONS and a resampling
+ * filter -- a copy pasted rotated, scaled, sheared or shifted by a fraction of
+ * a texel.  Both are SOURCE BRUSHES as above; only v_c(t) differs.  All of it
+ * is integer arithmetic, so host and device agree bit for bit.
+ *
+ * The map.  For a destination texel t (volume coordinates), a source of n_x *
+ * n_y * n_z texels and each axis a, in signed 64 bits,
+ *   P_a = origin[a] + sum_b m[a][b] * (t_b - pivot[b])
+ * a 16.16 position in source texel coordinates (|m| <= 2^24 and |t - pivot| <
+ * 2^32 keep it below 2^59).  The texel is OUTSIDE the source iff on some axis
+ * P_a < 0 or P_a > (n_a - 1) << 16.  VR_BORDER_SKIP: an outside texel is not
+ * touched -- nothing is read, written or folded for it.  VR_BORDER_CLAMP:
+ * every P_a is clamped to [0, (n_a - 1) << 16] (clamp-to-edge, as vr_clone)
+ * and the texel is processed.  Then i_a = P_a >> 16, and
+ *   VR_FILTER_NEAREST  v_c = channel c of source texel i_a + ((P_a & 0xFFFF) >=
+ *     0x8000) -- never past n_a - 1;
+ *   VR_FILTER_LINEAR   f_a = (P_a >> 8) & 255, j_a = min(i_a + 1, n_a - 1), and
+ *     v_c = (sum over the 8 corners of wx wy wz byte(corner) + 2^23) >> 24 with
+ *     weight 256 - f_a for i_a and f_a for j_a: exact in unsigned 32 bits
+ *     (the weights sum to 2^24), nothing rounded in between.  Equal corner
+ *     bytes give that byte back, so an affine SET over a uniform channel never
+ *     breaks it.
+ *
+ * vr_stamp_affine: the source is the caller's DEVICE RGBA8 box of sbx * sby *
+ * sbz texels (each 1..32768), tightly packed, x fastest, 4-byte aligned: what
+ * vr_get_volume_box_device writes.  A texel is touched iff it is inside the
+ * ellipsoid, inside the volume and (VR_BORDER_SKIP) not outside the source.
+ * ONE launch, asynchronous on `stream`, nothing allocated, no host wait, no
+ * scratch, then the layout rebuild over the brush's clipped box (vr_brush_box
+ * names it: what to hand to vr_update_footprint); everything else as vr_stamp.
+ *
+ * vr_clone_affine: the source is the installed volume AS IT WAS BEFORE THE
+ * CALL (a Jacobi step); n is the volume's size.  The device path is chosen on
+ * the host in integers: the 8 corners of the clipped box are mapped to P, per
+ * axis lo = min P and hi = max P, the read range is [lo >> 16, (hi >> 16) + 1]
+ * (LINEAR) or [(lo + 0x8000) >> 16, (hi + 0x8000) >> 16] (NEAREST), clamped
+ * to [0, n_a - 1]; when it misses the clipped box on at least one axis the
+ * path is DIRECT (one launch from the planes to the planes, no scratch), else
+ * STAGED (a stage launch into vr_blur's scratch and its commit launch: the
+ * same need, growth rule, VR_ERR_OOM rule and "blur_scratch_kib").  Both give
+ * the same bytes.  vr_affine_direct tells which.
+ *
+ * VR_ERR_INVALID: a null pointer, anything vr_paint refuses, a filter or
+ * border outside its enum, non-zero reserved, |m[a][b]| above
+ * VR_AFFINE_MAX_COEFF, a source extent outside 1..32768, a misaligned
+ * d_rgba8; VR_ERR_NO_VOLUME as for vr_paint.  A brush that misses the volume,
+ * or whose strengths are all 0, is VR_OK and launches nothing.  A refused
+ * call has launched nothing and leaves the volume untouched.                */
+typedef enum { VR_FILTER_NEAREST = 0, VR_FILTER_LINEAR = 1 } vr_filter;
+typedef enum { VR_BORDER_CLAMP = 0, VR_BORDER_SKIP = 1 } vr_border;
+#define VR_AFFINE_ONE       65536          /* 16.16 fixed point */
+#define VR_AFFINE_MAX_COEFF (256 * 65536)  /* |m[a][b]| <= 2^24 */
+#define VR_AFFINE_MAX_EXTENT 32768         /* of a vr_stamp_affine source, per axis */
+typedef struct {            /* 72 bytes */
+    int32_t m[3][3];        /* 16.16: source texels per destination texel */
+    int32_t pivot[3];       /* destination texel (volume coords, any int32) that lands on `origin` */
+    int32_t origin[3];      /* 16.16 position in SOURCE texel coordinates */
+    int32_t filter;         /* vr_filter */
+    int32_t border;         /* vr_border */
+    int32_t reserved;       /* must be 0 */
+} vr_affine;
+vr_status vr_stamp_affine(void* ctx, const vr_brush* brush, const void* d_rgba8, int sbx, int sby, int sbz,
+                          const vr_affine* map, void* stream);
+vr_status vr_clone_affine(void* ctx, const vr_brush* brush, const vr_affine* map, void* stream);
+/* The same on HOST arrays: the CPU statements, which the device calls
+ * reproduce bit for bit.  Pure host code; each works from a copy of what it
+ * reads (the stamp may lie inside rgba8).  VR_ERR_INVALID as above (no
+ * alignment is asked), and for a non-positive dimension; a refused call leaves
+ * the array as it was.                                                      */
+vr_status vr_brush_stamp_affine_apply(const vr_brush* brush, const uint8_t* stamp_rgba8, int sbx, int sby, int sbz,
+                                      const vr_affine* map, uint8_t* rgba8, int nx, int ny, int nz);
+vr_status vr_brush_clone_affine_apply(const vr_brush* brush, const vr_affine* map, uint8_t* rgba8, int nx, int ny, int nz);
+/* *direct = 1 when vr_clone_affine of this brush and map in an nx x ny x nz
+ * volume takes the direct path, 0 for the staged one (and for a brush that
+ * misses the volume).  Pure host code, validated as above.                  */
+vr_status vr_affine_direct(const vr_brush* brush, const vr_affine* map, int nx, int ny, int nz, int* direct);
+/* Builders, pure host code.  vr_affine_identity: m = the identity, pivot =
+ * origin = 0, NEAREST, CLAMP.  vr_affine_place: "rotate / scale the copy by
+ * `forward` (row-major, destination offset = forward * source offset) and put
+ * the source position src_centre (texels) on destination texel dst_centre":
+ * m = rint(inverse(forward) * 65536), pivot = dst_centre, origin =
+ * rint(src_centre * 65536).  VR_ERR_INVALID for a null pointer, a bad filter
+ * or border, a non-finite entry, a singular `forward` (|det| < 1e-12 times the
+ * cube of its largest absolute entry), a coefficient above
+ * VR_AFFINE_MAX_COEFF or an origin outside int32; *out is written only on
+ * success.                                                                  */
+vr_status vr_affine_identity(vr_affine* out);
+vr_status vr_affine_place(const double forward[9], const double src_centre[3], const int32_t dst_centre[3],
+                          int filter, int border, vr_affine* out);
+
 /* The read side of the brush: what is in the volume under it (DESIGN.md sec.
  * 5.2.8) -- the eyedropper, a histogram panel, and the answer to "has this
  * channel become constant again?".  Everything is an integer sum, so the

@@ -99,6 +99,30 @@ inline void BrushStampApply(const vr_brush& brush, const uint8_t* stamp_rgba, co
     Check(vr_brush_stamp_apply(&brush, stamp_rgba, &placement, rgba, nx, ny, nz), "vr_brush_stamp_apply");
 }
 
+// The transform paste on host arrays (vr_brush_stamp_affine_apply,
+// vr_brush_clone_affine_apply): the CPU statements of Renderer::StampAffine and
+// Renderer::CloneAffine.  Host code only.
+inline void BrushStampAffineApply(const vr_brush& brush, const uint8_t* stamp_rgba, int sbx, int sby, int sbz,
+                                  const vr_affine& map, uint8_t* rgba, int nx, int ny, int nz)
+{
+    Check(vr_brush_stamp_affine_apply(&brush, stamp_rgba, sbx, sby, sbz, &map, rgba, nx, ny, nz), "vr_brush_stamp_affine_apply");
+}
+inline void BrushCloneAffineApply(const vr_brush& brush, const vr_affine& map, uint8_t* rgba, int nx, int ny, int nz)
+{
+    Check(vr_brush_clone_affine_apply(&brush, &map, rgba, nx, ny, nz), "vr_brush_clone_affine_apply");
+}
+
+// The map that pastes the source turned / scaled by the row-major 3 x 3
+// `forward` with source position src_centre on destination texel dst_centre
+// (vr_affine_place).  Host code only; throws for a singular matrix.
+inline vr_affine AffinePlace(const double forward[9], const double src_centre[3], const int32_t dst_centre[3],
+                             int filter = VR_FILTER_LINEAR, int border = VR_BORDER_CLAMP)
+{
+    vr_affine a{};
+    Check(vr_affine_place(forward, src_centre, dst_centre, filter, border, &a), "vr_affine_place");
+    return a;
+}
+
 // What a stamp edits in an nx x ny x nz volume (vr_stamp_box): the brush's
 // clipped box intersected with the placement, what Renderer::UpdateFootprint
 // takes after Renderer::Stamp; false (and a zero extent) when it is empty.
@@ -210,6 +234,22 @@ public:
     void Stamp(const vr_brush& brush, const void* d_rgba, const vr_box& placement, void* stream = nullptr)
     {
         Check(vr_stamp(ctx_, &brush, d_rgba, &placement, stream), "vr_stamp");
+    }
+    // Paste a device RGBA8 box of sbx x sby x sbz texels through an affine map
+    // and a filter (vr_stamp_affine): rotated, scaled, sheared or shifted by a
+    // fraction of a texel.  One launch on `stream`; vr_brush_box names the box
+    // it edits.
+    void StampAffine(const vr_brush& brush, const void* d_rgba, int sbx, int sby, int sbz, const vr_affine& map,
+                     void* stream = nullptr)
+    {
+        Check(vr_stamp_affine(ctx_, &brush, d_rgba, sbx, sby, sbz, &map, stream), "vr_stamp_affine");
+    }
+    // The same with the volume itself, as it was before the call, as the
+    // source (vr_clone_affine): one launch when the read range misses the box,
+    // else vr_blur's staging scratch and commit.
+    void CloneAffine(const vr_brush& brush, const vr_affine& map, void* stream = nullptr)
+    {
+        Check(vr_clone_affine(ctx_, &brush, &map, stream), "vr_clone_affine");
     }
     // Paint under the brush with a function of each texel's own byte
     // (vr_remap): the value of channel c is lut.lut[c][old byte] -- levels,

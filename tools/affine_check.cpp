@@ -1,0 +1,289 @@
+// affine_check -- stand-alone host check of vr_brush_stamp_affine_apply,
+// vr_brush_clone_affine_apply, vr_affine_direct and the map builders
+// (volumetricrenderer_amd/csrc/vr_brush.cpp, vr_affine.h), built with
+// -fsanitize=address,undefined and run on the CPU (`make check-affine` builds
+// and runs it).  It links the brush's translation unit only: no libvr.so, no
+// HIP, no device.
+//
+// Every volume and every stamp is allocated exactly, so a read or write
+// outside one trips the address sanitizer, and a 32-bit product of a
+// coefficient and a coordinate trips the undefined-behaviour sanitizer.  Random
+// volumes, stamps, brushes and maps -- coefficients up to the limit, pivots and
+// origins at the ends of int32, both filters and borders.  Each result is
+// compared with a naive restatement of vr.h: a full copy of the source before
+// the call, plain loops over every texel, the ellipsoid in unsigned __int128,
+// positions in __int128 and the trilinear value as one sum over eight corners.
+// A direct path is checked against brute force: no texel it reads is written.
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <random>
+#include <vector>
+
+#include "vr.h"
+
+namespace {
+
+typedef unsigned __int128 u128;
+typedef __int128 i128;
+
+unsigned weight(const vr_brush& b, int x, int y, int z)
+{
+    u128 D2[3];
+    for (int a = 0; a < 3; ++a) D2[a] = (u128)(2 * b.radius[a] + 1) * (u128)(2 * b.radius[a] + 1);
+    const u128 S = D2[0] * D2[1] * D2[2];
+    const long long d[3] = {(long long)x - b.centre[0], (long long)y - b.centre[1], (long long)z - b.centre[2]};
+    for (int a = 0; a < 3; ++a)
+        if (d[a] < -(long long)b.radius[a] || d[a] > (long long)b.radius[a]) return 0u;
+    const u128 Q = (u128)(4 * d[0] * d[0]) * D2[1] * D2[2] + (u128)(4 * d[1] * d[1]) * D2[0] * D2[2] +
+                   (u128)(4 * d[2] * d[2]) * D2[0] * D2[1];
+    if (Q > S) return 0u;
+    return b.falloff ? 256u - (unsigned)((256 * Q) / (S + 1)) : 256u;
+}
+
+uint8_t blend(int op, long long old, long long v, long long a)
+{
+    const long long d = (v * a + 32640) / 65280;
+    if (op == VR_BRUSH_SET) return (uint8_t)((old * (65280 - a) + v * a + 32640) / 65280);
+    if (op == VR_BRUSH_ADD) return (uint8_t)(old + d > 255 ? 255 : old + d);
+    return (uint8_t)(old - d < 0 ? 0 : old - d);
+}
+
+// The texels (at most 8) texel t reads of a source of n[] texels, and their weights out of 2^24; false when the texel
+// is left alone.  vr.h, literally.
+struct Taps {
+    int count;
+    long long s[8][3];
+    unsigned long long w[8];
+};
+bool taps(const vr_affine& m, const int n[3], const int t[3], Taps& out)
+{
+    i128 P[3];
+    bool outside = false;
+    for (int a = 0; a < 3; ++a) {
+        P[a] = m.origin[a];
+        for (int b = 0; b < 3; ++b) P[a] += (i128)m.m[a][b] * ((i128)t[b] - m.pivot[b]);
+        const i128 last = (i128)(n[a] - 1) * 65536;
+        if (P[a] < 0 || P[a] > last) outside = true;
+        P[a] = P[a] < 0 ? 0 : P[a] > last ? last : P[a];
+    }
+    if (outside && m.border == VR_BORDER_SKIP) return false;
+    long long i[3], f16[3];
+    for (int a = 0; a < 3; ++a) { i[a] = (long long)(P[a] / 65536); f16[a] = (long long)(P[a] % 65536); }
+    if (m.filter == VR_FILTER_NEAREST) {
+        out.count = 1;
+        for (int a = 0; a < 3; ++a) out.s[0][a] = i[a] + (f16[a] >= 0x8000);
+        out.w[0] = 1ull << 24;
+        return true;
+    }
+    out.count = 8;
+    for (int k = 0; k < 8; ++k) {
+        out.w[k] = 1;
+        for (int a = 0; a < 3; ++a) {
+            const long long f = f16[a] / 256;
+            const bool second = (k >> a & 1) != 0;
+            out.s[k][a] = second ? (i[a] + 1 > n[a] - 1 ? n[a] - 1 : i[a] + 1) : i[a];
+            out.w[k] *= (unsigned long long)(second ? f : 256 - f);
+        }
+    }
+    return true;
+}
+
+// the source is `src` (n[] texels), or the volume before the call when src is null
+void restate(const vr_brush& b, const vr_affine& m, const uint8_t* src, const int ns[3], std::vector<uint8_t>& v, int nx, int ny,
+             int nz, bool* reads_written)
+{
+    const std::vector<uint8_t> before = v;
+    const int nv[3] = {nx, ny, nz};
+    const int* n = src ? ns : nv;
+    const uint8_t* s = src ? src : before.data();
+    std::vector<char> written((size_t)nx * ny * nz, 0), read((size_t)nx * ny * nz, 0);
+    for (int z = 0; z < nz; ++z)
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) {
+                const unsigned w = weight(b, x, y, z);
+                if (!w) continue;
+                const int t[3] = {x, y, z};
+                Taps tp;
+                if (!taps(m, n, t, tp)) continue;
+                written[((size_t)z * ny + y) * nx + x] = 1;
+                uint8_t* p = &v[(((size_t)z * ny + y) * nx + x) * 4];
+                for (int c = 0; c < 4; ++c) {
+                    if (!b.strength[c]) continue;
+                    unsigned long long sum = 0;
+                    for (int k = 0; k < tp.count; ++k) {
+                        const size_t at = ((size_t)tp.s[k][2] * n[1] + (size_t)tp.s[k][1]) * n[0] + (size_t)tp.s[k][0];
+                        sum += tp.w[k] * s[at * 4 + c];
+                        if (!src && tp.w[k]) read[at] = 1;   // a tap of weight 0 decides nothing
+                    }
+                    p[c] = blend(b.op, p[c], (long long)((sum + (1ull << 23)) >> 24), (long long)w * b.strength[c]);
+                }
+            }
+    *reads_written = false;
+    for (size_t i = 0; i < written.size(); ++i)
+        if (written[i] && read[i]) *reads_written = true;
+}
+
+long failures = 0;
+void expect(bool ok, const char* what, int it)
+{
+    if (!ok && ++failures <= 10) std::fprintf(stderr, "affine_check: %s (case %d)\n", what, it);
+}
+
+std::mt19937_64 rng(20241021);
+int pick(int a, int b) { return std::uniform_int_distribution<int>(a, b)(rng); }
+
+std::vector<uint8_t> random_bytes(size_t n)
+{
+    std::vector<uint8_t> v(n);
+    for (size_t i = 0; i < n; ++i) v[i] = (uint8_t)pick(0, 255);
+    return v;
+}
+
+}  // namespace
+
+int main()
+{
+    long applied = 0, changed = 0, skipped_some = 0, direct = 0, staged = 0, refused = 0;
+    const int far[] = {INT32_MAX, INT32_MIN, INT32_MAX - 255, INT32_MIN + 255, 1 << 30, -(1 << 30)};
+    for (int it = 0; it < 3000; ++it) {
+        const int kind = it % 6;
+        int nx = pick(1, 12), ny = pick(1, 12), nz = pick(1, 12);
+        if (kind == 1) nx = ny = nz = 1;
+        const int n[3] = {nx, ny, nz};
+        const int ns[3] = {pick(1, 9), pick(1, 9), pick(1, 9)};
+        vr_brush b{};
+        for (int a = 0; a < 3; ++a) { b.centre[a] = pick(-2, n[a] + 1); b.radius[a] = pick(0, 7); }
+        if (kind == 2)
+            for (int a = 0; a < 3; ++a) { b.radius[a] = VR_BRUSH_MAX_RADIUS; b.centre[a] = pick(-200, 200); }
+        b.op = it / 6 % 3;
+        b.falloff = it / 18 % 2;
+        for (int c = 0; c < 4; ++c) { b.value[c] = (uint8_t)pick(0, 255); b.strength[c] = (uint8_t)(pick(0, 3) ? pick(0, 255) : pick(0, 1) * 255); }
+        vr_affine m{};
+        m.filter = it / 2 % 2;
+        m.border = it / 4 % 2;
+        for (int a = 0; a < 3; ++a) {
+            for (int c = 0; c < 3; ++c) {
+                switch (pick(0, 5)) {
+                case 0: m.m[a][c] = 0; break;
+                case 1: m.m[a][c] = (a == c) * VR_AFFINE_ONE; break;
+                case 2: m.m[a][c] = pick(-3 * VR_AFFINE_ONE, 3 * VR_AFFINE_ONE); break;
+                case 3: m.m[a][c] = pick(0, 1) ? VR_AFFINE_MAX_COEFF : -VR_AFFINE_MAX_COEFF; break;
+                default: m.m[a][c] = pick(-VR_AFFINE_ONE, VR_AFFINE_ONE); break;
+                }
+            }
+            m.pivot[a] = b.centre[a] + pick(-1, 1);
+            m.origin[a] = pick(-VR_AFFINE_ONE, 10 * VR_AFFINE_ONE);
+        }
+        if (kind == 3)
+            for (int a = 0; a < 3; ++a) { m.pivot[a] = far[pick(0, 5)]; m.origin[a] = far[pick(0, 5)]; }
+        if (kind == 4) {   // a pure translation: the direct path is common
+            for (int a = 0; a < 3; ++a)
+                for (int c = 0; c < 3; ++c) m.m[a][c] = (a == c) * VR_AFFINE_ONE;
+            for (int a = 0; a < 3; ++a) m.origin[a] = (b.centre[a] + pick(-12, 12)) * VR_AFFINE_ONE + pick(0, 0xFFFF);
+        }
+        const std::vector<uint8_t> base = random_bytes((size_t)nx * ny * nz * 4);
+        const std::vector<uint8_t> stamp = random_bytes((size_t)ns[0] * ns[1] * ns[2] * 4);
+        bool rw = false;
+        {
+            std::vector<uint8_t> vol = base, want = base;
+            restate(b, m, stamp.data(), ns, want, nx, ny, nz, &rw);
+            expect(vr_brush_stamp_affine_apply(&b, stamp.data(), ns[0], ns[1], ns[2], &m, vol.data(), nx, ny, nz) == VR_OK,
+                   "vr_brush_stamp_affine_apply refused a valid call", it);
+            expect(vol == want, "vr_brush_stamp_affine_apply differs from the restatement", it);
+            ++applied;
+            changed += vol != base;
+        }
+        {
+            std::vector<uint8_t> vol = base, want = base;
+            restate(b, m, nullptr, nullptr, want, nx, ny, nz, &rw);
+            expect(vr_brush_clone_affine_apply(&b, &m, vol.data(), nx, ny, nz) == VR_OK, "vr_brush_clone_affine_apply refused a valid call", it);
+            expect(vol == want, "vr_brush_clone_affine_apply differs from the restatement", it);
+            ++applied;
+            changed += vol != base;
+            int d = -1;
+            expect(vr_affine_direct(&b, &m, nx, ny, nz, &d) == VR_OK && (d == 0 || d == 1), "vr_affine_direct refused a valid call", it);
+            if (d == 1) expect(!rw, "the direct path was chosen for a clone that reads a texel it writes", it);
+            direct += d == 1;
+            staged += d == 0;
+        }
+        if (m.border == VR_BORDER_SKIP) {
+            vr_affine cl = m;
+            cl.border = VR_BORDER_CLAMP;
+            std::vector<uint8_t> a = base, c = base;
+            vr_brush_stamp_affine_apply(&b, stamp.data(), ns[0], ns[1], ns[2], &m, a.data(), nx, ny, nz);
+            vr_brush_stamp_affine_apply(&b, stamp.data(), ns[0], ns[1], ns[2], &cl, c.data(), nx, ny, nz);
+            skipped_some += a != c;
+        }
+
+        // refusals: nothing written
+        std::vector<uint8_t> vol = base;
+        vr_brush bad = b;
+        vr_affine badm = m;
+        switch (it % 8) {
+        case 0: bad.op = 3; break;
+        case 1: bad.falloff = 2; break;
+        case 2: bad.radius[it % 3] = 256; break;
+        case 3: bad.reserved[it % 2] = 1; break;
+        case 4: badm.filter = it % 2 ? 2 : -1; break;
+        case 5: badm.border = it % 2 ? 2 : -1; break;
+        case 6: badm.reserved = 1; break;
+        default: badm.m[it % 3][it / 3 % 3] = it % 2 ? VR_AFFINE_MAX_COEFF + 1 : INT32_MIN; break;
+        }
+        int d = 7;
+        expect(vr_brush_stamp_affine_apply(&bad, stamp.data(), ns[0], ns[1], ns[2], &badm, vol.data(), nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_brush_clone_affine_apply(&bad, &badm, vol.data(), nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_affine_direct(&bad, &badm, nx, ny, nz, &d) == VR_ERR_INVALID && d == 7 && vol == base,
+               "a bad brush or map was accepted", it);
+        expect(vr_brush_stamp_affine_apply(&b, stamp.data(), it % 2 ? 0 : VR_AFFINE_MAX_EXTENT + 1, ns[1], ns[2], &m, vol.data(), nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_brush_stamp_affine_apply(&b, stamp.data(), ns[0], ns[1], ns[2], &m, vol.data(), nx, it % 2 ? 0 : -1, nz) == VR_ERR_INVALID &&
+                   vr_brush_clone_affine_apply(&b, &m, vol.data(), it % 2 ? 0 : nx, ny, it % 2 ? nz : -1) == VR_ERR_INVALID && vol == base,
+               "bad dimensions were accepted", it);
+        expect(vr_brush_stamp_affine_apply(nullptr, stamp.data(), ns[0], ns[1], ns[2], &m, vol.data(), nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_brush_stamp_affine_apply(&b, nullptr, ns[0], ns[1], ns[2], &m, vol.data(), nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_brush_stamp_affine_apply(&b, stamp.data(), ns[0], ns[1], ns[2], nullptr, vol.data(), nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_brush_stamp_affine_apply(&b, stamp.data(), ns[0], ns[1], ns[2], &m, nullptr, nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_brush_clone_affine_apply(nullptr, &m, vol.data(), nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_brush_clone_affine_apply(&b, nullptr, vol.data(), nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_brush_clone_affine_apply(&b, &m, nullptr, nx, ny, nz) == VR_ERR_INVALID &&
+                   vr_affine_direct(&b, &m, nx, ny, nz, nullptr) == VR_ERR_INVALID && vol == base,
+               "a null pointer was accepted", it);
+        refused += 14;
+    }
+    // ---- the builders
+    {
+        vr_affine a{};
+        a.reserved = 9;
+        expect(vr_affine_identity(&a) == VR_OK && a.m[0][0] == VR_AFFINE_ONE && a.m[1][1] == VR_AFFINE_ONE && a.m[2][2] == VR_AFFINE_ONE &&
+                   a.m[0][1] == 0 && a.reserved == 0 && a.filter == VR_FILTER_NEAREST && a.border == VR_BORDER_CLAMP,
+               "vr_affine_identity", 0);
+        const double two[9] = {2, 0, 0, 0, 2, 0, 0, 0, 2}, zero[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, nan[9] = {NAN, 0, 0, 0, 1, 0, 0, 0, 1};
+        const double tiny[9] = {1.0 / 300, 0, 0, 0, 1, 0, 0, 0, 1};
+        const double c[3] = {1.5, -2.25, 32767.5}, huge[3] = {40000.0, 0, 0};
+        const int32_t d[3] = {INT32_MAX, INT32_MIN, 0};
+        const vr_affine kept = a;
+        expect(vr_affine_place(two, c, d, VR_FILTER_LINEAR, VR_BORDER_SKIP, &a) == VR_OK && a.m[0][0] == 32768 && a.m[2][2] == 32768 &&
+                   a.m[1][0] == 0 && a.pivot[0] == INT32_MAX && a.pivot[1] == INT32_MIN && a.origin[0] == 98304 &&
+                   a.origin[1] == -147456 && a.origin[2] == 2147450880 && a.filter == VR_FILTER_LINEAR && a.border == VR_BORDER_SKIP,
+               "vr_affine_place of a scale", 1);
+        a = kept;
+        const auto untouched = [&] { return a.m[0][0] == kept.m[0][0] && a.filter == kept.filter && a.origin[0] == kept.origin[0]; };
+        expect(vr_affine_place(zero, c, d, 0, 0, &a) == VR_ERR_INVALID && untouched(), "a singular matrix was accepted", 2);
+        expect(vr_affine_place(nan, c, d, 0, 0, &a) == VR_ERR_INVALID && untouched(), "a NaN was accepted", 3);
+        expect(vr_affine_place(tiny, c, d, 0, 0, &a) == VR_ERR_INVALID && untouched(), "a coefficient above the limit was accepted", 4);
+        expect(vr_affine_place(two, huge, d, 0, 0, &a) == VR_ERR_INVALID && untouched(), "an origin outside int32 was accepted", 5);
+        expect(vr_affine_place(two, c, d, 2, 0, &a) == VR_ERR_INVALID && vr_affine_place(two, c, d, 0, -1, &a) == VR_ERR_INVALID && untouched(),
+               "a bad filter or border was accepted", 6);
+        expect(vr_affine_place(nullptr, c, d, 0, 0, &a) == VR_ERR_INVALID && vr_affine_place(two, nullptr, d, 0, 0, &a) == VR_ERR_INVALID &&
+                   vr_affine_place(two, c, nullptr, 0, 0, &a) == VR_ERR_INVALID && vr_affine_place(two, c, d, 0, 0, nullptr) == VR_ERR_INVALID &&
+                   vr_affine_identity(nullptr) == VR_ERR_INVALID,
+               "a null pointer was accepted by a builder", 7);
+    }
+    expect(changed > 1500, "too few cases changed a byte", (int)changed);
+    expect(skipped_some > 300, "VR_BORDER_SKIP seldom differed from VR_BORDER_CLAMP", (int)skipped_some);
+    expect(direct > 100 && staged > 1000, "the maps do not cover both paths", (int)direct);
+    std::printf("affine_check: %ld applied (%ld changed bytes; SKIP differed from CLAMP %ld times), %ld direct and %ld staged paths, "
+                "%ld refused, %ld failures\n", applied, changed, skipped_some, direct, staged, refused, failures);
+    return failures ? 1 : 0;
+}

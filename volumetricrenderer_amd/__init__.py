@@ -17,6 +17,9 @@ from ._lib import RANK_MAX_HALF, RANK_MEDIAN  # noqa: F401
 from .renderer import brush_rank_apply  # noqa: F401
 from ._lib import CloneMap  # noqa: F401
 from .renderer import brush_clone_apply, brush_stamp_apply, make_clone_map, stamp_box  # noqa: F401
+from ._lib import AFFINE_MAX_COEFF, AFFINE_ONE, BORDER_CLAMP, BORDER_SKIP, FILTER_LINEAR, FILTER_NEAREST, Affine  # noqa: F401
+from .renderer import (affine_direct, affine_identity, affine_place, brush_clone_affine_apply,  # noqa: F401
+                       brush_stamp_affine_apply, make_affine)
 from ._lib import LUT_BYTES, LUT_EQUALIZE, LUT_STRETCH, Lut  # noqa: F401
 from .renderer import brush_remap_apply, lut_compose, lut_identity, lut_levels, stats_lut  # noqa: F401
 from .renderer import brush_apply, brush_blur_apply, brush_box, brush_line, coalesce_boxes, make_brush  # noqa: F401
@@ -35,6 +38,9 @@ __all__ = [
     "brush_morph_apply", "MORPH_ERODE", "MORPH_DILATE", "MORPH_MAX_HALF",
     "brush_rank_apply", "RANK_MEDIAN", "RANK_MAX_HALF",
     "CloneMap", "make_clone_map", "brush_clone_apply", "brush_stamp_apply", "stamp_box",
+    "Affine", "FILTER_NEAREST", "FILTER_LINEAR", "BORDER_CLAMP", "BORDER_SKIP", "AFFINE_ONE", "AFFINE_MAX_COEFF",
+    "make_affine", "affine_identity", "affine_place", "affine_direct", "brush_stamp_affine_apply",
+    "brush_clone_affine_apply",
     "Lut", "LUT_BYTES", "LUT_EQUALIZE", "LUT_STRETCH", "lut_identity", "lut_levels", "lut_compose", "stats_lut",
     "brush_remap_apply",
     "VolumeStats", "StatsSummary", "VOLUME_STATS_BYTES", "Stats", "Summary", "brush_stats_host", "box_stats_host",

@@ -143,6 +143,20 @@ class CloneMap(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_int32 * 3), ("mirror", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32 * 2)]
 
 
+class Affine(ctypes.Structure):
+    """vr_affine: the map of vr_stamp_affine / vr_clone_affine from a destination texel to a 16.16 source position,
+    with its filter and border.  72 bytes."""
+    _fields_ = [("m", (ctypes.c_int32 * 3) * 3), ("pivot", ctypes.c_int32 * 3), ("origin", ctypes.c_int32 * 3),
+                ("filter", ctypes.c_int32), ("border", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+FILTER_NEAREST, FILTER_LINEAR = 0, 1        # vr.h vr_filter
+BORDER_CLAMP, BORDER_SKIP = 0, 1            # vr.h vr_border
+AFFINE_ONE = 65536                          # vr.h VR_AFFINE_ONE: 1.0 in 16.16
+AFFINE_MAX_COEFF = 256 * 65536              # vr.h VR_AFFINE_MAX_COEFF
+AFFINE_MAX_EXTENT = 32768                   # vr.h VR_AFFINE_MAX_EXTENT
+
+
 class VolumeStats(ctypes.Structure):
     """vr_volume_stats: what vr_brush_stats / vr_box_stats produce.  8240 bytes, all 64-bit words."""
     _fields_ = [("count", ctypes.c_uint64), ("weight", ctypes.c_uint64), ("wsum", ctypes.c_uint64 * 4),
@@ -203,6 +217,18 @@ _SIGS = {
                                             ctypes.c_int, ctypes.c_int]),
     "vr_stamp_box": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(Box), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     c_int_p, c_int_p]),
+    "vr_stamp_affine": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(Affine), _vp]),
+    "vr_clone_affine": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.POINTER(Affine), _vp]),
+    "vr_brush_stamp_affine_apply": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.POINTER(Affine), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vr_brush_clone_affine_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(Affine), _vp, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_int]),
+    "vr_affine_direct": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(Affine), ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, c_int_p]),
+    "vr_affine_identity": (ctypes.c_int, [ctypes.POINTER(Affine)]),
+    "vr_affine_place": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.POINTER(Affine)]),
     "vr_remap": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.POINTER(Lut), _vp]),
     "vr_remap_device": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, _vp]),
     "vr_stats_lut_device": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),

@@ -15,6 +15,7 @@
 // renders in vr_rect.cpp.
 #include "vr_blur.h"
 #include "vr_brush.h"
+#include "vr_affine.h"
 #include "vr_clone.h"
 #include "vr_ctx.h"
 #include "vr_morph.h"
@@ -898,6 +899,65 @@ try {
     return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
 } catch (...) {
     return caught_exception("vr_stamp");
+}
+
+// The transform paste on the device (vr_affine.h): what both calls share of the validated map.
+static void affine_args(const vr_affine* m, int snx, int sny, int snz, AffineArgs& g)
+{
+    for (int ax = 0; ax < 3; ++ax) {
+        for (int k = 0; k < 3; ++k) g.m[ax][k] = m->m[ax][k];
+        g.pivot[ax] = m->pivot[ax];
+        g.origin[ax] = m->origin[ax];
+    }
+    g.n[0] = snx; g.n[1] = sny; g.n[2] = snz;
+    g.filter = m->filter;
+    g.border = m->border;
+}
+
+// vr_stamp_affine: every check first, then k_stamp_affine over the brush's clipped box and what follows an edit of
+// that box.
+vr_status vr_stamp_affine(void* p, const vr_brush* b, const void* d_rgba8, int sbx, int sby, int sbz, const vr_affine* m,
+                          void* stream)
+try {
+    if (!p || !b || !d_rgba8 || !m) return fail(VR_ERR_INVALID, "vr_stamp_affine: null argument");
+    if (const char* why = vr::affine::invalid(b, m)) return fail(VR_ERR_INVALID, "vr_stamp_affine: %s", why);
+    if (const char* why = vr::affine::invalid_extent(sbx, sby, sbz)) return fail(VR_ERR_INVALID, "vr_stamp_affine: %s", why);
+    if ((reinterpret_cast<uintptr_t>(d_rgba8) & 3u) != 0u) return fail(VR_ERR_INVALID, "vr_stamp_affine: d_rgba8 is not 4-byte aligned");
+    Ctx* c = as_ctx(p);
+    if (vr_status st = check_target("vr_stamp_affine", c)) return st;
+    AffineArgs g{};
+    PaintArgs& a = g.p;
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
+    if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
+    affine_args(m, sbx, sby, sbz, g);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(launch_stamp_affine(g, static_cast<const uint8_t*>(d_rgba8), c->d_planar, c->d_mm, s));
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+} catch (...) {
+    return caught_exception("vr_stamp_affine");
+}
+
+// vr_clone_affine: every check first, then the host picks the path in integers (vr_affine.h direct), as vr_clone.
+vr_status vr_clone_affine(void* p, const vr_brush* b, const vr_affine* m, void* stream)
+try {
+    if (!p || !b || !m) return fail(VR_ERR_INVALID, "vr_clone_affine: null argument");
+    if (const char* why = vr::affine::invalid(b, m)) return fail(VR_ERR_INVALID, "vr_clone_affine: %s", why);
+    Ctx* c = as_ctx(p);
+    if (vr_status st = check_target("vr_clone_affine", c)) return st;
+    AffineArgs g{};
+    PaintArgs& a = g.p;
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
+    if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
+    affine_args(m, c->nx, c->ny, c->nz, g);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!vr::affine::direct(m, a.o, a.e, c->nx, c->ny, c->nz))
+        return staged_brush(c, a, s, "launch_clone_affine_stage", [&] { return launch_clone_affine_stage(g, c->d_planar, c->d_blur, s); });
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_clone_affine_direct(g, c->d_planar, c->d_mm, s));
+    return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
+} catch (...) {
+    return caught_exception("vr_clone_affine");
 }
 
 // The lookup-table brush on the device: every check first, then k_remap over the clipped box -- with the host table

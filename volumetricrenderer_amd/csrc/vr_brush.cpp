@@ -13,7 +13,10 @@
 // coordinate and the edited box are vr_clone.h's); vr_brush_remap_apply,
 // vr_lut_identity, vr_lut_levels, vr_lut_compose and vr_stats_lut: the
 // lookup-table brush on the host and its table builders (sec. 5.2.11; the
-// checks and the entries of a table are vr_remap.h's).
+// checks and the entries of a table are vr_remap.h's); vr_brush_stamp_affine_apply,
+// vr_brush_clone_affine_apply, vr_affine_direct, vr_affine_identity and
+// vr_affine_place: the transform paste on the host and its map builders
+// (sec. 5.2.13; the checks, the positions and the filters are vr_affine.h's).
 //
 // Pure host code in integers: no context, no device, no HIP call.  The
 // arithmetic is vr_brush.h's, which the paint kernel (vr_paint.hip) includes
@@ -23,10 +26,12 @@
 // of the bytes before the call is a Snapshot.  tools/brush_check.cpp compiles
 // this file alone (-DVR_BRUSH_STANDALONE, which only drops the vr_last_error
 // text) under the address and undefined-behaviour sanitizers.
+#include <cmath>
 #include <cstdint>
 #include <type_traits>
 #include <vector>
 
+#include "vr_affine.h"
 #include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_clone.h"
@@ -168,9 +173,142 @@ vr_status neighbourhood_apply(const vr_brush* b, int h, uint8_t* rgba8, int nx, 
     return VR_OK;
 }
 
+// The transform paste on checked arguments (vr_affine.h): the brush over its clipped box o, e of the volume with the
+// value of a texel resampled from `src`, an RGBA8 array of n[0] x n[1] x n[2] texels.  What the box reads of it (a box
+// inside the source: read_range) is copied first and every value reads the copy.  A texel outside the source is
+// left alone (VR_BORDER_SKIP) or reads the clamped position.
+void affine_apply(const vr_brush* b, const vr_affine* m, const int o[3], const int e[3], const uint8_t* src, const int n[3],
+                  uint8_t* rgba8, int nx, int ny)
+{
+    int lo[3], ext[3];
+    for (int a = 0; a < 3; ++a) {
+        int hi;
+        vr::affine::read_range(m, a, o, e, n[a], &lo[a], &hi);
+        ext[a] = hi - lo[a] + 1;
+    }
+    const Snapshot before(src, n[0], n[1], n[2], lo, ext);
+    const auto byte = [&](int x, int y, int z, int c) -> unsigned { return before.row(y, z)[(size_t)(x - lo[0]) * 4 + (size_t)c]; };
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    const bool linear = m->filter == VR_FILTER_LINEAR, skip = m->border == VR_BORDER_SKIP;
+    walk(b, t, o, e, no_row, [&](int, int x, int y, int z, uint64_t q) {
+        if (q > t.s) return;
+        int64_t p[3];
+        bool out = false;
+        for (int a = 0; a < 3; ++a) {
+            p[a] = vr::affine::position(m->m[a], m->origin[a], m->pivot, x, y, z);
+            out = out || vr::affine::outside(p[a], n[a]);
+            p[a] = vr::affine::clamp(p[a], n[a]);
+        }
+        if (out && skip) return;
+        const unsigned w = vr::brush::weight(q, t.s, b->falloff);
+        uint8_t* d = rgba8 + ((((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) + (size_t)x) * 4;
+        vr::affine::Axis ax[3];
+        int s[3];
+        for (int a = 0; a < 3; ++a) {
+            ax[a] = vr::affine::linear_weights(p[a], n[a]);
+            s[a] = vr::affine::nearest(p[a]);
+        }
+        for (int c = 0; c < 4; ++c) {
+            if (!b->strength[c]) continue;
+            unsigned v;
+            if (linear) {
+                unsigned corner[2][2][2];
+                for (int k = 0; k < 8; ++k)
+                    corner[k >> 2][k >> 1 & 1][k & 1] = byte(k & 1 ? ax[0].j : ax[0].i, k & 2 ? ax[1].j : ax[1].i, k & 4 ? ax[2].j : ax[2].i, c);
+                v = vr::affine::linear_value(corner, ax[0].f, ax[1].f, ax[2].f);
+            } else {
+                v = byte(s[0], s[1], s[2], c);
+            }
+            d[c] = (uint8_t)vr::brush::blend(b->op, d[c], v, w * b->strength[c]);
+        }
+    });
+}
+
 }  // namespace
 
 extern "C" {
+
+// The transform paste of a HOST stamp on the host (include/vr.h): the CPU statement of vr_stamp_affine.
+vr_status vr_brush_stamp_affine_apply(const vr_brush* b, const uint8_t* stamp, int sbx, int sby, int sbz, const vr_affine* m,
+                                      uint8_t* rgba8, int nx, int ny, int nz)
+{
+    if (vr_status st = check("vr_brush_stamp_affine_apply", b && stamp && m && rgba8, [&] { return vr::affine::invalid(b, m); }, nx, ny, nz))
+        return st;
+    if (const char* why = vr::affine::invalid_extent(sbx, sby, sbz)) return fail(VR_ERR_INVALID, "vr_brush_stamp_affine_apply: %s", why);
+    int o[3], e[3];
+    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
+    const int n[3] = {sbx, sby, sbz};
+    affine_apply(b, m, o, e, stamp, n, rgba8, nx, ny);
+    return VR_OK;
+}
+
+// The transform paste of the volume's own texels on the host: the CPU statement of vr_clone_affine (Jacobi: the
+// copy is taken before the first byte is written).
+vr_status vr_brush_clone_affine_apply(const vr_brush* b, const vr_affine* m, uint8_t* rgba8, int nx, int ny, int nz)
+{
+    if (vr_status st = check("vr_brush_clone_affine_apply", b && m && rgba8, [&] { return vr::affine::invalid(b, m); }, nx, ny, nz))
+        return st;
+    int o[3], e[3];
+    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
+    const int n[3] = {nx, ny, nz};
+    affine_apply(b, m, o, e, rgba8, n, rgba8, nx, ny);
+    return VR_OK;
+}
+
+vr_status vr_affine_direct(const vr_brush* b, const vr_affine* m, int nx, int ny, int nz, int* direct)
+{
+    if (vr_status st = check("vr_affine_direct", b && m && direct, [&] { return vr::affine::invalid(b, m); }, nx, ny, nz)) return st;
+    int o[3], e[3];
+    *direct = vr::brush::clip(b, nx, ny, nz, o, e) && vr::affine::direct(m, o, e, nx, ny, nz) ? 1 : 0;
+    return VR_OK;
+}
+
+vr_status vr_affine_identity(vr_affine* out)
+{
+    if (!out) return fail(VR_ERR_INVALID, "vr_affine_identity: null argument");
+    *out = vr_affine{};
+    for (int a = 0; a < 3; ++a) out->m[a][a] = VR_AFFINE_ONE;
+    return VR_OK;
+}
+
+// m = rint(inverse(forward) * 65536) by the adjugate: exact for the axis rotations and the powers of two
+vr_status vr_affine_place(const double forward[9], const double src_centre[3], const int32_t dst_centre[3], int filter,
+                          int border, vr_affine* out)
+{
+    if (!forward || !src_centre || !dst_centre || !out) return fail(VR_ERR_INVALID, "vr_affine_place: null argument");
+    if (filter != VR_FILTER_NEAREST && filter != VR_FILTER_LINEAR) return fail(VR_ERR_INVALID, "vr_affine_place: bad filter");
+    if (border != VR_BORDER_CLAMP && border != VR_BORDER_SKIP) return fail(VR_ERR_INVALID, "vr_affine_place: bad border");
+    double big = 0.0;
+    for (int i = 0; i < 9; ++i) {
+        if (!std::isfinite(forward[i])) return fail(VR_ERR_INVALID, "vr_affine_place: a non-finite entry");
+        if (std::fabs(forward[i]) > big) big = std::fabs(forward[i]);
+    }
+    const double* f = forward;
+    const double adj[9] = {f[4] * f[8] - f[5] * f[7], f[2] * f[7] - f[1] * f[8], f[1] * f[5] - f[2] * f[4],
+                           f[5] * f[6] - f[3] * f[8], f[0] * f[8] - f[2] * f[6], f[2] * f[3] - f[0] * f[5],
+                           f[3] * f[7] - f[4] * f[6], f[1] * f[6] - f[0] * f[7], f[0] * f[4] - f[1] * f[3]};
+    const double det = f[0] * adj[0] + f[1] * adj[3] + f[2] * adj[6];
+    if (!std::isfinite(det) || !(std::fabs(det) >= 1e-12 * big * big * big) || det == 0.0)
+        return fail(VR_ERR_INVALID, "vr_affine_place: forward is singular");
+    vr_affine r{};
+    for (int i = 0; i < 9; ++i) {
+        const double v = std::rint(adj[i] / det * (double)VR_AFFINE_ONE);
+        if (!(std::fabs(v) <= (double)VR_AFFINE_MAX_COEFF))
+            return fail(VR_ERR_INVALID, "vr_affine_place: a coefficient of the inverse is above 256.0 in magnitude");
+        r.m[i / 3][i % 3] = (int32_t)v;
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(src_centre[a])) return fail(VR_ERR_INVALID, "vr_affine_place: a non-finite entry");
+        const double v = std::rint(src_centre[a] * (double)VR_AFFINE_ONE);
+        if (!(std::fabs(v) <= 2147483647.0)) return fail(VR_ERR_INVALID, "vr_affine_place: src_centre leaves the 16.16 range");
+        r.origin[a] = (int32_t)v;
+        r.pivot[a] = dst_centre[a];
+    }
+    r.filter = filter;
+    r.border = border;
+    *out = r;
+    return VR_OK;
+}
 
 vr_status vr_brush_box(const vr_brush* b, int nx, int ny, int nz, int origin[3], int extent[3])
 {

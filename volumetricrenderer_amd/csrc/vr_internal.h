@@ -682,6 +682,21 @@ struct StampArgs {
     int sbx, sby;
 };
 hipError_t launch_paint_stamp(const StampArgs& a, const uint8_t* d_stamp, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+// vr_stamp_affine / vr_clone_affine: the brush as for launch_paint_planar (value is not
+// read) and the validated map (vr_affine.h); n is the source's extent in texels -- the stamp's (d_stamp: tightly
+// packed RGBA8, 4-byte aligned, each extent 1..32768) or the volume's own.  launch_stamp_affine and
+// launch_clone_affine_direct are one launch into the planes and fold the new bytes into mm, the latter only for a
+// map whose read range misses the clipped box on an axis (vr_affine.h direct); launch_clone_affine_stage has
+// launch_blur_stage's contract and slabs, and launch_blur_commit follows it.
+struct AffineArgs {
+    PaintArgs p;
+    int m[3][3], pivot[3], origin[3];
+    int n[3];
+    int filter, border;
+};
+hipError_t launch_stamp_affine(const AffineArgs& a, const uint8_t* d_stamp, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+hipError_t launch_clone_affine_direct(const AffineArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s);
+hipError_t launch_clone_affine_stage(const AffineArgs& a, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s);
 // vr_remap / vr_remap_device: the brush as for launch_paint_planar (value is not read) with
 // the value of a texel read from a table at the texel's old byte.  host_lut != null: the table is copied into the
 // kernel's arguments during the call (d_lut is not used); host_lut == null: d_lut, a 4-byte aligned DEVICE vr_lut, is

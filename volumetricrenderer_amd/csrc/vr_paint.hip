@@ -1,13 +1,14 @@
 // vr_paint.hip -- the brush kernels and their launchers: the edits applied in
 // place to the installed volume's planar planes (vr_paint, vr_paint_stroke,
-// vr_blur, vr_morph, vr_rank, vr_clone, vr_stamp, vr_remap; DESIGN.md
-// sec. 5.2.5 - 5.2.12) and the statistics under a brush or in a box
+// vr_blur, vr_morph, vr_rank, vr_clone, vr_stamp, vr_remap, vr_stamp_affine,
+// vr_clone_affine) and the statistics under a brush or in a box
 // (vr_brush_stats, vr_box_stats, vr_stats_lut_device).  The arithmetic is the
 // brush headers', which the host statements (vr_brush.cpp) include too: every
 // kernel here reproduces its statement bit for bit.
 #include <algorithm>
 #include <cstddef>
 
+#include "vr_affine.h"
 #include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_clone.h"
@@ -854,6 +855,182 @@ __global__ __launch_bounds__(kBlock) void k_paint_stamp(StampArgs g, const uint3
     fold_minmax(lo, hi, mm);
 }
 
+// vr_stamp_affine / vr_clone_affine: k_paint_planar
+// with the value of a texel resampled from a source at the 16.16 position P
+// that an affine map gives the texel (vr_affine.h).  Rows and lanes are
+// k_paint_planar's: a wave takes a box row, consecutive lanes consecutive
+// destination x.  The y, z and origin terms of P belong to the row --
+// wave-uniform 64-bit values, computed once per row (affine_row); per lane each
+// axis adds m[a][0] times the texel's x.  Consecutive lanes therefore read
+// along ONE straight line through the source, m[.][0] apart: a row of the
+// source for a translation or a scale, a diagonal for a rotation.  A row or a
+// texel outside the ellipsoid, and (VR_BORDER_SKIP) a texel whose position is
+// outside the source, is left before any load.
+struct AffineRow {
+    long long base[3];   // P of the row's texel x = 0 of the box
+};
+__device__ __forceinline__ AffineRow affine_row(const AffineArgs& g, int y, int z)
+{
+    const PaintArgs& a = g.p;
+    AffineRow r;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+        r.base[ax] = affine::position(g.m[ax], g.origin[ax], g.pivot, a.o[0], a.o[1] + y, a.o[2] + z);
+    return r;
+}
+// The clamped position of the row's texel x; false when VR_BORDER_SKIP leaves the texel alone.
+__device__ __forceinline__ bool affine_position(const AffineArgs& g, const AffineRow& rw, int x, long long (&p)[3])
+{
+    bool out = false;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        const long long v = rw.base[ax] + (long long)g.m[ax][0] * x;
+        out = out || affine::outside(v, g.n[ax]);
+        p[ax] = affine::clamp(v, g.n[ax]);
+    }
+    return !(out && g.border == VR_BORDER_SKIP);
+}
+
+// vr_stamp_affine: the source is the caller's box of dwords, one per texel with
+// all four channels.  NEAREST: one dword load per inside lane.  LINEAR: eight,
+// and the x stage of the trilinear sum runs on two channels at a time in the
+// 0x00FF00FF halves of a register (a half holds at most 255 * 256); the y and z
+// stages are vr_affine.h's per channel, so the bytes are the statement's.
+template <bool LINEAR>
+__global__ __launch_bounds__(kBlock) void k_stamp_affine(AffineArgs g, const uint32_t* __restrict__ stamp,
+                                                         uint8_t* __restrict__ dst, unsigned* __restrict__ mm)
+{
+    const PaintArgs& a = g.p;
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    struct Rows {
+        uint8_t* __restrict__ row;
+        AffineRow p;
+    };
+    const size_t sbx = (size_t)g.n[0], sby = (size_t)g.n[1];
+    walk_rows(
+        a, wave_index(), [&](unsigned, int y, int z) { return Rows{dst + box_row(a, y, z), affine_row(g, y, z)}; },
+        [&](const Rows& rw, int x, unsigned long long q) {
+            long long p[3];
+            if (!affine_position(g, rw.p, x, p)) return;
+            const unsigned w = brush::weight(q, a.s, a.falloff);
+            unsigned v[4];
+            if constexpr (LINEAR) {
+                const affine::Axis ax = affine::linear_weights(p[0], g.n[0]), ay = affine::linear_weights(p[1], g.n[1]),
+                                   az = affine::linear_weights(p[2], g.n[2]);
+                const size_t r00 = ((size_t)az.i * sby + (size_t)ay.i) * sbx, r01 = ((size_t)az.i * sby + (size_t)ay.j) * sbx,
+                             r10 = ((size_t)az.j * sby + (size_t)ay.i) * sbx, r11 = ((size_t)az.j * sby + (size_t)ay.j) * sbx;
+                const uint32_t c[4][2] = {{stamp[r00 + ax.i], stamp[r00 + ax.j]}, {stamp[r01 + ax.i], stamp[r01 + ax.j]},
+                                          {stamp[r10 + ax.i], stamp[r10 + ax.j]}, {stamp[r11 + ax.i], stamp[r11 + ax.j]}};
+                uint32_t ev[4], od[4];   // the x sums of channels 0, 2 and of 1, 3, per (z, y) pair
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    ev[k] = (c[k][0] & 0x00ff00ffu) * (256u - ax.f) + (c[k][1] & 0x00ff00ffu) * ax.f;
+                    od[k] = ((c[k][0] >> 8) & 0x00ff00ffu) * (256u - ax.f) + ((c[k][1] >> 8) & 0x00ff00ffu) * ax.f;
+                }
+#pragma unroll
+                for (int ch = 0; ch < 4; ++ch) {
+                    const int sh = 16 * (ch >> 1);
+                    const uint32_t* xs = ch & 1 ? od : ev;
+                    v[ch] = affine::linear_yz((xs[0] >> sh) & 0xffffu, (xs[1] >> sh) & 0xffffu, (xs[2] >> sh) & 0xffffu,
+                                              (xs[3] >> sh) & 0xffffu, ay.f, az.f);
+                }
+            } else {
+                const uint32_t t = stamp[((size_t)affine::nearest(p[2]) * sby + (size_t)affine::nearest(p[1])) * sbx +
+                                         (size_t)affine::nearest(p[0])];
+#pragma unroll
+                for (int ch = 0; ch < 4; ++ch) v[ch] = (t >> (8 * ch)) & 255u;
+            }
+#pragma unroll
+            for (int ch = 0; ch < 4; ++ch) {
+                if (a.strength[ch] == 0u) continue;
+                uint8_t* d = rw.row + x + ch * plane;
+                const unsigned old = *d;
+                commit(d, old, brush::blend(a.op, old, v[ch], w * a.strength[ch]), lo[ch], hi[ch]);
+            }
+        });
+    fold_minmax(lo, hi, mm);
+}
+
+// vr_clone_affine: the source is the planes themselves, byte gathers per painted
+// channel (one for NEAREST, eight for LINEAR).  STAGE = false
+// (k_clone_affine_direct): `out` is the planes; the host has checked
+// (vr_affine.h direct) that no texel of the box is read.  STAGE = true
+// (k_clone_affine_stage): the planes are read only and the new byte of every
+// processed texel and painted channel goes to the staging slabs, as
+// k_clone_stage leaves them; k_blur_commit follows.  A texel VR_BORDER_SKIP
+// leaves alone stages its old bytes: the commit then stores nothing for it and
+// folds a byte that the range holds already.
+template <bool STAGE, bool LINEAR>
+__device__ __forceinline__ void affine_rows(const AffineArgs& g, const uint8_t* planes, uint8_t* out, unsigned (&lo)[4],
+                                            unsigned (&hi)[4])
+{
+    const PaintArgs& a = g.p;
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    const size_t slab = (size_t)a.e[0] * (size_t)a.e[1] * (size_t)a.e[2];
+    struct Rows {
+        long long drow;   // the box row in a plane
+        size_t stage;     // the box row in a slab
+        AffineRow p;
+    };
+    walk_rows(
+        a, wave_index(),
+        [&](unsigned r, int y, int z) { return Rows{box_row(a, y, z), (size_t)r * (size_t)a.e[0], affine_row(g, y, z)}; },
+        [&](const Rows& rw, int x, unsigned long long q) {
+            long long p[3];
+            const bool touched = affine_position(g, rw.p, x, p);
+            if (!STAGE && !touched) return;
+            const unsigned w = brush::weight(q, a.s, a.falloff);
+            const affine::Axis ax = affine::linear_weights(p[0], a.nx), ay = affine::linear_weights(p[1], a.ny),
+                               az = affine::linear_weights(p[2], a.nz);
+            const long long r00 = ((long long)az.i * a.ny + ay.i) * a.nx, r01 = ((long long)az.i * a.ny + ay.j) * a.nx,
+                            r10 = ((long long)az.j * a.ny + ay.i) * a.nx, r11 = ((long long)az.j * a.ny + ay.j) * a.nx;
+            const long long near = ((long long)affine::nearest(p[2]) * a.ny + affine::nearest(p[1])) * a.nx + affine::nearest(p[0]);
+            int k = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (a.strength[c] == 0u) continue;
+                const uint8_t* pc = planes + c * plane;
+                const unsigned old = pc[rw.drow + x];
+                unsigned nw = old;
+                if (touched) {
+                    unsigned v;
+                    if constexpr (LINEAR) {
+                        const unsigned gx = 256u - ax.f;
+                        v = affine::linear_yz(pc[r00 + ax.i] * gx + pc[r00 + ax.j] * ax.f, pc[r01 + ax.i] * gx + pc[r01 + ax.j] * ax.f,
+                                              pc[r10 + ax.i] * gx + pc[r10 + ax.j] * ax.f, pc[r11 + ax.i] * gx + pc[r11 + ax.j] * ax.f,
+                                              ay.f, az.f);
+                    } else {
+                        v = pc[near];
+                    }
+                    nw = brush::blend(a.op, old, v, w * a.strength[c]);
+                }
+                if constexpr (STAGE) {
+                    out[(size_t)k * slab + rw.stage + (size_t)x] = (uint8_t)nw;
+                    ++k;
+                } else {
+                    commit(out + c * plane + rw.drow + x, old, nw, lo[c], hi[c]);
+                }
+            }
+        });
+}
+
+template <bool LINEAR>
+__global__ __launch_bounds__(kBlock) void k_clone_affine_direct(AffineArgs g, uint8_t* planes, unsigned* __restrict__ mm)
+{
+    unsigned lo[4] = {255u, 255u, 255u, 255u}, hi[4] = {0u, 0u, 0u, 0u};
+    affine_rows<false, LINEAR>(g, planes, planes, lo, hi);
+    fold_minmax(lo, hi, mm);
+}
+
+template <bool LINEAR>
+__global__ __launch_bounds__(kBlock) void k_clone_affine_stage(AffineArgs g, const uint8_t* __restrict__ src,
+                                                               uint8_t* __restrict__ stage)
+{
+    unsigned lo[4], hi[4];   // not used
+    affine_rows<true, LINEAR>(g, src, stage, lo, hi);
+}
+
 // vr_remap / vr_remap_device: k_paint_planar with the
 // value of a texel read from a table at the texel's own old byte
 // (vr_remap.h).  Rows and lanes are k_paint_planar's.  At workgroup start the
@@ -1161,6 +1338,44 @@ hipError_t launch_paint_stamp(const StampArgs& a, const uint8_t* d_stamp, uint8_
     const long long rows = (long long)a.p.e[1] * a.p.e[2];
     hipLaunchKernelGGL(k_paint_stamp, dim3(grid_for(rows * 64)), dim3(kBlock), 0, s, a,
                        reinterpret_cast<const uint32_t*>(d_stamp), d_planar, mm);
+    return hipGetLastError();
+}
+
+// vr_stamp_affine and vr_clone_affine: a wave per box row, as launch_paint_planar; one instantiation per filter
+static bool affine_args_ok(const AffineArgs& a)
+{
+    if (a.p.e[0] < 1 || a.p.e[1] < 1 || a.p.e[2] < 1 || a.n[0] < 1 || a.n[1] < 1 || a.n[2] < 1) return false;
+    if (a.filter != VR_FILTER_NEAREST && a.filter != VR_FILTER_LINEAR) return false;
+    return a.border == VR_BORDER_CLAMP || a.border == VR_BORDER_SKIP;
+}
+
+hipError_t launch_stamp_affine(const AffineArgs& a, const uint8_t* d_stamp, uint8_t* d_planar, unsigned* mm, hipStream_t s)
+{
+    if (!affine_args_ok(a) || !d_planar || !d_stamp || (reinterpret_cast<uintptr_t>(d_stamp) & 3u) != 0u) return hipErrorInvalidValue;
+    if (a.n[0] > VR_AFFINE_MAX_EXTENT || a.n[1] > VR_AFFINE_MAX_EXTENT || a.n[2] > VR_AFFINE_MAX_EXTENT) return hipErrorInvalidValue;
+    const dim3 g(grid_for((long long)a.p.e[1] * a.p.e[2] * 64)), b(kBlock);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(d_stamp);
+    if (a.filter == VR_FILTER_LINEAR) hipLaunchKernelGGL(k_stamp_affine<true>, g, b, 0, s, a, src, d_planar, mm);
+    else hipLaunchKernelGGL(k_stamp_affine<false>, g, b, 0, s, a, src, d_planar, mm);
+    return hipGetLastError();
+}
+
+hipError_t launch_clone_affine_direct(const AffineArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s)
+{
+    if (!affine_args_ok(a) || !d_planar || a.n[0] != a.p.nx || a.n[1] != a.p.ny || a.n[2] != a.p.nz) return hipErrorInvalidValue;
+    const dim3 g(grid_for((long long)a.p.e[1] * a.p.e[2] * 64)), b(kBlock);
+    if (a.filter == VR_FILTER_LINEAR) hipLaunchKernelGGL(k_clone_affine_direct<true>, g, b, 0, s, a, d_planar, mm);
+    else hipLaunchKernelGGL(k_clone_affine_direct<false>, g, b, 0, s, a, d_planar, mm);
+    return hipGetLastError();
+}
+
+hipError_t launch_clone_affine_stage(const AffineArgs& a, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s)
+{
+    if (!affine_args_ok(a) || !d_planar || !d_stage || a.n[0] != a.p.nx || a.n[1] != a.p.ny || a.n[2] != a.p.nz)
+        return hipErrorInvalidValue;
+    const dim3 g(grid_for((long long)a.p.e[1] * a.p.e[2] * 64)), b(kBlock);
+    if (a.filter == VR_FILTER_LINEAR) hipLaunchKernelGGL(k_clone_affine_stage<true>, g, b, 0, s, a, d_planar, d_stage);
+    else hipLaunchKernelGGL(k_clone_affine_stage<false>, g, b, 0, s, a, d_planar, d_stage);
     return hipGetLastError();
 }
 

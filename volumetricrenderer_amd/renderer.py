@@ -38,6 +38,7 @@ from ._lib import (BRUSH_ADD, BRUSH_SET, BRUSH_SUB, BYTES_PER_PIXEL, CHANNELS, F
                    Rect, Target, VolumeRecipe, VR_MAX_RECTS, VRError, call)
 from ._lib import VOLUME_STATS_BYTES, StatsSummary, VolumeStats
 from ._lib import Box, CloneMap
+from ._lib import BORDER_CLAMP, FILTER_NEAREST, Affine
 from ._lib import RANK_MEDIAN
 from ._lib import LUT_BYTES, LUT_EQUALIZE, LUT_STRETCH, Lut  # noqa: F401
 
@@ -401,6 +402,89 @@ def stamp_box(brush: Brush, placement, dims):
     o, e = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
     call("vr_stamp_box", ctypes.byref(brush), ctypes.byref(box), nx, ny, nz, o, e)
     return (tuple(o), tuple(e)) if e[0] > 0 else None
+
+
+def make_affine(m=((65536, 0, 0), (0, 65536, 0), (0, 0, 65536)), pivot=(0, 0, 0), origin=(0, 0, 0),
+                filter: int = FILTER_NEAREST, border: int = BORDER_CLAMP) -> Affine:
+    """A vr_affine from its 16.16 tables, as they stand: per axis a the source
+    position of destination texel t is ``origin[a] + sum_b m[a][b] * (t[b] -
+    pivot[b])`` -- `m` and `origin` in 1/65536 of a source texel, `pivot` a
+    destination texel.  :func:`affine_place` builds one from a rotation."""
+    a = Affine()
+    for i in range(3):
+        a.m[i][:] = [int(v) for v in m[i]]
+    a.pivot[:] = [int(v) for v in pivot]
+    a.origin[:] = [int(v) for v in origin]
+    a.filter, a.border = int(filter), int(border)
+    return a
+
+
+def affine_identity() -> Affine:
+    """vr_affine_identity: the map that reads every texel at its own coordinates,
+    FILTER_NEAREST and BORDER_CLAMP."""
+    a = Affine()
+    call("vr_affine_identity", ctypes.byref(a))
+    return a
+
+
+def affine_place(forward, src_centre, dst_centre, filter: int = FILTER_NEAREST, border: int = BORDER_CLAMP) -> Affine:
+    """vr_affine_place: the map that pastes the source rotated / scaled by the
+    3 x 3 matrix `forward` with the source position `src_centre` (texels, may
+    be fractional) on the destination texel `dst_centre` -- the map stores the
+    inverse, rounded to 16.16.  Raises VRError for a singular or non-finite
+    matrix and for a coefficient above 256 in magnitude."""
+    f = (ctypes.c_double * 9)(*np.asarray(forward, np.float64).reshape(9))
+    s = (ctypes.c_double * 3)(*(float(v) for v in src_centre))
+    d = (ctypes.c_int32 * 3)(*(int(v) for v in dst_centre))
+    a = Affine()
+    call("vr_affine_place", f, s, d, int(filter), int(border), ctypes.byref(a))
+    return a
+
+
+def affine_direct(brush: Brush, affine: Affine, dims) -> bool:
+    """vr_affine_direct: True when :meth:`Renderer.clone_affine` of this brush
+    and map in a volume of `dims` = (nx, ny, nz) takes the direct path (one
+    launch, no scratch), False for the staged one."""
+    nx, ny, nz = (int(v) for v in dims)
+    d = ctypes.c_int()
+    call("vr_affine_direct", ctypes.byref(brush), ctypes.byref(affine), nx, ny, nz, ctypes.byref(d))
+    return bool(d.value)
+
+
+def brush_stamp_affine_apply(brush: Brush, stamp: np.ndarray, affine: Affine, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_stamp_affine_apply: the transform paste of `stamp` (a contiguous
+    uint8 array shaped (bz, by, bx, 4)) into a host RGBA8 volume shaped
+    (nz, ny, nx, 4) -- `brush` blended as :func:`brush_apply` blends it, with
+    the value of each texel resampled from the stamp at the position `affine`
+    maps it to (nearest or trilinear; outside the stamp clamped to its edge or,
+    BORDER_SKIP, left alone).  The CPU statement of what
+    :meth:`Renderer.stamp_affine` does on the device.  Writes `rgba` and
+    returns it."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_stamp_affine_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    if (not isinstance(stamp, np.ndarray) or stamp.dtype != np.uint8 or stamp.ndim != 4 or stamp.shape[3] != 4
+            or not stamp.flags.c_contiguous or stamp.size == 0):
+        raise ValueError("brush_stamp_affine_apply: the stamp is a non-empty contiguous uint8 array shaped (bz, by, bx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    bz, by, bx, _ = stamp.shape
+    call("vr_brush_stamp_affine_apply", ctypes.byref(brush), stamp.ctypes.data_as(ctypes.c_void_p), bx, by, bz,
+         ctypes.byref(affine), rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz)
+    return rgba
+
+
+def brush_clone_affine_apply(brush: Brush, affine: Affine, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_clone_affine_apply: the same with the volume itself, as it was
+    before the call, as the source.  The CPU statement of what
+    :meth:`Renderer.clone_affine` does on the device.  Writes `rgba` and
+    returns it."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_clone_affine_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    call("vr_brush_clone_affine_apply", ctypes.byref(brush), ctypes.byref(affine), rgba.ctypes.data_as(ctypes.c_void_p),
+         nx, ny, nz)
+    return rgba
 
 
 def _lut_struct(fn: str, lut) -> Lut:
@@ -800,6 +884,49 @@ class Renderer:
         if stream is None:
             torch.cuda.current_stream().synchronize()
         return stamp_box(b, placement, self.volume_dims())
+
+    def stamp_affine(self, stamp_tensor, affine: Affine, centre, radius, op=BRUSH_SET, falloff: int = 0,
+                     strength=(255, 255, 255, 255), stream=None):
+        """Paste a device box rotated, scaled, sheared or shifted by a fraction
+        of a texel (vr_stamp_affine): `stamp_tensor` is a contiguous CUDA uint8
+        tensor shaped (bz, by, bx, 4) -- what :meth:`get_volume_box` returns on
+        the device; the brush is :meth:`paint`'s, with the value of a texel
+        resampled from the stamp at the position `affine`
+        (:func:`affine_place`, :func:`make_affine`) maps it to, nearest or
+        trilinear; a position outside the stamp reads its edge (BORDER_CLAMP)
+        or leaves the texel alone (BORDER_SKIP).  Bit for bit what
+        :func:`brush_stamp_affine_apply` gives on the host.  Returns
+        ``(origin, extent)`` of the brush's clipped box, or None when it misses
+        the volume.  One launch queued on `stream` as :meth:`paint` is: no
+        scratch, no host wait; the tensor must be 4-byte aligned and stay alive
+        until the launch has run."""
+        if (not isinstance(stamp_tensor, torch.Tensor) or not stamp_tensor.is_cuda
+                or stamp_tensor.device.index != self.device or stamp_tensor.dtype != torch.uint8
+                or stamp_tensor.dim() != 4 or stamp_tensor.shape[3] != 4 or not stamp_tensor.is_contiguous()):
+            raise ValueError(f"stamp_affine: a contiguous uint8 tensor shaped (bz, by, bx, 4) on cuda:{self.device}")
+        bz, by, bx, _ = stamp_tensor.shape
+        b = make_brush(centre, radius, op, falloff, 0, strength)
+        # an empty stamp has no buffer to hand over: the library refuses the extent either way
+        ptr = ctypes.c_void_p(stamp_tensor.data_ptr()) if stamp_tensor.numel() else ctypes.c_void_p(4)
+        call("vr_stamp_affine", self._ctx, ctypes.byref(b), ptr, bx, by, bz, ctypes.byref(affine), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return brush_box(b, self.volume_dims())
+
+    def clone_affine(self, centre, radius, affine: Affine, op=BRUSH_SET, falloff: int = 0, strength=(255, 255, 255, 255),
+                     stream=None):
+        """The same with the installed volume itself, as it was before the
+        call, as the source (vr_clone_affine): :meth:`clone` through an affine
+        map and a filter.  Bit for bit what :func:`brush_clone_affine_apply`
+        gives on the host.  A read range that does not meet the brush's box
+        costs one launch and no scratch (:func:`affine_direct`); one that does
+        goes through :meth:`blur`'s staging scratch (``blur_scratch_kib``),
+        which grows by the same rule."""
+        b = make_brush(centre, radius, op, falloff, 0, strength)
+        call("vr_clone_affine", self._ctx, ctypes.byref(b), ctypes.byref(affine), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return brush_box(b, self.volume_dims())
 
     def remap(self, centre, radius, lut, op=BRUSH_SET, falloff: int = 0, strength=(255, 255, 255, 255), stream=None):
         """Paint the installed volume under an ellipsoidal brush with a function
