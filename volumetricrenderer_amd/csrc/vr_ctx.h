@@ -284,6 +284,9 @@ struct Ctx {
     int quad_split = 1;            // option "quad_split": a QUAD launch of COL48 / BRICK4832 splits each tap's loads
                                    // between the lanes of a quad; 0 = every lane loads all
     long long quad_split_launches = 0;   // read-only option "quad_split_launches": those launches so far
+    int quad_steps = 1;            // option "quad_steps": a split launch's lanes each fetch and blend one step of four
+                                   // and exchange the terms; 0 = the split fetch by pairs
+    long long quad_steps_launches = 0;   // read-only option "quad_steps_launches": those launches so far
     uint2* d_lat = nullptr;
     size_t lat_cap = 0;            // bytes allocated
     long long lat_key[3] = {0, 0, -1};

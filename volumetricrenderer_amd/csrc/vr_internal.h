@@ -281,8 +281,30 @@ constexpr bool quad_instance(int layout, bool early, bool zero_offsets, int umas
 // frame), the QUAD instance, or the QUAD instance whose lanes split each tap's loads between
 // them (option quad_split; vr_march_kernels.h march_pixel_quad_split).  The split fetch is
 // built for the layouts whose footprint slice packs into one dword, 32 bytes apart in z.
-enum QuadMode : int { QUAD_NONE = 0, QUAD_FRAMES = 1, QUAD_SPLIT = 2 };
+// QUAD_STEPS (option quad_steps; march_pixel_quad_steps) is a split launch of the same layouts
+// in which each lane of the quad fetches and blends one step of four.
+enum QuadMode : int { QUAD_NONE = 0, QUAD_FRAMES = 1, QUAD_SPLIT = 2, QUAD_STEPS = 3 };
 constexpr bool quad_split_layout(int layout) { return layout == LAYOUT_COL48 || layout == LAYOUT_BRICK4832; }
+
+// One round of march_pixel_quad_steps' accumulation: t[j] is the term of step base + j (formed
+// by quad lane j), n the ray's steps.  The terms are added in step order, each only where the
+// ray has that step and no earlier sum passed acc_limit (EARLY), so acc takes the values of
+// the sequential loop `acc = acc + term; if (EARLY && acc > acc_limit) break;` one after the
+// other.  *stop: the early-out ended the march in this round.  tools/round_check.cpp compares
+// the two on the host.
+template <bool EARLY>
+__host__ __device__ inline float quad_round_accumulate(float acc, float t0, float t1, float t2, float t3, int base, int n,
+                                                       float acc_limit, bool* stop)
+{
+    bool st = false;
+    const float t[4] = {t0, t1, t2, t3};
+    for (int j = 0; j < 4; ++j) {
+        acc = base + j < n && !st ? acc + t[j] : acc;
+        if (EARLY) st = acc > acc_limit;
+    }
+    *stop = st;
+    return acc;
+}
 
 // The part of MarchArgs that differs between the frames of one multi-frame launch
 // (vr_render_pair, vr_render_group): the camera (ray basis, r2 / r3, cam, tap_T), the
@@ -526,7 +548,7 @@ hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, co
 constexpr bool pair_layout(int layout) { return list_has(FrameLayouts{}, layout); }
 // quad (a QuadMode; other than QUAD_NONE for nf = 4, frames_share_camera(fr, nf) and no step
 // counter only): the kernels' QUAD instance, the four frames in the lanes of a quad
-// (vr_march_kernels.h regions_frames_body); QUAD_SPLIT for a quad_split_layout only
+// (vr_march_kernels.h regions_frames_body); QUAD_SPLIT and QUAD_STEPS for a quad_split_layout only
 hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
                                int deal, int quad, hipStream_t s);
 hipError_t launch_march_frames_cornerh(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc,

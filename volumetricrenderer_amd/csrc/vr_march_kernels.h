@@ -506,6 +506,118 @@ __device__ __forceinline__ void march_pixel_quad_split(const MarchArgs& a, const
     }
 }
 
+// ---- the QUAD kernels' step rounds (option quad_steps) ----
+// The split fetch above shares a quad's loads and leaves its arithmetic fourfold: every lane
+// forms the coordinates, the weights and the blend of both steps of a pair.  Here the march
+// runs in rounds of four steps and quad lane fl owns step base + fl: it fetches that step
+// as fetch_u does (both z-slices, two b64 loads per loaded tap -- per quad and tap the pieces
+// the split fetch asks for over two pairs), blends it with blend_u and forms the step's term
+// ((t0 * t1) * (t2 + t3)) * scale as march_pixel does, rounded on the owning lane.  The term
+// is the only value that crosses lanes: every lane reads the round's four through DPP
+// quad_perm [J, J, J, J] and adds them to its own acc in step order (quad_round_accumulate),
+// so acc takes march_pixel's values one after the other, and every lane keeps its own acc,
+// early-out and store.  This is march_pixel_split<K>'s scheme with DPP in place of __shfl.
+//
+// Every lane advances the ray point by march_pixel's chain of single adds, four per round,
+// and picks its own step's point from the chain; a point is never formed as p0 + k * s.  A
+// lane whose step lies past the ray's last one takes the current round's first point, which
+// is in the box: no load names a point outside it.
+//
+// The exchange needs every lane of a quad active wherever one is.  That holds for the reason
+// given above march_pixel_quad_split: the lanes of a quad share the ray, so r.n, the
+// early-out (each lane adds the same four terms in the same order) and the edge-of-frame
+// case are the same in all four, and a quad takes every branch below as one.
+//
+// Software-pipelined like march_pixel, by rounds: the loads of round base + 4 are issued
+// before round base is blended, two rounds of 2 x b64 x loaded taps in flight per lane.
+//
+// The fetch is tap_fetch's for these layouts (fetch_u / tap_fetch_at: the same coordinates,
+// offset and two b64 loads) with the shift by off & 3 left to the consumer: tap_fetch shifts
+// in the round that loads, which makes that round wait for its own look-ahead loads.  A
+// StepRaw carries the loaded dwords over the loop's back edge and step_tap turns it into
+// the TapRaw that blend_u takes.
+struct StepRaw {
+    unsigned s00, s01, s10, s11, off;
+    float wx, wy, wz;
+};
+template <int UM, int T, bool ZO>
+__device__ __forceinline__ StepRaw step_fetch(const MarchArgs& a, const FastCtx& f, f2 pxy, float pz)
+{
+    if constexpr ((UM >> T) & 1) {
+        return StepRaw{};
+    } else {
+        const f2 Tt = ZO ? f2{0.5f, 0.5f} : f2{a.tap_T[T][0], a.tap_T[T][1]};
+        const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[T][0], a.tap_S[T][1]}, Tt);
+        const float gz = fmaf(pz, a.tap_S[T][2], ZO ? 0.5f : a.tap_T[T][2]);
+        const unsigned off = f.tx[cvt_flr(gxy.x)] + f.ty[cvt_flr(gxy.y)] + f.tz[cvt_flr(gz)];
+        const auto s0 = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], off & ~3u, 0, 0);
+        const auto s1 = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], (off & ~3u) + kSplitZ, 0, 0);
+        return StepRaw{s0[0], s0[1], s1[0], s1[1], off, fract_(gxy.x), fract_(gxy.y), fract_(gz)};
+    }
+}
+__device__ __forceinline__ TapRaw step_tap(const StepRaw& r)
+{
+    return TapRaw{__builtin_amdgcn_alignbyte(r.s01, r.s00, r.off), __builtin_amdgcn_alignbyte(r.s01, r.s01, r.off),
+                  __builtin_amdgcn_alignbyte(r.s11, r.s10, r.off), __builtin_amdgcn_alignbyte(r.s11, r.s11, r.off),
+                  r.wx, r.wy, r.wz};
+}
+template <int J>
+__device__ __forceinline__ float quad_lane_f(float v)
+{
+    return __builtin_bit_cast(float, quad_lane<J>(__builtin_bit_cast(unsigned, v)));
+}
+template <int LAYOUT, bool EARLY, bool ZO, int UM>
+__device__ __forceinline__ void march_pixel_quad_steps(const MarchArgs& a, const FastCtx& f, int x, int orow, int fl)
+{
+    static_assert(quad_split_layout(LAYOUT), "built for the layouts of the split fetch");
+    const Ray r = setup_ray(a, x, orow);
+    float uv[4] = {};
+    if constexpr (UM != 0)
+        for (int t = 0; t < 4; ++t)
+            if ((UM >> t) & 1) uv[t] = noise::in_vgpr(a.uval[t]);
+    float acc = 0.0f;
+    if (r.n > 0) {
+        // the point of step base + fl out of the chain's four
+        const auto own = [fl](auto p0, auto p1, auto p2, auto p3) { return fl & 2 ? (fl & 1 ? p3 : p2) : (fl & 1 ? p1 : p0); };
+        f2 axy = r.pxy;                                         // the points of steps base .. base + 3   // :74
+        float az = r.pz;
+        f2 bxy = axy + r.sxy, cxy = bxy + r.sxy, dxy = cxy + r.sxy;
+        float bz = az + r.sz, cz = bz + r.sz, dz = cz + r.sz;
+        bool mine = fl < r.n;
+        f2 qxy = mine ? own(axy, bxy, cxy, dxy) : axy;
+        float qz = mine ? own(az, bz, cz, dz) : az;
+        StepRaw c0 = step_fetch<UM, 0, ZO>(a, f, qxy, qz), c1 = step_fetch<UM, 1, ZO>(a, f, qxy, qz);
+        StepRaw c2 = step_fetch<UM, 2, ZO>(a, f, qxy, qz), c3 = step_fetch<UM, 3, ZO>(a, f, qxy, qz);
+        for (int base = 0;;) {
+            const f2 exy = dxy + r.sxy, fxy = exy + r.sxy, gxy = fxy + r.sxy, hxy = gxy + r.sxy;   // steps base + 4 .. base + 7
+            const float ez = dz + r.sz, fz = ez + r.sz, gz = fz + r.sz, hz = gz + r.sz;
+            mine = base + 4 + fl < r.n;
+            qxy = mine ? own(exy, fxy, gxy, hxy) : axy;
+            qz = mine ? own(ez, fz, gz, hz) : az;
+            const StepRaw n0 = step_fetch<UM, 0, ZO>(a, f, qxy, qz), n1 = step_fetch<UM, 1, ZO>(a, f, qxy, qz);
+            const StepRaw n2 = step_fetch<UM, 2, ZO>(a, f, qxy, qz), n3 = step_fetch<UM, 3, ZO>(a, f, qxy, qz);
+            const float t0 = blend_u<UM, 0, LAYOUT>(step_tap(c0), uv), t1 = blend_u<UM, 1, LAYOUT>(step_tap(c1), uv);
+            const float t2 = blend_u<UM, 2, LAYOUT>(step_tap(c2), uv), t3 = blend_u<UM, 3, LAYOUT>(step_tap(c3), uv);
+            const float term = ((t0 * t1) * (t2 + t3)) * a.scale;                        // :71-73
+            // the look-ahead loads stay above this line: without it the compiler sinks them below the
+            // loop's exit test, into the branch that goes round again, and waits for them there
+            __builtin_amdgcn_sched_barrier(0);
+            bool stop;
+            acc = quad_round_accumulate<EARLY>(acc, quad_lane_f<0>(term), quad_lane_f<1>(term), quad_lane_f<2>(term),
+                                               quad_lane_f<3>(term), base, r.n, a.acc_limit, &stop);
+            base += 4;
+            if (stop || base >= r.n) break;
+            c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+            axy = exy; az = ez;
+            dxy = hxy; dz = hz;
+        }
+    }
+    if (r.live) {
+        const float at = acc * a.step_size;
+        store_pixel(a, x, orow, r.n >= 0, 1.0f - spec_expf(a.density * fminf(-at, 0.0f)));
+    }
+}
+
 // Kernel prologue for the fast layouts: buffer descriptors (wave-uniform,
 // from kernargs only) and the per-axis offset tables, built in LDS by the
 // whole workgroup.  The tables are the only LDS use and are read-only after
@@ -726,13 +838,17 @@ __global__ __launch_bounds__(kThreads) void march_regions_u(const MarchArgs a, c
 //   QUAD, SPLIT:  COL48 / BRICK4832 only (option quad_split): the same
 //                 mapping, and the quad's lanes split the loads of two steps between them
 //                 (march_pixel_quad_split) instead of each issuing all of them.
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false>
+//   SPLIT, STEPS: the same launches (option quad_steps): the quad's lanes
+//                 each fetch and blend one step of four and exchange the terms
+//                 (march_pixel_quad_steps).
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false>
 __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, const unsigned* __restrict__ tiles,
                                                     const int* __restrict__ hdr, int nwx, int deal, unsigned* lds)
 {
     static_assert(NF == 2 || NF == 4, "a 4-wave workgroup is 4 / NF entry waves x NF frames");
     static_assert(!QUAD || NF == 4, "a quad of lanes is four frames");
     static_assert(!SPLIT || QUAD, "the lanes of a quad split a fetch only where they hold one ray");
+    static_assert(!STEPS || SPLIT, "the step rounds are a split launch's");
     const int xcd = blockIdx.x & 7, wg = (int)(blockIdx.x >> 3);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int fr = wave, first = wg, w = wg;   // the frame, the workgroup's first entry wave, this wave's
@@ -767,7 +883,8 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
         for (int k = wg; wg < nwx && k < qcount; k += nwx) {
             const unsigned t = tiles[begin + k];
             const int tx = (int)(t & 0xffffu), ty = (int)(t >> 16);
-            if constexpr (SPLIT) march_pixel_quad_split<LAYOUT, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
+            if constexpr (STEPS) march_pixel_quad_steps<LAYOUT, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
+            else if constexpr (SPLIT) march_pixel_quad_split<LAYOUT, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
             else (void)march_pixel<LAYOUT, WRAP, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy);
         }
         return;
@@ -786,21 +903,24 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
 // The split-fetch instances are built for 5 or more waves per SIMD: left to itself the
 // scheduler spreads a pair's six blends over 102 VGPRs (4 waves), with the floor it needs 75
 // and no scratch.  1 is the floor a kernel of 4-wave workgroups has without the attribute, so
-// every other instance is compiled as before.
-#define VR_SPLIT_WAVES __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : 1)))
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF, bool QUAD = false, bool SPLIT = false>
+// every other instance is compiled as before.  The step-round instances
+// take the same floor where the tap offsets are zero (102 VGPRs without it, 96 or fewer and no
+// scratch with it); with tap offsets the floor costs 8 bytes of scratch, so those two keep 1
+// (124 VGPRs, 4 waves).
+#define VR_SPLIT_WAVES __attribute__((amdgpu_waves_per_eu(SPLIT && (!STEPS || ZO) ? 5 : 1)))
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false>
 __global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES void march_regions_frames(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
                                                                 const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF, QUAD, SPLIT>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF, QUAD, SPLIT, STEPS>(g, tiles, hdr, nwx, deal, lds);
 }
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false>
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false>
 __global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES void march_regions_frames_u(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
                                                                   const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF, QUAD, SPLIT>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF, QUAD, SPLIT, STEPS>(g, tiles, hdr, nwx, deal, lds);
 }
 #undef VR_SPLIT_WAVES
 
@@ -1077,17 +1197,18 @@ hipError_t launch_lw(const MarchArgs& a, bool early, const Schedule& sc, hipStre
 // workgroups, and that L is one of FrameLayouts.  XCD x runs
 // sc.map.nwx entry waves, 4 / NF to a workgroup (regions_frames_body).
 // quad (QuadMode): the QUAD instance (nf = 4 only; the caller has proved frames_share_camera), with
-// the split fetch or without -- the same grid.
+// the split fetch, with the step rounds or without either -- the same grid.
 template <int L, int W>
 hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc, int deal, int quad,
                            hipStream_t s)
 {
     if (quad != QUAD_NONE && (nf != kGroupFrames || !quad_instance(L, early, a.zero_offsets != 0, a.umask)))
         return hipErrorInvalidValue;   // no such kernel
-    if (quad == QUAD_SPLIT && !quad_split_layout(L)) return hipErrorInvalidValue;
-    return with_value<2, kGroupFrames>(nf, [&](auto NF) { return with_value<QUAD_NONE, QUAD_FRAMES, QUAD_SPLIT>(quad, [&](auto QD) {
+    if ((quad == QUAD_SPLIT || quad == QUAD_STEPS) && !quad_split_layout(L)) return hipErrorInvalidValue;
+    return with_value<2, kGroupFrames>(nf, [&](auto NF) { return with_value<QUAD_NONE, QUAD_FRAMES, QUAD_SPLIT, QUAD_STEPS>(quad, [&](auto QD) {
         constexpr bool Q = decltype(QD)::value != QUAD_NONE && decltype(NF)::value == kGroupFrames;   // instantiated for NF = 4 only
-        constexpr bool SP = Q && decltype(QD)::value == QUAD_SPLIT && quad_split_layout(L);
+        constexpr bool ST = Q && decltype(QD)::value == QUAD_STEPS && quad_split_layout(L);   // a split launch too
+        constexpr bool SP = (Q && decltype(QD)::value == QUAD_SPLIT && quad_split_layout(L)) || ST;
         FramesArgs<NF> g;
         g.c = a;
         for (int k = 0; k < NF; ++k) g.fr[k] = fr[k];
@@ -1100,12 +1221,12 @@ hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool
         const dim3 grid((unsigned)(NF == 4 ? 8 * nwx : dl ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
         if (u_kernel_channel(early, a.zero_offsets, a.umask) >= 0)
             return with_value<1, 2, 4, 8>(a.umask, [&](auto U) {
-                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF, Q, SP>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF, Q, SP, ST>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
                 return hipGetLastError();
             }, hipErrorInvalidValue);
         return with_bool(early, [&](auto E) { return with_bool(a.zero_offsets, [&](auto Z) {
             constexpr bool QG = Q && quad_instance(L, decltype(E)::value, decltype(Z)::value, 0);
-            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF, QG, QG && SP>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF, QG, QG && SP, QG && ST>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
             return hipGetLastError();
         }); });
     }, hipErrorInvalidValue); }, hipErrorInvalidValue);   // no kernel for this many frames or this mode

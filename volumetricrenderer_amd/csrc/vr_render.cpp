@@ -395,10 +395,13 @@ vr_status render_frames(void* p, const vr_target* t, int n, const vr_object_shad
     for (int k = 0; k < n; ++k) quad = quad && !fr[k].step_counter;
     // the lanes of the quad split each tap's loads where the layout has that fetch (quad_split)
     const bool split = quad && c->quad_split && quad_split_layout(f[0].pl.layout);
+    // and in such a launch each lane fetches and blends one step of four (quad_steps)
+    const bool steps = split && c->quad_steps;
     HIP_TRY(launch_march_frames(f[0].a, fr, n, f[0].pl.layout, f[0].pl.early, sc, c->pair_deal,
-                                split ? QUAD_SPLIT : quad ? QUAD_FRAMES : QUAD_NONE, hs));
+                                steps ? QUAD_STEPS : split ? QUAD_SPLIT : quad ? QUAD_FRAMES : QUAD_NONE, hs));
     c->quad_launches += quad;
     c->quad_split_launches += split;
+    c->quad_steps_launches += steps;
     c->group_launches += n == VR_MAX_GROUP;
     c->pair_launches += n / 2;   // (pairs of frames that shared a launch)
     c->renders_since_build += n - 1;   // the later renders with these lists (build_regions counted the first)
