@@ -1281,7 +1281,17 @@ vr_status vr_set_layout_preference(void* ctx, int pref);
  *                     global memory (the default; built when the seed or the
  *                     lattice range changes, at most 2^24 cells, 128 MiB);
  *                     0 = it hashes every corner.  Results are identical.
- * vr_get_option returns -1 for an unknown name.                            */
+ *   "quad_pairs"      0/1, vr_render_group of four frames of one camera on
+ *                     col48 / brick4832, where "frame_quad", "quad_split" and
+ *                     "quad_steps" (each 0/1, default 1) select the march by
+ *                     rounds of four steps: 1 (default) = the four lanes of a
+ *                     ray load each round's texels in pairs of z-slices, so
+ *                     one load instruction names fewer cache lines; 0 = every
+ *                     lane loads its own step.  Results are identical.
+ *                     Read-only: "quad_pairs_launches", such launches so far
+ *                     (they also count in "quad_steps_launches",
+ *                     "quad_split_launches" and "quad_launches").
+ * vr_get_option returns -1 for an unknown name.                           */
 vr_status vr_set_option(void* ctx, const char* name, int value);
 int       vr_get_option(void* ctx, const char* name);
 

@@ -287,6 +287,9 @@ struct Ctx {
     int quad_steps = 1;            // option "quad_steps": a split launch's lanes each fetch and blend one step of four
                                    // and exchange the terms; 0 = the split fetch by pairs
     long long quad_steps_launches = 0;   // read-only option "quad_steps_launches": those launches so far
+    int quad_pairs = 1;            // option "quad_pairs": a step-round launch issues its loads in slice pairs, a split
+                                   // launch's addresses; 0 = every lane loads its own step
+    long long quad_pairs_launches = 0;   // read-only option "quad_pairs_launches": those launches so far
     uint2* d_lat = nullptr;
     size_t lat_cap = 0;            // bytes allocated
     long long lat_key[3] = {0, 0, -1};

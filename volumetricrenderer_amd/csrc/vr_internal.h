@@ -283,8 +283,35 @@ constexpr bool quad_instance(int layout, bool early, bool zero_offsets, int umas
 // built for the layouts whose footprint slice packs into one dword, 32 bytes apart in z.
 // QUAD_STEPS (option quad_steps; march_pixel_quad_steps) is a split launch of the same layouts
 // in which each lane of the quad fetches and blends one step of four.
-enum QuadMode : int { QUAD_NONE = 0, QUAD_FRAMES = 1, QUAD_SPLIT = 2, QUAD_STEPS = 3 };
+// QUAD_PAIRS (option quad_pairs; march_pixel_quad_steps<PAIRS>) is a step-round launch whose
+// loads are issued in slice pairs (the lane maps below).
+enum QuadMode : int { QUAD_NONE = 0, QUAD_FRAMES = 1, QUAD_SPLIT = 2, QUAD_STEPS = 3, QUAD_PAIRS = 4 };
 constexpr bool quad_split_layout(int layout) { return layout == LAYOUT_COL48 || layout == LAYOUT_BRICK4832; }
+constexpr unsigned kSplitZ = 32;   // bytes between the z-slices of those layouts (vr_march_kernels.h tap_fetch's kZ)
+
+// The lane maps of the paired fetch.  A round of four steps loads a tap
+// with two b64 instructions, I = 0 (A) and 1 (B).  In instruction I quad lane fl loads z-slice
+// pair_load_slice(fl) of the round's step pair_load_step(I, fl), the step that quad lane of the
+// same number owns: one instruction names both slices of two steps, the split fetch's address
+// set.  The owner of step j then finds slice z of its step in the register of instruction
+// pair_owner_instr(j) on quad lane pair_owner_lane(j, z).  quad_perm_ctrl is the DPP control
+// with which lane k of a quad reads lane l[k].  tools/pair_check.cpp runs a quad through them.
+constexpr __host__ __device__ int pair_load_step(int instr, int fl) { return 2 * instr + (fl >> 1); }
+constexpr __host__ __device__ int pair_load_slice(int fl) { return fl & 1; }
+constexpr __host__ __device__ int pair_owner_instr(int j) { return j >> 1; }
+constexpr __host__ __device__ int pair_owner_lane(int j, int z) { return 2 * (j & 1) + z; }
+constexpr __host__ __device__ int quad_perm_ctrl(int l0, int l1, int l2, int l3) { return l0 | l1 << 2 | l2 << 4 | l3 << 6; }
+// the loaders' read of the owners' offsets for instruction I, and the owners' read of slice z
+constexpr __host__ __device__ int pair_load_ctrl(int instr)
+{
+    return quad_perm_ctrl(pair_load_step(instr, 0), pair_load_step(instr, 1), pair_load_step(instr, 2), pair_load_step(instr, 3));
+}
+constexpr __host__ __device__ int pair_owner_ctrl(int z)
+{
+    return quad_perm_ctrl(pair_owner_lane(0, z), pair_owner_lane(1, z), pair_owner_lane(2, z), pair_owner_lane(3, z));
+}
+static_assert(pair_load_ctrl(0) == 0x50 && pair_load_ctrl(1) == 0xfa, "quad_perm [0,0,1,1] and [2,2,3,3]");
+static_assert(pair_owner_ctrl(0) == 0x88 && pair_owner_ctrl(1) == 0xdd, "quad_perm [0,2,0,2] and [1,3,1,3]");
 
 // One round of march_pixel_quad_steps' accumulation: t[j] is the term of step base + j (formed
 // by quad lane j), n the ray's steps.  The terms are added in step order, each only where the
@@ -548,7 +575,7 @@ hipError_t launch_march(const MarchArgs& a, int layout, int wrap, bool early, co
 constexpr bool pair_layout(int layout) { return list_has(FrameLayouts{}, layout); }
 // quad (a QuadMode; other than QUAD_NONE for nf = 4, frames_share_camera(fr, nf) and no step
 // counter only): the kernels' QUAD instance, the four frames in the lanes of a quad
-// (vr_march_kernels.h regions_frames_body); QUAD_SPLIT and QUAD_STEPS for a quad_split_layout only
+// (vr_march_kernels.h regions_frames_body); QUAD_SPLIT, QUAD_STEPS and QUAD_PAIRS for a quad_split_layout only
 hipError_t launch_march_frames(const MarchArgs& a, const FrameArgs* fr, int nf, int layout, bool early, const Schedule& sc,
                                int deal, int quad, hipStream_t s);
 hipError_t launch_march_frames_cornerh(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc,

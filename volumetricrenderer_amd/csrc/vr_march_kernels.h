@@ -401,8 +401,6 @@ __device__ __forceinline__ unsigned quad_lane(unsigned v)
 template <int K>
 __device__ __forceinline__ float ubyte_of(unsigned v) { return (float)((v >> (8 * K)) & 0xffu); }
 
-constexpr unsigned kSplitZ = 32;   // bytes between the z-slices of COL48 / BRICK4832 (tap_fetch's kZ)
-
 // one lane's part of a step pair's fetch of one tap: its slice, and the offset whose low bits shift it
 struct SliceRaw {
     unsigned s0, s1, off;
@@ -540,8 +538,39 @@ struct StepRaw {
     unsigned s00, s01, s10, s11, off;
     float wx, wy, wz;
 };
-template <int UM, int T, bool ZO>
-__device__ __forceinline__ StepRaw step_fetch(const MarchArgs& a, const FastCtx& f, f2 pxy, float pz)
+template <int J>
+__device__ __forceinline__ float quad_lane_f(float v)
+{
+    return __builtin_bit_cast(float, quad_lane<J>(__builtin_bit_cast(unsigned, v)));
+}
+// v of the quad lanes a quad_perm control names (vr_internal.h quad_perm_ctrl)
+template <int CTRL>
+__device__ __forceinline__ unsigned quad_read(unsigned v)
+{
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+}
+// ---- the step rounds' paired fetch (option quad_pairs) ----
+// A step_fetch instruction names one z-slice of the round's four steps, up to four 128-byte
+// lines per quad; a split_fetch instruction names both slices of two steps, which are 32 bytes
+// apart and mostly share a line.  With PAIRS the round keeps its one blend per lane and takes
+// the split fetch's address pattern.  The owner side is unchanged: lane fl forms its own step's
+// coordinates, weights and offset.  The loads are dealt again (vr_internal.h pair_load_step /
+// pair_load_slice): instruction A serves steps base + 0 and base + 1, B base + 2 and base + 3,
+// and in each quad lane fl loads z-slice fl & 1 of the instruction's step fl >> 1, at the owning
+// lane's offset, read through DPP.  Per quad, tap and round these are the eight pieces the
+// lanes load without PAIRS, each once; every owner's offset is in the plane (a lane past the
+// ray's end takes the round's first point), so the descriptor and its range check are
+// tap_fetch's.  The StepRaw then holds A's dwords in s00, s01, B's in s10, s11, and in off the
+// loaded steps' off & 3: A's in bits 0-1, B's from bit 2 up.
+//
+// The round that consumes the loads shifts and packs them (pair_blend): the loader shifts its
+// slice by the loaded step's off & 3 and packs the footprint's four texels into one dword
+// (split_pack), and owner j reads slice z of its step from instruction pair_owner_instr(j),
+// quad lane pair_owner_lane(j, z), and blends with its own weights in split_blend's form -- the
+// floats tap_blend sees.  Every DPP read has an active source for the reason given above
+// march_pixel_quad_split.
+template <int UM, int T, bool ZO, bool PAIRS = false>
+__device__ __forceinline__ StepRaw step_fetch(const MarchArgs& a, const FastCtx& f, f2 pxy, float pz, int fl = 0)
 {
     if constexpr ((UM >> T) & 1) {
         return StepRaw{};
@@ -550,9 +579,19 @@ __device__ __forceinline__ StepRaw step_fetch(const MarchArgs& a, const FastCtx&
         const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[T][0], a.tap_S[T][1]}, Tt);
         const float gz = fmaf(pz, a.tap_S[T][2], ZO ? 0.5f : a.tap_T[T][2]);
         const unsigned off = f.tx[cvt_flr(gxy.x)] + f.ty[cvt_flr(gxy.y)] + f.tz[cvt_flr(gz)];
-        const auto s0 = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], off & ~3u, 0, 0);
-        const auto s1 = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], (off & ~3u) + kSplitZ, 0, 0);
-        return StepRaw{s0[0], s0[1], s1[0], s1[1], off, fract_(gxy.x), fract_(gxy.y), fract_(gz)};
+        if constexpr (PAIRS) {
+            const unsigned zoff = (unsigned)pair_load_slice(fl) * kSplitZ;
+            // the owner aligns, the loader adds its slice: one v_add_u32 with a DPP source per address
+            const unsigned al = off & ~3u;
+            const auto sa = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], quad_read<pair_load_ctrl(0)>(al) + zoff, 0, 0);
+            const auto sb = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], quad_read<pair_load_ctrl(1)>(al) + zoff, 0, 0);
+            const unsigned sh = (quad_read<pair_load_ctrl(0)>(off) & 3u) | (quad_read<pair_load_ctrl(1)>(off) << 2);
+            return StepRaw{sa[0], sa[1], sb[0], sb[1], sh, fract_(gxy.x), fract_(gxy.y), fract_(gz)};
+        } else {
+            const auto s0 = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], off & ~3u, 0, 0);
+            const auto s1 = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], (off & ~3u) + kSplitZ, 0, 0);
+            return StepRaw{s0[0], s0[1], s1[0], s1[1], off, fract_(gxy.x), fract_(gxy.y), fract_(gz)};
+        }
     }
 }
 __device__ __forceinline__ TapRaw step_tap(const StepRaw& r)
@@ -561,12 +600,23 @@ __device__ __forceinline__ TapRaw step_tap(const StepRaw& r)
                   __builtin_amdgcn_alignbyte(r.s11, r.s10, r.off), __builtin_amdgcn_alignbyte(r.s11, r.s11, r.off),
                   r.wx, r.wy, r.wz};
 }
-template <int J>
-__device__ __forceinline__ float quad_lane_f(float v)
+template <int UM, int T>
+__device__ __forceinline__ float pair_blend(const StepRaw& r, int fl, const float* uv)
 {
-    return __builtin_bit_cast(float, quad_lane<J>(__builtin_bit_cast(unsigned, v)));
+    if constexpr ((UM >> T) & 1) {
+        return uv[T];
+    } else {
+        const unsigned pa = split_pack(SliceRaw{r.s00, r.s01, r.off}), pb = split_pack(SliceRaw{r.s10, r.s11, r.off >> 2});
+        const unsigned a0 = quad_read<pair_owner_ctrl(0)>(pa), b0 = quad_read<pair_owner_ctrl(0)>(pb);
+        const unsigned a1 = quad_read<pair_owner_ctrl(1)>(pa), b1 = quad_read<pair_owner_ctrl(1)>(pb);
+        const bool second = pair_owner_instr(fl) != 0;
+        const unsigned z0 = second ? b0 : a0, z1 = second ? b1 : a1;
+        return blend(f2{ubyte_of<0>(z0), ubyte_of<0>(z1)}, f2{ubyte_of<1>(z0), ubyte_of<1>(z1)},
+                     f2{ubyte_of<2>(z0), ubyte_of<2>(z1)}, f2{ubyte_of<3>(z0), ubyte_of<3>(z1)}, r.wx, r.wy, r.wz);
+    }
 }
-template <int LAYOUT, bool EARLY, bool ZO, int UM>
+
+template <int LAYOUT, bool EARLY, bool ZO, int UM, bool PAIRS = false>
 __device__ __forceinline__ void march_pixel_quad_steps(const MarchArgs& a, const FastCtx& f, int x, int orow, int fl)
 {
     static_assert(quad_split_layout(LAYOUT), "built for the layouts of the split fetch");
@@ -586,18 +636,20 @@ __device__ __forceinline__ void march_pixel_quad_steps(const MarchArgs& a, const
         bool mine = fl < r.n;
         f2 qxy = mine ? own(axy, bxy, cxy, dxy) : axy;
         float qz = mine ? own(az, bz, cz, dz) : az;
-        StepRaw c0 = step_fetch<UM, 0, ZO>(a, f, qxy, qz), c1 = step_fetch<UM, 1, ZO>(a, f, qxy, qz);
-        StepRaw c2 = step_fetch<UM, 2, ZO>(a, f, qxy, qz), c3 = step_fetch<UM, 3, ZO>(a, f, qxy, qz);
+        StepRaw c0 = step_fetch<UM, 0, ZO, PAIRS>(a, f, qxy, qz, fl), c1 = step_fetch<UM, 1, ZO, PAIRS>(a, f, qxy, qz, fl);
+        StepRaw c2 = step_fetch<UM, 2, ZO, PAIRS>(a, f, qxy, qz, fl), c3 = step_fetch<UM, 3, ZO, PAIRS>(a, f, qxy, qz, fl);
         for (int base = 0;;) {
             const f2 exy = dxy + r.sxy, fxy = exy + r.sxy, gxy = fxy + r.sxy, hxy = gxy + r.sxy;   // steps base + 4 .. base + 7
             const float ez = dz + r.sz, fz = ez + r.sz, gz = fz + r.sz, hz = gz + r.sz;
             mine = base + 4 + fl < r.n;
             qxy = mine ? own(exy, fxy, gxy, hxy) : axy;
             qz = mine ? own(ez, fz, gz, hz) : az;
-            const StepRaw n0 = step_fetch<UM, 0, ZO>(a, f, qxy, qz), n1 = step_fetch<UM, 1, ZO>(a, f, qxy, qz);
-            const StepRaw n2 = step_fetch<UM, 2, ZO>(a, f, qxy, qz), n3 = step_fetch<UM, 3, ZO>(a, f, qxy, qz);
-            const float t0 = blend_u<UM, 0, LAYOUT>(step_tap(c0), uv), t1 = blend_u<UM, 1, LAYOUT>(step_tap(c1), uv);
-            const float t2 = blend_u<UM, 2, LAYOUT>(step_tap(c2), uv), t3 = blend_u<UM, 3, LAYOUT>(step_tap(c3), uv);
+            const StepRaw n0 = step_fetch<UM, 0, ZO, PAIRS>(a, f, qxy, qz, fl), n1 = step_fetch<UM, 1, ZO, PAIRS>(a, f, qxy, qz, fl);
+            const StepRaw n2 = step_fetch<UM, 2, ZO, PAIRS>(a, f, qxy, qz, fl), n3 = step_fetch<UM, 3, ZO, PAIRS>(a, f, qxy, qz, fl);
+            const float t0 = PAIRS ? pair_blend<UM, 0>(c0, fl, uv) : blend_u<UM, 0, LAYOUT>(step_tap(c0), uv);
+            const float t1 = PAIRS ? pair_blend<UM, 1>(c1, fl, uv) : blend_u<UM, 1, LAYOUT>(step_tap(c1), uv);
+            const float t2 = PAIRS ? pair_blend<UM, 2>(c2, fl, uv) : blend_u<UM, 2, LAYOUT>(step_tap(c2), uv);
+            const float t3 = PAIRS ? pair_blend<UM, 3>(c3, fl, uv) : blend_u<UM, 3, LAYOUT>(step_tap(c3), uv);
             const float term = ((t0 * t1) * (t2 + t3)) * a.scale;                        // :71-73
             // the look-ahead loads stay above this line: without it the compiler sinks them below the
             // loop's exit test, into the branch that goes round again, and waits for them there
@@ -841,7 +893,10 @@ __global__ __launch_bounds__(kThreads) void march_regions_u(const MarchArgs a, c
 //   SPLIT, STEPS: the same launches (option quad_steps): the quad's lanes
 //                 each fetch and blend one step of four and exchange the terms
 //                 (march_pixel_quad_steps).
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false>
+//   STEPS, PAIRS: the same launches (option quad_pairs): a round's loads are
+//                 issued in slice pairs, a split launch's addresses (march_pixel_quad_steps<PAIRS>).
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false,
+          bool PAIRS = false>
 __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, const unsigned* __restrict__ tiles,
                                                     const int* __restrict__ hdr, int nwx, int deal, unsigned* lds)
 {
@@ -849,6 +904,7 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
     static_assert(!QUAD || NF == 4, "a quad of lanes is four frames");
     static_assert(!SPLIT || QUAD, "the lanes of a quad split a fetch only where they hold one ray");
     static_assert(!STEPS || SPLIT, "the step rounds are a split launch's");
+    static_assert(!PAIRS || STEPS, "the paired fetch is the step rounds'");
     const int xcd = blockIdx.x & 7, wg = (int)(blockIdx.x >> 3);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int fr = wave, first = wg, w = wg;   // the frame, the workgroup's first entry wave, this wave's
@@ -883,7 +939,7 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
         for (int k = wg; wg < nwx && k < qcount; k += nwx) {
             const unsigned t = tiles[begin + k];
             const int tx = (int)(t & 0xffffu), ty = (int)(t >> 16);
-            if constexpr (STEPS) march_pixel_quad_steps<LAYOUT, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
+            if constexpr (STEPS) march_pixel_quad_steps<LAYOUT, EARLY, ZO, UM, PAIRS>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
             else if constexpr (SPLIT) march_pixel_quad_split<LAYOUT, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
             else (void)march_pixel<LAYOUT, WRAP, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy);
         }
@@ -907,20 +963,23 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
 // take the same floor where the tap offsets are zero (102 VGPRs without it, 96 or fewer and no
 // scratch with it); with tap offsets the floor costs 8 bytes of scratch, so those two keep 1
 // (124 VGPRs, 4 waves).
-#define VR_SPLIT_WAVES __attribute__((amdgpu_waves_per_eu(SPLIT && (!STEPS || ZO) ? 5 : 1)))
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false>
-__global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES void march_regions_frames(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
+// The paired-fetch instances follow the step rounds' but for the general early-out one, which spills
+// 40 bytes under the floor and keeps 1.
+#define VR_SPLIT_WAVES(E) __attribute__((amdgpu_waves_per_eu(SPLIT && (!STEPS || ZO) && !(PAIRS && (E)) ? 5 : 1)))
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false, bool PAIRS = false>
+__global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES(EARLY) void march_regions_frames(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
                                                                 const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF, QUAD, SPLIT, STEPS>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF, QUAD, SPLIT, STEPS, PAIRS>(g, tiles, hdr, nwx, deal, lds);
 }
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false>
-__global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES void march_regions_frames_u(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false,
+          bool PAIRS = false>
+__global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES(false) void march_regions_frames_u(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
                                                                   const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF, QUAD, SPLIT, STEPS>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF, QUAD, SPLIT, STEPS, PAIRS>(g, tiles, hdr, nwx, deal, lds);
 }
 #undef VR_SPLIT_WAVES
 
@@ -1197,17 +1256,18 @@ hipError_t launch_lw(const MarchArgs& a, bool early, const Schedule& sc, hipStre
 // workgroups, and that L is one of FrameLayouts.  XCD x runs
 // sc.map.nwx entry waves, 4 / NF to a workgroup (regions_frames_body).
 // quad (QuadMode): the QUAD instance (nf = 4 only; the caller has proved frames_share_camera), with
-// the split fetch, with the step rounds or without either -- the same grid.
+// the split fetch, with the step rounds, with the step rounds' paired fetch or without any -- the same grid.
 template <int L, int W>
 hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc, int deal, int quad,
                            hipStream_t s)
 {
     if (quad != QUAD_NONE && (nf != kGroupFrames || !quad_instance(L, early, a.zero_offsets != 0, a.umask)))
         return hipErrorInvalidValue;   // no such kernel
-    if ((quad == QUAD_SPLIT || quad == QUAD_STEPS) && !quad_split_layout(L)) return hipErrorInvalidValue;
-    return with_value<2, kGroupFrames>(nf, [&](auto NF) { return with_value<QUAD_NONE, QUAD_FRAMES, QUAD_SPLIT, QUAD_STEPS>(quad, [&](auto QD) {
+    if ((quad == QUAD_SPLIT || quad == QUAD_STEPS || quad == QUAD_PAIRS) && !quad_split_layout(L)) return hipErrorInvalidValue;
+    return with_value<2, kGroupFrames>(nf, [&](auto NF) { return with_value<QUAD_NONE, QUAD_FRAMES, QUAD_SPLIT, QUAD_STEPS, QUAD_PAIRS>(quad, [&](auto QD) {
         constexpr bool Q = decltype(QD)::value != QUAD_NONE && decltype(NF)::value == kGroupFrames;   // instantiated for NF = 4 only
-        constexpr bool ST = Q && decltype(QD)::value == QUAD_STEPS && quad_split_layout(L);   // a split launch too
+        constexpr bool PR = Q && decltype(QD)::value == QUAD_PAIRS && quad_split_layout(L);   // a step-round launch too
+        constexpr bool ST = (Q && decltype(QD)::value == QUAD_STEPS && quad_split_layout(L)) || PR;   // a split launch too
         constexpr bool SP = (Q && decltype(QD)::value == QUAD_SPLIT && quad_split_layout(L)) || ST;
         FramesArgs<NF> g;
         g.c = a;
@@ -1221,12 +1281,12 @@ hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool
         const dim3 grid((unsigned)(NF == 4 ? 8 * nwx : dl ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
         if (u_kernel_channel(early, a.zero_offsets, a.umask) >= 0)
             return with_value<1, 2, 4, 8>(a.umask, [&](auto U) {
-                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF, Q, SP, ST>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF, Q, SP, ST, PR>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
                 return hipGetLastError();
             }, hipErrorInvalidValue);
         return with_bool(early, [&](auto E) { return with_bool(a.zero_offsets, [&](auto Z) {
             constexpr bool QG = Q && quad_instance(L, decltype(E)::value, decltype(Z)::value, 0);
-            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF, QG, QG && SP, QG && ST>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF, QG, QG && SP, QG && ST, QG && PR>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
             return hipGetLastError();
         }); });
     }, hipErrorInvalidValue); }, hipErrorInvalidValue);   // no kernel for this many frames or this mode

@@ -397,11 +397,14 @@ vr_status render_frames(void* p, const vr_target* t, int n, const vr_object_shad
     const bool split = quad && c->quad_split && quad_split_layout(f[0].pl.layout);
     // and in such a launch each lane fetches and blends one step of four (quad_steps)
     const bool steps = split && c->quad_steps;
+    // whose loads, in turn, are issued in slice pairs (quad_pairs)
+    const bool pairs = steps && c->quad_pairs;
     HIP_TRY(launch_march_frames(f[0].a, fr, n, f[0].pl.layout, f[0].pl.early, sc, c->pair_deal,
-                                steps ? QUAD_STEPS : split ? QUAD_SPLIT : quad ? QUAD_FRAMES : QUAD_NONE, hs));
+                                pairs ? QUAD_PAIRS : steps ? QUAD_STEPS : split ? QUAD_SPLIT : quad ? QUAD_FRAMES : QUAD_NONE, hs));
     c->quad_launches += quad;
     c->quad_split_launches += split;
     c->quad_steps_launches += steps;
+    c->quad_pairs_launches += pairs;
     c->group_launches += n == VR_MAX_GROUP;
     c->pair_launches += n / 2;   // (pairs of frames that shared a launch)
     c->renders_since_build += n - 1;   // the later renders with these lists (build_regions counted the first)
