@@ -688,6 +688,90 @@ vr_status vr_affine_identity(vr_affine* out);
 vr_status vr_affine_place(const double forward[9], const double src_centre[3], const int32_t dst_centre[3],
                           int filter, int border, vr_affine* out);
 
+/* The flood-fill brush: the bucket fill / magic wand.
+ * Every other brush selects an ellipsoid of texels; vr_fill selects, inside
+ * that ellipsoid, the texels CONNECTED to a seed whose bytes resemble it, and
+ * applies vr_paint's brush to those only.  Integers throughout.
+ *
+ * PASSABLE.  With s_c the seed texel's byte of channel c, a texel t is
+ * passable iff, on the bytes AS THEY WERE BEFORE THE CALL,
+ *   - t is inside the brush (vr_paint's inside test, clipped to the volume),
+ *   - and for every channel c with select[c] != 0 its byte b satisfies
+ *       relative == 0:  lo[c] <= b <= hi[c]
+ *       relative == 1:  max(0, s_c - lo[c]) <= b <= min(255, s_c + hi[c]).
+ * REGION.  The passable texels reachable from the seed by steps of +-1 on one
+ * axis (6-connectivity), every texel of the path passable.  A path may not
+ * leave the ellipsoid: two parts of one blob joined only outside the brush
+ * are two regions.  If the seed itself is not passable (outside the
+ * ellipsoid, or out of range with relative == 0) the region is empty.
+ * EFFECT.  vr_paint's brush on the texels of the region only: the same weight
+ * w, a = w * strength[c], the same SET / ADD / SUB blends with brush->value.
+ * A channel with strength 0 is neither read nor written unless it is a select
+ * channel, which is read; the selected and the painted channels are
+ * independent of each other.  The region is a fixed point that does not
+ * depend on the order of processing, so the host statement and the device
+ * agree bit for bit, in the volume and in the report.
+ *
+ * REPORT (optional).  filled = the texels of the region; passable = the
+ * passable texels, connected to the seed or not; min / max = the region's
+ * inclusive bounds in volume coordinates.  The EMPTY report is filled =
+ * passable = 0, min = {nx, ny, nz}, max = {-1, -1, -1}; a region that is
+ * empty because the seed is not passable still counts `passable`, with the
+ * empty bounds.  d_report is a DEVICE vr_fill_report, 8-byte aligned, which
+ * the call overwrites on `stream`.
+ *
+ * With every strength 0 and a report the call runs and writes nothing but the
+ * report (the magic wand as a measurement); with every strength 0 and no
+ * report it launches nothing.  A brush that misses the volume, or a seed
+ * outside the brush's clipped box (vr_brush_box), is VR_OK: the report, if
+ * given, is set to the empty one and nothing else is launched.
+ *
+ * Device path: three launches and what follows an edit of the clipped box --
+ * (1) a workgroup per 8 x 8 x 8 tile of the box evaluates `passable` and
+ * labels the tile's passable texels by tile-local connected component in LDS
+ * (a union-find), writing per texel the box-linear index of its component's
+ * smallest member; (2) a thread per texel on a tile's low face whose
+ * neighbour across the face is passable too unites the two labels in global
+ * memory (agent-scope atomic loads and atomicMin only); (3) vr_paint's rows
+ * over the box: a texel whose root is the seed's root is blended, the new
+ * bytes are folded into the channels' byte ranges, the report is accumulated.
+ * No kernel waits for another workgroup and every loop is bounded by the
+ * box's texel count.  The labels (4 bytes per texel of the clipped box) live
+ * in the scratch vr_blur, vr_morph and vr_rank share: same growth rule (device
+ * synchronisation, whole MiB, VR_ERR_OOM holds nothing and leaves the volume
+ * untouched), same option "blur_scratch_kib".  Within what is held the call
+ * allocates nothing and never waits on the host, so pick -> vr_fill ->
+ * vr_update_footprint -> vr_render_rect queue on one stream.  The edited box
+ * is the brush's clipped box; a caller who reads the report back may use its
+ * tighter bounds.
+ * VR_ERR_INVALID: a null ctx, brush or rule, anything vr_paint refuses, a seed
+ * outside the volume, relative not 0 or 1, no selected channel, relative == 0
+ * with lo[c] > hi[c] on a selected channel, non-zero reserved, d_report not
+ * 8-byte aligned; VR_ERR_NO_VOLUME as for vr_paint.  A refused call has
+ * launched nothing.                                                         */
+typedef struct {              /* 32 bytes */
+    int32_t seed[3];          /* texel (x, y, z); must lie inside the volume */
+    int32_t relative;         /* 0: lo / hi are bytes; 1: distances below / above the seed's byte */
+    uint8_t lo[4], hi[4];     /* per channel R, G, B, A */
+    uint8_t select[4];        /* non-zero: the channel takes part in the test; at least one */
+    int32_t reserved;         /* must be 0 */
+} vr_fill_rule;
+typedef struct {              /* 40 bytes */
+    uint64_t filled;          /* texels of the region */
+    uint64_t passable;        /* texels of the brush that pass the test, connected to the seed or not */
+    int32_t  min[3], max[3];  /* inclusive bounds of the region; {nx, ny, nz} / {-1, -1, -1} when filled == 0 */
+} vr_fill_report;
+vr_status vr_fill(void* ctx, const vr_brush* brush, const vr_fill_rule* rule,
+                  vr_fill_report* d_report /* DEVICE, may be NULL */, void* stream);
+/* The same on a HOST RGBA8 volume (x fastest): the CPU statement, which
+ * vr_fill reproduces bit for bit -- a breadth-first search with a queue over
+ * the passable mask of the clipped box, taken before any byte is written.
+ * Pure host code.  VR_ERR_INVALID as above (no alignment is asked), and for a
+ * null rgba8 or a non-positive dimension; a refused call leaves the array and
+ * *report as they were.                                                     */
+vr_status vr_brush_fill_apply(const vr_brush* brush, const vr_fill_rule* rule, uint8_t* rgba8,
+                              int nx, int ny, int nz, vr_fill_report* report /* HOST, may be NULL */);
+
 /* The read side of the brush: what is in the volume under it (DESIGN.md sec.
  * 5.2.8) -- the eyedropper, a histogram panel, and the answer to "has this
  * channel become constant again?".  Everything is an integer sum, so the

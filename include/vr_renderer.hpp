@@ -84,6 +84,15 @@ inline void BrushRankApply(const vr_brush& brush, int rank, int half_width, uint
     Check(vr_brush_rank_apply(&brush, rank, half_width, rgba, nx, ny, nz), "vr_brush_rank_apply");
 }
 
+// The flood-fill brush on a host RGBA8 volume (vr_brush_fill_apply): the CPU
+// statement of Renderer::Fill; *report (optional) receives what it found.
+// Host code only.
+inline void BrushFillApply(const vr_brush& brush, const vr_fill_rule& rule, uint8_t* rgba, int nx, int ny, int nz,
+                           vr_fill_report* report = nullptr)
+{
+    Check(vr_brush_fill_apply(&brush, &rule, rgba, nx, ny, nz, report), "vr_brush_fill_apply");
+}
+
 // The clone brush on a host RGBA8 volume (vr_brush_clone_apply): the CPU
 // statement of Renderer::Clone.  Host code only.
 inline void BrushCloneApply(const vr_brush& brush, const vr_clone_map& map, uint8_t* rgba, int nx, int ny, int nz)
@@ -216,6 +225,17 @@ public:
     void Rank(const vr_brush& brush, int rank = VR_RANK_MEDIAN, int half_width = 1, void* stream = nullptr)
     {
         Check(vr_rank(ctx_, &brush, rank, half_width, stream), "vr_rank");
+    }
+    // Bucket fill / magic wand (vr_fill): the brush blended, as Paint blends
+    // it, into the texels under it that pass `rule` and are connected to
+    // rule.seed by axis steps over such texels inside the ellipsoid.
+    // d_report (optional): a DEVICE vr_fill_report, 8-byte aligned, that
+    // receives the region's size and bounds; with every strength 0 the call
+    // only measures.  Queued on `stream` as Blur is; the labels (4 bytes per
+    // texel of the clipped box) live in the same scratch.
+    void Fill(const vr_brush& brush, const vr_fill_rule& rule, vr_fill_report* d_report = nullptr, void* stream = nullptr)
+    {
+        Check(vr_fill(ctx_, &brush, &rule, d_report, stream), "vr_fill");
     }
     // Paint under the brush with the volume's own texels from elsewhere
     // (vr_clone): the value of texel t is the texel at t + map.offset (per

@@ -1,0 +1,373 @@
+// fill_check -- stand-alone host check of vr_brush_fill_apply
+// (volumetricrenderer_amd/csrc/vr_brush.cpp) and of the tiled labelling of
+// vr_fill's device path (volumetricrenderer_amd/csrc/vr_fill.h), built with
+// -fsanitize=address,undefined and run on the CPU (`make check-fill` builds
+// and runs it).  It links the brush's translation unit only: no libvr.so, no
+// HIP, no device.
+//
+// Three statements of one fill are compared, bytes and report:
+//   1. vr_brush_fill_apply, the library's breadth-first search;
+//   2. a naive restatement of vr.h that shares nothing with it: the ellipsoid
+//      in unsigned __int128, the region by repeated sweeps over the whole
+//      volume until nothing changes, no queue;
+//   3. the device path's sequence run on the CPU with the templates of
+//      vr_fill.h over plain arrays: label every 8 x 8 x 8 tile of the clipped
+//      box (tile_init / tile_link / tile_root), merge across the tiles' faces
+//      (merge_texel) -- in ascending, descending and shuffled texel order, the
+//      fixed point must not depend on it -- then commit where find(texel) ==
+//      find(seed).
+// Every volume is allocated exactly, so a read or write outside it trips the
+// address sanitizer.  The volumes: two interleaved corridors between walls one
+// above the range, thresholded smooth fields with several blobs, noise with
+// few distinct bytes, a fully passable box; extents that cut the 8-tiles on
+// every axis (and 1 x 1 x 1, 9 x 1 x 17); centres at the ends of int32; random
+// rules, relative and absolute, one to four selected channels; seeds inside
+// and outside the ellipsoid and the box.  Then every refusal.
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <random>
+#include <vector>
+
+#include "vr.h"
+#include "../volumetricrenderer_amd/csrc/vr_fill.h"
+
+namespace {
+
+typedef unsigned __int128 u128;
+
+struct Vol {
+    int nx, ny, nz;
+    std::vector<uint8_t> v;
+    size_t at(int x, int y, int z) const { return (((size_t)z * ny + y) * nx + x) * 4; }
+};
+
+bool same(const vr_fill_report& a, const vr_fill_report& b)
+{
+    return a.filled == b.filled && a.passable == b.passable && !std::memcmp(a.min, b.min, sizeof a.min) &&
+           !std::memcmp(a.max, b.max, sizeof a.max);
+}
+
+// include/vr.h, literally
+struct Naive {
+    std::vector<uint8_t> inside, pass, region;
+    std::vector<unsigned> weight;
+};
+
+Naive masks(const vr_brush& b, const vr_fill_rule& r, const Vol& vol)
+{
+    const size_t n = (size_t)vol.nx * vol.ny * vol.nz;
+    Naive m{std::vector<uint8_t>(n, 0), std::vector<uint8_t>(n, 0), std::vector<uint8_t>(n, 0), std::vector<unsigned>(n, 0u)};
+    u128 D2[3];
+    for (int a = 0; a < 3; ++a) D2[a] = (u128)(2 * b.radius[a] + 1) * (u128)(2 * b.radius[a] + 1);
+    const u128 S = D2[0] * D2[1] * D2[2];
+    const uint8_t* seed = &vol.v[vol.at(r.seed[0], r.seed[1], r.seed[2])];
+    for (int z = 0; z < vol.nz; ++z)
+        for (int y = 0; y < vol.ny; ++y)
+            for (int x = 0; x < vol.nx; ++x) {
+                const long long d[3] = {(long long)x - b.centre[0], (long long)y - b.centre[1], (long long)z - b.centre[2]};
+                bool in = true;
+                for (int a = 0; a < 3; ++a) in = in && d[a] >= -(long long)b.radius[a] && d[a] <= (long long)b.radius[a];
+                if (!in) continue;
+                const u128 Q = (u128)(4 * d[0] * d[0]) * D2[1] * D2[2] + (u128)(4 * d[1] * d[1]) * D2[0] * D2[2] +
+                               (u128)(4 * d[2] * d[2]) * D2[0] * D2[1];
+                if (Q > S) continue;
+                const size_t i = vol.at(x, y, z) / 4;
+                m.inside[i] = 1;
+                m.weight[i] = b.falloff ? 256u - (unsigned)((256 * Q) / (S + 1)) : 256u;
+                bool ok = true;
+                for (int c = 0; c < 4; ++c) {
+                    if (!r.select[c]) continue;
+                    const int v = vol.v[4 * i + c];
+                    const int lo = r.relative ? std::max(0, (int)seed[c] - (int)r.lo[c]) : (int)r.lo[c];
+                    const int hi = r.relative ? std::min(255, (int)seed[c] + (int)r.hi[c]) : (int)r.hi[c];
+                    ok = ok && lo <= v && v <= hi;
+                }
+                m.pass[i] = ok;
+            }
+    return m;
+}
+
+bool seed_in_box(const vr_brush& b, const vr_fill_rule& r, const Vol& vol)
+{
+    const int n[3] = {vol.nx, vol.ny, vol.nz};
+    for (int a = 0; a < 3; ++a) {
+        const long long lo = std::max(0ll, (long long)b.centre[a] - b.radius[a]), hi = std::min((long long)n[a] - 1, (long long)b.centre[a] + b.radius[a]);
+        if (r.seed[a] < lo || r.seed[a] > hi) return false;
+    }
+    return true;
+}
+
+void blend_region(const vr_brush& b, const Naive& m, Vol& vol)
+{
+    for (size_t i = 0; i < m.region.size(); ++i) {
+        if (!m.region[i]) continue;
+        for (int c = 0; c < 4; ++c) {
+            if (!b.strength[c]) continue;
+            const long long a = (long long)m.weight[i] * b.strength[c], old = vol.v[4 * i + c], val = b.value[c];
+            const long long d = (val * a + 32640) / 65280;
+            long long nw;
+            if (b.op == VR_BRUSH_SET) nw = (old * (65280 - a) + val * a + 32640) / 65280;
+            else if (b.op == VR_BRUSH_ADD) nw = std::min(255ll, old + d);
+            else nw = std::max(0ll, old - d);
+            vol.v[4 * i + c] = (uint8_t)nw;
+        }
+    }
+}
+
+vr_fill_report report_of(const Naive& m, const Vol& vol)
+{
+    vr_fill_report rep{};
+    rep.min[0] = vol.nx; rep.min[1] = vol.ny; rep.min[2] = vol.nz;
+    rep.max[0] = rep.max[1] = rep.max[2] = -1;
+    for (int z = 0; z < vol.nz; ++z)
+        for (int y = 0; y < vol.ny; ++y)
+            for (int x = 0; x < vol.nx; ++x) {
+                const size_t i = vol.at(x, y, z) / 4;
+                rep.passable += m.pass[i];
+                if (!m.region[i]) continue;
+                ++rep.filled;
+                const int p[3] = {x, y, z};
+                for (int a = 0; a < 3; ++a) { rep.min[a] = std::min(rep.min[a], p[a]); rep.max[a] = std::max(rep.max[a], p[a]); }
+            }
+    return rep;
+}
+
+// 2. the restatement: sweeps until nothing changes
+vr_fill_report restate(const vr_brush& b, const vr_fill_rule& r, Vol& vol)
+{
+    if (!seed_in_box(b, r, vol)) {
+        Naive none{{}, std::vector<uint8_t>((size_t)vol.nx * vol.ny * vol.nz, 0), std::vector<uint8_t>((size_t)vol.nx * vol.ny * vol.nz, 0), {}};
+        return report_of(none, vol);
+    }
+    Naive m = masks(b, r, vol);
+    const size_t s = vol.at(r.seed[0], r.seed[1], r.seed[2]) / 4;
+    m.region[s] = m.pass[s];
+    for (bool changed = true; changed;) {
+        changed = false;
+        for (int z = 0; z < vol.nz; ++z)
+            for (int y = 0; y < vol.ny; ++y)
+                for (int x = 0; x < vol.nx; ++x) {
+                    const size_t i = vol.at(x, y, z) / 4;
+                    if (!m.pass[i] || m.region[i]) continue;
+                    const bool reach = (x > 0 && m.region[i - 1]) || (x + 1 < vol.nx && m.region[i + 1]) ||
+                                       (y > 0 && m.region[i - vol.nx]) || (y + 1 < vol.ny && m.region[i + vol.nx]) ||
+                                       (z > 0 && m.region[i - (size_t)vol.nx * vol.ny]) ||
+                                       (z + 1 < vol.nz && m.region[i + (size_t)vol.nx * vol.ny]);
+                    if (reach) { m.region[i] = 1; changed = true; }
+                }
+    }
+    const vr_fill_report rep = report_of(m, vol);
+    blend_region(b, m, vol);
+    return rep;
+}
+
+// 3. the device path's sequence on the CPU
+struct Plain {
+    uint32_t* l;
+    uint32_t load(uint32_t i) { return l[i]; }
+    void store(uint32_t i, uint32_t v) { l[i] = v; }
+    uint32_t fetch_min(uint32_t i, uint32_t v) { const uint32_t old = l[i]; if (v < old) l[i] = v; return old; }
+};
+
+bool invariant_ok = true;
+
+vr_fill_report tiled(const vr_brush& b, const vr_fill_rule& r, Vol& vol, int order, std::mt19937_64& rng)
+{
+    using namespace vr::fill;
+    vr_fill_report rep;
+    empty_report(&rep, vol.nx, vol.ny, vol.nz);
+    int o[3], e[3];
+    if (!vr::brush::clip(&b, vol.nx, vol.ny, vol.nz, o, e) || !seed_in_box(b, r, vol)) return rep;
+    const vr::brush::Terms t = vr::brush::terms(b.radius);
+    const uint32_t total = (uint32_t)e[0] * (uint32_t)e[1] * (uint32_t)e[2];
+    std::vector<uint32_t> labels(total, 0x12345678u);   // whatever the last call left
+    unsigned seed[4];
+    for (int c = 0; c < 4; ++c) seed[c] = vol.v[vol.at(r.seed[0], r.seed[1], r.seed[2]) + c];
+    auto q_of = [&](int x, int y, int z) {
+        return vr::brush::axis_term(o[0] + x - b.centre[0], t.k[0]) + vr::brush::axis_term(o[1] + y - b.centre[1], t.k[1]) +
+               vr::brush::axis_term(o[2] + z - b.centre[2], t.k[2]);
+    };
+    auto box_at = [&](int x, int y, int z) { return ((uint32_t)z * e[1] + y) * e[0] + x; };
+    // launch 1: a tile at a time
+    for (int tz = 0; tz < e[2]; tz += kTile)
+        for (int ty = 0; ty < e[1]; ty += kTile)
+            for (int tx = 0; tx < e[0]; tx += kTile) {
+                uint32_t lds[kTileTexels];
+                Plain lab{lds};
+                auto pos = [&](uint32_t k, int& x, int& y, int& z) {
+                    x = tx + (int)(k % kTile); y = ty + (int)(k / kTile % kTile); z = tz + (int)(k / (kTile * kTile));
+                    return x < e[0] && y < e[1] && z < e[2];
+                };
+                for (uint32_t k = 0; k < (uint32_t)kTileTexels; ++k) {
+                    int x, y, z;
+                    const bool in_box = pos(k, x, y, z);
+                    const uint8_t* p = in_box ? &vol.v[vol.at(o[0] + x, o[1] + y, o[2] + z)] : nullptr;
+                    tile_init(lab, k, passable(r, seed, in_box && q_of(x, y, z) <= t.s, [&](int c) -> unsigned { return p[c]; }));
+                }
+                for (uint32_t k = 0; k < (uint32_t)kTileTexels; ++k) tile_link(lab, k);
+                for (uint32_t k = 0; k < (uint32_t)kTileTexels; ++k) {
+                    int x, y, z;
+                    if (!pos(k, x, y, z)) continue;
+                    const uint32_t root = tile_root(lab, k);
+                    int rx, ry, rz;
+                    if (root != kNone) pos(root, rx, ry, rz);
+                    labels[box_at(x, y, z)] = root == kNone ? kNone : box_at(rx, ry, rz);
+                }
+            }
+    for (uint32_t i = 0; i < total; ++i) invariant_ok = invariant_ok && (labels[i] == kNone || labels[i] <= i);
+    // launch 2: a texel at a time, in the order asked for
+    std::vector<uint32_t> seq(total);
+    for (uint32_t i = 0; i < total; ++i) seq[i] = order == 1 ? total - 1 - i : i;
+    if (order == 2) std::shuffle(seq.begin(), seq.end(), rng);
+    Plain lab{labels.data()};
+    for (uint32_t i : seq) merge_texel(lab, e, (int)(i % e[0]), (int)(i / e[0] % e[1]), (int)(i / e[0] / e[1]));
+    for (uint32_t i = 0; i < total; ++i) invariant_ok = invariant_ok && (labels[i] == kNone || labels[i] <= i);
+    // launch 3
+    const uint32_t seed_at = box_at(r.seed[0] - o[0], r.seed[1] - o[1], r.seed[2] - o[2]);
+    const uint32_t seed_root = labels[seed_at] == kNone ? kNone : find(lab, seed_at, total);
+    for (int z = 0; z < e[2]; ++z)
+        for (int y = 0; y < e[1]; ++y)
+            for (int x = 0; x < e[0]; ++x) {
+                const uint32_t i = box_at(x, y, z);
+                const uint64_t q = q_of(x, y, z);
+                if (q > t.s || labels[i] == kNone) continue;
+                ++rep.passable;
+                if (find(lab, i, total) != seed_root) continue;
+                ++rep.filled;
+                const int p[3] = {o[0] + x, o[1] + y, o[2] + z};
+                for (int a = 0; a < 3; ++a) { rep.min[a] = std::min(rep.min[a], p[a]); rep.max[a] = std::max(rep.max[a], p[a]); }
+                const unsigned w = vr::brush::weight(q, t.s, b.falloff);
+                uint8_t* d = &vol.v[vol.at(p[0], p[1], p[2])];
+                for (int c = 0; c < 4; ++c)
+                    if (b.strength[c]) d[c] = (uint8_t)vr::brush::blend(b.op, d[c], b.value[c], w * b.strength[c]);
+            }
+    return rep;
+}
+
+long failures = 0;
+
+void expect(bool ok, const char* what, int it)
+{
+    if (!ok && ++failures <= 10) std::fprintf(stderr, "fill_check: %s (case %d)\n", what, it);
+}
+
+}  // namespace
+
+int main()
+{
+    std::mt19937_64 rng(20241021);
+    auto pick = [&](int a, int b) { return std::uniform_int_distribution<int>(a, b)(rng); };
+    long applied = 0, filled = 0, partial = 0, empty = 0, refused = 0;
+    const int far[] = {INT32_MAX, INT32_MIN, INT32_MAX - 255, INT32_MIN + 255};
+    for (int it = 0; it < 900; ++it) {
+        const int kind = it % 6;
+        Vol vol{pick(1, 29), pick(1, 21), pick(1, 27), {}};
+        if (kind == 1 && it % 12 == 1) { vol.nx = vol.ny = vol.nz = 1; }
+        if (kind == 1 && it % 12 == 7) { vol.nx = 9; vol.ny = 1; vol.nz = 17; }
+        if (kind == 0) { vol.nx = pick(17, 29); vol.ny = pick(9, 21); vol.nz = pick(9, 27); }   // the corridors: more than a tile
+        vol.v.resize((size_t)vol.nx * vol.ny * vol.nz * 4);
+        for (size_t i = 0; i < vol.v.size(); ++i) {
+            const int c = (int)(i % 4);
+            const int x = (int)(i / 4 % vol.nx), y = (int)(i / 4 / vol.nx % vol.ny), z = (int)(i / 4 / vol.nx / vol.ny);
+            switch (kind) {
+            case 0: {   // corridors along x on rows (y, z) both even, joined at alternating ends; walls one above the range
+                const bool row = y % 2 == 0 && z % 2 == 0;
+                const bool link = z % 2 == 0 && y % 2 == 1 && x == (y / 2 % 2 ? 0 : vol.nx - 1) && y / 2 % 3 != 2;
+                const bool up = y == 0 && z % 2 == 1 && x == 3 * (z / 2 % 2);
+                vol.v[i] = c == 0 ? (row || link || up ? (uint8_t)(100 + (7 * x + 3 * y + z) % 41) : 141) : (uint8_t)pick(0, 255);
+                break;
+            }
+            case 1: case 2: {   // blobs
+                const int f = (x * x * 3 + y * y * 5 + z * z * 7 + x * y) % 97;
+                vol.v[i] = c == 0 ? (uint8_t)(f * 2 + pick(0, 3)) : c == 1 ? (uint8_t)(200 - f) : (uint8_t)pick(0, 255);
+                break;
+            }
+            case 3: vol.v[i] = (uint8_t)(pick(0, 3) * 60); break;   // noise with four bytes
+            case 4: vol.v[i] = (uint8_t)(c == 0 ? 77 : pick(0, 255)); break;   // fully passable on R
+            default: vol.v[i] = (uint8_t)pick(0, 255); break;
+            }
+        }
+        const int n[3] = {vol.nx, vol.ny, vol.nz};
+        vr_brush b{};
+        vr_fill_rule r{};
+        for (int a = 0; a < 3; ++a) {
+            b.centre[a] = pick(-2, n[a] + 1);
+            b.radius[a] = it % 5 == 0 ? VR_BRUSH_MAX_RADIUS : pick(0, 24);
+            r.seed[a] = pick(0, n[a] - 1);
+        }
+        if (it % 7 == 3)   // the seed near the centre: more often inside
+            for (int a = 0; a < 3; ++a) r.seed[a] = std::min(n[a] - 1, std::max(0, b.centre[a] + pick(-1, 1)));
+        if (it % 41 == 5) { const int a = pick(0, 2); b.centre[a] = far[pick(0, 3)]; b.radius[a] = 255; }
+        b.op = pick(0, 2);
+        b.falloff = pick(0, 1);
+        for (int c = 0; c < 4; ++c) { b.value[c] = (uint8_t)pick(0, 255); b.strength[c] = (uint8_t)(pick(0, 3) ? pick(0, 255) : pick(0, 1) * 255); }
+        r.relative = pick(0, 1);
+        r.select[0] = 1;
+        if (kind == 0) {
+            const int s = vol.v[vol.at(r.seed[0], r.seed[1], r.seed[2])];
+            if (r.relative && s >= 100 && s <= 140) { r.lo[0] = (uint8_t)(s - 100); r.hi[0] = (uint8_t)(140 - s); }
+            else { r.relative = 0; r.lo[0] = 100; r.hi[0] = 140; }
+        } else {
+            for (int c = 0; c < 4; ++c) {
+                r.select[c] = c == 0 || pick(0, 3) == 0;
+                const int a = pick(0, 255), d = pick(0, 255);
+                r.lo[c] = (uint8_t)(r.relative ? pick(0, 120) : std::min(a, d));
+                r.hi[c] = (uint8_t)(r.relative ? pick(0, 120) : std::max(a, d));
+            }
+        }
+        const Vol before = vol;
+        Vol want = vol, lib = vol;
+        const vr_fill_report want_rep = restate(b, r, want);
+        vr_fill_report lib_rep;
+        std::memset(&lib_rep, 0x5A, sizeof lib_rep);
+        expect(vr_brush_fill_apply(&b, &r, lib.v.data(), vol.nx, vol.ny, vol.nz, &lib_rep) == VR_OK, "vr_brush_fill_apply refused a valid call", it);
+        expect(lib.v == want.v, "vr_brush_fill_apply differs from the restatement", it);
+        expect(same(lib_rep, want_rep), "vr_brush_fill_apply's report differs from the restatement's", it);
+        for (int order = 0; order < 3; ++order) {
+            Vol dev = before;
+            const vr_fill_report dev_rep = tiled(b, r, dev, order, rng);
+            expect(dev.v == want.v, "the tiled sequence differs from the restatement", it);
+            expect(same(dev_rep, want_rep), "the tiled sequence's report differs from the restatement's", it);
+        }
+        Vol none = before;   // without a report
+        expect(vr_brush_fill_apply(&b, &r, none.v.data(), vol.nx, vol.ny, vol.nz, nullptr) == VR_OK && none.v == want.v, "no report, other bytes", it);
+        ++applied;
+        filled += want_rep.filled != 0;
+        partial += want_rep.filled != 0 && want_rep.filled < want_rep.passable;
+        empty += want_rep.filled == 0;
+        // refusals: nothing written
+        vr_brush bad_b = b;
+        vr_fill_rule bad_r = r;
+        switch (it % 10) {
+        case 0: bad_r.relative = 2; break;
+        case 1: bad_r.relative = -1; break;
+        case 2: std::memset(bad_r.select, 0, 4); break;
+        case 3: bad_r.relative = 0; bad_r.select[2] = 1; bad_r.lo[2] = 9; bad_r.hi[2] = 8; break;
+        case 4: bad_r.reserved = 1; break;
+        case 5: bad_r.seed[it % 3] = n[it % 3]; break;
+        case 6: bad_r.seed[it % 3] = -1; break;
+        case 7: bad_b.op = 3; break;
+        case 8: bad_b.radius[it % 3] = 256; break;
+        default: bad_b.reserved[it % 2] = 1; break;
+        }
+        Vol keep = lib;
+        vr_fill_report rep_keep = lib_rep;
+        expect(vr_brush_fill_apply(&bad_b, &bad_r, lib.v.data(), vol.nx, vol.ny, vol.nz, &lib_rep) == VR_ERR_INVALID && lib.v == keep.v &&
+                   same(lib_rep, rep_keep), "a bad call was applied", it);
+        expect(vr_brush_fill_apply(&b, &r, lib.v.data(), it % 2 ? 0 : vol.nx, vol.ny, it % 2 ? vol.nz : -1, &lib_rep) == VR_ERR_INVALID &&
+                   lib.v == keep.v, "bad dimensions were accepted", it);
+        expect(vr_brush_fill_apply(nullptr, &r, lib.v.data(), vol.nx, vol.ny, vol.nz, nullptr) == VR_ERR_INVALID &&
+                   vr_brush_fill_apply(&b, nullptr, lib.v.data(), vol.nx, vol.ny, vol.nz, nullptr) == VR_ERR_INVALID &&
+                   vr_brush_fill_apply(&b, &r, nullptr, vol.nx, vol.ny, vol.nz, nullptr) == VR_ERR_INVALID,
+               "a null pointer was accepted", it);
+        refused += 5;
+    }
+    expect(invariant_ok, "a label above its own index", 0);
+    expect(filled > 300 && partial > 100 && empty > 100, "too few cases filled, filled a part, or filled nothing", (int)filled);
+    std::printf("fill_check: %ld applied (%ld filled, %ld a part of what passes, %ld nothing), %ld refused, %ld failures\n", applied,
+                filled, partial, empty, refused, failures);
+    return failures ? 1 : 0;
+}

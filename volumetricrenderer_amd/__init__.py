@@ -15,6 +15,8 @@ from ._lib import MORPH_DILATE, MORPH_ERODE, MORPH_MAX_HALF  # noqa: F401
 from .renderer import brush_morph_apply  # noqa: F401
 from ._lib import RANK_MAX_HALF, RANK_MEDIAN  # noqa: F401
 from .renderer import brush_rank_apply  # noqa: F401
+from ._lib import FILL_REPORT_BYTES, FillReport, FillRule  # noqa: F401
+from .renderer import Fill, brush_fill_apply, make_fill_rule, unpack_fill_report  # noqa: F401
 from ._lib import CloneMap  # noqa: F401
 from .renderer import brush_clone_apply, brush_stamp_apply, make_clone_map, stamp_box  # noqa: F401
 from ._lib import AFFINE_MAX_COEFF, AFFINE_ONE, BORDER_CLAMP, BORDER_SKIP, FILTER_LINEAR, FILTER_NEAREST, Affine  # noqa: F401
@@ -37,6 +39,7 @@ __all__ = [
     "brush_line", "coalesce_boxes", "VR_MAX_DABS", "Box", "brush_blur_apply", "BLUR_MAX_HALF",
     "brush_morph_apply", "MORPH_ERODE", "MORPH_DILATE", "MORPH_MAX_HALF",
     "brush_rank_apply", "RANK_MEDIAN", "RANK_MAX_HALF",
+    "FillRule", "FillReport", "FILL_REPORT_BYTES", "Fill", "make_fill_rule", "brush_fill_apply", "unpack_fill_report",
     "CloneMap", "make_clone_map", "brush_clone_apply", "brush_stamp_apply", "stamp_box",
     "Affine", "FILTER_NEAREST", "FILTER_LINEAR", "BORDER_CLAMP", "BORDER_SKIP", "AFFINE_ONE", "AFFINE_MAX_COEFF",
     "make_affine", "affine_identity", "affine_place", "affine_direct", "brush_stamp_affine_apply",

@@ -132,6 +132,21 @@ RANK_MEDIAN = -1                            # vr.h VR_RANK_MEDIAN: the middle ra
 RANK_MAX_HALF = 3                           # vr.h VR_RANK_MAX_HALF: the widest cube of vr_rank (7 texels)
 
 
+class FillRule(ctypes.Structure):
+    """vr_fill_rule: the seed and the per-channel test of vr_fill.  32 bytes."""
+    _fields_ = [("seed", ctypes.c_int32 * 3), ("relative", ctypes.c_int32), ("lo", ctypes.c_uint8 * 4),
+                ("hi", ctypes.c_uint8 * 4), ("select", ctypes.c_uint8 * 4), ("reserved", ctypes.c_int32)]
+
+
+class FillReport(ctypes.Structure):
+    """vr_fill_report: what vr_fill found -- the region's size and bounds, and the passable texels.  40 bytes."""
+    _fields_ = [("filled", ctypes.c_uint64), ("passable", ctypes.c_uint64), ("min", ctypes.c_int32 * 3),
+                ("max", ctypes.c_int32 * 3)]
+
+
+FILL_REPORT_BYTES = ctypes.sizeof(FillReport)   # 40
+
+
 class Box(ctypes.Structure):
     """vr_box: a texel box (vr_boxes_coalesce).  24 bytes."""
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("z", ctypes.c_int32), ("bx", ctypes.c_int32),
@@ -241,6 +256,9 @@ _SIGS = {
     "vr_rank": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, _vp]),
     "vr_brush_rank_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int]),
+    "vr_fill": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.POINTER(FillRule), _vp, _vp]),
+    "vr_brush_fill_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(FillRule), _vp, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.POINTER(FillReport)]),
     "vr_brush_stats": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, _vp]),
     "vr_box_stats": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp, _vp]),
     "vr_brush_stats_host": (ctypes.c_int, [ctypes.POINTER(Brush), _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,

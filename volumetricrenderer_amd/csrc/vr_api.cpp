@@ -19,6 +19,7 @@
 #include "vr_clone.h"
 #include "vr_ctx.h"
 #include "vr_morph.h"
+#include "vr_fill.h"
 #include "vr_rank.h"
 #include "vr_remap.h"
 #include "vr_stats.h"
@@ -850,6 +851,44 @@ try {
     });
 } catch (...) {
     return caught_exception("vr_rank");
+}
+
+// The flood-fill brush on the device: every check first (a refused call has launched nothing), then the labels in
+// the family's scratch (4 bytes per texel of the clipped box; same growth rule, same option), the three launches of
+// vr_fill.hip and what follows an edit of the clipped box.  A brush that misses the volume and a seed outside the
+// clipped box give the empty report and nothing else; with every strength 0 the call is a measurement: it runs for
+// the report alone, and without one it launches nothing.
+vr_status vr_fill(void* p, const vr_brush* b, const vr_fill_rule* rule, vr_fill_report* d_report, void* stream)
+try {
+    if (!p || !b || !rule) return fail(VR_ERR_INVALID, "vr_fill: null argument");
+    if (const char* why = vr::fill::invalid(b, rule)) return fail(VR_ERR_INVALID, "vr_fill: %s", why);
+    if ((reinterpret_cast<uintptr_t>(d_report) & 7u) != 0u) return fail(VR_ERR_INVALID, "vr_fill: d_report is not 8-byte aligned");
+    Ctx* c = as_ctx(p);
+    if (vr_status st = check_target("vr_fill", c)) return st;
+    if (const char* why = vr::fill::invalid_seed(rule, c->nx, c->ny, c->nz)) return fail(VR_ERR_INVALID, "vr_fill: %s", why);
+    FillArgs a{};
+    a.rule = *rule;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    bool reached = vr::brush::clip(b, c->nx, c->ny, c->nz, a.p.o, a.p.e);
+    for (int ax = 0; ax < 3; ++ax) reached = reached && rule->seed[ax] >= a.p.o[ax] && rule->seed[ax] - a.p.o[ax] < a.p.e[ax];
+    if (!reached) {   // the brush misses the volume, or the seed lies outside its clipped box: the region is empty
+        if (!d_report) return VR_OK;
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(launch_fill_empty_report(c->nx, c->ny, c->nz, d_report, s));
+        return VR_OK;
+    }
+    const bool paints = source_brush_args(c, b, a.p);
+    if (!paints && !d_report) return VR_OK;   // nothing to write and nobody to tell
+    if (vr_status st = ensure_blur(c, fill_label_bytes(a.p))) return st;
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t* labels = reinterpret_cast<uint32_t*>(c->d_blur);
+    HIP_TRY(launch_fill_label(a, c->d_planar, labels, d_report, s));
+    HIP_TRY(launch_fill_merge(a, labels, s));
+    HIP_TRY(launch_fill_commit(a, labels, c->d_planar, c->d_mm, d_report, s));
+    if (!paints) return VR_OK;                // a measurement: no byte was written
+    return box_edited(c, a.p.o[0], a.p.o[1], a.p.o[2], a.p.e[0], a.p.e[1], a.p.e[2], s);
+} catch (...) {
+    return caught_exception("vr_fill");
 }
 
 // The clone brush on the device: every check first, then the host picks the path in integers (vr_clone.h direct).

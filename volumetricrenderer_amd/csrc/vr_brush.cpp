@@ -16,7 +16,9 @@
 // checks and the entries of a table are vr_remap.h's); vr_brush_stamp_affine_apply,
 // vr_brush_clone_affine_apply, vr_affine_direct, vr_affine_identity and
 // vr_affine_place: the transform paste on the host and its map builders
-// (sec. 5.2.13; the checks, the positions and the filters are vr_affine.h's).
+// (sec. 5.2.13; the checks, the positions and the filters are vr_affine.h's);
+// vr_brush_fill_apply: the flood-fill brush of vr_fill on the host (sec.
+// 5.2.14; the checks and the passable test are vr_fill.h's).
 //
 // Pure host code in integers: no context, no device, no HIP call.  The
 // arithmetic is vr_brush.h's, which the paint kernel (vr_paint.hip) includes
@@ -35,6 +37,7 @@
 #include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_clone.h"
+#include "vr_fill.h"
 #include "vr_morph.h"
 #include "vr_rank.h"
 #include "vr_remap.h"
@@ -554,6 +557,76 @@ vr_status vr_brush_rank_apply(const vr_brush* b, int rank, int half_width, uint8
             return below;
         });
     });
+}
+
+// The flood-fill brush on the host (include/vr.h): the passable mask of the clipped box from the bytes BEFORE the
+// call, a breadth-first search with a queue from the seed over that mask (6-connectivity; a path never leaves the
+// box's inside texels), then vr_brush_apply's blend on the texels it reached.  *report (optional) as vr_fill leaves
+// it; a brush that misses the volume and a seed outside the clipped box give the empty one.
+vr_status vr_brush_fill_apply(const vr_brush* b, const vr_fill_rule* rule, uint8_t* rgba8, int nx, int ny, int nz,
+                              vr_fill_report* report)
+{
+    if (vr_status st = check("vr_brush_fill_apply", b && rule && rgba8, [&] { return vr::fill::invalid(b, rule); }, nx, ny, nz))
+        return st;
+    if (const char* why = vr::fill::invalid_seed(rule, nx, ny, nz)) return fail(VR_ERR_INVALID, "vr_brush_fill_apply: %s", why);
+    vr_fill_report rep;
+    vr::fill::empty_report(&rep, nx, ny, nz);
+    int o[3], e[3];
+    bool reached = vr::brush::clip(b, nx, ny, nz, o, e);
+    for (int a = 0; a < 3; ++a) reached = reached && rule->seed[a] >= o[a] && rule->seed[a] - o[a] < e[a];
+    if (!reached) {
+        if (report) *report = rep;
+        return VR_OK;
+    }
+    const auto texel = [&](int x, int y, int z) { return rgba8 + ((((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx) + (size_t)x) * 4; };
+    const auto at = [&](int x, int y, int z) { return ((size_t)(z - o[2]) * (size_t)e[1] + (size_t)(y - o[1])) * (size_t)e[0] + (size_t)(x - o[0]); };
+    unsigned seed[4];
+    for (int c = 0; c < 4; ++c) seed[c] = texel(rule->seed[0], rule->seed[1], rule->seed[2])[c];
+    // 0: not passable, 1: passable, 2: of the region
+    std::vector<uint8_t> state((size_t)e[0] * (size_t)e[1] * (size_t)e[2], 0);
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    walk(b, t, o, e, no_row, [&](int, int x, int y, int z, uint64_t q) {
+        const uint8_t* p = texel(x, y, z);
+        if (vr::fill::passable(*rule, seed, q <= t.s, [&](int c) -> unsigned { return p[c]; })) {
+            state[at(x, y, z)] = 1;
+            ++rep.passable;
+        }
+    });
+    struct Texel { int x, y, z; };
+    std::vector<Texel> queue;
+    if (state[at(rule->seed[0], rule->seed[1], rule->seed[2])] == 1) {
+        state[at(rule->seed[0], rule->seed[1], rule->seed[2])] = 2;
+        queue.push_back(Texel{rule->seed[0], rule->seed[1], rule->seed[2]});
+    }
+    for (size_t head = 0; head < queue.size(); ++head) {
+        const Texel cur = queue[head];
+        const int p[3] = {cur.x, cur.y, cur.z};
+        for (int a = 0; a < 3; ++a) {
+            if (p[a] < rep.min[a]) rep.min[a] = p[a];
+            if (p[a] > rep.max[a]) rep.max[a] = p[a];
+            for (int d = -1; d <= 1; d += 2) {
+                int n[3] = {cur.x, cur.y, cur.z};
+                n[a] += d;
+                if (n[a] < o[a] || n[a] - o[a] >= e[a]) continue;
+                uint8_t& st = state[at(n[0], n[1], n[2])];
+                if (st != 1) continue;
+                st = 2;
+                queue.push_back(Texel{n[0], n[1], n[2]});
+            }
+        }
+    }
+    rep.filled = queue.size();
+    walk(b, t, o, e, no_row, [&](int, int x, int y, int z, uint64_t q) {
+        if (q > t.s || state[at(x, y, z)] != 2) return;
+        const unsigned w = vr::brush::weight(q, t.s, b->falloff);
+        uint8_t* p = texel(x, y, z);
+        for (int c = 0; c < 4; ++c) {
+            if (!b->strength[c]) continue;
+            p[c] = (uint8_t)vr::brush::blend(b->op, p[c], b->value[c], w * b->strength[c]);
+        }
+    });
+    if (report) *report = rep;
+    return VR_OK;
 }
 
 // The dabs of a drag (include/vr.h): n segments of at most `spacing` texels on the longest axis, dab i at the

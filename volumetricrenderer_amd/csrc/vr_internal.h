@@ -712,6 +712,25 @@ hipError_t launch_morph_stage(const PaintArgs& a, int op, int half_width, const 
 // as the value, rank already resolved to 0..(2 half_width + 1)^3 - 1; launch_blur_commit follows it.
 hipError_t launch_rank_stage(const PaintArgs& a, int rank, int half_width, const uint8_t* d_planar, uint8_t* d_stage,
                              hipStream_t s);
+// vr_fill (vr_fill.hip): the brush as for launch_paint_planar and the validated rule, whose
+// seed lies in the clipped box.  d_labels holds fill_label_bytes(p) bytes, 4-byte aligned: one 32-bit label per texel
+// of the box, x fastest.  Three launches in this order on one stream: launch_fill_label writes every label (the
+// box-linear index of the smallest member of the texel's component within its 8 x 8 x 8 tile, 0xFFFFFFFF for a texel
+// that is not passable) and, with d_report, the empty report; launch_fill_merge joins the components across the
+// tiles' faces; launch_fill_commit blends the brush into the planes where a texel's root is the seed's, folds the
+// new bytes into mm and, with d_report (a DEVICE vr_fill_report, 8-byte aligned, or null), adds up the report.
+// launch_fill_empty_report writes the empty report and nothing else.
+struct FillArgs {
+    PaintArgs p;
+    vr_fill_rule rule;
+};
+size_t fill_label_bytes(const PaintArgs& p);
+hipError_t launch_fill_empty_report(int nx, int ny, int nz, vr_fill_report* d_report, hipStream_t s);
+hipError_t launch_fill_label(const FillArgs& a, const uint8_t* d_planar, uint32_t* d_labels, vr_fill_report* d_report,
+                             hipStream_t s);
+hipError_t launch_fill_merge(const FillArgs& a, uint32_t* d_labels, hipStream_t s);
+hipError_t launch_fill_commit(const FillArgs& a, const uint32_t* d_labels, uint8_t* d_planar, unsigned* mm,
+                              vr_fill_report* d_report, hipStream_t s);
 // vr_clone: the brush as for launch_paint_planar (value is not read) and the validated map.
 // launch_clone_direct goes from the planes to the planes in one launch and folds the new bytes into mm: only for a
 // map whose source range misses the clipped box on an axis (vr_clone.h direct).  launch_clone_stage has

@@ -40,6 +40,7 @@ from ._lib import VOLUME_STATS_BYTES, StatsSummary, VolumeStats
 from ._lib import Box, CloneMap
 from ._lib import BORDER_CLAMP, FILTER_NEAREST, Affine
 from ._lib import RANK_MEDIAN
+from ._lib import FILL_REPORT_BYTES, FillReport, FillRule
 from ._lib import LUT_BYTES, LUT_EQUALIZE, LUT_STRETCH, Lut  # noqa: F401
 
 _lib.load()  # fail at import if the HIP library is missing
@@ -336,6 +337,63 @@ def brush_rank_apply(brush: Brush, rank: int, half_width: int, rgba: np.ndarray)
     call("vr_brush_rank_apply", ctypes.byref(brush), int(rank), int(half_width), rgba.ctypes.data_as(ctypes.c_void_p),
          nx, ny, nz)
     return rgba
+
+
+class Fill(NamedTuple):
+    """A vr_fill_report on the host: the region's texel count, the passable texels
+    under the brush, and the region's inclusive bounds (x, y, z) -- (nx, ny, nz) /
+    (-1, -1, -1) when nothing was filled."""
+    filled: int
+    passable: int
+    min: tuple
+    max: tuple
+
+
+def make_fill_rule(seed, lo, hi, select=(1, 0, 0, 0), relative: int = 1) -> FillRule:
+    """A vr_fill_rule: `seed` = texel (x, y, z) inside the volume; `select` marks
+    the channels R, G, B, A that take part in the test; with `relative` = 1 a
+    texel passes when each selected byte lies within `lo` below and `hi` above
+    the seed's byte of that channel (clamped to 0..255), with 0 when it lies in
+    lo..hi as given.  `lo`, `hi` and `select` are per channel (one int = every
+    channel)."""
+    r = FillRule()
+    r.seed[:] = [int(v) for v in seed]
+    r.relative = int(relative)
+    r.lo[:] = [int(lo)] * 4 if np.isscalar(lo) else [int(v) for v in lo]
+    r.hi[:] = [int(hi)] * 4 if np.isscalar(hi) else [int(v) for v in hi]
+    r.select[:] = [int(select)] * 4 if np.isscalar(select) else [int(v) for v in select]
+    return r
+
+
+def unpack_fill_report(buf) -> Fill:
+    """The :class:`Fill` in a vr_fill_report given as a :class:`FillReport`, or as
+    its 40 bytes in a uint8 numpy array or tensor (a CUDA tensor is copied to
+    the host, which waits for the work queued before the copy on the current
+    stream)."""
+    if not isinstance(buf, FillReport):
+        if isinstance(buf, torch.Tensor):
+            buf = buf.cpu().numpy()
+        if not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 or buf.size != FILL_REPORT_BYTES:
+            raise ValueError(f"unpack_fill_report: a FillReport or {FILL_REPORT_BYTES} uint8 bytes")
+        buf = FillReport.from_buffer_copy(np.ascontiguousarray(buf).tobytes())
+    return Fill(int(buf.filled), int(buf.passable), tuple(buf.min), tuple(buf.max))
+
+
+def brush_fill_apply(brush: Brush, rule: FillRule, rgba: np.ndarray):
+    """vr_brush_fill_apply: the flood-fill brush applied IN PLACE to a host RGBA8
+    volume shaped (nz, ny, nx, 4) (a contiguous uint8 array) -- the brush is
+    blended, as :func:`brush_apply` blends it, into the texels under it that
+    pass `rule` and are connected to its seed by axis steps over such texels.
+    The CPU statement of what :meth:`Renderer.fill` does on the device.
+    Returns ``(rgba, report)`` with the report a :class:`Fill`."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_fill_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    rep = FillReport()
+    call("vr_brush_fill_apply", ctypes.byref(brush), ctypes.byref(rule), rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz,
+         ctypes.byref(rep))
+    return rgba, unpack_fill_report(rep)
 
 
 def make_clone_map(offset=(0, 0, 0), mirror=(0, 0, 0)) -> CloneMap:
@@ -834,6 +892,45 @@ class Renderer:
         if stream is None:
             torch.cuda.current_stream().synchronize()
         return brush_box(b, self.volume_dims())
+
+    def fill(self, seed, centre, radius, op=BRUSH_SET, falloff: int = 0, value=(255, 255, 255, 255),
+             strength=(255, 255, 255, 255), rule: FillRule | None = None, report=None, stream=None):
+        """Bucket fill / magic wand on the device (vr_fill): the brush of
+        :meth:`paint` blended into the texels under it that pass `rule` (a
+        :func:`make_fill_rule`; its seed is replaced by `seed` when that is
+        not None) and are connected to the seed texel by steps of one texel
+        along an axis over such texels, never leaving the ellipsoid -- bit for
+        bit what :func:`brush_fill_apply` gives on the host.  Returns
+        ``(origin, extent)`` of the brush's clipped bounding box (the edited
+        box, what :meth:`update_footprint` takes) or None when the brush misses
+        the volume, and queues on `stream` as :meth:`paint` does.  With
+        ``report=True`` a CUDA uint8 tensor of 40 bytes is allocated for the
+        vr_fill_report, with ``report=`` such a tensor (8-byte aligned) that one
+        is used; either way the result is ``((origin, extent), tensor)`` and
+        :func:`unpack_fill_report` reads the tensor later.  With every strength
+        0 and a report the call only measures.  The labels live in
+        :meth:`blur`'s scratch (``blur_scratch_kib``), 4 bytes per texel of the
+        clipped box, grown by the same rule."""
+        if rule is None:
+            raise ValueError("fill: a rule is needed (make_fill_rule)")
+        r = FillRule.from_buffer_copy(bytes(rule))
+        if seed is not None:
+            r.seed[:] = [int(v) for v in seed]
+        b = make_brush(centre, radius, op, falloff, value, strength)
+        buf = None
+        if report is True:
+            buf = torch.empty(FILL_REPORT_BYTES, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        elif report is not None and report is not False:
+            if (not isinstance(report, torch.Tensor) or not report.is_cuda or report.device.index != self.device
+                    or report.dtype != torch.uint8 or report.numel() != FILL_REPORT_BYTES or not report.is_contiguous()):
+                raise ValueError(f"fill: report must be a contiguous uint8 tensor of {FILL_REPORT_BYTES} bytes on cuda:{self.device}")
+            buf = report
+        call("vr_fill", self._ctx, ctypes.byref(b), ctypes.byref(r), ctypes.c_void_p(buf.data_ptr()) if buf is not None else None,
+             _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        box = brush_box(b, self.volume_dims())
+        return box if buf is None else (box, buf)
 
     def clone(self, centre, radius, offset, mirror=(0, 0, 0), op=BRUSH_SET, falloff: int = 0,
               strength=(255, 255, 255, 255), stream=None):
