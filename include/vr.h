@@ -935,7 +935,8 @@ vr_status vr_stats_lut_device(void* ctx, const void* d_stats /* DEVICE vr_volume
  * it was.                                                                    */
 vr_status vr_brush_remap_apply(const vr_brush* brush, const vr_lut* lut, uint8_t* rgba8, int nx, int ny, int nz);
 /* 1 if vr_set_volume / vr_set_volume_device accept an nx x ny x nz extent
- * (the device layouts index a plane with 32-bit offsets), else 0          */
+ * (the device layouts index a plane with 32-bit offsets), else 0: every
+ * axis positive and (nx + 2)(ny + 2)(nz + 2) < 2^31, for any int arguments */
 int       vr_volume_extent_ok(int nx, int ny, int nz);
 
 /* ---- volume generation on the GPU: replaces the host start-up loops of

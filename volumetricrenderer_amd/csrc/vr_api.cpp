@@ -99,8 +99,11 @@ void free_volume(Ctx* c)
 bool dims_ok(int nx, int ny, int nz)
 {
     if (nx <= 0 || ny <= 0 || nz <= 0) return false;
-    const long long pt = (long long)(nx + 2) * (ny + 2) * (nz + 2);
-    return pt < (1ll << 31);  // kernels index a plane with 32-bit ints
+    // widened before the + 2 (INT_MAX + 2 is no int), and one factor at a time: each padded axis is
+    // at most 2^31 + 1, so the first product fits 64 bits, and once it is below 2^31 so does the second
+    const long long limit = 1ll << 31;   // kernels index a plane with 32-bit ints
+    const long long xy = ((long long)nx + 2) * ((long long)ny + 2);
+    return xy < limit && xy * ((long long)nz + 2) < limit;
 }
 
 int wanted_fast_layout(const Ctx* c)
