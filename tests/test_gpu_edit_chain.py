@@ -47,6 +47,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import edit_chain as ec  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from quad_cases import (BRICK4832, COL48, CORNERH, LADDER, MODES, SPLIT_LAYOUTS, counters, predict, refill,  # noqa: E402
+                        set_options as setup)
+import quad_cases as qc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -55,30 +58,10 @@ if torch.cuda.is_available():
     from volumetricrenderer_amd.distributed import RcclBandPipeline
 
 W, H, FMT = ec.W, ec.H, ec.FMT
-COL48, BRICK4832, CORNERH = 15, 12, 14
 NAMES = {COL48: "col48", BRICK4832: "brick4832", CORNERH: "cornerh"}
-SPLIT_LAYOUTS = (COL48, BRICK4832)
 CASES = [(lay, v) for lay in SPLIT_LAYOUTS for v in ec.VARIANTS] + [(CORNERH, None), (CORNERH, 1)]
 CASE_IDS = [f"{NAMES[lay]}-{ec.VARIANT_IDS[ec.VARIANTS.index(v)]}" for lay, v in CASES]
-COUNTERS = ("quad_launches", "quad_split_launches", "quad_steps_launches", "quad_pairs_launches")
-# (quad_split, quad_steps, quad_pairs): quad_pairs 1, then quad_pairs 0, then quad_steps 0, then quad_split 0
-LADDER = [(1, 1, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1)]
-MODES = {(1, 1, 1, 1): "QUAD_PAIRS", (1, 1, 1, 0): "QUAD_STEPS", (1, 1, 0, 0): "QUAD_SPLIT", (1, 0, 0, 0): "QUAD_FRAMES",
-         (0, 0, 0, 0): "QUAD_NONE"}
 EARLIES = (0.0, ec.EARLY)
-
-
-def predict(layout, early, mask, split, steps, pairs):
-    """(QUAD, split, step-round, paired) launches of one vr_render_group of four frames of one camera with zero tap
-    offsets and no step counter: vr_internal.h quad_instance, quad_split_layout and vr_render.cpp render_frames,
-    restated."""
-    b4 = layout in SPLIT_LAYOUTS                                     # is_b4_family, of the layouts used here
-    u_kernel = not early and mask in (1, 2, 4, 8)                    # u_kernel_channel(...) >= 0
-    quad = u_kernel or not (b4 and not early)
-    split = quad and bool(split) and layout in SPLIT_LAYOUTS         # quad_split_layout
-    steps = split and bool(steps)
-    pairs = steps and bool(pairs)
-    return int(quad), int(split), int(steps), int(pairs)
 
 
 def end_early(variant, k):
@@ -87,24 +70,8 @@ def end_early(variant, k):
     return 0.0 if ec.expected_mask(variant, k) or k % 2 == 0 else ec.EARLY
 
 
-def setup(rr, pref):
-    rr.set_procedural(enabled=0)
-    for k, v in (("uniform_skip", 1), ("count", 0), ("split", 1), ("slab", 0), ("empty_fill", 1), ("region_gpu", 1),
-                 ("region_interval", 32), ("pair_deal", 0), ("frame_quad", 1), ("quad_split", 1), ("quad_steps", 1),
-                 ("quad_pairs", 1)):
-        rr.set_option(k, v)
-    rr.set_layout_preference(pref)
-
-
 def target(rr):
-    out = rr.alloc_target(W, H, FMT)
-    out.view(torch.uint8).fill_(0xA5)
-    return out
-
-
-def refill(outs):
-    for o in outs:
-        o.view(torch.uint8).fill_(0xA5)
+    return qc.target(rr, (W, H), FMT)
 
 
 def same(got, want, what):
@@ -113,10 +80,6 @@ def same(got, want, what):
     assert g.shape == want.shape, what
     bad = np.argwhere(g != want)
     assert bad.size == 0, f"{what}: {len(bad)} bytes differ from the oracle's frame, first (y, x, c) {bad[:4].tolist()}"
-
-
-def counters(rr):
-    return tuple(rr.get_option(k) for k in COUNTERS)
 
 
 @pytest.mark.parametrize("layout,variant", CASES, ids=CASE_IDS)

@@ -52,6 +52,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import blur_spec as bs  # noqa: E402
 import edit_chain as ec  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from quad_cases import (BRICK4832, COL48, CORNER8, CORNERH, FRAME_LAYOUTS, LADDER, MODES, PLANAR, QUAD_MODES,  # noqa: E402
+                        SPLIT_LAYOUTS, counters, predict, refill, set_options as setup)
+import quad_cases as qc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -62,21 +65,12 @@ from volumetricrenderer_amd._lib import FMT_RGBA8_UNORM, FMT_RGBA32F  # noqa: E4
 W, H, STEPS = 70, 37, 16
 RECT = (9, 5, 43, 21)            # interior, on no tile edge
 WHOLE = (0, 0, W, H)
-PLANAR, CORNER8, BRICK4832, CORNERH, COL48 = 1, 5, 12, 14, 15
 NAMES = {PLANAR: "planar", CORNER8: "corner8", BRICK4832: "brick4832", CORNERH: "cornerh", COL48: "col48"}
 BUILT = [PLANAR, CORNER8, BRICK4832, CORNERH, COL48]
 FAST = [CORNER8, BRICK4832, CORNERH, COL48]
-FRAME_LAYOUTS = (COL48, BRICK4832, CORNERH)     # vr_internal.h FrameLayouts: the layouts with multi-frame kernels
-SPLIT_LAYOUTS = (COL48, BRICK4832)              # quad_split_layout; also the is_b4_family members built by default
 FORMATS = [(FMT_RGBA8_UNORM, "rgba8"), (FMT_RGBA32F, "rgba32f")]
 EARLIES = (0.0, 0.98)
 SCALES = (1.0, 4.0)
-COUNTERS = ("quad_launches", "quad_split_launches", "quad_steps_launches", "quad_pairs_launches")
-LADDER = [(1, 1, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1)]    # (quad_split, quad_steps, quad_pairs), test_gpu_edit_chain's
-MODES = {(1, 1, 1, 1): "QUAD_PAIRS", (1, 1, 1, 0): "QUAD_STEPS", (1, 1, 0, 0): "QUAD_SPLIT", (1, 0, 0, 0): "QUAD_FRAMES",
-         (0, 0, 0, 0): "QUAD_NONE"}
-QUAD_MODES = ("QUAD_PAIRS", "QUAD_STEPS", "QUAD_SPLIT", "QUAD_FRAMES")
-
 THIN = [(1, 1, 1), (1, 40, 40), (40, 1, 40), (40, 40, 1), (2, 40, 40), (40, 40, 2), (1, 1, 64), (3, 2, 1)]
 LONG = [(4096, 2, 2), (2, 4096, 3), (3, 2, 4096), (600, 5, 700)]
 TABLE_WORDS = 12288              # 48 KiB of LDS offset tables
@@ -92,22 +86,6 @@ TALLY = {"thin": Counter(), "long": Counter()}   # (mode or "planar", "u" or "ge
 
 def dims_id(d):
     return "x".join(str(v) for v in d)
-
-
-def predict(layout, early, mask, split, steps, pairs):
-    """(QUAD, split, step-round, paired) launches of one vr_render_group of four frames of one camera with zero tap
-    offsets and no step counter, for the layout that marches: vr_internal.h pair_layout, quad_instance and
-    quad_split_layout and vr_render.cpp render_frames, restated (test_gpu_edit_chain.predict, and the layouts
-    without a multi-frame kernel, whose group is four plain renders)."""
-    if layout not in FRAME_LAYOUTS:
-        return 0, 0, 0, 0
-    b4 = layout in SPLIT_LAYOUTS
-    u_kernel = not early and mask in (1, 2, 4, 8)
-    quad = u_kernel or not (b4 and not early)
-    split = quad and bool(split) and layout in SPLIT_LAYOUTS
-    steps = split and bool(steps)
-    pairs = steps and bool(pairs)
-    return int(quad), int(split), int(steps), int(pairs)
 
 
 def volume(dims, uniform):
@@ -169,24 +147,8 @@ def r():
         yield rr
 
 
-def setup(rr, pref):
-    rr.set_procedural(enabled=0)
-    for k, v in (("uniform_skip", 1), ("count", 0), ("split", 1), ("slab", 0), ("empty_fill", 1), ("region_gpu", 1),
-                 ("region_interval", 32), ("pair_deal", 0), ("frame_quad", 1), ("quad_split", 1), ("quad_steps", 1),
-                 ("quad_pairs", 1)):
-        rr.set_option(k, v)
-    rr.set_layout_preference(pref)
-
-
 def target(rr, fmt):
-    out = rr.alloc_target(W, H, fmt)
-    out.view(torch.uint8).fill_(0xA5)
-    return out
-
-
-def refill(outs):
-    for o in outs:
-        o.view(torch.uint8).fill_(0xA5)
+    return qc.target(rr, (W, H), fmt)
 
 
 def counter():
@@ -203,10 +165,6 @@ def same(got, want, what):
     assert g.shape == want.shape and g.dtype == want.dtype, what
     bad = np.argwhere(g.view(np.uint8) != want.view(np.uint8))
     assert bad.size == 0, f"{what}: {len(bad)} bytes differ from the oracle's frame, first (y, x, byte) {bad[:4].tolist()}"
-
-
-def counters(rr):
-    return tuple(rr.get_option(k) for k in COUNTERS)
 
 
 def expect_variant(rr, layout, early, mask, what):

@@ -29,26 +29,26 @@ reads the executed steps of every ray from vr_query_rect (the non-QUAD path) and
 that all four residues occur among the rays the early-out ended: at 0.99 in the recipe
 frame, at 0.98 in the random volume's.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from quad_cases import (BRICK4832, COL48, LAYOUTS, N, SCALES, SIZE_IDS, SIZES, STEPS, cam, check_option, group,  # noqa: E402,F401
+                        plain, random_volume_bytes, scrolled, setup)
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     import volumetricrenderer_amd as vr
-from volumetricrenderer_amd._lib import FMT_RGBA8_UNORM, VRError  # noqa: E402
+from volumetricrenderer_amd._lib import VRError  # noqa: E402
 
-N, STEPS = 40, 16
-COL48, BRICK4832 = 15, 12
-LAYOUTS = pytest.mark.parametrize("pref", [COL48, BRICK4832], ids=["col48", "brick4832"])
-FMT = FMT_RGBA8_UNORM
-SIZES = [(64, 48), (70, 37)]
-SIZE_IDS = ["64x48", "70x37"]
 EARLY = [0.05, 0.98, 0.99]   # ends no ray; ends rays on every step of a round (random volume; recipe volume)
 EARLY_IDS = ["early_0.05", "early_0.98", "early_0.99"]
 ROUND_EARLY = {"recipe": 0.99, "random": 0.98}
-SCALES = pytest.mark.parametrize("scale", [4.0, 1.0], ids=["scale4", "scale1"])
 STEP_COUNTS = pytest.mark.parametrize("steps", [1, 2, 3, 4, 5, 7, 8, 9, 16])
 
 
@@ -63,70 +63,12 @@ def r():
 
 @pytest.fixture(scope="module")
 def random_volume():
-    return np.random.default_rng(20261021).integers(0, 256, size=(N, N, N, 4), dtype=np.uint8)
-
-
-def setup(rr, pref=COL48, **march):
-    rr.set_procedural(enabled=0)
-    for k, v in (("uniform_skip", 1), ("count", 0), ("split", 1), ("slab", 0), ("empty_fill", 1), ("region_gpu", 1),
-                 ("region_interval", 32), ("pair_deal", 0), ("frame_quad", 1), ("quad_split", 1), ("quad_steps", 1)):
-        rr.set_option(k, v)
-    rr.set_layout_preference(pref)
-    rr.set_march(vr.march_defaults(**{"max_steps": STEPS, **march}))
-
-
-def cam(size, phi=20.0, theta=-35.0):
-    return vr.reference_shader_data(size[0] / size[1], phi, theta, 0.0)
-
-
-def scrolled(size):
-    c = cam(size)
-    c[1].media_scroll[1 * 4 + 1] = 0.01
-    c[1].media_scroll[2 * 4 + 2] = -0.02
-    return c
-
-
-def target(rr, size, **band):
-    out = rr.alloc_target(*size, FMT, **band)
-    out.view(torch.uint8).fill_(0xA5)
-    return out
-
-
-def plain(rr, c, size, **band):
-    rr.set_shader_data(*c)
-    out = rr.render(*size, FMT, out=target(rr, size, **band), **band)
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-COUNTERS = ("quad_launches", "quad_split_launches", "quad_steps_launches")
-
-
-def group(rr, c, size, **band):
-    """(the four targets, (QUAD, split, step-round) launches) of one vr_render_group of camera c."""
-    outs = [target(rr, size, **band) for _ in range(4)]
-    before = [rr.get_option(k) for k in COUNTERS]
-    rr.render_group(*size, FMT, outs, cameras=[c] * 4, **band)
-    torch.cuda.synchronize()
-    return [o.cpu().numpy() for o in outs], tuple(rr.get_option(k) - b for k, b in zip(COUNTERS, before))
+    return random_volume_bytes()
 
 
 def check_steps(rr, size, c=None, **band):
     """The step-round launch, then the same launch with quad_steps = 0, against the plain render."""
-    c = c if c is not None else cam(size)
-    want = plain(rr, c, size, **band)
-    for steps in (1, 0):
-        rr.set_option("quad_steps", steps)
-        try:
-            assert rr.get_option("quad_steps") == steps
-            got, counts = group(rr, c, size, **band)
-        finally:
-            rr.set_option("quad_steps", 1)
-        assert counts == (1, 1, steps), f"quad_steps {steps}: (QUAD, split, step-round) launches {counts}"
-        for i in range(4):
-            bad = np.argwhere(got[i] != want)
-            assert bad.size == 0, f"quad_steps {steps}, frame {i}: differs at (y, x, c) {bad[:4].tolist()}"
-    return want
+    return check_option(rr, "quad_steps", size, c=c, **band)
 
 
 @SCALES
@@ -245,6 +187,6 @@ def test_without_the_split_the_option_is_idle(r, size):
         got, counts = group(r, c, size)
     finally:
         r.set_option("quad_split", 1)
-    assert counts == (1, 0, 0), f"(QUAD, split, step-round) launches {counts}"
+    assert counts == (1, 0, 0, 0), f"(QUAD, split, step-round, paired) launches {counts}"
     for i in range(4):
         assert np.array_equal(got[i], want), f"frame {i} differs from the plain render"

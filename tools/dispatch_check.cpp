@@ -9,7 +9,8 @@
 // nested with_bool / with_value hand their tags on in argument order (a swapped
 // template argument in a launcher is the bug this guards against); the layout
 // lists partition the build's layouts as the translation units expect; the _u
-// rule and march_lds_bytes give the values the launchers had written out.
+// rule and march_lds_bytes give the values the launchers had written out; the mode a
+// multi-frame launch runs in (quad_kernel_mode) is the request cut down to what the kernel has.
 #include <cstdio>
 #include <initializer_list>
 #include <type_traits>
@@ -107,6 +108,43 @@ void check_lds_all(std::integer_sequence<int, Ls...>)
     (check_lds<Ls + 1>(), ...);
 }
 
+// quad_kernel_mode over every multi-frame launch, and quad_waves_floor over every instance
+template <int... Ls>
+void check_quad_modes(value_list<Ls...>)
+{
+    for (int l : {Ls...})
+        for (int nf : {2, kGroupFrames})
+            for (int early = 0; early < 2; ++early)
+                for (int zo = 0; zo < 2; ++zo)
+                    for (int um = 0; um <= 15; ++um)
+                        for (int req = QUAD_NONE; req <= QUAD_PAIRS; ++req) {
+                            const int m = quad_kernel_mode(l, nf, early != 0, zo != 0, um, req);
+                            CHECK(m >= QUAD_NONE && m <= req);
+                            if (nf == 2 || !quad_instance(l, early != 0, zo != 0, um)) CHECK(m == QUAD_NONE);
+                            else if (!quad_split_layout(l)) CHECK(m == (req < QUAD_FRAMES ? req : QUAD_FRAMES));
+                            else CHECK(m == req);
+                            // the launcher's general kernel is instantiated for umask 0: the same mode
+                            if (u_kernel_channel(early != 0, zo != 0, um) < 0)
+                                CHECK(m == quad_kernel_mode(l, nf, early != 0, zo != 0, 0, req));
+                            const int w = quad_waves_floor(m, zo != 0, early != 0);
+                            CHECK(w == 1 || w == 5);
+                            if (w == 5) CHECK(quad_splits(m));
+                        }
+    // the predicates are the chain: each mode is the one before it and one thing more
+    for (int m = QUAD_NONE; m <= QUAD_PAIRS; ++m) {
+        CHECK(quad_is_quad(m) == (m != QUAD_NONE));
+        CHECK(quad_splits(m) == (m == QUAD_SPLIT || m == QUAD_STEPS || m == QUAD_PAIRS));
+        CHECK(quad_rounds(m) == (m == QUAD_STEPS || m == QUAD_PAIRS));
+        CHECK(quad_paired(m) == (m == QUAD_PAIRS));
+    }
+    // the options' ladder: an option counts only where the one before it is on
+    for (int b = 0; b < 32; ++b) {
+        const bool el = b & 1, fq = b & 2, sp = b & 4, st = b & 8, pr = b & 16;
+        const int want = !(el && fq) ? QUAD_NONE : !sp ? QUAD_FRAMES : !st ? QUAD_SPLIT : !pr ? QUAD_STEPS : QUAD_PAIRS;
+        CHECK(quad_requested(el, fq, sp, st, pr) == want);
+    }
+}
+
 }  // namespace
 
 int main()
@@ -196,6 +234,7 @@ int main()
             }
 
     check_lds_all(std::make_integer_sequence<int, kNumLayouts - 1>{});
+    check_quad_modes(FrameLayouts{});
 
     std::printf("dispatch_check: %s (VR_EXPERIMENTS=%d)\n", g_fail ? "FAILED" : "ok", VR_EXPERIMENTS);
     return g_fail ? 1 : 0;

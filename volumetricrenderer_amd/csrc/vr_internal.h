@@ -277,17 +277,71 @@ constexpr bool quad_instance(int layout, bool early, bool zero_offsets, int umas
     return !(is_b4_family(layout) && !early && zero_offsets);
 }
 
-// How a four-frame launch uses the lanes of a quad (launch_march_frames): not at all (wave =
-// frame), the QUAD instance, or the QUAD instance whose lanes split each tap's loads between
-// them (option quad_split; vr_march_kernels.h march_pixel_quad_split).  The split fetch is
-// built for the layouts whose footprint slice packs into one dword, 32 bytes apart in z.
-// QUAD_STEPS (option quad_steps; march_pixel_quad_steps) is a split launch of the same layouts
-// in which each lane of the quad fetches and blends one step of four.
-// QUAD_PAIRS (option quad_pairs; march_pixel_quad_steps<PAIRS>) is a step-round launch whose
-// loads are issued in slice pairs (the lane maps below).
+// How a four-frame launch uses the lanes of a quad (launch_march_frames; the multi-frame
+// kernels' template parameter QM).  Each mode is the one before it and one thing more, so the
+// order of the enum is the meaning and the predicates below are the only place that says so:
+//   QUAD_NONE    wave = frame, a quad's lanes are four pixels
+//   QUAD_FRAMES  the QUAD instance: a quad's lanes are the four frames of one pixel, one ray
+//   QUAD_SPLIT   and the lanes split each tap's loads between them (option quad_split;
+//                vr_march_kernels.h march_pixel_quad_split)
+//   QUAD_STEPS   and each lane fetches and blends one step of four (option quad_steps;
+//                march_pixel_quad_steps)
+//   QUAD_PAIRS   and a round's loads are issued in slice pairs (option quad_pairs;
+//                march_pixel_quad_steps<QUAD_PAIRS>, the lane maps below)
+// The split fetch and all that builds on it exist for the layouts whose footprint slice packs
+// into one dword, 32 bytes apart in z (quad_split_layout).
 enum QuadMode : int { QUAD_NONE = 0, QUAD_FRAMES = 1, QUAD_SPLIT = 2, QUAD_STEPS = 3, QUAD_PAIRS = 4 };
+constexpr int kGroupFrames = 4;   // the frames of a group launch (vr_render_group): the lanes of a quad
+constexpr __host__ __device__ bool quad_is_quad(int mode) { return mode >= QUAD_FRAMES; }
+constexpr __host__ __device__ bool quad_splits(int mode) { return mode >= QUAD_SPLIT; }
+constexpr __host__ __device__ bool quad_rounds(int mode) { return mode >= QUAD_STEPS; }
+constexpr __host__ __device__ bool quad_paired(int mode) { return mode >= QUAD_PAIRS; }
 constexpr bool quad_split_layout(int layout) { return layout == LAYOUT_COL48 || layout == LAYOUT_BRICK4832; }
 constexpr unsigned kSplitZ = 32;   // bytes between the z-slices of those layouts (vr_march_kernels.h tap_fetch's kZ)
+
+// The mode a context's options ask for (vr_render.cpp render_frames): each option switches on
+// the mode that builds on the one before it.  eligible: four frames of one camera, none counted.
+constexpr int quad_requested(bool eligible, bool frame_quad, bool quad_split, bool quad_steps, bool quad_pairs)
+{
+    return !(eligible && frame_quad) ? QUAD_NONE : !quad_split ? QUAD_FRAMES : !quad_steps ? QUAD_SPLIT
+         : !quad_pairs ? QUAD_STEPS : QUAD_PAIRS;
+}
+// The mode of the kernel that runs a launch of nf frames for a requested mode: the request cut
+// down to what the kernel has.  render_frames launches this mode; launch_frames_l instantiates
+// it for every (layout, nf, early, zero_offsets, umask, request) and refuses a request it cuts.
+constexpr int quad_kernel_mode(int layout, int nf, bool early, bool zero_offsets, int umask, int requested)
+{
+    if (nf != kGroupFrames || !quad_instance(layout, early, zero_offsets, umask)) return QUAD_NONE;   // a quad is four frames
+    if (!quad_split_layout(layout)) return requested < QUAD_FRAMES ? requested : QUAD_FRAMES;
+    return requested;
+}
+
+// The occupancy floor (amdgpu_waves_per_eu) of a multi-frame kernel.  1 is the floor a kernel
+// of 4-wave workgroups has without the attribute.
+constexpr int quad_waves_floor(int mode, bool zero_offsets, bool early)
+{
+    if (!quad_splits(mode)) return 1;
+    if (quad_rounds(mode) && !zero_offsets) return 1;
+    if (quad_paired(mode) && early) return 1;
+    return 5;
+}
+// (mode, zero_offsets, early) -> the floor
+static_assert(quad_waves_floor(QUAD_NONE, false, false) == 1 && quad_waves_floor(QUAD_NONE, false, true) == 1 &&
+              quad_waves_floor(QUAD_NONE, true, false) == 1 && quad_waves_floor(QUAD_NONE, true, true) == 1 &&
+              quad_waves_floor(QUAD_FRAMES, false, false) == 1 && quad_waves_floor(QUAD_FRAMES, false, true) == 1 &&
+              quad_waves_floor(QUAD_FRAMES, true, false) == 1 && quad_waves_floor(QUAD_FRAMES, true, true) == 1,
+              "no split fetch: compiled as before it");
+static_assert(quad_waves_floor(QUAD_SPLIT, false, false) == 5 && quad_waves_floor(QUAD_SPLIT, false, true) == 5 &&
+              quad_waves_floor(QUAD_SPLIT, true, false) == 5 && quad_waves_floor(QUAD_SPLIT, true, true) == 5,
+              "left alone the scheduler spreads a pair's six blends over 102 VGPRs (4 waves); with the floor 75, no scratch");
+static_assert(quad_waves_floor(QUAD_STEPS, true, false) == 5 && quad_waves_floor(QUAD_STEPS, true, true) == 5,
+              "zero tap offsets: 102 VGPRs without the floor, 96 or fewer and no scratch with it");
+static_assert(quad_waves_floor(QUAD_STEPS, false, false) == 1 && quad_waves_floor(QUAD_STEPS, false, true) == 1,
+              "tap offsets: the floor costs 8 bytes of scratch (124 VGPRs, 4 waves without it)");
+static_assert(quad_waves_floor(QUAD_PAIRS, true, false) == 5 && quad_waves_floor(QUAD_PAIRS, false, false) == 1 &&
+              quad_waves_floor(QUAD_PAIRS, false, true) == 1,
+              "the paired fetch follows the step rounds");
+static_assert(quad_waves_floor(QUAD_PAIRS, true, true) == 1, "but the early-out instance spills 40 bytes under the floor");
 
 // The lane maps of the paired fetch.  A round of four steps loads a tap
 // with two b64 instructions, I = 0 (A) and 1 (B).  In instruction I quad lane fl loads z-slice
@@ -301,6 +355,7 @@ constexpr __host__ __device__ int pair_load_slice(int fl) { return fl & 1; }
 constexpr __host__ __device__ int pair_owner_instr(int j) { return j >> 1; }
 constexpr __host__ __device__ int pair_owner_lane(int j, int z) { return 2 * (j & 1) + z; }
 constexpr __host__ __device__ int quad_perm_ctrl(int l0, int l1, int l2, int l3) { return l0 | l1 << 2 | l2 << 4 | l3 << 6; }
+constexpr __host__ __device__ int quad_lane_ctrl(int j) { return quad_perm_ctrl(j, j, j, j); }   // every lane reads lane j
 // the loaders' read of the owners' offsets for instruction I, and the owners' read of slice z
 constexpr __host__ __device__ int pair_load_ctrl(int instr)
 {
@@ -374,8 +429,7 @@ __host__ __device__ inline void set_frame(MarchArgs* a, const FrameArgs& f)
     a->step_counter = f.step_counter;
 }
 // A multi-frame launch's kernel argument: the common part (frame 0's MarchArgs) and the
-// NF frames' own parts, NF = 2 (vr_render_pair) or 4 (vr_render_group)
-constexpr int kGroupFrames = 4;
+// NF frames' own parts, NF = 2 (vr_render_pair) or kGroupFrames (vr_render_group)
 template <int NF>
 struct FramesArgs {
     MarchArgs c;

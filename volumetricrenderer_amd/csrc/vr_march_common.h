@@ -1,6 +1,7 @@
 // vr_march_common.h -- what the grid march (vr_march_kernels.h) and the
 // procedural medium (vr_proc_kernels.h) share: the ray setup, the
-// render-target store, the spec's exp, the lane -> pixel map of a wave tile,
+// render-target store, the spec's exp, the ray epilogue, the tap coordinate,
+// the lane -> pixel map of a wave tile,
 // the ring tile order, the step counter and the VR_TIMELINE recorder.  No
 // kernel lives here, so a translation unit compiles only the kernels of the
 // headers it includes.  Everything is in an anonymous namespace, so each
@@ -128,6 +129,37 @@ __device__ __forceinline__ void store_pixel(const MarchArgs& a, int x, int orow,
         if (a.format <= 2) reinterpret_cast<unsigned int*>(row)[x] = q | (q << 8) | (q << 16) | 0xff000000u;
         else reinterpret_cast<unsigned char*>(row)[x] = (unsigned char)q;
     }
+}
+
+// A ray's epilogue (frag.glsl:76-79): the grey of its accumulated density.  A march ends with
+//     if (r.live) store_pixel(a, x, orow, r.n >= 0, ray_grey(a, acc));
+// The store is not folded into a helper of its own: one more level of inlining makes the
+// compiler order store_pixel's byte packing differently.
+__device__ __forceinline__ float ray_grey(const MarchArgs& a, float acc)
+{
+    const float at = acc * a.step_size;                              // :76
+    return 1.0f - spec_expf(a.density * fminf(-at, 0.0f));           // :79
+}
+
+// Tap t at ray point P: the padded texel coordinate g = fma(P, S_t, T_t) (MarchArgs.tap_S;
+// DESIGN.md sec. 3.2), xy as one packed fma and z as one fmaf.  ZO (MarchArgs.zero_offsets):
+// every T is the literal 0.5.  Every march forms its coordinates here, so they agree bit for
+// bit.  sz, tz: tap t's z scale and offset where they are not MarchArgs' (CORNERH keeps them in
+// VGPRs, vr_march_kernels.h FastCtx).
+struct TapPos {
+    f2 gxy;
+    float gz;
+};
+template <bool ZO>
+__device__ __forceinline__ TapPos tap_pos(const MarchArgs& a, int t, f2 pxy, float pz, float sz, float tz)
+{
+    const f2 T = ZO ? f2{0.5f, 0.5f} : f2{a.tap_T[t][0], a.tap_T[t][1]};
+    return TapPos{__builtin_elementwise_fma(pxy, f2{a.tap_S[t][0], a.tap_S[t][1]}, T), fmaf(pz, sz, ZO ? 0.5f : tz)};
+}
+template <bool ZO>
+__device__ __forceinline__ TapPos tap_pos(const MarchArgs& a, int t, f2 pxy, float pz)
+{
+    return tap_pos<ZO>(a, t, pxy, pz, a.tap_S[t][2], a.tap_T[t][2]);
 }
 
 // Lane -> pixel inside an 8x8 wave tile.  Default row-major, so each 16-lane

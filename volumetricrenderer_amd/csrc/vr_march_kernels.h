@@ -216,11 +216,8 @@ __device__ __forceinline__ float tap_fast(const FastCtx& f, int ch, float gx, fl
 template <int LAYOUT, bool ZO = false>
 __device__ __forceinline__ TapRaw tap_fetch_at(const MarchArgs& a, const FastCtx& f, int t, f2 pxy, float pz)
 {
-    const f2 T = ZO ? f2{0.5f, 0.5f} : f2{a.tap_T[t][0], a.tap_T[t][1]};
-    const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[t][0], a.tap_S[t][1]}, T);
-    const float gz = LAYOUT == LAYOUT_CORNERH ? fmaf(pz, f.sz[t], ZO ? 0.5f : f.oz[t])
-                                             : fmaf(pz, a.tap_S[t][2], ZO ? 0.5f : a.tap_T[t][2]);
-    return tap_fetch<LAYOUT>(f, t, gxy.x, gxy.y, gz);
+    const TapPos g = LAYOUT == LAYOUT_CORNERH ? tap_pos<ZO>(a, t, pxy, pz, f.sz[t], f.oz[t]) : tap_pos<ZO>(a, t, pxy, pz);
+    return tap_fetch<LAYOUT>(f, t, g.gxy.x, g.gxy.y, g.gz);
 }
 
 // One trilinear tap from the planar layout with full wrap semantics.
@@ -251,12 +248,11 @@ __device__ __forceinline__ float tap_planar(const uint8_t* __restrict__ pl, cons
 template <int LAYOUT, int WRAP>
 __device__ __forceinline__ float tap(const MarchArgs& a, const FastCtx& f, int t, f2 pxy, float pz)
 {
-    const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[t][0], a.tap_S[t][1]}, f2{a.tap_T[t][0], a.tap_T[t][1]});
-    const float gz = fmaf(pz, a.tap_S[t][2], a.tap_T[t][2]);
+    const TapPos g = tap_pos<false>(a, t, pxy, pz);
     if constexpr (LAYOUT == LAYOUT_PLANAR)
-        return tap_planar<WRAP>(a.vol + (size_t)t * a.plane_stride, a, gxy.x, gxy.y, gz);
+        return tap_planar<WRAP>(a.vol + (size_t)t * a.plane_stride, a, g.gxy.x, g.gxy.y, g.gz);
     else
-        return tap_fast<LAYOUT>(f, t, gxy.x, gxy.y, gz);
+        return tap_fast<LAYOUT>(f, t, g.gxy.x, g.gxy.y, g.gz);
 }
 
 // One ray of the grid path: setup, the march (frag.glsl:57-75), the
@@ -271,7 +267,9 @@ __device__ __forceinline__ float tap(const MarchArgs& a, const FastCtx& f, int t
 // with or without pipelining.
 //
 // Taps of a march with uniform channels UM (MarchArgs.umask): a uniform
-// channel's tap is the constant uv[T], with no load.
+// channel's tap is the constant uv[T], with no load.  Every march fills uv[] with the same
+// four lines at its top; they stay written out, because the early-out QUAD instances
+// compile to other code when the lines come from a helper (profiles/quadmode).
 // COL48Z: taps 0-2 are COL48's, tap 3 ZPAIR's (its own tables and plane).
 template <int UM, int T, int LAYOUT, bool ZO>
 __device__ __forceinline__ TapRaw fetch_u(const MarchArgs& a, const FastCtx& f, f2 pxy, float pz)
@@ -333,10 +331,7 @@ __device__ __forceinline__ unsigned march_pixel(const MarchArgs& a, const FastCt
                 }
             }
         }
-        if (r.live) {
-            const float at = acc * a.step_size;
-            store_pixel(a, x, orow, r.n >= 0, 1.0f - spec_expf(a.density * fminf(-at, 0.0f)));
-        }
+        if (r.live) store_pixel(a, x, orow, r.n >= 0, ray_grey(a, acc));                  // :76-79
         return r.n > 0 ? (unsigned)i : 0u;
     }
     f2 pxy = r.pxy;
@@ -363,10 +358,7 @@ __device__ __forceinline__ unsigned march_pixel(const MarchArgs& a, const FastCt
             if (acc > a.acc_limit) { ++i; break; }
         }
     }
-    if (r.live) {
-        const float at = acc * a.step_size;                                          // :76
-        store_pixel(a, x, orow, r.n >= 0, 1.0f - spec_expf(a.density * fminf(-at, 0.0f)));   // :79
-    }
+    if (r.live) store_pixel(a, x, orow, r.n >= 0, ray_grey(a, acc));                  // :76-79
     return r.n > 0 ? (unsigned)i : 0u;
 }
 
@@ -390,16 +382,35 @@ __device__ __forceinline__ unsigned march_pixel(const MarchArgs& a, const FastCt
 // The exchange needs every lane of a quad active wherever one is.  That holds because the
 // lanes of a quad share the ray: r.n, the early-out and the edge-of-frame case are the
 // same in all four, so a quad takes every branch below as one.
-template <int J>
-__device__ __forceinline__ unsigned quad_lane(unsigned v)
+//
+// The one cross-lane primitive: v of the quad lanes a quad_perm control names (vr_internal.h
+// quad_perm_ctrl; quad_lane_ctrl(J) names lane J in all four).
+template <int CTRL>
+__device__ __forceinline__ unsigned quad_read(unsigned v)
 {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, J * 0x55, 0xf, 0xf, true);
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
 }
-// byte K of v as float.  Not ubyte<K>(): the compiler folds quad_lane's DPP move into
+template <int J>
+__device__ __forceinline__ float quad_lane_f(float v)
+{
+    return __builtin_bit_cast(float, quad_read<quad_lane_ctrl(J)>(__builtin_bit_cast(unsigned, v)));
+}
+// byte K of v as float.  Not ubyte<K>(): the compiler folds quad_read's DPP move into
 // this v_cvt_f32_ubyteK, which it cannot do through an asm statement, and it keeps the
 // wait states between the pack and the DPP read
 template <int K>
 __device__ __forceinline__ float ubyte_of(unsigned v) { return (float)((v >> (8 * K)) & 0xffu); }
+// blend()'s first four arguments from a footprint's two packed z-slices (split_pack), z0 and z1,
+// each read from the quad lane that loaded it.  The weights are not passed through here: a
+// caller that forms them in the blend's argument list (split_blend) keeps them after the converts.
+struct Footprint {
+    f2 lo_a, hi_a, lo_b, hi_b;
+};
+__device__ __forceinline__ Footprint packed_footprint(unsigned z0, unsigned z1)
+{
+    return Footprint{f2{ubyte_of<0>(z0), ubyte_of<0>(z1)}, f2{ubyte_of<1>(z0), ubyte_of<1>(z1)},
+                     f2{ubyte_of<2>(z0), ubyte_of<2>(z1)}, f2{ubyte_of<3>(z0), ubyte_of<3>(z1)}};
+}
 
 // one lane's part of a step pair's fetch of one tap: its slice, and the offset whose low bits shift it
 struct SliceRaw {
@@ -411,10 +422,8 @@ __device__ __forceinline__ SliceRaw split_fetch(const MarchArgs& a, const FastCt
     if constexpr ((UM >> T) & 1) {
         return SliceRaw{};
     } else {
-        const f2 Tt = ZO ? f2{0.5f, 0.5f} : f2{a.tap_T[T][0], a.tap_T[T][1]};
-        const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[T][0], a.tap_S[T][1]}, Tt);
-        const float gz = fmaf(pz, a.tap_S[T][2], ZO ? 0.5f : a.tap_T[T][2]);
-        const unsigned off = f.tx[cvt_flr(gxy.x)] + f.ty[cvt_flr(gxy.y)] + f.tz[cvt_flr(gz)];
+        const TapPos g = tap_pos<ZO>(a, T, pxy, pz);
+        const unsigned off = f.tx[cvt_flr(g.gxy.x)] + f.ty[cvt_flr(g.gxy.y)] + f.tz[cvt_flr(g.gz)];
         const auto s = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], (off & ~3u) + zoff, 0, 0);
         return SliceRaw{s[0], s[1], off};
     }
@@ -432,13 +441,9 @@ __device__ __forceinline__ float split_blend(const MarchArgs& a, unsigned pk, f2
     if constexpr ((UM >> T) & 1) {
         return uv[T];
     } else {
-        const f2 Tt = ZO ? f2{0.5f, 0.5f} : f2{a.tap_T[T][0], a.tap_T[T][1]};
-        const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[T][0], a.tap_S[T][1]}, Tt);
-        const float gz = fmaf(pz, a.tap_S[T][2], ZO ? 0.5f : a.tap_T[T][2]);
-        const unsigned z0 = quad_lane<2 * H>(pk), z1 = quad_lane<2 * H + 1>(pk);
-        return blend(f2{ubyte_of<0>(z0), ubyte_of<0>(z1)}, f2{ubyte_of<1>(z0), ubyte_of<1>(z1)},
-                     f2{ubyte_of<2>(z0), ubyte_of<2>(z1)}, f2{ubyte_of<3>(z0), ubyte_of<3>(z1)},
-                     fract_(gxy.x), fract_(gxy.y), fract_(gz));
+        const TapPos g = tap_pos<ZO>(a, T, pxy, pz);
+        const Footprint p = packed_footprint(quad_read<quad_lane_ctrl(2 * H)>(pk), quad_read<quad_lane_ctrl(2 * H + 1)>(pk));
+        return blend(p.lo_a, p.hi_a, p.lo_b, p.hi_b, fract_(g.gxy.x), fract_(g.gxy.y), fract_(g.gz));
     }
 }
 // march_pixel for quad lane fl of a QUAD kernel (COL48 / BRICK4832).  Software-pipelined
@@ -498,10 +503,7 @@ __device__ __forceinline__ void march_pixel_quad_split(const MarchArgs& a, const
             bxy = dxy; bz = dz;
         }
     }
-    if (r.live) {
-        const float at = acc * a.step_size;
-        store_pixel(a, x, orow, r.n >= 0, 1.0f - spec_expf(a.density * fminf(-at, 0.0f)));
-    }
+    if (r.live) store_pixel(a, x, orow, r.n >= 0, ray_grey(a, acc));                  // :76-79
 }
 
 // ---- the QUAD kernels' step rounds (option quad_steps) ----
@@ -538,27 +540,16 @@ struct StepRaw {
     unsigned s00, s01, s10, s11, off;
     float wx, wy, wz;
 };
-template <int J>
-__device__ __forceinline__ float quad_lane_f(float v)
-{
-    return __builtin_bit_cast(float, quad_lane<J>(__builtin_bit_cast(unsigned, v)));
-}
-// v of the quad lanes a quad_perm control names (vr_internal.h quad_perm_ctrl)
-template <int CTRL>
-__device__ __forceinline__ unsigned quad_read(unsigned v)
-{
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
 // ---- the step rounds' paired fetch (option quad_pairs) ----
 // A step_fetch instruction names one z-slice of the round's four steps, up to four 128-byte
 // lines per quad; a split_fetch instruction names both slices of two steps, which are 32 bytes
-// apart and mostly share a line.  With PAIRS the round keeps its one blend per lane and takes
+// apart and mostly share a line.  With QUAD_PAIRS the round keeps its one blend per lane and takes
 // the split fetch's address pattern.  The owner side is unchanged: lane fl forms its own step's
 // coordinates, weights and offset.  The loads are dealt again (vr_internal.h pair_load_step /
 // pair_load_slice): instruction A serves steps base + 0 and base + 1, B base + 2 and base + 3,
 // and in each quad lane fl loads z-slice fl & 1 of the instruction's step fl >> 1, at the owning
 // lane's offset, read through DPP.  Per quad, tap and round these are the eight pieces the
-// lanes load without PAIRS, each once; every owner's offset is in the plane (a lane past the
+// lanes load without it, each once; every owner's offset is in the plane (a lane past the
 // ray's end takes the round's first point), so the descriptor and its range check are
 // tap_fetch's.  The StepRaw then holds A's dwords in s00, s01, B's in s10, s11, and in off the
 // loaded steps' off & 3: A's in bits 0-1, B's from bit 2 up.
@@ -569,28 +560,26 @@ __device__ __forceinline__ unsigned quad_read(unsigned v)
 // quad lane pair_owner_lane(j, z), and blends with its own weights in split_blend's form -- the
 // floats tap_blend sees.  Every DPP read has an active source for the reason given above
 // march_pixel_quad_split.
-template <int UM, int T, bool ZO, bool PAIRS = false>
-__device__ __forceinline__ StepRaw step_fetch(const MarchArgs& a, const FastCtx& f, f2 pxy, float pz, int fl = 0)
+template <int UM, int T, bool ZO, int QM>
+__device__ __forceinline__ StepRaw step_fetch(const MarchArgs& a, const FastCtx& f, f2 pxy, float pz, int fl)
 {
     if constexpr ((UM >> T) & 1) {
         return StepRaw{};
     } else {
-        const f2 Tt = ZO ? f2{0.5f, 0.5f} : f2{a.tap_T[T][0], a.tap_T[T][1]};
-        const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[T][0], a.tap_S[T][1]}, Tt);
-        const float gz = fmaf(pz, a.tap_S[T][2], ZO ? 0.5f : a.tap_T[T][2]);
-        const unsigned off = f.tx[cvt_flr(gxy.x)] + f.ty[cvt_flr(gxy.y)] + f.tz[cvt_flr(gz)];
-        if constexpr (PAIRS) {
+        const TapPos g = tap_pos<ZO>(a, T, pxy, pz);
+        const unsigned off = f.tx[cvt_flr(g.gxy.x)] + f.ty[cvt_flr(g.gxy.y)] + f.tz[cvt_flr(g.gz)];
+        if constexpr (quad_paired(QM)) {
             const unsigned zoff = (unsigned)pair_load_slice(fl) * kSplitZ;
             // the owner aligns, the loader adds its slice: one v_add_u32 with a DPP source per address
             const unsigned al = off & ~3u;
             const auto sa = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], quad_read<pair_load_ctrl(0)>(al) + zoff, 0, 0);
             const auto sb = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], quad_read<pair_load_ctrl(1)>(al) + zoff, 0, 0);
             const unsigned sh = (quad_read<pair_load_ctrl(0)>(off) & 3u) | (quad_read<pair_load_ctrl(1)>(off) << 2);
-            return StepRaw{sa[0], sa[1], sb[0], sb[1], sh, fract_(gxy.x), fract_(gxy.y), fract_(gz)};
+            return StepRaw{sa[0], sa[1], sb[0], sb[1], sh, fract_(g.gxy.x), fract_(g.gxy.y), fract_(g.gz)};
         } else {
             const auto s0 = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], off & ~3u, 0, 0);
             const auto s1 = __builtin_amdgcn_raw_buffer_load_b64(f.rsrc[T], (off & ~3u) + kSplitZ, 0, 0);
-            return StepRaw{s0[0], s0[1], s1[0], s1[1], off, fract_(gxy.x), fract_(gxy.y), fract_(gz)};
+            return StepRaw{s0[0], s0[1], s1[0], s1[1], off, fract_(g.gxy.x), fract_(g.gxy.y), fract_(g.gz)};
         }
     }
 }
@@ -610,16 +599,16 @@ __device__ __forceinline__ float pair_blend(const StepRaw& r, int fl, const floa
         const unsigned a0 = quad_read<pair_owner_ctrl(0)>(pa), b0 = quad_read<pair_owner_ctrl(0)>(pb);
         const unsigned a1 = quad_read<pair_owner_ctrl(1)>(pa), b1 = quad_read<pair_owner_ctrl(1)>(pb);
         const bool second = pair_owner_instr(fl) != 0;
-        const unsigned z0 = second ? b0 : a0, z1 = second ? b1 : a1;
-        return blend(f2{ubyte_of<0>(z0), ubyte_of<0>(z1)}, f2{ubyte_of<1>(z0), ubyte_of<1>(z1)},
-                     f2{ubyte_of<2>(z0), ubyte_of<2>(z1)}, f2{ubyte_of<3>(z0), ubyte_of<3>(z1)}, r.wx, r.wy, r.wz);
+        const Footprint p = packed_footprint(second ? b0 : a0, second ? b1 : a1);
+        return blend(p.lo_a, p.hi_a, p.lo_b, p.hi_b, r.wx, r.wy, r.wz);
     }
 }
 
-template <int LAYOUT, bool EARLY, bool ZO, int UM, bool PAIRS = false>
+template <int LAYOUT, bool EARLY, bool ZO, int UM, int QM>
 __device__ __forceinline__ void march_pixel_quad_steps(const MarchArgs& a, const FastCtx& f, int x, int orow, int fl)
 {
-    static_assert(quad_split_layout(LAYOUT), "built for the layouts of the split fetch");
+    static_assert(quad_split_layout(LAYOUT) && quad_rounds(QM), "built for the layouts of the split fetch");
+    constexpr bool PAIRS = quad_paired(QM);
     const Ray r = setup_ray(a, x, orow);
     float uv[4] = {};
     if constexpr (UM != 0)
@@ -636,16 +625,16 @@ __device__ __forceinline__ void march_pixel_quad_steps(const MarchArgs& a, const
         bool mine = fl < r.n;
         f2 qxy = mine ? own(axy, bxy, cxy, dxy) : axy;
         float qz = mine ? own(az, bz, cz, dz) : az;
-        StepRaw c0 = step_fetch<UM, 0, ZO, PAIRS>(a, f, qxy, qz, fl), c1 = step_fetch<UM, 1, ZO, PAIRS>(a, f, qxy, qz, fl);
-        StepRaw c2 = step_fetch<UM, 2, ZO, PAIRS>(a, f, qxy, qz, fl), c3 = step_fetch<UM, 3, ZO, PAIRS>(a, f, qxy, qz, fl);
+        StepRaw c0 = step_fetch<UM, 0, ZO, QM>(a, f, qxy, qz, fl), c1 = step_fetch<UM, 1, ZO, QM>(a, f, qxy, qz, fl);
+        StepRaw c2 = step_fetch<UM, 2, ZO, QM>(a, f, qxy, qz, fl), c3 = step_fetch<UM, 3, ZO, QM>(a, f, qxy, qz, fl);
         for (int base = 0;;) {
             const f2 exy = dxy + r.sxy, fxy = exy + r.sxy, gxy = fxy + r.sxy, hxy = gxy + r.sxy;   // steps base + 4 .. base + 7
             const float ez = dz + r.sz, fz = ez + r.sz, gz = fz + r.sz, hz = gz + r.sz;
             mine = base + 4 + fl < r.n;
             qxy = mine ? own(exy, fxy, gxy, hxy) : axy;
             qz = mine ? own(ez, fz, gz, hz) : az;
-            const StepRaw n0 = step_fetch<UM, 0, ZO, PAIRS>(a, f, qxy, qz, fl), n1 = step_fetch<UM, 1, ZO, PAIRS>(a, f, qxy, qz, fl);
-            const StepRaw n2 = step_fetch<UM, 2, ZO, PAIRS>(a, f, qxy, qz, fl), n3 = step_fetch<UM, 3, ZO, PAIRS>(a, f, qxy, qz, fl);
+            const StepRaw n0 = step_fetch<UM, 0, ZO, QM>(a, f, qxy, qz, fl), n1 = step_fetch<UM, 1, ZO, QM>(a, f, qxy, qz, fl);
+            const StepRaw n2 = step_fetch<UM, 2, ZO, QM>(a, f, qxy, qz, fl), n3 = step_fetch<UM, 3, ZO, QM>(a, f, qxy, qz, fl);
             const float t0 = PAIRS ? pair_blend<UM, 0>(c0, fl, uv) : blend_u<UM, 0, LAYOUT>(step_tap(c0), uv);
             const float t1 = PAIRS ? pair_blend<UM, 1>(c1, fl, uv) : blend_u<UM, 1, LAYOUT>(step_tap(c1), uv);
             const float t2 = PAIRS ? pair_blend<UM, 2>(c2, fl, uv) : blend_u<UM, 2, LAYOUT>(step_tap(c2), uv);
@@ -664,10 +653,7 @@ __device__ __forceinline__ void march_pixel_quad_steps(const MarchArgs& a, const
             dxy = hxy; dz = hz;
         }
     }
-    if (r.live) {
-        const float at = acc * a.step_size;
-        store_pixel(a, x, orow, r.n >= 0, 1.0f - spec_expf(a.density * fminf(-at, 0.0f)));
-    }
+    if (r.live) store_pixel(a, x, orow, r.n >= 0, ray_grey(a, acc));                  // :76-79
 }
 
 // Kernel prologue for the fast layouts: buffer descriptors (wave-uniform,
@@ -878,7 +864,10 @@ __global__ __launch_bounds__(kThreads) void march_regions_u(const MarchArgs a, c
 //                 entry waves x 2 frames, both readers on one CU (L1 and L2)
 //   NF 2, deal 1: f = the workgroup's parity on its XCD -- a workgroup keeps 4 consecutive
 //                 entry waves (the 2x2 supertile) of one frame; L2 only (option pair_deal)
-//   NF 4, QUAD:   frames whose cameras the host has proved equal (vr_internal.h
+// QM (vr_internal.h QuadMode) says how an NF 4 launch uses the lanes of a quad; each mode is
+// the one above it and one thing more (quad_is_quad, quad_splits, quad_rounds, quad_paired):
+//   QUAD_NONE:    the list above
+//   QUAD_FRAMES:  frames whose cameras the host has proved equal (vr_internal.h
 //                 frames_share_camera).  The four waves of workgroup g
 //                 all take entry wave g's entries; wave w marches the 4x4-pixel quadrant
 //                 (w & 1, w >> 1) of the 8x8 tile, and lane l is frame l & 3 at the pixel
@@ -887,24 +876,20 @@ __global__ __launch_bounds__(kThreads) void march_regions_u(const MarchArgs a, c
 //                 address, where four waves used to present it one after the other.  The ray
 //                 runs on the common arguments; a lane's own part is its target pointer.
 //                 Steps are not counted: the host sends a counted launch down the NF 4 path.
-//   QUAD, SPLIT:  COL48 / BRICK4832 only (option quad_split): the same
+//   QUAD_SPLIT:   COL48 / BRICK4832 only (option quad_split): the same
 //                 mapping, and the quad's lanes split the loads of two steps between them
 //                 (march_pixel_quad_split) instead of each issuing all of them.
-//   SPLIT, STEPS: the same launches (option quad_steps): the quad's lanes
+//   QUAD_STEPS:   the same launches (option quad_steps): the quad's lanes
 //                 each fetch and blend one step of four and exchange the terms
 //                 (march_pixel_quad_steps).
-//   STEPS, PAIRS: the same launches (option quad_pairs): a round's loads are
-//                 issued in slice pairs, a split launch's addresses (march_pixel_quad_steps<PAIRS>).
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false,
-          bool PAIRS = false>
+//   QUAD_PAIRS:   the same launches (option quad_pairs): a round's loads are
+//                 issued in slice pairs, a split launch's addresses (march_pixel_quad_steps<QUAD_PAIRS>).
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, int QM = QUAD_NONE>
 __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, const unsigned* __restrict__ tiles,
                                                     const int* __restrict__ hdr, int nwx, int deal, unsigned* lds)
 {
     static_assert(NF == 2 || NF == 4, "a 4-wave workgroup is 4 / NF entry waves x NF frames");
-    static_assert(!QUAD || NF == 4, "a quad of lanes is four frames");
-    static_assert(!SPLIT || QUAD, "the lanes of a quad split a fetch only where they hold one ray");
-    static_assert(!STEPS || SPLIT, "the step rounds are a split launch's");
-    static_assert(!PAIRS || STEPS, "the paired fetch is the step rounds'");
+    static_assert(QM == quad_kernel_mode(LAYOUT, NF, EARLY, ZO, UM, QM), "a mode this kernel has (a quad of lanes is four frames)");
     const int xcd = blockIdx.x & 7, wg = (int)(blockIdx.x >> 3);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int fr = wave, first = wg, w = wg;   // the frame, the workgroup's first entry wave, this wave's
@@ -924,7 +909,7 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
     if (first >= (every ? marched : all)) return;   // whole workgroup, before the barrier
     FastCtx f = fast_prologue<LAYOUT>(g.c, lds);   // volume and layout geometry: the frames' common part
     const int lane = threadIdx.x & 63;
-    if constexpr (QUAD) {
+    if constexpr (quad_is_quad(QM)) {
         // fr[0..3] equal the common part in all but the target and the counter: the ray and
         // the prologue (CORNERH's oz too) are the common part's, in SGPRs
         MarchArgs q = g.c;
@@ -939,8 +924,8 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
         for (int k = wg; wg < nwx && k < qcount; k += nwx) {
             const unsigned t = tiles[begin + k];
             const int tx = (int)(t & 0xffffu), ty = (int)(t >> 16);
-            if constexpr (STEPS) march_pixel_quad_steps<LAYOUT, EARLY, ZO, UM, PAIRS>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
-            else if constexpr (SPLIT) march_pixel_quad_split<LAYOUT, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
+            if constexpr (quad_rounds(QM)) march_pixel_quad_steps<LAYOUT, EARLY, ZO, UM, QM>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
+            else if constexpr (quad_splits(QM)) march_pixel_quad_split<LAYOUT, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy, fl);
             else (void)march_pixel<LAYOUT, WRAP, EARLY, ZO, UM>(q, f, tx * 8 + qx, ty * 8 + qy);
         }
         return;
@@ -956,32 +941,21 @@ __device__ __forceinline__ void regions_frames_body(const FramesArgs<NF>& g, con
     }
     if (a.step_counter) add_steps(a, steps);
 }
-// The split-fetch instances are built for 5 or more waves per SIMD: left to itself the
-// scheduler spreads a pair's six blends over 102 VGPRs (4 waves), with the floor it needs 75
-// and no scratch.  1 is the floor a kernel of 4-wave workgroups has without the attribute, so
-// every other instance is compiled as before.  The step-round instances
-// take the same floor where the tap offsets are zero (102 VGPRs without it, 96 or fewer and no
-// scratch with it); with tap offsets the floor costs 8 bytes of scratch, so those two keep 1
-// (124 VGPRs, 4 waves).
-// The paired-fetch instances follow the step rounds' but for the general early-out one, which spills
-// 40 bytes under the floor and keeps 1.
-#define VR_SPLIT_WAVES(E) __attribute__((amdgpu_waves_per_eu(SPLIT && (!STEPS || ZO) && !(PAIRS && (E)) ? 5 : 1)))
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false, bool PAIRS = false>
-__global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES(EARLY) void march_regions_frames(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
-                                                                const int* __restrict__ hdr, int nwx, int deal)
+// The occupancy floor of each instance is vr_internal.h quad_waves_floor's table (the _u kernels have no early-out).
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int NF, int QM = QUAD_NONE>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(quad_waves_floor(QM, ZO, EARLY))))
+void march_regions_frames(const FramesArgs<NF> g, const unsigned* __restrict__ tiles, const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF, QUAD, SPLIT, STEPS, PAIRS>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, 0, NF, QM>(g, tiles, hdr, nwx, deal, lds);
 }
-template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, bool QUAD = false, bool SPLIT = false, bool STEPS = false,
-          bool PAIRS = false>
-__global__ __launch_bounds__(kThreads) VR_SPLIT_WAVES(false) void march_regions_frames_u(const FramesArgs<NF> g, const unsigned* __restrict__ tiles,
-                                                                  const int* __restrict__ hdr, int nwx, int deal)
+template <int LAYOUT, int WRAP, bool EARLY, bool ZO, int UM, int NF, int QM = QUAD_NONE>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(quad_waves_floor(QM, ZO, false))))
+void march_regions_frames_u(const FramesArgs<NF> g, const unsigned* __restrict__ tiles, const int* __restrict__ hdr, int nwx, int deal)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned lds[];
-    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF, QUAD, SPLIT, STEPS, PAIRS>(g, tiles, hdr, nwx, deal, lds);
+    regions_frames_body<LAYOUT, WRAP, EARLY, ZO, UM, NF, QM>(g, tiles, hdr, nwx, deal, lds);
 }
-#undef VR_SPLIT_WAVES
 
 
 // ---- step-split rays (regions schedule) ----
@@ -1044,10 +1018,7 @@ __device__ __forceinline__ unsigned march_pixel_split(const MarchArgs& a, const 
             c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         }
     }
-    if (r.live && k == 0) {
-        const float at = acc * a.step_size;
-        store_pixel(a, x, orow, n >= 0, 1.0f - spec_expf(a.density * fminf(-at, 0.0f)));
-    }
+    if (r.live && k == 0) store_pixel(a, x, orow, n >= 0, ray_grey(a, acc));
     return (n > 0 && k == 0) ? (unsigned)i : 0u;
 }
 
@@ -1255,20 +1226,17 @@ hipError_t launch_lw(const MarchArgs& a, bool early, const Schedule& sc, hipStre
 // arguments (vr_render.cpp), that sc is a regions schedule without split, slab or wide
 // workgroups, and that L is one of FrameLayouts.  XCD x runs
 // sc.map.nwx entry waves, 4 / NF to a workgroup (regions_frames_body).
-// quad (QuadMode): the QUAD instance (nf = 4 only; the caller has proved frames_share_camera), with
-// the split fetch, with the step rounds, with the step rounds' paired fetch or without any -- the same grid.
+// quad (QuadMode): how the launch uses the lanes of a quad -- the same grid in every mode.  The
+// kernel is instantiated with quad_kernel_mode (vr_internal.h) of every request; a request that
+// function cuts down (other than QUAD_NONE for nf = 2 or an instance quad_instance excludes, past
+// QUAD_FRAMES for a layout without the split fetch) is refused: the caller asks for the mode it
+// gets, having proved frames_share_camera.
 template <int L, int W>
 hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool early, const Schedule& sc, int deal, int quad,
                            hipStream_t s)
 {
-    if (quad != QUAD_NONE && (nf != kGroupFrames || !quad_instance(L, early, a.zero_offsets != 0, a.umask)))
-        return hipErrorInvalidValue;   // no such kernel
-    if ((quad == QUAD_SPLIT || quad == QUAD_STEPS || quad == QUAD_PAIRS) && !quad_split_layout(L)) return hipErrorInvalidValue;
+    if (quad_kernel_mode(L, nf, early, a.zero_offsets != 0, a.umask, quad) != quad) return hipErrorInvalidValue;   // no such kernel
     return with_value<2, kGroupFrames>(nf, [&](auto NF) { return with_value<QUAD_NONE, QUAD_FRAMES, QUAD_SPLIT, QUAD_STEPS, QUAD_PAIRS>(quad, [&](auto QD) {
-        constexpr bool Q = decltype(QD)::value != QUAD_NONE && decltype(NF)::value == kGroupFrames;   // instantiated for NF = 4 only
-        constexpr bool PR = Q && decltype(QD)::value == QUAD_PAIRS && quad_split_layout(L);   // a step-round launch too
-        constexpr bool ST = (Q && decltype(QD)::value == QUAD_STEPS && quad_split_layout(L)) || PR;   // a split launch too
-        constexpr bool SP = (Q && decltype(QD)::value == QUAD_SPLIT && quad_split_layout(L)) || ST;
         FramesArgs<NF> g;
         g.c = a;
         for (int k = 0; k < NF; ++k) g.fr[k] = fr[k];
@@ -1281,12 +1249,11 @@ hipError_t launch_frames_l(const MarchArgs& a, const FrameArgs* fr, int nf, bool
         const dim3 grid((unsigned)(NF == 4 ? 8 * nwx : dl ? 16 * ((nwx + 3) / 4) : 8 * ((nwx + 1) / 2)));
         if (u_kernel_channel(early, a.zero_offsets, a.umask) >= 0)
             return with_value<1, 2, 4, 8>(a.umask, [&](auto U) {
-                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF, Q, SP, ST, PR>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+                hipLaunchKernelGGL((march_regions_frames_u<L, W, false, true, U, NF, quad_kernel_mode(L, NF, false, true, U, QD)>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
                 return hipGetLastError();
             }, hipErrorInvalidValue);
         return with_bool(early, [&](auto E) { return with_bool(a.zero_offsets, [&](auto Z) {
-            constexpr bool QG = Q && quad_instance(L, decltype(E)::value, decltype(Z)::value, 0);
-            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF, QG, QG && SP, QG && ST, QG && PR>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
+            hipLaunchKernelGGL((march_regions_frames<L, W, E, Z, NF, quad_kernel_mode(L, NF, E, Z, 0, QD)>), grid, block, lds, s, g, sc.tiles, sc.hdr, nwx, dl);
             return hipGetLastError();
         }); });
     }, hipErrorInvalidValue); }, hipErrorInvalidValue);   // no kernel for this many frames or this mode

@@ -152,13 +152,11 @@ __device__ __forceinline__ unsigned march_pixel_slab(const MarchArgs& a, const _
             float t[4];
 #pragma unroll
             for (int ch = 0; ch < 4; ++ch) {
-                const f2 T = ZO ? f2{0.5f, 0.5f} : f2{a.tap_T[ch][0], a.tap_T[ch][1]};
-                const f2 gxy = __builtin_elementwise_fma(pxy, f2{a.tap_S[ch][0], a.tap_S[ch][1]}, T);
-                const float gz = fmaf(pz, a.tap_S[ch][2], ZO ? 0.5f : a.tap_T[ch][2]);
+                const TapPos g = tap_pos<ZO>(a, ch, pxy, pz);
                 TapRaw q{};
-                q.wx = fract_(gxy.x); q.wy = fract_(gxy.y); q.wz = fract_(gz);
-                const float2 qa = tx2[cvt_flr(gxy.x)], qb = ty2[cvt_flr(gxy.y)];
-                const float cf = floorf(gz);
+                q.wx = fract_(g.gxy.x); q.wy = fract_(g.gxy.y); q.wz = fract_(g.gz);
+                const float2 qa = tx2[cvt_flr(g.gxy.x)], qb = ty2[cvt_flr(g.gxy.y)];
+                const float cf = floorf(g.gz);
                 const float row = qb.y + qa.y;   // 4 (b % 7) + a % 3: the byte in its slice
                 if (bx[ch].fit) {
                     const SlabBox& b = bx[ch];
@@ -193,10 +191,7 @@ __device__ __forceinline__ unsigned march_pixel_slab(const MarchArgs& a, const _
         }
         __builtin_amdgcn_wave_barrier();   // the slab's reads before the next step's writes
     }
-    if (r.live) {
-        const float at = acc * a.step_size;                                          // :76
-        store_pixel(a, x, orow, r.n >= 0, 1.0f - spec_expf(a.density * fminf(-at, 0.0f)));   // :79
-    }
+    if (r.live) store_pixel(a, x, orow, r.n >= 0, ray_grey(a, acc));                      // :76-79
     (void)slab_lds;
     return r.n > 0 ? (unsigned)i : 0u;
 }

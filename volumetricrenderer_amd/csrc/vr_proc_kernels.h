@@ -208,8 +208,7 @@ __device__ __forceinline__ float proc_epilogue(const MarchArgs& a, float acc, fl
     if constexpr (SHADOW) {
         return rad;
     } else {
-        const float at = acc * a.step_size;
-        return 1.0f - spec_expf(a.density * fminf(-at, 0.0f));
+        return ray_grey(a, acc);
     }
 }
 

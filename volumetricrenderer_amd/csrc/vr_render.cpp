@@ -390,21 +390,18 @@ vr_status render_frames(void* p, const vr_target* t, int n, const vr_object_shad
     // pixel for all four; every other group launches the kernel it always did.  The QUAD
     // instance counts no steps (the per-lane sum's registers would cost it a wave per SIMD),
     // so a counted launch is one of those others
-    bool quad = c->frame_quad && frames_share_camera(fr, n) &&
-                quad_instance(f[0].pl.layout, f[0].pl.early, f[0].a.zero_offsets != 0, f[0].a.umask);
-    for (int k = 0; k < n; ++k) quad = quad && !fr[k].step_counter;
-    // the lanes of the quad split each tap's loads where the layout has that fetch (quad_split)
-    const bool split = quad && c->quad_split && quad_split_layout(f[0].pl.layout);
-    // and in such a launch each lane fetches and blends one step of four (quad_steps)
-    const bool steps = split && c->quad_steps;
-    // whose loads, in turn, are issued in slice pairs (quad_pairs)
-    const bool pairs = steps && c->quad_pairs;
-    HIP_TRY(launch_march_frames(f[0].a, fr, n, f[0].pl.layout, f[0].pl.early, sc, c->pair_deal,
-                                pairs ? QUAD_PAIRS : steps ? QUAD_STEPS : split ? QUAD_SPLIT : quad ? QUAD_FRAMES : QUAD_NONE, hs));
-    c->quad_launches += quad;
-    c->quad_split_launches += split;
-    c->quad_steps_launches += steps;
-    c->quad_pairs_launches += pairs;
+    bool eligible = frames_share_camera(fr, n);
+    for (int k = 0; k < n; ++k) eligible = eligible && !fr[k].step_counter;
+    // what the options ask for (each builds on the one before: quad_split splits each tap's loads
+    // between the lanes, quad_steps gives each lane one step of four, quad_pairs issues a round's
+    // loads in slice pairs), cut down to what this plan's kernel has
+    const int mode = quad_kernel_mode(f[0].pl.layout, n, f[0].pl.early, f[0].a.zero_offsets != 0, f[0].a.umask,
+                                      quad_requested(eligible, c->frame_quad, c->quad_split, c->quad_steps, c->quad_pairs));
+    HIP_TRY(launch_march_frames(f[0].a, fr, n, f[0].pl.layout, f[0].pl.early, sc, c->pair_deal, mode, hs));
+    c->quad_launches += quad_is_quad(mode);
+    c->quad_split_launches += quad_splits(mode);
+    c->quad_steps_launches += quad_rounds(mode);
+    c->quad_pairs_launches += quad_paired(mode);
     c->group_launches += n == VR_MAX_GROUP;
     c->pair_launches += n / 2;   // (pairs of frames that shared a launch)
     c->renders_since_build += n - 1;   // the later renders with these lists (build_regions counted the first)
