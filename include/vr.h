@@ -688,6 +688,76 @@ vr_status vr_affine_identity(vr_affine* out);
 vr_status vr_affine_place(const double forward[9], const double src_centre[3], const int32_t dst_centre[3],
                           int filter, int border, vr_affine* out);
 
+/* The liquify brush: push, pinch, bloat, twirl.  What
+ * is under the brush MOVES, by an amount that fades out towards the rim:
+ * vr_clone_affine's resampling with the brush weight blending the POSITION
+ * with the identity, not the moved copy with the original.  Integers only.
+ *
+ * vr_warp is a source brush that reads the installed volume AS IT WAS BEFORE
+ * THE CALL (a Jacobi step).  For a texel t inside the ellipsoid and inside the
+ * volume, with w vr_paint's weight (256 for falloff 0; 256 at the centre down
+ * to 1 on the rim for falloff 1) and per axis a, in signed 64 bits,
+ *   I_a = t_a << 16
+ *   A_a = map->origin[a] + sum_b map->m[a][b] * (t_b - map->pivot[b])
+ *   D_a = A_a - I_a
+ *   P_a = I_a + ((w * D_a) >> 8)          (>> arithmetic: floor)
+ * so w = 256 gives P = A exactly and a small w leaves P next to the texel
+ * itself.  The outside test, the clamp, VR_BORDER_SKIP / VR_BORDER_CLAMP,
+ * VR_FILTER_NEAREST and VR_FILTER_LINEAR are vr_clone_affine's, applied to P,
+ * with n the volume's size.  The blend is the SET blend with a = 256 *
+ * strength[c]: falloff shapes the displacement, not the mix -- no ghost image,
+ * and the motion fades to nothing at the rim.  brush->op must be
+ * VR_BRUSH_SET; brush->value is not read; a channel with strength 0 is
+ * neither read nor written.  The identity map leaves every byte as it was;
+ * with falloff 0 the result is vr_clone_affine's with the same map, SET and
+ * falloff 0; a warp never breaks a uniform channel.
+ *
+ * The maps.  A push is vr_warp_push: m = the identity, pivot = centre,
+ * origin[a] = (centre[a] << 16) - d16[a], so the content under the brush moves
+ * by +d16 / 65536 texels; a drag is a sequence of pushes.  The others need no
+ * builder: they are vr_affine_place(forward, centre, centre, ...) with the
+ * brush centre as both centres, e.g.
+ *   pinch  forward = diag(0.8, 0.8, 0.8)   (bloat: diag(1.25, 1.25, 1.25))
+ *   twirl  forward = the rotation by 20 degrees about z,
+ *          {c, -s, 0,  s, c, 0,  0, 0, 1} with c = cos 20, s = sin 20.
+ *
+ * Device path: always staged (a soft warp reads texels that it writes).  The
+ * scratch is vr_blur's -- one byte per texel of the clipped box and painted
+ * channel, the same growth rule, VR_ERR_OOM rule and "blur_scratch_kib" --
+ * then a stage launch (a workgroup per 8 x 8 x 8 tile of the clipped box; a
+ * tile whose source footprint is at most 4096 texels reads it through LDS,
+ * option "warp_lds", default 1; 0 = every tile gathers from memory), vr_blur's
+ * commit launch, the layout rebuild over the clipped box (vr_brush_box) and
+ * the uniform-channel re-arm.  Within the scratch held it allocates nothing
+ * and never waits on the host, so pick -> vr_warp -> vr_update_footprint ->
+ * vr_render_rect queue on one stream.
+ *
+ * VR_ERR_INVALID: everything vr_clone_affine refuses, an op other than
+ * VR_BRUSH_SET, and a map whose |D_a| passes VR_WARP_MAX_DISP << 16 at one of
+ * the 8 corners of the UNCLIPPED box [centre - radius, centre + radius] (D is
+ * affine in t, so the corners bound it under the whole brush; the limit keeps
+ * w * D below 2^40).  vr_warp_reach tells the largest |D_a| per axis.
+ * VR_ERR_NO_VOLUME as for vr_paint.  A brush that misses the volume, or whose
+ * strengths are all 0, is VR_OK and launches nothing.  A refused call has
+ * launched nothing and leaves the volume untouched.                         */
+#define VR_WARP_MAX_DISP 32768             /* texels: |D_a| <= 2^31 in 16.16 */
+vr_status vr_warp(void* ctx, const vr_brush* brush, const vr_affine* map, void* stream);
+/* The same on a HOST RGBA8 volume (x fastest): the CPU statement, which
+ * vr_warp reproduces bit for bit.  Pure host code; it works from a copy of
+ * what it reads.  VR_ERR_INVALID as above, and for a null rgba8 or a
+ * non-positive dimension; a refused call leaves the array as it was.        */
+vr_status vr_brush_warp_apply(const vr_brush* brush, const vr_affine* map, uint8_t* rgba8, int nx, int ny, int nz);
+/* reach16[a] = max |D_a| over the 8 corners of the unclipped box, in 16.16,
+ * saturated at INT32_MAX (the limit itself, 2^31, and anything above it read
+ * INT32_MAX).  Pure host code; VR_ERR_INVALID for a null pointer and for what
+ * vr_clone_affine refuses of the brush and the map -- not for the op or the
+ * reach, so that a caller can see why vr_warp refused a map.                */
+vr_status vr_warp_reach(const vr_brush* brush, const vr_affine* map, int32_t reach16[3]);
+/* The map of a push by d16 (16.16 texels per axis), integer-exact.  Pure host
+ * code; VR_ERR_INVALID for a null pointer, a bad filter or border, or an
+ * origin outside int32; *out is written only on success.                    */
+vr_status vr_warp_push(const int32_t centre[3], const int32_t d16[3], int filter, int border, vr_affine* out);
+
 /* The flood-fill brush: the bucket fill / magic wand.
  * Every other brush selects an ellipsoid of texels; vr_fill selects, inside
  * that ellipsoid, the texels CONNECTED to a seed whose bytes resemble it, and

@@ -132,6 +132,21 @@ inline vr_affine AffinePlace(const double forward[9], const double src_centre[3]
     return a;
 }
 
+// The liquify brush on a host array (vr_brush_warp_apply): the CPU statement of
+// Renderer::Warp; and the map of a push by d16 (16.16 texels per axis) under a
+// brush at `centre` (vr_warp_push).  Host code only.
+inline void BrushWarpApply(const vr_brush& brush, const vr_affine& map, uint8_t* rgba, int nx, int ny, int nz)
+{
+    Check(vr_brush_warp_apply(&brush, &map, rgba, nx, ny, nz), "vr_brush_warp_apply");
+}
+inline vr_affine WarpPush(const int32_t centre[3], const int32_t d16[3], int filter = VR_FILTER_LINEAR,
+                          int border = VR_BORDER_CLAMP)
+{
+    vr_affine a{};
+    Check(vr_warp_push(centre, d16, filter, border, &a), "vr_warp_push");
+    return a;
+}
+
 // What a stamp edits in an nx x ny x nz volume (vr_stamp_box): the brush's
 // clipped box intersected with the placement, what Renderer::UpdateFootprint
 // takes after Renderer::Stamp; false (and a zero extent) when it is empty.
@@ -270,6 +285,14 @@ public:
     void CloneAffine(const vr_brush& brush, const vr_affine& map, void* stream = nullptr)
     {
         Check(vr_clone_affine(ctx_, &brush, &map, stream), "vr_clone_affine");
+    }
+    // Liquify (vr_warp): what is under the brush (op VR_BRUSH_SET) moves along
+    // `map` -- WarpPush for a push, AffinePlace about the brush centre for a
+    // pinch, a bloat or a twirl -- by an amount that fades out towards the rim.
+    // vr_blur's staging scratch and commit; vr_brush_box names the edited box.
+    void Warp(const vr_brush& brush, const vr_affine& map, void* stream = nullptr)
+    {
+        Check(vr_warp(ctx_, &brush, &map, stream), "vr_warp");
     }
     // Paint under the brush with a function of each texel's own byte
     // (vr_remap): the value of channel c is lut.lut[c][old byte] -- levels,

@@ -22,6 +22,8 @@ from .renderer import brush_clone_apply, brush_stamp_apply, make_clone_map, stam
 from ._lib import AFFINE_MAX_COEFF, AFFINE_ONE, BORDER_CLAMP, BORDER_SKIP, FILTER_LINEAR, FILTER_NEAREST, Affine  # noqa: F401
 from .renderer import (affine_direct, affine_identity, affine_place, brush_clone_affine_apply,  # noqa: F401
                        brush_stamp_affine_apply, make_affine)
+from ._lib import WARP_MAX_DISP  # noqa: F401
+from .renderer import brush_warp_apply, warp_push, warp_reach  # noqa: F401
 from ._lib import LUT_BYTES, LUT_EQUALIZE, LUT_STRETCH, Lut  # noqa: F401
 from .renderer import brush_remap_apply, lut_compose, lut_identity, lut_levels, stats_lut  # noqa: F401
 from .renderer import brush_apply, brush_blur_apply, brush_box, brush_line, coalesce_boxes, make_brush  # noqa: F401
@@ -44,6 +46,7 @@ __all__ = [
     "Affine", "FILTER_NEAREST", "FILTER_LINEAR", "BORDER_CLAMP", "BORDER_SKIP", "AFFINE_ONE", "AFFINE_MAX_COEFF",
     "make_affine", "affine_identity", "affine_place", "affine_direct", "brush_stamp_affine_apply",
     "brush_clone_affine_apply",
+    "WARP_MAX_DISP", "brush_warp_apply", "warp_reach", "warp_push",
     "Lut", "LUT_BYTES", "LUT_EQUALIZE", "LUT_STRETCH", "lut_identity", "lut_levels", "lut_compose", "stats_lut",
     "brush_remap_apply",
     "VolumeStats", "StatsSummary", "VOLUME_STATS_BYTES", "Stats", "Summary", "brush_stats_host", "box_stats_host",

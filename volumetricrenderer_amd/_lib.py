@@ -170,6 +170,7 @@ BORDER_CLAMP, BORDER_SKIP = 0, 1            # vr.h vr_border
 AFFINE_ONE = 65536                          # vr.h VR_AFFINE_ONE: 1.0 in 16.16
 AFFINE_MAX_COEFF = 256 * 65536              # vr.h VR_AFFINE_MAX_COEFF
 AFFINE_MAX_EXTENT = 32768                   # vr.h VR_AFFINE_MAX_EXTENT
+WARP_MAX_DISP = 32768                       # vr.h VR_WARP_MAX_DISP: texels a vr_warp map may displace under its brush
 
 
 class VolumeStats(ctypes.Structure):
@@ -244,6 +245,12 @@ _SIGS = {
     "vr_affine_identity": (ctypes.c_int, [ctypes.POINTER(Affine)]),
     "vr_affine_place": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.POINTER(Affine)]),
+    "vr_warp": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.POINTER(Affine), _vp]),
+    "vr_brush_warp_apply": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(Affine), _vp, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int]),
+    "vr_warp_reach": (ctypes.c_int, [ctypes.POINTER(Brush), ctypes.POINTER(Affine), ctypes.POINTER(ctypes.c_int32)]),
+    "vr_warp_push": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(Affine)]),
     "vr_remap": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), ctypes.POINTER(Lut), _vp]),
     "vr_remap_device": (ctypes.c_int, [_vp, ctypes.POINTER(Brush), _vp, _vp]),
     "vr_stats_lut_device": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),

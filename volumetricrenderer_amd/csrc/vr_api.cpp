@@ -16,6 +16,7 @@
 #include "vr_blur.h"
 #include "vr_brush.h"
 #include "vr_affine.h"
+#include "vr_warp.h"
 #include "vr_clone.h"
 #include "vr_ctx.h"
 #include "vr_morph.h"
@@ -1000,6 +1001,25 @@ try {
     return box_edited(c, a.o[0], a.o[1], a.o[2], a.e[0], a.e[1], a.e[2], s);
 } catch (...) {
     return caught_exception("vr_clone_affine");
+}
+
+// The liquify brush on the device (vr_warp.h): every check first, then always the staged sequence -- a soft warp reads
+// texels that it writes -- with k_warp_stage as its first launch.
+vr_status vr_warp(void* p, const vr_brush* b, const vr_affine* m, void* stream)
+try {
+    if (!p || !b || !m) return fail(VR_ERR_INVALID, "vr_warp: null argument");
+    if (const char* why = vr::warp::invalid(b, m)) return fail(VR_ERR_INVALID, "vr_warp: %s", why);
+    Ctx* c = as_ctx(p);
+    if (vr_status st = check_target("vr_warp", c)) return st;
+    AffineArgs g{};
+    PaintArgs& a = g.p;
+    if (!vr::brush::clip(b, c->nx, c->ny, c->nz, a.o, a.e)) return VR_OK;   // the brush misses the volume
+    if (!source_brush_args(c, b, a)) return VR_OK;                          // every strength is 0
+    affine_args(m, c->nx, c->ny, c->nz, g);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return staged_brush(c, a, s, "launch_warp_stage", [&] { return launch_warp_stage(g, c->warp_lds != 0, c->d_planar, c->d_blur, s); });
+} catch (...) {
+    return caught_exception("vr_warp");
 }
 
 // The lookup-table brush on the device: every check first, then k_remap over the clipped box -- with the host table

@@ -18,7 +18,10 @@
 // vr_affine_place: the transform paste on the host and its map builders
 // (sec. 5.2.13; the checks, the positions and the filters are vr_affine.h's);
 // vr_brush_fill_apply: the flood-fill brush of vr_fill on the host (sec.
-// 5.2.14; the checks and the passable test are vr_fill.h's).
+// 5.2.14; the checks and the passable test are vr_fill.h's);
+// vr_brush_warp_apply, vr_warp_reach and vr_warp_push: the liquify brush of
+// vr_warp on the host and its push map (sec. 5.2.15; the checks, the reach and
+// the weighted position are vr_warp.h's).
 //
 // Pure host code in integers: no context, no device, no HIP call.  The
 // arithmetic is vr_brush.h's, which the paint kernel (vr_paint.hip) includes
@@ -42,6 +45,7 @@
 #include "vr_rank.h"
 #include "vr_remap.h"
 #include "vr_stats.h"
+#include "vr_warp.h"
 
 #ifdef VR_BRUSH_STANDALONE
 namespace {
@@ -227,9 +231,89 @@ void affine_apply(const vr_brush* b, const vr_affine* m, const int o[3], const i
     });
 }
 
+// The liquify brush on checked arguments (vr_warp.h): the brush over its clipped box o, e of the volume with the value of
+// a texel resampled from the volume itself at the position the weight leaves between the texel's own and its affine
+// one.  What the box reads (vr_warp.h read_range) is copied first and every value reads the copy (Jacobi).
+void warp_apply(const vr_brush* b, const vr_affine* m, const int o[3], const int e[3], uint8_t* rgba8, const int n[3])
+{
+    int lo[3], ext[3];
+    for (int a = 0; a < 3; ++a) {
+        int hi;
+        vr::warp::read_range(m, a, o, e, n[a], &lo[a], &hi);
+        ext[a] = hi - lo[a] + 1;
+    }
+    const Snapshot before(rgba8, n[0], n[1], n[2], lo, ext);
+    const auto byte = [&](int x, int y, int z, int c) -> unsigned { return before.row(y, z)[(size_t)(x - lo[0]) * 4 + (size_t)c]; };
+    const vr::brush::Terms t = vr::brush::terms(b->radius);
+    const bool linear = m->filter == VR_FILTER_LINEAR, skip = m->border == VR_BORDER_SKIP;
+    walk(b, t, o, e, no_row, [&](int, int x, int y, int z, uint64_t q) {
+        if (q > t.s) return;
+        const unsigned w = vr::brush::weight(q, t.s, b->falloff);
+        const int tc[3] = {x, y, z};
+        int64_t p[3];
+        bool out = false;
+        for (int a = 0; a < 3; ++a) {
+            p[a] = vr::warp::position(tc[a], vr::warp::displacement(m->m[a], m->origin[a], m->pivot, x, y, z, tc[a]), w);
+            out = out || vr::affine::outside(p[a], n[a]);
+            p[a] = vr::affine::clamp(p[a], n[a]);
+        }
+        if (out && skip) return;
+        uint8_t* d = rgba8 + ((((size_t)z * (size_t)n[1] + (size_t)y) * (size_t)n[0]) + (size_t)x) * 4;
+        vr::affine::Axis ax[3];
+        int s[3];
+        for (int a = 0; a < 3; ++a) {
+            ax[a] = vr::affine::linear_weights(p[a], n[a]);
+            s[a] = vr::affine::nearest(p[a]);
+        }
+        for (int c = 0; c < 4; ++c) {
+            if (!b->strength[c]) continue;
+            unsigned v;
+            if (linear) {
+                unsigned corner[2][2][2];
+                for (int k = 0; k < 8; ++k)
+                    corner[k >> 2][k >> 1 & 1][k & 1] = byte(k & 1 ? ax[0].j : ax[0].i, k & 2 ? ax[1].j : ax[1].i, k & 4 ? ax[2].j : ax[2].i, c);
+                v = vr::affine::linear_value(corner, ax[0].f, ax[1].f, ax[2].f);
+            } else {
+                v = byte(s[0], s[1], s[2], c);
+            }
+            d[c] = (uint8_t)vr::brush::blend(VR_BRUSH_SET, d[c], v, 256u * b->strength[c]);
+        }
+    });
+}
+
 }  // namespace
 
 extern "C" {
+
+// The liquify brush on the host (include/vr.h): the CPU statement of vr_warp.
+vr_status vr_brush_warp_apply(const vr_brush* b, const vr_affine* m, uint8_t* rgba8, int nx, int ny, int nz)
+{
+    if (vr_status st = check("vr_brush_warp_apply", b && m && rgba8, [&] { return vr::warp::invalid(b, m); }, nx, ny, nz)) return st;
+    int o[3], e[3];
+    if (!vr::brush::clip(b, nx, ny, nz, o, e)) return VR_OK;
+    const int n[3] = {nx, ny, nz};
+    warp_apply(b, m, o, e, rgba8, n);
+    return VR_OK;
+}
+
+vr_status vr_warp_reach(const vr_brush* b, const vr_affine* m, int32_t reach16[3])
+{
+    if (!b || !m || !reach16) return fail(VR_ERR_INVALID, "vr_warp_reach: null argument");
+    if (const char* why = vr::affine::invalid(b, m)) return fail(VR_ERR_INVALID, "vr_warp_reach: %s", why);
+    int64_t r[3];
+    vr::warp::reach(b, m, r);
+    for (int a = 0; a < 3; ++a) reach16[a] = r[a] > 2147483647ll ? 2147483647 : (int32_t)r[a];
+    return VR_OK;
+}
+
+vr_status vr_warp_push(const int32_t centre[3], const int32_t d16[3], int filter, int border, vr_affine* out)
+{
+    if (!centre || !d16 || !out) return fail(VR_ERR_INVALID, "vr_warp_push: null argument");
+    if (filter != VR_FILTER_NEAREST && filter != VR_FILTER_LINEAR) return fail(VR_ERR_INVALID, "vr_warp_push: bad filter");
+    if (border != VR_BORDER_CLAMP && border != VR_BORDER_SKIP) return fail(VR_ERR_INVALID, "vr_warp_push: bad border");
+    if (!vr::warp::push(centre, d16, filter, border, out)) return fail(VR_ERR_INVALID, "vr_warp_push: an origin leaves the 16.16 range");
+    return VR_OK;
+}
 
 // The transform paste of a HOST stamp on the host (include/vr.h): the CPU statement of vr_stamp_affine.
 vr_status vr_brush_stamp_affine_apply(const vr_brush* b, const uint8_t* stamp, int sbx, int sby, int sbz, const vr_affine* m,

@@ -113,6 +113,7 @@ struct Ctx {
     // after a device sync (ensure_blur), reserved by option "blur_scratch_kib", kept across installs
     uint8_t* d_blur = nullptr;
     size_t blur_bytes = 0;
+    int warp_lds = 1;              // option "warp_lds": 0 = vr_warp gathers every tile from the planes, none through LDS
     // uniforms
     bool has_camera = false;
     float obj[48];

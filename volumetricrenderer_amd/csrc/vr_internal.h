@@ -819,6 +819,11 @@ struct AffineArgs {
 hipError_t launch_stamp_affine(const AffineArgs& a, const uint8_t* d_stamp, uint8_t* d_planar, unsigned* mm, hipStream_t s);
 hipError_t launch_clone_affine_direct(const AffineArgs& a, uint8_t* d_planar, unsigned* mm, hipStream_t s);
 hipError_t launch_clone_affine_stage(const AffineArgs& a, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s);
+// vr_warp: the brush (op VR_BRUSH_SET; value is not read) and the validated map (vr_warp.h),
+// n the volume's own extent.  launch_blur_stage's contract and slabs, and launch_blur_commit follows it.  use_lds
+// (option warp_lds): a tile whose read footprint fits the budget stages it in LDS; false = every tile gathers from
+// the planes.  Both give the same bytes.
+hipError_t launch_warp_stage(const AffineArgs& a, bool use_lds, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s);
 // vr_remap / vr_remap_device: the brush as for launch_paint_planar (value is not read) with
 // the value of a texel read from a table at the texel's old byte.  host_lut != null: the table is copied into the
 // kernel's arguments during the call (d_lut is not used); host_lut == null: d_lut, a 4-byte aligned DEVICE vr_lut, is

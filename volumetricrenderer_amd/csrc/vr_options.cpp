@@ -224,6 +224,11 @@ try {
         if (value < 0) return fail(VR_ERR_INVALID, "vr_set_option: blur_scratch_kib >= 0");
         return value == 0 ? release_blur(c) : ensure_blur(c, (size_t)value * 1024);
     }
+    if (n == "warp_lds") {   // vr_warp: tiles whose read footprint fits the budget stage it in LDS
+        if (value < 0 || value > 1) return fail(VR_ERR_INVALID, "vr_set_option: warp_lds is 0 or 1");
+        c->warp_lds = value;
+        return VR_OK;
+    }
     if (n == "lattice") {
         if (value < 0 || value > 1) return fail(VR_ERR_INVALID, "vr_set_option: lattice is 0 or 1");
         c->lattice = value;
@@ -267,6 +272,7 @@ try {
         return (int)std::min<size_t>((b + 1023) / 1024, 0x7fffffff);
     }
     if (n == "blur_scratch_kib") return (int)std::min<size_t>(c->blur_bytes / 1024, 0x7fffffff);   // the KiB held now
+    if (n == "warp_lds") return c->warp_lds;
     if (n == "slab_cap") return c->slab_cap;
     if (n == "region_order") return c->region_order;
     if (n == "sort_reuse") return c->sort_reuse;

@@ -1,7 +1,7 @@
 // vr_paint.hip -- the brush kernels and their launchers: the edits applied in
 // place to the installed volume's planar planes (vr_paint, vr_paint_stroke,
 // vr_blur, vr_morph, vr_rank, vr_clone, vr_stamp, vr_remap, vr_stamp_affine,
-// vr_clone_affine) and the statistics under a brush or in a box
+// vr_clone_affine, vr_warp) and the statistics under a brush or in a box
 // (vr_brush_stats, vr_box_stats, vr_stats_lut_device).  The arithmetic is the
 // brush headers', which the host statements (vr_brush.cpp) include too: every
 // kernel here reproduces its statement bit for bit.
@@ -18,6 +18,7 @@
 #include "vr_remap.h"
 #include "vr_stats.h"
 #include "vr_volume_kernels.h"
+#include "vr_warp.h"
 
 namespace vr {
 namespace {
@@ -1031,6 +1032,180 @@ __global__ __launch_bounds__(kBlock) void k_clone_affine_stage(AffineArgs g, con
     affine_rows<true, LINEAR>(g, src, stage, lo, hi);
 }
 
+// vr_warp, first launch: k_clone_affine_stage's
+// contract -- the planes read only, the new byte of every inside texel and
+// painted channel to the staging slabs, a texel VR_BORDER_SKIP leaves alone
+// staged with its old byte, so k_blur_commit follows unchanged -- with the
+// position of a texel blended with its own by the brush weight (vr_warp.h).
+// The read footprint moves with the texel but stays near it, so a workgroup
+// takes a kWarpT^3 tile of the clipped box, two texels per thread (z and z +
+// kWarpT / 2 of one (x, y)), and
+//  1. every thread forms its texels' weights and clamped positions and the
+//     texels they read per axis (both of a LINEAR position, the nearest of a
+//     NEAREST one); a wave reduce and one LDS atomic per wave and bound leave
+//     the tile's footprint box in LDS;
+//  2. after the barrier every thread reads the same box back.  At most
+//     kWarpBudget texels (and option warp_lds): the box goes to LDS, per
+//     painted channel, as aligned dwords of the plane wherever such a dword
+//     lies inside the planes' allocation and as bytes elsewhere, rows dense;
+//     the corners are then gathered from LDS.  Otherwise (extreme scales, a
+//     collapse) they are gathered from the planes as affine_rows does;
+//  3. either way the filter is vr_affine.h's and the blend the SET blend with
+//     a = 256 * strength.
+// Every thread reaches all three barriers: nothing returns, a tile without a
+// touched texel has an empty footprint (lo > hi) and loads nothing, and every
+// loop is bounded by the tile or by kWarpBudget.
+constexpr int kWarpT = 8, kWarpBudget = 4096;
+static_assert(kWarpT * kWarpT * (kWarpT / 2) == kBlock && kWarpT * kWarpT == 64, "two texels per thread, a wave per z pair");
+
+template <bool LINEAR>
+__global__ __launch_bounds__(kBlock) void k_warp_stage(AffineArgs g, int use_lds, const uint8_t* __restrict__ src,
+                                                       uint8_t* __restrict__ stage)
+{
+    const PaintArgs& a = g.p;
+    __shared__ int fp[6];                                  // the footprint box: first texel per axis, then last
+    __shared__ uint32_t foot32[4 * kWarpBudget / 4];       // a painted channel's footprint, rows dense, per kWarpBudget bytes
+    uint8_t* foot = reinterpret_cast<uint8_t*>(foot32);
+
+    const int tid = threadIdx.x, lx = tid % kWarpT, ly = tid / kWarpT % kWarpT, lz = tid / (kWarpT * kWarpT);
+    const Tile t0 = tile_origin(a, kWarpT, kWarpT, kWarpT);
+    const int x = t0.x + lx, y = t0.y + ly;   // in the box
+    if (tid < 6) fp[tid] = tid < 3 ? 0x7fffffff : -1;
+
+    unsigned wgt[2] = {0u, 0u};     // 0 outside the ellipsoid or the box
+    bool touched[2] = {false, false};
+    long long p[2][3];
+    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
+    const bool column = x < a.e[0] && y < a.e[1];
+    const unsigned long long qxy =
+        column ? brush::axis_term(a.d0[0] + x, a.k[0]) + brush::axis_term(a.d0[1] + y, a.k[1]) : 0ull;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int z = t0.z + lz + j * (kWarpT / 2);
+        p[j][0] = p[j][1] = p[j][2] = 0;
+        if (column && z < a.e[2]) {
+            const unsigned long long q = qxy + brush::axis_term(a.d0[2] + z, a.k[2]);
+            if (q <= a.s) wgt[j] = brush::weight(q, a.s, a.falloff);
+        }
+        if (wgt[j] == 0u) continue;
+        const int t[3] = {a.o[0] + x, a.o[1] + y, a.o[2] + z};
+        bool out = false;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            const long long v =
+                warp::position(t[ax], warp::displacement(g.m[ax], g.origin[ax], g.pivot, t[0], t[1], t[2], t[ax]), wgt[j]);
+            out = out || affine::outside(v, g.n[ax]);
+            p[j][ax] = affine::clamp(v, g.n[ax]);
+        }
+        touched[j] = !(out && g.border == VR_BORDER_SKIP);
+        if (!touched[j]) continue;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            int first, last;
+            if constexpr (LINEAR) {
+                const affine::Axis w = affine::linear_weights(p[j][ax], g.n[ax]);
+                first = w.i; last = w.j;
+            } else {
+                first = last = affine::nearest(p[j][ax]);
+            }
+            mn[ax] = min(mn[ax], first);
+            mx[ax] = max(mx[ax], last);
+        }
+    }
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            mn[ax] = min(mn[ax], __shfl_xor(mn[ax], d));
+            mx[ax] = max(mx[ax], __shfl_xor(mx[ax], d));
+        }
+    __syncthreads();   // fp holds the empty box
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            atomicMin(&fp[ax], mn[ax]);
+            atomicMax(&fp[3 + ax], mx[ax]);
+        }
+    }
+    __syncthreads();
+    const int f0[3] = {fp[0], fp[1], fp[2]};
+    const int ex = fp[3] - f0[0] + 1, ey = fp[4] - f0[1] + 1, ez = fp[5] - f0[2] + 1;   // <= 0 on every axis: no touched texel
+    const bool lds = use_lds != 0 && ex > 0 && (long long)ex * ey * ez <= kWarpBudget;   // workgroup-uniform
+
+    const long long plane = (long long)a.nx * a.ny * a.nz;
+    if (lds) {
+        const int rows = ey * ez, nd = (ex + 6) / 4;   // the dwords a row of ex bytes can meet at any alignment
+        const uint8_t* const end = src + 4 * plane;
+        int k = 0;
+#pragma unroll 1
+        for (int c = 0; c < 4; ++c) {
+            if (a.strength[c] == 0u) continue;
+            const uint8_t* __restrict__ pc = src + c * plane;
+            uint8_t* __restrict__ fl = foot + k * kWarpBudget;
+            for (int i = tid; i < rows * nd; i += kBlock) {   // rows * nd <= 7 * kWarpBudget / 4
+                const int r = i / nd, d = i - r * nd, zi = r / ey, yi = r - zi * ey;
+                const uint8_t* row = pc + ((long long)(f0[2] + zi) * a.ny + (f0[1] + yi)) * a.nx + f0[0];
+                const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 3u), x0 = 4 * d - mis;   // the dword's first byte, in the row
+                if (x0 >= ex) continue;
+                const uint8_t* q = row + x0;   // 4-byte aligned
+                uint8_t* o = fl + r * ex;
+                if (q >= src && q + 4 <= end) {
+                    const uint32_t v = *reinterpret_cast<const uint32_t*>(q);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (x0 + b >= 0 && x0 + b < ex) o[x0 + b] = (uint8_t)(v >> (8 * b));
+                } else {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (x0 + b >= 0 && x0 + b < ex) o[x0 + b] = row[x0 + b];
+                }
+            }
+            ++k;
+        }
+    }
+    __syncthreads();   // the footprint is staged
+
+    const size_t slab = (size_t)a.e[0] * (size_t)a.e[1] * (size_t)a.e[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (wgt[j] == 0u) continue;
+        const int z = t0.z + lz + j * (kWarpT / 2);
+        const long long drow = box_row(a, y, z) + x;
+        const size_t srow = ((size_t)z * (size_t)a.e[1] + (size_t)y) * (size_t)a.e[0] + (size_t)x;
+        const affine::Axis wx = affine::linear_weights(p[j][0], a.nx), wy = affine::linear_weights(p[j][1], a.ny),
+                           wz = affine::linear_weights(p[j][2], a.nz);
+        const int sx = affine::nearest(p[j][0]), sy = affine::nearest(p[j][1]), sz = affine::nearest(p[j][2]);
+        int k = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (a.strength[c] == 0u) continue;
+            const uint8_t* __restrict__ pc = src + c * plane;
+            const unsigned old = pc[drow];
+            unsigned nw = old;
+            if (touched[j]) {
+                const uint8_t* fl = foot + k * kWarpBudget;
+                const auto texel = [&](int tx, int ty, int tz) -> unsigned {
+                    return lds ? fl[((tz - f0[2]) * ey + (ty - f0[1])) * ex + (tx - f0[0])]
+                               : pc[((long long)tz * a.ny + ty) * a.nx + tx];
+                };
+                unsigned v;
+                if constexpr (LINEAR) {
+                    const unsigned gx = 256u - wx.f;
+                    v = affine::linear_yz(texel(wx.i, wy.i, wz.i) * gx + texel(wx.j, wy.i, wz.i) * wx.f,
+                                          texel(wx.i, wy.j, wz.i) * gx + texel(wx.j, wy.j, wz.i) * wx.f,
+                                          texel(wx.i, wy.i, wz.j) * gx + texel(wx.j, wy.i, wz.j) * wx.f,
+                                          texel(wx.i, wy.j, wz.j) * gx + texel(wx.j, wy.j, wz.j) * wx.f, wy.f, wz.f);
+                } else {
+                    v = texel(sx, sy, sz);
+                }
+                nw = brush::blend(VR_BRUSH_SET, old, v, 256u * a.strength[c]);
+            }
+            stage[(size_t)k * slab + srow] = (uint8_t)nw;
+            ++k;
+        }
+    }
+}
+
 // vr_remap / vr_remap_device: k_paint_planar with the
 // value of a texel read from a table at the texel's own old byte
 // (vr_remap.h).  Rows and lanes are k_paint_planar's.  At workgroup start the
@@ -1376,6 +1551,20 @@ hipError_t launch_clone_affine_stage(const AffineArgs& a, const uint8_t* d_plana
     const dim3 g(grid_for((long long)a.p.e[1] * a.p.e[2] * 64)), b(kBlock);
     if (a.filter == VR_FILTER_LINEAR) hipLaunchKernelGGL(k_clone_affine_stage<true>, g, b, 0, s, a, d_planar, d_stage);
     else hipLaunchKernelGGL(k_clone_affine_stage<false>, g, b, 0, s, a, d_planar, d_stage);
+    return hipGetLastError();
+}
+
+// vr_warp: a workgroup per kWarpT^3 tile of the clipped box (at most 64^3 of them), one instantiation per filter
+hipError_t launch_warp_stage(const AffineArgs& a, bool use_lds, const uint8_t* d_planar, uint8_t* d_stage, hipStream_t s)
+{
+    if (!affine_args_ok(a) || !d_planar || !d_stage || a.n[0] != a.p.nx || a.n[1] != a.p.ny || a.n[2] != a.p.nz)
+        return hipErrorInvalidValue;
+    if (a.p.op != VR_BRUSH_SET || (reinterpret_cast<uintptr_t>(d_planar) & 3u) != 0u) return hipErrorInvalidValue;
+    const long long tiles = stage_tiles(a.p, kWarpT, kWarpT, kWarpT);
+    if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+    const dim3 g((unsigned)tiles), b(kBlock);
+    if (a.filter == VR_FILTER_LINEAR) hipLaunchKernelGGL(k_warp_stage<true>, g, b, 0, s, a, use_lds ? 1 : 0, d_planar, d_stage);
+    else hipLaunchKernelGGL(k_warp_stage<false>, g, b, 0, s, a, use_lds ? 1 : 0, d_planar, d_stage);
     return hipGetLastError();
 }
 

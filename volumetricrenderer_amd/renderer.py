@@ -38,7 +38,7 @@ from ._lib import (BRUSH_ADD, BRUSH_SET, BRUSH_SUB, BYTES_PER_PIXEL, CHANNELS, F
                    Rect, Target, VolumeRecipe, VR_MAX_RECTS, VRError, call)
 from ._lib import VOLUME_STATS_BYTES, StatsSummary, VolumeStats
 from ._lib import Box, CloneMap
-from ._lib import BORDER_CLAMP, FILTER_NEAREST, Affine
+from ._lib import BORDER_CLAMP, FILTER_LINEAR, FILTER_NEAREST, Affine
 from ._lib import RANK_MEDIAN
 from ._lib import FILL_REPORT_BYTES, FillReport, FillRule
 from ._lib import LUT_BYTES, LUT_EQUALIZE, LUT_STRETCH, Lut  # noqa: F401
@@ -545,6 +545,40 @@ def brush_clone_affine_apply(brush: Brush, affine: Affine, rgba: np.ndarray) -> 
     return rgba
 
 
+def brush_warp_apply(brush: Brush, affine: Affine, rgba: np.ndarray) -> np.ndarray:
+    """vr_brush_warp_apply: the liquify brush on a host RGBA8 volume shaped
+    (nz, ny, nx, 4) -- every texel under `brush` (op BRUSH_SET) resampled from
+    the volume as it was at a position between its own and the one `affine`
+    maps it to, by the brush weight.  The CPU statement of what
+    :meth:`Renderer.warp` does on the device.  Writes `rgba` and returns it."""
+    if (not isinstance(rgba, np.ndarray) or rgba.dtype != np.uint8 or rgba.ndim != 4 or rgba.shape[3] != 4
+            or not rgba.flags.c_contiguous or not rgba.flags.writeable):
+        raise ValueError("brush_warp_apply: a writeable contiguous uint8 array shaped (nz, ny, nx, 4)")
+    nz, ny, nx, _ = rgba.shape
+    call("vr_brush_warp_apply", ctypes.byref(brush), ctypes.byref(affine), rgba.ctypes.data_as(ctypes.c_void_p), nx, ny, nz)
+    return rgba
+
+
+def warp_reach(brush: Brush, affine: Affine):
+    """vr_warp_reach: per axis the largest displacement ``|A - I|`` (16.16, as
+    ints, saturated at 2**31 - 1) that `affine` asks for at the 8 corners of the
+    brush's unclipped box; :meth:`Renderer.warp` refuses a map that passes
+    ``WARP_MAX_DISP << 16`` on an axis."""
+    r = (ctypes.c_int32 * 3)()
+    call("vr_warp_reach", ctypes.byref(brush), ctypes.byref(affine), r)
+    return tuple(r)
+
+
+def warp_push(centre, d16, filter: int = FILTER_LINEAR, border: int = BORDER_CLAMP) -> Affine:
+    """vr_warp_push: the map with which :meth:`Renderer.warp` pushes what is
+    under a brush at `centre` by `d16` = (dx, dy, dz) in 1/65536 of a texel."""
+    c = (ctypes.c_int32 * 3)(*(int(v) for v in centre))
+    d = (ctypes.c_int32 * 3)(*(int(v) for v in d16))
+    a = Affine()
+    call("vr_warp_push", c, d, int(filter), int(border), ctypes.byref(a))
+    return a
+
+
 def _lut_struct(fn: str, lut) -> Lut:
     """The vr_lut of a (4, 256) uint8 array (or a Lut, as it is): a copy."""
     if isinstance(lut, Lut):
@@ -1021,6 +1055,25 @@ class Renderer:
         which grows by the same rule."""
         b = make_brush(centre, radius, op, falloff, 0, strength)
         call("vr_clone_affine", self._ctx, ctypes.byref(b), ctypes.byref(affine), _stream_handle(stream))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        return brush_box(b, self.volume_dims())
+
+    def warp(self, centre, radius, affine: Affine, falloff: int = 1, strength=(255, 255, 255, 255), stream=None):
+        """Liquify (vr_warp): move what is under the brush -- push
+        (:func:`warp_push`), pinch, bloat or twirl (:func:`affine_place` with
+        `centre` as both centres) -- by an amount that fades out towards the
+        rim.  Every texel under the brush is resampled from the volume as it
+        was before the call at a position between its own and the one `affine`
+        maps it to, blended by the brush weight; `strength` sets how much of
+        the resampled value replaces the old byte.  Bit for bit what
+        :func:`brush_warp_apply` gives on the host.  Returns ``(origin,
+        extent)`` of the brush's clipped box, or None when it misses the
+        volume.  Two launches through :meth:`blur`'s staging scratch
+        (``blur_scratch_kib``), which grows by the same rule; queued on
+        `stream` as :meth:`paint` is."""
+        b = make_brush(centre, radius, BRUSH_SET, falloff, 0, strength)
+        call("vr_warp", self._ctx, ctypes.byref(b), ctypes.byref(affine), _stream_handle(stream))
         if stream is None:
             torch.cuda.current_stream().synchronize()
         return brush_box(b, self.volume_dims())
