@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import affine_spec as af  # noqa: E402
 import clone_spec as cs  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import assert_exact, base  # noqa: E402,F401
 
 DIMS = (ps.NX, ps.NY, ps.NZ)
 VOLUME_BRUSHES = ["interior", "texel", "corner", "outside_centre", "straddle", "whole", "max", "miss"]
@@ -33,18 +34,8 @@ def affine(table, filt=af.NEAREST, border=af.CLAMP):
 
 
 @pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
-
-
-@pytest.fixture(scope="module")
 def stamp():
     return af.stamp_bytes()
-
-
-def assert_exact(got, want):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 # ---- 1. the host statements are the numpy restatement's ---------------------------------------

@@ -14,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import blur_spec as bs  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import assert_exact, base  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vr_blur", "vr_brush_blur_apply")
@@ -22,16 +23,6 @@ NEW = ("vr_blur", "vr_brush_blur_apply")
 def brush(centre, radius, falloff=0, strength=bs.STRENGTH, op=0):
     import volumetricrenderer_amd as vr
     return vr.make_brush(centre, radius, op, falloff, (1, 2, 3, 4), strength)
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
-
-
-def assert_exact(got, want):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 @pytest.mark.parametrize("falloff,fname", ps.FALLOFFS, ids=[n for _, n in ps.FALLOFFS])

@@ -15,6 +15,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import clone_spec as cs  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import assert_exact, base  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIMS = (ps.NX, ps.NY, ps.NZ)
@@ -23,16 +24,6 @@ DIMS = (ps.NX, ps.NY, ps.NZ)
 def brush(centre, radius, op=ps.SET, falloff=0, strength=cs.STRENGTH):
     import volumetricrenderer_amd as vr
     return vr.make_brush(centre, radius, op, falloff, (1, 2, 3, 4), strength)
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
-
-
-def assert_exact(got, want):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def test_the_inputs_tell_wrong_implementations_apart(base):

@@ -16,6 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fill_spec as fs  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import assert_exact  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ["blobs", "snakes", "detour", "edges"]
@@ -34,11 +35,6 @@ def lib_rule(rule):
 def brush(centre, radius, op=0, falloff=0, strength=fs.STRENGTH, value=fs.VALUE):
     import volumetricrenderer_amd as vr
     return vr.make_brush(centre, radius, op, falloff, value, strength)
-
-
-def assert_exact(got, want):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def apply(vol, centre, radius, op, falloff, rule, strength=fs.STRENGTH):

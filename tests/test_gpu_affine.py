@@ -7,7 +7,7 @@ fresh install and the CPU oracle, per layout; uniform channels; refusals.
 Everything is exact.
 
 The volume is paint_spec.base_volume() (37 x 22 x 45 random bytes); frame,
-march and cameras are test_gpu_clone.py's: the reference camera at 64 x 64,
+march and cameras are brush_harness.py's: the reference camera at 64 x 64,
 32 steps.
 """
 import ctypes
@@ -22,6 +22,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import affine_spec as af  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import (FULL, H, LAYOUT_IDS, LAYOUTS, UNIFORM_LAYOUTS, VOLUME_BRUSHES, W, assert_exact,  # noqa: E402,F401
+                           assert_marches, base, check_frame, check_fresh_install, check_needs_a_volume, frame, fresh,
+                           oracle_frame, r, recipe_volume, setup)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,30 +35,6 @@ from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
 
 NX, NY, NZ = ps.NX, ps.NY, ps.NZ
 DIMS = (NX, NY, NZ)
-W = H = 64
-STEPS = 32
-LAYOUTS = [(1, "planar"), (5, "corner8"), (12, "brick4832"), (14, "cornerh"), (15, "col48")]
-LAYOUT_IDS = [n for _, n in LAYOUTS]
-UNIFORM_LAYOUTS = [(12, "brick4832"), (14, "cornerh"), (15, "col48")]
-VOLUME_BRUSHES = ["interior", "texel", "corner", "outside_centre", "straddle", "whole", "max", "miss"]
-FULL = af.FULL
-
-_oracle_frames = {}
-
-
-def oracle_frame(oracle, vol, angles=(0.0, 0.0), density=1.0):
-    """The oracle's frame and executed steps for `vol`, computed once per (volume, camera, density)."""
-    osd, gsd = vr.reference_shader_data(1.0, *angles)
-    obj, glob = vr.shader_data_arrays(osd, gsd)
-    key = (hash(vol.tobytes()), angles, density)
-    if key not in _oracle_frames:
-        _oracle_frames[key] = oracle.render(vol, obj, glob, oracle.march(STEPS, density=density), W, H, FMT_RGBA32F)
-    return _oracle_frames[key]
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
 
 
 @pytest.fixture(scope="module")
@@ -66,45 +45,6 @@ def stamp():
 @pytest.fixture(scope="module")
 def d_stamp(stamp):
     return torch.from_numpy(stamp).cuda()
-
-
-@pytest.fixture(scope="module")
-def r():
-    with vr.Renderer(0) as rr:
-        yield rr
-        rr.set_layout_preference(0)
-
-
-@pytest.fixture(scope="module")
-def fresh():
-    with vr.Renderer(0) as rr:
-        yield rr
-
-
-def setup(rr, pref, vol, angles=(0.0, 0.0), density=1.0):
-    rr.set_option("uniform_skip", 1)
-    rr.set_layout_preference(pref)
-    rr.set_volume(vol)
-    rr.set_shader_data(*vr.reference_shader_data(1.0, *angles))
-    rr.set_march(vr.march_defaults(max_steps=STEPS, density=density))
-
-
-def frame(rr, stream=None):
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    img = rr.render(W, H, FMT_RGBA32F, step_counter=cnt, stream=stream)
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), int(cnt.item())
-
-
-def assert_marches(rr, name):
-    """The intended layout really marches: a silent planar fallback must not pass."""
-    assert rr.kernel_variant.startswith(f"grid_{name}_clamp"), rr.kernel_variant
-
-
-def assert_exact(img, ref):
-    assert img.shape == ref.shape
-    bad = np.argwhere(img != ref)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def affine(table, filt=af.NEAREST, border=af.CLAMP):
@@ -227,37 +167,17 @@ def test_copy_rotate_paste_rerender_on_a_side_stream(r, fresh, oracle, base, pre
     img, steps = frame(r)
     assert_exact(img, want)
     assert steps == want_steps
-    setup(fresh, pref, pasted)
-    assert_marches(fresh, lname)
-    img2, steps2 = frame(fresh)
-    assert_exact(img, img2)
-    assert steps == steps2
+    check_fresh_install(fresh, pref, lname, pasted, img, steps)
 
 
 # ---- 5. uniform channels on the recipe volume --------------------------------------------------
-@pytest.fixture(scope="module")
-def recipe_volume():
-    with vr.Renderer(0) as rr:
-        rr.generate_volume(vr.volume_recipe_defaults(size=32))
-        vol = rr.get_volume()
-    g = int(vol[0, 0, 0, 1])
-    assert (vol[..., 1] == g).all(), "the recipe's G is not uniform"
-    assert all(len(np.unique(vol[..., c])) > 1 for c in (0, 2, 3))
-    return vol, g
 
 
-def check_frame(rr, fresh, oracle, pref, vol, uniform):
+def check_uniform(rr, fresh, oracle, pref, lname, vol, uniform):
     assert bool(rr.get_option("uniform_mask") & 2) == uniform
     assert rr.kernel_variant.endswith("_uG") == uniform
-    img, steps = frame(rr)
-    ref, ref_steps = oracle_frame(oracle, vol)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    assert_exact(rr.get_volume(), vol)
-    setup(fresh, pref, vol)
-    img2, steps2 = frame(fresh)
-    assert_exact(img, img2)
-    assert steps == steps2
+    img, steps = check_frame(rr, oracle, vol)
+    check_fresh_install(fresh, pref, lname, vol, img, steps)
 
 
 @pytest.mark.parametrize("pref,lname", UNIFORM_LAYOUTS, ids=[n for _, n in UNIFORM_LAYOUTS])
@@ -281,14 +201,14 @@ def test_uniform_channel(r, fresh, oracle, recipe_volume, pref, lname):
     new = af.spec_affine(vol, src, table, af.LINEAR, af.CLAMP, centre, radius, ps.SET, 1, FULL)
     assert (new != vol).any() and (new[..., 1] == g).all()
     vol = new
-    check_frame(r, fresh, oracle, pref, vol, True)
+    check_uniform(r, fresh, oracle, pref, lname, vol, True)
     # an ADD paste changes G where it is painted: the bit goes before the next render
     setup(r, pref, vol)
     assert r.get_option("uniform_mask") & 2
     r.clone_affine(centre, radius, affine(table, af.LINEAR), ps.ADD, 1, FULL)
     added = af.spec_affine(vol, None, table, af.LINEAR, af.CLAMP, centre, radius, ps.ADD, 1, FULL)
     assert len(np.unique(added[..., 1])) > 1
-    check_frame(r, fresh, oracle, pref, added, False)
+    check_uniform(r, fresh, oracle, pref, lname, added, False)
     assert_marches(r, lname)
 
 
@@ -356,20 +276,8 @@ def test_refusals(r, base, d_stamp):
     assert r.clone_affine(centre, radius, good, strength=(0, 0, 0, 0)) is not None   # nothing to do is VR_OK too
     assert r.stamp_affine(d_stamp, good, centre, radius, strength=(0, 0, 0, 0)) is not None
     assert np.array_equal(r.get_volume(), base)
-    with vr.Renderer(0) as empty:                                       # no volume installed
-        for call in (lambda: empty.clone_affine(centre, radius, good), lambda: empty.stamp_affine(d_stamp, good, centre, radius)):
-            with pytest.raises(vr.VRError) as e:
-                call()
-            assert e.value.status == 3                                  # VR_ERR_NO_VOLUME
-        assert empty.get_option("blur_scratch_kib") == 0
-    r.set_procedural()                                                  # a procedural medium reads no volume
-    try:
-        for call in (lambda: r.clone_affine(centre, radius, good), lambda: r.stamp_affine(d_stamp, good, centre, radius)):
-            with pytest.raises(vr.VRError) as e:
-                call()
-            assert e.value.status == 3
-    finally:
-        r.set_procedural(vr.procedural_defaults(enabled=0))
+    check_needs_a_volume(r, lambda rr: rr.clone_affine(centre, radius, good),
+                         lambda rr: rr.stamp_affine(d_stamp, good, centre, radius))
     assert np.array_equal(r.get_volume(), base)
 
 

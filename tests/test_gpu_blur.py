@@ -5,7 +5,7 @@ blurred volume and against the CPU oracle, per layout; two blurs and a
 render_rects queued on one side stream; uniform channels; the staging scratch;
 undo; refusals.  Everything is exact.
 
-The volume, frame, march and cameras are test_gpu_paint.py's: 37 x 22 x 45, the
+The volume, frame, march and cameras are brush_harness.py's: 37 x 22 x 45, the
 reference camera at 64 x 64, 32 steps, `straddle` and `whole` from (0, 0).
 """
 import ctypes
@@ -19,6 +19,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import blur_spec as bs  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import (FULL, H, LAYOUT_IDS, LAYOUTS, UNIFORM_LAYOUTS, VOLUME_BRUSHES, W, assert_exact,  # noqa: E402,F401
+                           assert_marches, base, check_frame, check_fresh_install, check_needs_a_volume, frame, fresh,
+                           oracle_frame, r, recipe_volume, setup)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,69 +31,6 @@ from volumetricrenderer_amd import _lib  # noqa: E402
 from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
 
 NX, NY, NZ = ps.NX, ps.NY, ps.NZ
-W = H = 64
-STEPS = 32
-LAYOUTS = [(1, "planar"), (5, "corner8"), (12, "brick4832"), (14, "cornerh"), (15, "col48")]
-LAYOUT_IDS = [n for _, n in LAYOUTS]
-UNIFORM_LAYOUTS = [(12, "brick4832"), (14, "cornerh"), (15, "col48")]
-VOLUME_BRUSHES = ["interior", "texel", "corner", "outside_centre", "straddle", "whole", "max", "miss"]
-FULL = (255, 255, 255, 255)
-
-_oracle_frames = {}
-
-
-def oracle_frame(oracle, vol, angles=(0.0, 0.0), density=1.0):
-    """The oracle's frame and executed steps for `vol`, computed once per (volume, camera, density)."""
-    osd, gsd = vr.reference_shader_data(1.0, *angles)
-    obj, glob = vr.shader_data_arrays(osd, gsd)
-    key = (hash(vol.tobytes()), angles, density)
-    if key not in _oracle_frames:
-        _oracle_frames[key] = oracle.render(vol, obj, glob, oracle.march(STEPS, density=density), W, H, FMT_RGBA32F)
-    return _oracle_frames[key]
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
-
-
-@pytest.fixture(scope="module")
-def r():
-    with vr.Renderer(0) as rr:
-        yield rr
-        rr.set_layout_preference(0)
-
-
-@pytest.fixture(scope="module")
-def fresh():
-    with vr.Renderer(0) as rr:
-        yield rr
-
-
-def setup(rr, pref, vol, angles=(0.0, 0.0), density=1.0):
-    rr.set_option("uniform_skip", 1)
-    rr.set_layout_preference(pref)
-    rr.set_volume(vol)
-    rr.set_shader_data(*vr.reference_shader_data(1.0, *angles))
-    rr.set_march(vr.march_defaults(max_steps=STEPS, density=density))
-
-
-def frame(rr, stream=None):
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    img = rr.render(W, H, FMT_RGBA32F, step_counter=cnt, stream=stream)
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), int(cnt.item())
-
-
-def assert_marches(rr, name):
-    """The intended layout really marches: a silent planar fallback must not pass."""
-    assert rr.kernel_variant.startswith(f"grid_{name}_clamp"), rr.kernel_variant
-
-
-def assert_exact(img, ref):
-    assert img.shape == ref.shape
-    bad = np.argwhere(img != ref)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def blur(rr, name, h, falloff, strength=bs.STRENGTH, stream=None):
@@ -146,15 +86,8 @@ def test_blurred_render_equals_fresh_install(r, fresh, oracle, base, pref, lname
         assert (ref != before).any(), "the blur does not change the oracle's frame"
         blur(r, name, h, 1)
         assert_marches(r, lname)
-        img, steps = frame(r)
-        assert_exact(img, ref)
-        assert steps == ref_steps
-        assert_exact(r.get_volume(), vol)
-        setup(fresh, pref, vol)
-        assert_marches(fresh, lname)
-        img2, steps2 = frame(fresh)
-        assert_exact(img, img2)
-        assert steps == steps2
+        img, steps = check_frame(r, oracle, vol)
+        check_fresh_install(fresh, pref, lname, vol, img, steps)
 
 
 # ---- 4. one stream, no host wait ---------------------------------------------------------------
@@ -183,15 +116,6 @@ def test_two_blurs_then_render_rects_on_a_side_stream(r, oracle, base, pref, lna
 
 
 # ---- 5. uniform channels on the recipe volume --------------------------------------------------
-@pytest.fixture(scope="module")
-def recipe_volume():
-    with vr.Renderer(0) as rr:
-        rr.generate_volume(vr.volume_recipe_defaults(size=32))
-        vol = rr.get_volume()
-    g = int(vol[0, 0, 0, 1])
-    assert (vol[..., 1] == g).all(), "the recipe's G is not uniform"
-    assert all(len(np.unique(vol[..., c])) > 1 for c in (0, 2, 3))
-    return vol, g
 
 
 @pytest.mark.parametrize("pref,lname", UNIFORM_LAYOUTS, ids=[n for _, n in UNIFORM_LAYOUTS])
@@ -204,16 +128,9 @@ def test_uniform_channel(r, fresh, oracle, recipe_volume, pref, lname):
     blurred = bs.spec_blur(vol, centre, radius, 2, 1, FULL)
     assert (blurred != vol).any() and (blurred[..., 1] == g).all()
     assert r.get_option("uniform_mask") & 2 and r.kernel_variant.endswith("_uG")
-    img, steps = frame(r)
-    ref, ref_steps = oracle_frame(oracle, blurred)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    assert_exact(r.get_volume(), blurred)
-    setup(fresh, pref, blurred)
+    img, steps = check_frame(r, oracle, blurred)
+    check_fresh_install(fresh, pref, lname, blurred, img, steps)
     assert fresh.kernel_variant.endswith("_uG")
-    img2, steps2 = frame(fresh)
-    assert_exact(img, img2)
-    assert steps == steps2
     # a paint breaks G; the blur that follows spreads the dab and still renders exactly
     value = (0, (g + 120) % 256, 0, 0)
     r.paint((16, 16, 16), (3, 3, 3), ps.SET, 0, value, (0, 255, 0, 0))
@@ -223,11 +140,7 @@ def test_uniform_channel(r, fresh, oracle, recipe_volume, pref, lname):
     assert len(np.unique(final[..., 1])) > 2
     assert r.get_option("uniform_mask") & 2 == 0
     assert_marches(r, lname)
-    img, steps = frame(r)
-    ref, ref_steps = oracle_frame(oracle, final)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    assert_exact(r.get_volume(), final)
+    check_frame(r, oracle, final)
 
 
 # ---- 6. the staging scratch --------------------------------------------------------------------
@@ -307,16 +220,5 @@ def test_refusals(r, base):
     assert r.blur((-10, -10, -10), (4, 4, 4)) is None             # a miss is VR_OK
     assert r.blur(strength=(0, 0, 0, 0), **good) is not None      # nothing to do is VR_OK too
     assert np.array_equal(r.get_volume(), base)
-    with vr.Renderer(0) as empty:                                 # no volume installed
-        with pytest.raises(vr.VRError) as e:
-            empty.blur(**good)
-        assert e.value.status == 3                                # VR_ERR_NO_VOLUME
-        assert empty.get_option("blur_scratch_kib") == 0
-    r.set_procedural()                                            # a procedural medium reads no volume
-    try:
-        with pytest.raises(vr.VRError) as e:
-            r.blur(**good)
-        assert e.value.status == 3
-    finally:
-        r.set_procedural(vr.procedural_defaults(enabled=0))
+    check_needs_a_volume(r, lambda rr: rr.blur(**good))
     assert np.array_equal(r.get_volume(), base)

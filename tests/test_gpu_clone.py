@@ -7,7 +7,7 @@ CPU oracle, per layout; pick -> clone -> footprint -> render_rect on one side
 stream; uniform channels; refusals.  Everything is exact.
 
 The volume is paint_spec.base_volume() (37 x 22 x 45 random bytes); frame,
-march and cameras are test_gpu_paint.py's: the reference camera at 64 x 64,
+march and cameras are brush_harness.py's: the reference camera at 64 x 64,
 32 steps.
 """
 import ctypes
@@ -23,6 +23,9 @@ import blur_spec as bs  # noqa: E402
 import clone_spec as cs  # noqa: E402
 import morph_spec as ms  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import (FULL, H, LAYOUT_IDS, LAYOUTS, UNIFORM_LAYOUTS, VOLUME_BRUSHES, W, assert_exact,  # noqa: E402,F401
+                           assert_marches, base, check_frame, check_fresh_install, check_needs_a_volume, frame, fresh,
+                           oracle_frame, r, recipe_volume, setup)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,69 +36,6 @@ from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
 
 NX, NY, NZ = ps.NX, ps.NY, ps.NZ
 DIMS = (NX, NY, NZ)
-W = H = 64
-STEPS = 32
-LAYOUTS = [(1, "planar"), (5, "corner8"), (12, "brick4832"), (14, "cornerh"), (15, "col48")]
-LAYOUT_IDS = [n for _, n in LAYOUTS]
-UNIFORM_LAYOUTS = [(12, "brick4832"), (14, "cornerh"), (15, "col48")]
-VOLUME_BRUSHES = ["interior", "texel", "corner", "outside_centre", "straddle", "whole", "max", "miss"]
-FULL = cs.FULL
-
-_oracle_frames = {}
-
-
-def oracle_frame(oracle, vol, angles=(0.0, 0.0), density=1.0):
-    """The oracle's frame and executed steps for `vol`, computed once per (volume, camera, density)."""
-    osd, gsd = vr.reference_shader_data(1.0, *angles)
-    obj, glob = vr.shader_data_arrays(osd, gsd)
-    key = (hash(vol.tobytes()), angles, density)
-    if key not in _oracle_frames:
-        _oracle_frames[key] = oracle.render(vol, obj, glob, oracle.march(STEPS, density=density), W, H, FMT_RGBA32F)
-    return _oracle_frames[key]
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
-
-
-@pytest.fixture(scope="module")
-def r():
-    with vr.Renderer(0) as rr:
-        yield rr
-        rr.set_layout_preference(0)
-
-
-@pytest.fixture(scope="module")
-def fresh():
-    with vr.Renderer(0) as rr:
-        yield rr
-
-
-def setup(rr, pref, vol, angles=(0.0, 0.0), density=1.0):
-    rr.set_option("uniform_skip", 1)
-    rr.set_layout_preference(pref)
-    rr.set_volume(vol)
-    rr.set_shader_data(*vr.reference_shader_data(1.0, *angles))
-    rr.set_march(vr.march_defaults(max_steps=STEPS, density=density))
-
-
-def frame(rr, stream=None):
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    img = rr.render(W, H, FMT_RGBA32F, step_counter=cnt, stream=stream)
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), int(cnt.item())
-
-
-def assert_marches(rr, name):
-    """The intended layout really marches: a silent planar fallback must not pass."""
-    assert rr.kernel_variant.startswith(f"grid_{name}_clamp"), rr.kernel_variant
-
-
-def assert_exact(img, ref):
-    assert img.shape == ref.shape
-    bad = np.argwhere(img != ref)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def clone(rr, name, mname, op=ps.SET, falloff=0, strength=cs.STRENGTH, stream=None):
@@ -313,15 +253,8 @@ def test_edited_render_equals_fresh_install(r, fresh, oracle, base, pref, lname)
         assert (ref != before).any(), "the edit does not change the oracle's frame"
         assert apply() is not None
         assert_marches(r, lname)
-        img, steps = frame(r)
-        assert_exact(img, ref)
-        assert steps == ref_steps
-        assert_exact(r.get_volume(), vol)
-        setup(fresh, pref, vol)
-        assert_marches(fresh, lname)
-        img2, steps2 = frame(fresh)
-        assert_exact(img, img2)
-        assert steps == steps2
+        img, steps = check_frame(r, oracle, vol)
+        check_fresh_install(fresh, pref, lname, vol, img, steps)
 
 
 # ---- 6. one stream, no host wait ---------------------------------------------------------------
@@ -361,29 +294,13 @@ def test_pick_clone_footprint_rerender_on_a_side_stream(r, oracle, base, pref, l
 
 
 # ---- 7. uniform channels on the recipe volume --------------------------------------------------
-@pytest.fixture(scope="module")
-def recipe_volume():
-    with vr.Renderer(0) as rr:
-        rr.generate_volume(vr.volume_recipe_defaults(size=32))
-        vol = rr.get_volume()
-    g = int(vol[0, 0, 0, 1])
-    assert (vol[..., 1] == g).all(), "the recipe's G is not uniform"
-    assert all(len(np.unique(vol[..., c])) > 1 for c in (0, 2, 3))
-    return vol, g
 
 
-def check_frame(rr, fresh, oracle, pref, vol, uniform):
+def check_uniform(rr, fresh, oracle, pref, lname, vol, uniform):
     assert bool(rr.get_option("uniform_mask") & 2) == uniform
     assert rr.kernel_variant.endswith("_uG") == uniform
-    img, steps = frame(rr)
-    ref, ref_steps = oracle_frame(oracle, vol)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    assert_exact(rr.get_volume(), vol)
-    setup(fresh, pref, vol)
-    img2, steps2 = frame(fresh)
-    assert_exact(img, img2)
-    assert steps == steps2
+    img, steps = check_frame(rr, oracle, vol)
+    check_fresh_install(fresh, pref, lname, vol, img, steps)
 
 
 @pytest.mark.parametrize("pref,lname", UNIFORM_LAYOUTS, ids=[n for _, n in UNIFORM_LAYOUTS])
@@ -399,14 +316,14 @@ def test_uniform_channel(r, fresh, oracle, recipe_volume, pref, lname):
         new = cs.spec_clone(vol, centre, radius, offset, mirror, ps.SET, 1, FULL)
         assert (new != vol).any() and (new[..., 1] == g).all()
         vol = new
-    check_frame(r, fresh, oracle, pref, vol, True)
+    check_uniform(r, fresh, oracle, pref, lname, vol, True)
     # an ADD clone changes G where it is painted: the bit goes before the next render
     setup(r, pref, vol)
     assert r.get_option("uniform_mask") & 2
     r.clone(centre, radius, (14, 0, 0), (0, 0, 0), ps.ADD, 1, FULL)
     added = cs.spec_clone(vol, centre, radius, (14, 0, 0), (0, 0, 0), ps.ADD, 1, FULL)
     assert len(np.unique(added[..., 1])) > 1
-    check_frame(r, fresh, oracle, pref, added, False)
+    check_uniform(r, fresh, oracle, pref, lname, added, False)
     assert_marches(r, lname)
     # a stamp that changes G loses the bit too; one that leaves G alone (strength 0) keeps it
     setup(r, pref, vol)
@@ -416,12 +333,12 @@ def test_uniform_channel(r, fresh, oracle, recipe_volume, pref, lname):
     r.stamp(d_stamp, origin, centre, radius, ps.SET, 1, (255, 0, 255, 255))
     kept = cs.spec_stamp(vol, stamp, origin, centre, radius, ps.SET, 1, (255, 0, 255, 255))
     assert (kept != vol).any() and (kept[..., 1] == g).all()
-    check_frame(r, fresh, oracle, pref, kept, True)
+    check_uniform(r, fresh, oracle, pref, lname, kept, True)
     setup(r, pref, vol)
     r.stamp(d_stamp, origin, centre, radius, ps.SET, 1, FULL)
     stamped = cs.spec_stamp(vol, stamp, origin, centre, radius, ps.SET, 1, FULL)
     assert len(np.unique(stamped[..., 1])) > 1
-    check_frame(r, fresh, oracle, pref, stamped, False)
+    check_uniform(r, fresh, oracle, pref, lname, stamped, False)
     assert_marches(r, lname)
 
 
@@ -471,18 +388,5 @@ def test_refusals(r, base):
     assert r.stamp(strength=(0, 0, 0, 0), **sgood) is not None
     assert r.stamp(**dict(sgood, placement_origin=(30, 10, 22))) is None
     assert np.array_equal(r.get_volume(), base)
-    with vr.Renderer(0) as empty:                                       # no volume installed
-        for call in (lambda: empty.clone(**good), lambda: empty.stamp(**sgood)):
-            with pytest.raises(vr.VRError) as e:
-                call()
-            assert e.value.status == 3                                  # VR_ERR_NO_VOLUME
-        assert empty.get_option("blur_scratch_kib") == 0
-    r.set_procedural()                                                  # a procedural medium reads no volume
-    try:
-        for call in (lambda: r.clone(**good), lambda: r.stamp(**sgood)):
-            with pytest.raises(vr.VRError) as e:
-                call()
-            assert e.value.status == 3
-    finally:
-        r.set_procedural(vr.procedural_defaults(enabled=0))
+    check_needs_a_volume(r, lambda rr: rr.clone(**good), lambda rr: rr.stamp(**sgood))
     assert np.array_equal(r.get_volume(), base)

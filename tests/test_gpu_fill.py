@@ -7,7 +7,7 @@ specification's volume and against the CPU oracle, per layout; a fill and a
 render_rect queued on one side stream; uniform channels; the scratch it shares
 with vr_blur; undo; refusals.  Everything is exact.
 
-Frame, march and cameras are test_gpu_paint.py's: the reference camera at
+Frame, march and cameras are brush_harness.py's: the reference camera at
 64 x 64, 32 steps.
 """
 import ctypes
@@ -22,6 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import blur_spec as bs  # noqa: E402
 import fill_spec as fs  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import (H, LAYOUT_IDS, LAYOUTS, UNIFORM_LAYOUTS, W, assert_exact, assert_marches, check_frame,  # noqa: E402,F401
+                           check_fresh_install, check_needs_a_volume, frame, fresh, oracle_frame, r, recipe_volume, setup)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,68 +34,12 @@ from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
 
 NX, NY, NZ = ps.NX, ps.NY, ps.NZ
 DIMS = (NX, NY, NZ)
-W = H = 64
-STEPS = 32
-LAYOUTS = [(1, "planar"), (5, "corner8"), (12, "brick4832"), (14, "cornerh"), (15, "col48")]
-LAYOUT_IDS = [n for _, n in LAYOUTS]
-UNIFORM_LAYOUTS = [(12, "brick4832"), (14, "cornerh"), (15, "col48")]
 CASES = ["blobs", "snakes", "detour", "edges"]
-
-_oracle_frames = {}
-
-
-def oracle_frame(oracle, vol, angles=(0.0, 0.0), density=1.0):
-    """The oracle's frame and executed steps for `vol`, computed once per (volume, camera, density)."""
-    osd, gsd = vr.reference_shader_data(1.0, *angles)
-    obj, glob = vr.shader_data_arrays(osd, gsd)
-    key = (hash(vol.tobytes()), angles, density)
-    if key not in _oracle_frames:
-        _oracle_frames[key] = oracle.render(vol, obj, glob, oracle.march(STEPS, density=density), W, H, FMT_RGBA32F)
-    return _oracle_frames[key]
 
 
 @pytest.fixture(scope="module")
 def cases():
     return fs.cases()
-
-
-@pytest.fixture(scope="module")
-def r():
-    with vr.Renderer(0) as rr:
-        yield rr
-        rr.set_layout_preference(0)
-
-
-@pytest.fixture(scope="module")
-def fresh():
-    with vr.Renderer(0) as rr:
-        yield rr
-
-
-def setup(rr, pref, vol, angles=(0.0, 0.0), density=1.0):
-    rr.set_option("uniform_skip", 1)
-    rr.set_layout_preference(pref)
-    rr.set_volume(vol)
-    rr.set_shader_data(*vr.reference_shader_data(1.0, *angles))
-    rr.set_march(vr.march_defaults(max_steps=STEPS, density=density))
-
-
-def frame(rr, stream=None):
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    img = rr.render(W, H, FMT_RGBA32F, step_counter=cnt, stream=stream)
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), int(cnt.item())
-
-
-def assert_marches(rr, name):
-    """The intended layout really marches: a silent planar fallback must not pass."""
-    assert rr.kernel_variant.startswith(f"grid_{name}_clamp"), rr.kernel_variant
-
-
-def assert_exact(img, ref):
-    assert img.shape == ref.shape
-    bad = np.argwhere(img != ref)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def lib_rule(rule):
@@ -244,15 +190,8 @@ def test_filled_render_equals_fresh_install(r, fresh, oracle, cases, pref, lname
         box, rep = fill(r, centre, radius, op, 1, rule, fs.FULL)
         assert rep == want_rep
         assert_marches(r, lname)
-        img, steps = frame(r)
-        assert_exact(img, ref)
-        assert steps == ref_steps
-        assert_exact(r.get_volume(), vol)
-        setup(fresh, pref, vol)
-        assert_marches(fresh, lname)
-        img2, steps2 = frame(fresh)
-        assert_exact(img, img2)
-        assert steps == steps2
+        img, steps = check_frame(r, oracle, vol)
+        check_fresh_install(fresh, pref, lname, vol, img, steps)
 
 
 # ---- 5. one stream, no host wait ---------------------------------------------------------------
@@ -286,15 +225,6 @@ def test_a_fill_then_render_rect_on_a_side_stream(r, oracle, cases, pref, lname)
 
 
 # ---- 6. uniform channels on the recipe volume --------------------------------------------------
-@pytest.fixture(scope="module")
-def recipe_volume():
-    with vr.Renderer(0) as rr:
-        rr.generate_volume(vr.volume_recipe_defaults(size=32))
-        vol = rr.get_volume()
-    g = int(vol[0, 0, 0, 1])
-    assert (vol[..., 1] == g).all(), "the recipe's G is not uniform"
-    assert all(len(np.unique(vol[..., c])) > 1 for c in (0, 2, 3))
-    return vol, g
 
 
 @pytest.mark.parametrize("pref,lname", UNIFORM_LAYOUTS, ids=[n for _, n in UNIFORM_LAYOUTS])
@@ -311,11 +241,7 @@ def test_uniform_channel(r, fresh, oracle, recipe_volume, pref, lname):
     kept, rep = fs.spec_fill(vol, centre, radius, ps.SET, 1, rule, value=value, strength=fs.FULL)
     assert rep[0] > 1 and (kept != vol).any() and (kept[..., 1] == g).all()
     assert r.get_option("uniform_mask") & 2 and r.kernel_variant.endswith("_uG")
-    img, steps = frame(r)
-    ref, ref_steps = oracle_frame(oracle, kept)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    assert_exact(r.get_volume(), kept)
+    check_frame(r, oracle, kept)
     # one that changes a byte of G loses it before the next render
     value = (200, (g + 90) % 256, 60, 255)
     rule2 = fs.Rule(seed, (255, 0, 0, 0), (255, 0, 0, 0), (1, 0, 0, 0), 1)
@@ -414,16 +340,5 @@ def test_refusals(r, cases):
     assert r.fill(None, (-10, -10, -10), (4, 4, 4), rule=rule()) is None               # a miss is VR_OK
     assert r.fill(None, (17, 11, 23), (3, 2, 4), strength=0, rule=rule()) is not None  # nothing to do is VR_OK too
     assert np.array_equal(r.get_volume(), base)
-    with vr.Renderer(0) as empty:                                  # no volume installed
-        with pytest.raises(vr.VRError) as e:
-            empty.fill(None, (17, 11, 23), (3, 2, 4), rule=rule())
-        assert e.value.status == 3                                 # VR_ERR_NO_VOLUME
-        assert empty.get_option("blur_scratch_kib") == 0
-    r.set_procedural()                                             # a procedural medium reads no volume
-    try:
-        with pytest.raises(vr.VRError) as e:
-            r.fill(None, (17, 11, 23), (3, 2, 4), rule=rule())
-        assert e.value.status == 3
-    finally:
-        r.set_procedural(vr.procedural_defaults(enabled=0))
+    check_needs_a_volume(r, lambda rr: rr.fill(None, (17, 11, 23), (3, 2, 4), rule=rule()))
     assert np.array_equal(r.get_volume(), base)

@@ -5,9 +5,9 @@ channels; stream order; the pick -> paint -> footprint -> re-render loop; undo
 through vr_get_volume_box; refusals.  Everything is exact (volumes byte for
 byte, frames bit for bit, step counters equal).
 
-The volume, frame and march are test_gpu_update.py's: 37 x 22 x 45 (no axis a
-multiple of a brick edge), the reference camera at 64 x 64, 32 steps.  As
-there, a march that sparse sees a small edit from few angles only, so the two
+The volume, frame and march are tests/brush_harness.py's: 37 x 22 x 45 (no axis
+a multiple of a brick edge), the reference camera at 64 x 64, 32 steps.  As in
+test_gpu_update.py, a march that sparse sees a small edit from few angles only, so the two
 small brushes render from the (phi, theta) of a 30-degree grid at which the
 ORACLE's frame changes in the most pixels under both tested blends: `corner`
 from (210, 60) (120 and 134 pixels; 27 and 29 at (0, 0)) and `outside_centre`
@@ -24,6 +24,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import paint_spec as ps  # noqa: E402
+from brush_harness import (H, LAYOUT_IDS, LAYOUTS, W, assert_exact, assert_marches, base, check_frame,  # noqa: E402,F401
+                           check_fresh_install, check_needs_a_volume, frame, fresh, oracle_frame, r, setup)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,70 +35,10 @@ from volumetricrenderer_amd import _lib  # noqa: E402
 from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
 
 NX, NY, NZ = ps.NX, ps.NY, ps.NZ
-W = H = 64
-STEPS = 32
-LAYOUTS = [(1, "planar"), (5, "corner8"), (12, "brick4832"), (14, "cornerh"), (15, "col48")]
-LAYOUT_IDS = [n for _, n in LAYOUTS]
 UNIFORM_VARIANTS = {12, 14, 15}   # the layouts whose march has the _uX (no loads for one channel) kernels
 RENDER_BRUSHES = {"straddle": (0.0, 0.0), "corner": (210.0, 60.0), "outside_centre": (210.0, 0.0),
                   "whole": (0.0, 0.0)}
 RENDER_MODES = [(ps.SET, 1, "smooth_set"), (ps.ADD, 0, "hard_add")]
-
-_oracle_frames = {}
-
-
-def oracle_frame(oracle, vol, angles=(0.0, 0.0), density=1.0):
-    """The oracle's frame and executed steps for `vol`, computed once per (volume, camera, density)."""
-    osd, gsd = vr.reference_shader_data(1.0, *angles)
-    obj, glob = vr.shader_data_arrays(osd, gsd)
-    key = (hash(vol.tobytes()), angles, density)
-    if key not in _oracle_frames:
-        _oracle_frames[key] = oracle.render(vol, obj, glob, oracle.march(STEPS, density=density), W, H, FMT_RGBA32F)
-    return _oracle_frames[key]
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
-
-
-@pytest.fixture(scope="module")
-def r():
-    with vr.Renderer(0) as rr:
-        yield rr
-        rr.set_layout_preference(0)
-
-
-@pytest.fixture(scope="module")
-def fresh():
-    with vr.Renderer(0) as rr:
-        yield rr
-
-
-def setup(rr, pref, vol, angles=(0.0, 0.0), density=1.0):
-    rr.set_option("uniform_skip", 1)
-    rr.set_layout_preference(pref)
-    rr.set_volume(vol)
-    rr.set_shader_data(*vr.reference_shader_data(1.0, *angles))
-    rr.set_march(vr.march_defaults(max_steps=STEPS, density=density))
-
-
-def frame(rr, stream=None):
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    img = rr.render(W, H, FMT_RGBA32F, step_counter=cnt, stream=stream)
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), int(cnt.item())
-
-
-def assert_marches(rr, name):
-    """The intended layout really marches: a silent planar fallback must not pass."""
-    assert rr.kernel_variant.startswith(f"grid_{name}_clamp"), rr.kernel_variant
-
-
-def assert_exact(img, ref):
-    assert img.shape == ref.shape
-    bad = np.argwhere(img != ref)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def paint(rr, name, op, falloff, value=ps.VALUE, strength=ps.STRENGTH, stream=None):
@@ -138,15 +80,8 @@ def test_painted_render_equals_fresh_install(r, fresh, oracle, base, pref, lname
     assert_exact(pre, before)
     paint(r, name, op, falloff)
     assert_marches(r, lname)
-    img, steps = frame(r)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    assert_exact(r.get_volume(), painted)
-    setup(fresh, pref, painted, angles)
-    assert_marches(fresh, lname)
-    img2, steps2 = frame(fresh)
-    assert_exact(img, img2)
-    assert steps == steps2
+    img, steps = check_frame(r, oracle, painted, angles)
+    check_fresh_install(fresh, pref, lname, painted, img, steps, angles)
 
 
 # ---- 3. uniform channels ---------------------------------------------------------------------
@@ -171,11 +106,7 @@ def test_uniform_channel(r, oracle, base, pref, lname):
         assert bool(r.get_option("uniform_mask") & 2) == keeps, what
         assert r.kernel_variant.endswith("_uG") == (keeps and pref in UNIFORM_VARIANTS), what
         assert_marches(r, lname)
-        img, steps = frame(r)
-        ref, ref_steps = oracle_frame(oracle, painted)
-        assert_exact(img, ref)
-        assert steps == ref_steps, what
-        assert_exact(r.get_volume(), painted)
+        check_frame(r, oracle, painted)
 
 
 # ---- 4. one stream, no host wait -------------------------------------------------------------
@@ -309,19 +240,10 @@ def test_refusals(r, base):
     assert np.array_equal(r.get_volume(), base)
     with pytest.raises(ValueError):   # the wrapper's shape check
         r.get_volume_box((0, 0, 0), (2, 2, 2), out=torch.zeros((2, 2, 3, 4), dtype=torch.uint8, device="cuda"))
-    with vr.Renderer(0) as empty:     # no volume installed
-        with pytest.raises(vr.VRError) as e:
-            empty.paint(**good)
-        assert e.value.status == 3    # VR_ERR_NO_VOLUME
+    check_needs_a_volume(r, lambda rr: rr.paint(**good))
+    with vr.Renderer(0) as empty:     # no volume installed: no box to read back either
         for fn, tail in (("vr_get_volume_box", (hp,)), ("vr_get_volume_box_device", (dp, None))):
             with pytest.raises(vr.VRError) as e:
                 _lib.call(fn, empty._ctx, 0, 0, 0, 1, 1, 1, *tail)
             assert e.value.status == 3
-    r.set_procedural()                # a procedural medium reads no volume: nothing to paint
-    try:
-        with pytest.raises(vr.VRError) as e:
-            r.paint(**good)
-        assert e.value.status == 3
-    finally:
-        r.set_procedural(vr.procedural_defaults(enabled=0))
     assert np.array_equal(r.get_volume(), base)

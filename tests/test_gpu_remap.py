@@ -9,7 +9,7 @@ layout; uniform channels; a remap among a blur and a staged clone; refusals.
 Everything is exact.
 
 The volume is paint_spec.base_volume() (37 x 22 x 45 random bytes); frame,
-march and cameras are test_gpu_clone.py's: the reference camera at 64 x 64,
+march and cameras are brush_harness.py's: the reference camera at 64 x 64,
 32 steps.
 """
 import ctypes
@@ -25,6 +25,9 @@ import blur_spec as bs  # noqa: E402
 import clone_spec as cs  # noqa: E402
 import paint_spec as ps  # noqa: E402
 import remap_spec as rs  # noqa: E402
+from brush_harness import (FULL, H, LAYOUT_IDS, LAYOUTS, UNIFORM_LAYOUTS, VOLUME_BRUSHES, W, assert_exact,  # noqa: E402,F401
+                           assert_marches, base, check_frame, check_fresh_install, frame, fresh, oracle_frame, r,
+                           recipe_volume, setup)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,75 +38,12 @@ from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
 
 NX, NY, NZ = ps.NX, ps.NY, ps.NZ
 DIMS = (NX, NY, NZ)
-W = H = 64
-STEPS = 32
-LAYOUTS = [(1, "planar"), (5, "corner8"), (12, "brick4832"), (14, "cornerh"), (15, "col48")]
-LAYOUT_IDS = [n for _, n in LAYOUTS]
-UNIFORM_LAYOUTS = [(12, "brick4832"), (14, "cornerh"), (15, "col48")]
-VOLUME_BRUSHES = ["interior", "texel", "corner", "outside_centre", "straddle", "whole", "max", "miss"]
-FULL = rs.FULL
 T = rs.TABLES
-
-_oracle_frames = {}
-
-
-def oracle_frame(oracle, vol, angles=(0.0, 0.0), density=1.0):
-    """The oracle's frame and executed steps for `vol`, computed once per (volume, camera, density)."""
-    osd, gsd = vr.reference_shader_data(1.0, *angles)
-    obj, glob = vr.shader_data_arrays(osd, gsd)
-    key = (hash(vol.tobytes()), angles, density)
-    if key not in _oracle_frames:
-        _oracle_frames[key] = oracle.render(vol, obj, glob, oracle.march(STEPS, density=density), W, H, FMT_RGBA32F)
-    return _oracle_frames[key]
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
 
 
 @pytest.fixture(scope="module")
 def skewed():
     return rs.skewed_volume()
-
-
-@pytest.fixture(scope="module")
-def r():
-    with vr.Renderer(0) as rr:
-        yield rr
-        rr.set_layout_preference(0)
-
-
-@pytest.fixture(scope="module")
-def fresh():
-    with vr.Renderer(0) as rr:
-        yield rr
-
-
-def setup(rr, pref, vol, angles=(0.0, 0.0), density=1.0):
-    rr.set_option("uniform_skip", 1)
-    rr.set_layout_preference(pref)
-    rr.set_volume(vol)
-    rr.set_shader_data(*vr.reference_shader_data(1.0, *angles))
-    rr.set_march(vr.march_defaults(max_steps=STEPS, density=density))
-
-
-def frame(rr, stream=None):
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    img = rr.render(W, H, FMT_RGBA32F, step_counter=cnt, stream=stream)
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), int(cnt.item())
-
-
-def assert_marches(rr, name):
-    """The intended layout really marches: a silent planar fallback must not pass."""
-    assert rr.kernel_variant.startswith(f"grid_{name}_clamp"), rr.kernel_variant
-
-
-def assert_exact(img, ref):
-    assert img.shape == ref.shape
-    bad = np.argwhere(img != ref)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def dev(lut):
@@ -301,10 +241,7 @@ def test_stats_table_remap_footprint_rerender_on_a_side_stream(r, fresh, oracle,
     img, steps = frame(r)
     assert_exact(img, want)
     assert steps == want_steps
-    setup(fresh, pref, want_vol, density=density)
-    img2, steps2 = frame(fresh)
-    assert_exact(img, img2)
-    assert steps == steps2
+    check_fresh_install(fresh, pref, lname, want_vol, img, steps, density=density)
 
 
 # ---- 6. the edited context renders what a fresh install of the specification's volume renders --
@@ -328,41 +265,18 @@ def test_edited_render_equals_fresh_install(r, fresh, oracle, base, pref, lname)
         assert (ref != before).any(), "the edit does not change the oracle's frame"
         assert apply() is not None
         assert_marches(r, lname)
-        img, steps = frame(r)
-        assert_exact(img, ref)
-        assert steps == ref_steps
-        assert_exact(r.get_volume(), vol)
-        setup(fresh, pref, vol)
-        assert_marches(fresh, lname)
-        img2, steps2 = frame(fresh)
-        assert_exact(img, img2)
-        assert steps == steps2
+        img, steps = check_frame(r, oracle, vol)
+        check_fresh_install(fresh, pref, lname, vol, img, steps)
 
 
 # ---- 7. uniform channels on the recipe volume --------------------------------------------------
-@pytest.fixture(scope="module")
-def recipe_volume():
-    with vr.Renderer(0) as rr:
-        rr.generate_volume(vr.volume_recipe_defaults(size=32))
-        vol = rr.get_volume()
-    g = int(vol[0, 0, 0, 1])
-    assert (vol[..., 1] == g).all(), "the recipe's G is not uniform"
-    assert all(len(np.unique(vol[..., c])) > 1 for c in (0, 2, 3))
-    return vol, g
 
 
-def check_frame(rr, fresh, oracle, pref, vol, uniform):
+def check_uniform(rr, fresh, oracle, pref, lname, vol, uniform):
     assert bool(rr.get_option("uniform_mask") & 2) == uniform
     assert rr.kernel_variant.endswith("_uG") == uniform
-    img, steps = frame(rr)
-    ref, ref_steps = oracle_frame(oracle, vol)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    assert_exact(rr.get_volume(), vol)
-    setup(fresh, pref, vol)
-    img2, steps2 = frame(fresh)
-    assert_exact(img, img2)
-    assert steps == steps2
+    img, steps = check_frame(rr, oracle, vol)
+    check_fresh_install(fresh, pref, lname, vol, img, steps)
 
 
 @pytest.mark.parametrize("pref,lname", UNIFORM_LAYOUTS, ids=[n for _, n in UNIFORM_LAYOUTS])
@@ -375,20 +289,20 @@ def test_uniform_channel(r, fresh, oracle, recipe_volume, pref, lname):
     assert r.get_option("uniform_mask") & 2 and r.kernel_variant.endswith("_uG")
     r.remap(centre, radius, T["identity"], ps.SET, 1, FULL)
     r.remap(centre, radius, dev(T["identity"]), ps.SET, 0, FULL)
-    check_frame(r, fresh, oracle, pref, vol, True)
+    check_uniform(r, fresh, oracle, pref, lname, vol, True)
     # invert on the others with strength 0 on G keeps it
     setup(r, pref, vol)
     r.remap(centre, radius, T["invert"], ps.SET, 1, (255, 0, 255, 255))
     kept = rs.spec_remap(vol, T["invert"], centre, radius, ps.SET, 1, (255, 0, 255, 255))
     assert (kept != vol).any() and (kept[..., 1] == g).all()
-    check_frame(r, fresh, oracle, pref, kept, True)
+    check_uniform(r, fresh, oracle, pref, lname, kept, True)
     # invert on all four changes G where it is painted: the bit goes before the next render
     setup(r, pref, vol)
     assert r.get_option("uniform_mask") & 2
     r.remap(centre, radius, dev(T["invert"]), ps.SET, 1, FULL)
     inverted = rs.spec_remap(vol, T["invert"], centre, radius, ps.SET, 1, FULL)
     assert len(np.unique(inverted[..., 1])) > 1
-    check_frame(r, fresh, oracle, pref, inverted, False)
+    check_uniform(r, fresh, oracle, pref, lname, inverted, False)
     assert_marches(r, lname)
 
 

@@ -5,7 +5,7 @@ holds waves; volumes that take and that defeat the kernel's one-atomic path;
 stream order against paints; the context left as it was; the eyedropper round
 trip; refusals.  Everything is exact.
 
-The volume is test_gpu_paint.py's: 37 x 22 x 45, the reference camera at
+The volume is brush_harness.py's: 37 x 22 x 45, the reference camera at
 64 x 64, 32 steps.
 """
 import ctypes
@@ -19,6 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import paint_spec as ps  # noqa: E402
 import stats_spec as ss  # noqa: E402
+from brush_harness import STEPS, H, W, base, r  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,21 +29,7 @@ from volumetricrenderer_amd import _lib  # noqa: E402
 from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
 
 NX, NY, NZ = ps.NX, ps.NY, ps.NZ
-W = H = 64
-STEPS = 32
 BYTES = 8240
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
-
-
-@pytest.fixture(scope="module")
-def r():
-    with vr.Renderer(0) as rr:
-        yield rr
-        rr.set_layout_preference(0)
 
 
 def poisoned():

@@ -8,7 +8,7 @@ stream order; refusals.  Everything is exact.
 
 Volume A is the 37 x 22 x 45 of the paint tests (no axis a multiple of a brick
 edge), volume B is 150 x 9 x 7, whose rows exceed a wave's 64 lanes.  Frames
-are the paint tests': the reference camera at 64 x 64, 32 steps.  Each case
+are brush_harness.py's: the reference camera at 64 x 64, 32 steps.  Each case
 also asserts, on the CPU side, the condition that makes its input a test of
 what it names (order dependence, overlap depth, the clamp, ...).
 """
@@ -22,6 +22,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import paint_spec as ps  # noqa: E402
+from brush_harness import (H, LAYOUT_IDS, LAYOUTS, W, assert_exact, assert_marches, base, check_frame,  # noqa: E402,F401
+                           check_fresh_install, check_needs_a_volume, frame, fresh, oracle_frame, r, recipe_volume, setup)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,23 +34,7 @@ from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
 
 NX, NY, NZ = ps.NX, ps.NY, ps.NZ
 BX, BY, BZ = 150, 9, 7
-W = H = 64
-STEPS = 32
-LAYOUTS = [(1, "planar"), (5, "corner8"), (12, "brick4832"), (14, "cornerh"), (15, "col48")]
-LAYOUT_IDS = [n for _, n in LAYOUTS]
 UNIFORM_VARIANTS = {12, 14, 15}   # the layouts whose march has the _uX (no loads for one channel) kernels
-
-_oracle_frames = {}
-
-
-def oracle_frame(oracle, vol, angles=(0.0, 0.0)):
-    """The oracle's frame and executed steps for `vol`, computed once per (volume, camera)."""
-    osd, gsd = vr.reference_shader_data(1.0, *angles)
-    obj, glob = vr.shader_data_arrays(osd, gsd)
-    key = (hash(vol.tobytes()), vol.shape, angles)
-    if key not in _oracle_frames:
-        _oracle_frames[key] = oracle.render(vol, obj, glob, oracle.march(STEPS), W, H, FMT_RGBA32F)
-    return _oracle_frames[key]
 
 
 def cpu_stroke(vol, dabs):
@@ -68,26 +54,8 @@ def coverage(shape, dabs):
 
 
 @pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
-
-
-@pytest.fixture(scope="module")
 def long_base():
     return np.random.default_rng(ps.SEED + 1).integers(0, 256, size=(BZ, BY, BX, 4), dtype=np.uint8)
-
-
-@pytest.fixture(scope="module")
-def r():
-    with vr.Renderer(0) as rr:
-        yield rr
-        rr.set_layout_preference(0)
-
-
-@pytest.fixture(scope="module")
-def fresh():
-    with vr.Renderer(0) as rr:
-        yield rr
 
 
 @pytest.fixture(scope="module")
@@ -105,32 +73,6 @@ def heavy(base):
     assert coverage(base.shape, dabs).max() >= 4, "no texel is covered by four dabs"
     assert (painted[..., 2] == base[..., 2]).all() and (painted[..., :2] != base[..., :2]).any()
     return dabs, painted
-
-
-def setup(rr, pref, vol, angles=(0.0, 0.0)):
-    rr.set_option("uniform_skip", 1)
-    rr.set_layout_preference(pref)
-    rr.set_volume(vol)
-    rr.set_shader_data(*vr.reference_shader_data(1.0, *angles))
-    rr.set_march(vr.march_defaults(max_steps=STEPS))
-
-
-def frame(rr, stream=None):
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    img = rr.render(W, H, FMT_RGBA32F, step_counter=cnt, stream=stream)
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), int(cnt.item())
-
-
-def assert_marches(rr, name):
-    """The intended layout really marches: a silent planar fallback must not pass."""
-    assert rr.kernel_variant.startswith(f"grid_{name}_clamp"), rr.kernel_variant
-
-
-def assert_exact(got, want):
-    assert got.shape == want.shape
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def stroke_equals_cpu(rr, vol, dabs, dims=(NX, NY, NZ)):
@@ -246,10 +188,7 @@ def test_stroke_render_per_layout(r, fresh, oracle, base, heavy, pref, lname):
     assert_exact(pre, before)
     r.paint_stroke(dabs)
     assert_marches(r, lname)
-    img, steps = frame(r)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    assert_exact(r.get_volume(), painted)
+    img, steps = check_frame(r, oracle, painted)
     setup(fresh, pref, base)          # the same dabs as 64 vr_paint calls on a second context
     for b in dabs:
         _lib.call("vr_paint", fresh._ctx, ctypes.byref(b), None)
@@ -258,23 +197,10 @@ def test_stroke_render_per_layout(r, fresh, oracle, base, heavy, pref, lname):
     img3, steps3 = frame(fresh)
     assert_exact(img3, img)
     assert steps3 == steps
-    setup(fresh, pref, painted)       # a fresh install of the CPU-painted volume
-    assert_marches(fresh, lname)
-    img2, steps2 = frame(fresh)
-    assert_exact(img, img2)
-    assert steps == steps2
+    check_fresh_install(fresh, pref, lname, painted, img, steps)   # the CPU-painted volume
 
 
 # ---- 8. uniform channels on the recipe volume ------------------------------------------------
-@pytest.fixture(scope="module")
-def recipe_volume():
-    with vr.Renderer(0) as rr:
-        rr.generate_volume(vr.volume_recipe_defaults(size=32))
-        vol = rr.get_volume()
-    g = int(vol[0, 0, 0, 1])
-    assert (vol[..., 1] == g).all(), "the recipe's G is not uniform"
-    assert all(len(np.unique(vol[..., c])) > 1 for c in (0, 2, 3))
-    return vol, g
 
 
 @pytest.mark.parametrize("case", ["strength0", "changed", "undone"])
@@ -307,11 +233,7 @@ def test_uniform_channel(r, oracle, recipe_volume, pref, lname, case):
     r.paint_stroke(dabs)
     assert bool(r.get_option("uniform_mask") & 2) == keeps
     assert r.kernel_variant.endswith("_uG") == (keeps and uses_u)
-    img, steps = frame(r)
-    ref, ref_steps = oracle_frame(oracle, painted)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    assert_exact(r.get_volume(), painted)
+    check_frame(r, oracle, painted)
 
 
 # ---- 9. stroke and render_rects on a side stream, no host sync -------------------------------
@@ -363,15 +285,5 @@ def test_refusals(r, base):
     torch.cuda.synchronize()
     assert_exact(r.get_volume(), cpu_stroke(base, [good[0]] * 64))
     r.set_volume(base)
-    with vr.Renderer(0) as empty:     # no volume installed
-        with pytest.raises(vr.VRError) as e:
-            empty.paint_stroke(good)
-        assert e.value.status == 3    # VR_ERR_NO_VOLUME
-    r.set_procedural()                # a procedural medium reads no volume: nothing to paint
-    try:
-        with pytest.raises(vr.VRError) as e:
-            r.paint_stroke(good)
-        assert e.value.status == 3
-    finally:
-        r.set_procedural(vr.procedural_defaults(enabled=0))
+    check_needs_a_volume(r, lambda rr: rr.paint_stroke(good))
     assert np.array_equal(r.get_volume(), base)

@@ -17,10 +17,16 @@ that texel is inverted (6 to 11 pixels; at phi = theta = 0 six of the eight
 corners change nothing, and "the frame differs" could not hold).
 """
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from brush_harness import (H, LAYOUT_IDS, LAYOUTS, W, assert_exact, assert_marches, base, check_frame,  # noqa: E402,F401
+                           check_fresh_install, frame, fresh, oracle_frame, r, setup)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +36,6 @@ from volumetricrenderer_amd import _lib  # noqa: E402
 from volumetricrenderer_amd._lib import FMT_RGBA32F  # noqa: E402
 
 NX, NY, NZ = 37, 22, 45
-W = H = 64
-STEPS = 32
-LAYOUTS = [(1, "planar"), (5, "corner8"), (12, "brick4832"), (14, "cornerh"), (15, "col48")]
-LAYOUT_IDS = [n for _, n in LAYOUTS]
 UNIFORM_VARIANTS = {12, 14, 15}   # the layouts whose march has the _uX (no loads for one channel) kernels
 
 # name -> (origin (x0, y0, z0), extent (bx, by, bz), camera (phi, theta))
@@ -60,67 +62,6 @@ def straddle_box():
     return BOXES["straddle_5x9x34"]
 
 
-_oracle_frames = {}
-
-
-def oracle_frame(oracle, vol, angles=(0.0, 0.0), gsd=None):
-    """The oracle's frame and executed steps for `vol`, computed once per
-    (volume, camera)."""
-    osd, g = vr.reference_shader_data(1.0, *angles)
-    if gsd is not None:
-        g = gsd
-    obj, glob = vr.shader_data_arrays(osd, g)
-    key = (hash(vol.tobytes()), angles, glob.tobytes())
-    if key not in _oracle_frames:
-        _oracle_frames[key] = oracle.render(vol, obj, glob, oracle.march(STEPS), W, H, FMT_RGBA32F)
-    return _oracle_frames[key]
-
-
-@pytest.fixture(scope="module")
-def base():
-    return np.random.default_rng(20240607).integers(0, 256, size=(NZ, NY, NX, 4), dtype=np.uint8)
-
-
-@pytest.fixture(scope="module")
-def r():
-    with vr.Renderer(0) as rr:
-        yield rr
-        rr.set_layout_preference(0)
-
-
-@pytest.fixture(scope="module")
-def fresh():
-    with vr.Renderer(0) as rr:
-        yield rr
-
-
-def setup(rr, pref, vol, angles=(0.0, 0.0)):
-    rr.set_option("uniform_skip", 1)
-    rr.set_layout_preference(pref)
-    rr.set_volume(vol)
-    osd, gsd = vr.reference_shader_data(1.0, *angles)
-    rr.set_shader_data(osd, gsd)
-    rr.set_march(vr.march_defaults(max_steps=STEPS))
-
-
-def frame(rr, stream=None):
-    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    img = rr.render(W, H, FMT_RGBA32F, step_counter=cnt, stream=stream)
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), int(cnt.item())
-
-
-def assert_marches(rr, name):
-    """The intended layout really marches: a silent planar fallback must not pass."""
-    assert rr.kernel_variant.startswith(f"grid_{name}_clamp"), rr.kernel_variant
-
-
-def assert_exact(img, ref):
-    assert img.shape == ref.shape
-    bad = np.argwhere(img != ref)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
-
-
 def patch_into(vol, box, origin):
     x0, y0, z0 = origin
     bz, by, bx, _ = box.shape
@@ -130,17 +71,9 @@ def patch_into(vol, box, origin):
 
 
 def check_against_oracle_and_fresh(rr, fresh, oracle, pref, name, patched, angles=(0.0, 0.0)):
-    assert np.array_equal(rr.get_volume(), patched)
     assert_marches(rr, name)
-    img, steps = frame(rr)
-    ref, ref_steps = oracle_frame(oracle, patched, angles)
-    assert_exact(img, ref)
-    assert steps == ref_steps
-    setup(fresh, pref, patched, angles)
-    assert_marches(fresh, name)
-    img2, steps2 = frame(fresh)
-    assert_exact(img, img2)
-    assert steps == steps2
+    img, steps = check_frame(rr, oracle, patched, angles)
+    check_fresh_install(fresh, pref, name, patched, img, steps, angles)
     return img
 
 

@@ -15,6 +15,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import morph_spec as ms  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import assert_exact  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -27,11 +28,6 @@ def brush(centre, radius, falloff=0, strength=ms.STRENGTH, op=0):
 @pytest.fixture(scope="module")
 def base():
     return ms.morph_volume()
-
-
-def assert_exact(got, want):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def test_the_input_tells_wrong_implementations_apart(base):

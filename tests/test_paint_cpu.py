@@ -15,6 +15,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import paint_spec as ps  # noqa: E402
+from brush_harness import base  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vr_paint", "vr_brush_box", "vr_brush_apply", "vr_get_volume_box", "vr_get_volume_box_device")
@@ -30,11 +31,6 @@ def header_source():
 def brush(centre, radius, op=0, falloff=0, value=ps.VALUE, strength=ps.STRENGTH):
     import volumetricrenderer_amd as vr
     return vr.make_brush(centre, radius, op, falloff, value, strength)
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
 
 
 def test_brush_layout_in_header_ctypes_and_hpp(tmp_path):

@@ -16,6 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import morph_spec as ms  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import assert_exact  # noqa: E402,F401
 import rank_spec as rs  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,11 +35,6 @@ def inputs():
 
 def ranks(h):
     return (rs.MEDIAN, 0, rs.window(h) - 1, 5)
-
-
-def assert_exact(got, want):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 def test_the_input_tells_wrong_implementations_apart(inputs):

@@ -16,6 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import clone_spec as cs  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import base  # noqa: E402,F401
 import remap_spec as rs  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,11 +27,6 @@ OUT_PAIRS = [(0, 255), (255, 0), (10, 240), (240, 10), (7, 7), (200, 3), (0, 1)]
 def brush(centre, radius, op=ps.SET, falloff=0, strength=cs.STRENGTH):
     import volumetricrenderer_amd as vr
     return vr.make_brush(centre, radius, op, falloff, (1, 2, 3, 4), strength)
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
 
 
 @pytest.fixture(scope="module")

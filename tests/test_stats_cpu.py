@@ -14,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import paint_spec as ps  # noqa: E402
+from brush_harness import base  # noqa: E402,F401
 import stats_spec as ss  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,11 +24,6 @@ NEW = {"vr_brush_stats": 4, "vr_box_stats": 10, "vr_brush_stats_host": 6, "vr_bo
 def brush(centre, radius, falloff=0, strength=ss.FULL, op=0, value=(1, 2, 3, 4)):
     import volumetricrenderer_amd as vr
     return vr.make_brush(centre, radius, op, falloff, value, strength)
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
 
 
 @pytest.mark.parametrize("strength", ss.STRENGTHS, ids=["rgb", "a"])

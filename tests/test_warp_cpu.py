@@ -16,6 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import affine_spec as af  # noqa: E402
 import paint_spec as ps  # noqa: E402
+from brush_harness import assert_exact, base  # noqa: E402,F401
 import warp_spec as ws  # noqa: E402
 
 DIMS = (ps.NX, ps.NY, ps.NZ)
@@ -29,16 +30,6 @@ def brush(centre, radius, op=ps.SET, falloff=0, strength=ws.STRENGTH):
 def affine(table, filt=ws.NEAREST, border=ws.CLAMP):
     import volumetricrenderer_amd as vr
     return vr.make_affine(*table, filt, border)
-
-
-@pytest.fixture(scope="module")
-def base():
-    return ps.base_volume()
-
-
-def assert_exact(got, want):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{len(bad)} mismatches, first {bad[:5].tolist()}"
 
 
 # ---- 1. the host statement is the numpy restatement's -----------------------------------------

@@ -18,11 +18,9 @@
 #include <random>
 #include <vector>
 
-#include "vr.h"
+#include "check_common.hpp"
 
 namespace {
-
-typedef unsigned __int128 u128;
 
 // include/vr.h, literally, from a padded copy of the volume before the call
 void restate(const vr_brush& b, int h, std::vector<uint8_t>& v, int nx, int ny, int nz)
@@ -36,21 +34,12 @@ void restate(const vr_brush& b, int h, std::vector<uint8_t>& v, int nx, int ny, 
                 for (int c = 0; c < 4; ++c)
                     pad[(((size_t)z * py + y) * px + x) * 4 + c] =
                         v[(((size_t)cl(z - h, nz) * ny + cl(y - h, ny)) * nx + cl(x - h, nx)) * 4 + c];
-    u128 D2[3];
-    for (int a = 0; a < 3; ++a) D2[a] = (u128)(2 * b.radius[a] + 1) * (u128)(2 * b.radius[a] + 1);
-    const u128 S = D2[0] * D2[1] * D2[2];
     const long long N = (long long)(2 * h + 1) * (2 * h + 1) * (2 * h + 1);
     for (int z = 0; z < nz; ++z)
         for (int y = 0; y < ny; ++y)
             for (int x = 0; x < nx; ++x) {
-                const long long d[3] = {(long long)x - b.centre[0], (long long)y - b.centre[1], (long long)z - b.centre[2]};
-                bool in = true;
-                for (int a = 0; a < 3; ++a) in = in && d[a] >= -(long long)b.radius[a] && d[a] <= (long long)b.radius[a];
-                if (!in) continue;
-                const u128 Q = (u128)(4 * d[0] * d[0]) * D2[1] * D2[2] + (u128)(4 * d[1] * d[1]) * D2[0] * D2[2] +
-                               (u128)(4 * d[2] * d[2]) * D2[0] * D2[1];
-                if (Q > S) continue;
-                const unsigned w = b.falloff ? 256u - (unsigned)((256 * Q) / (S + 1)) : 256u;
+                const unsigned w = weight(b, x, y, z);
+                if (!w) continue;
                 uint8_t* p = &v[(((size_t)z * ny + y) * nx + x) * 4];
                 for (int c = 0; c < 4; ++c) {
                     if (!b.strength[c]) continue;
@@ -63,13 +52,6 @@ void restate(const vr_brush& b, int h, std::vector<uint8_t>& v, int nx, int ny, 
                     p[c] = (uint8_t)((old * (65280 - a) + m * a + 32640) / 65280);
                 }
             }
-}
-
-long failures = 0;
-
-void expect(bool ok, const char* what, int it)
-{
-    if (!ok && ++failures <= 10) std::fprintf(stderr, "blur_check: %s (case %d)\n", what, it);
 }
 
 }  // namespace
@@ -152,7 +134,7 @@ int main()
         ++applied;
     }
     expect(changed > 300, "too few cases changed a byte", (int)changed);
-    std::printf("blur_check: %ld applied (%ld changed bytes), %ld missed, %ld refused, %ld failures\n", applied, changed, missed,
-                refused, failures);
-    return failures ? 1 : 0;
+    std::printf("blur_check: %ld applied (%ld changed bytes), %ld missed, %ld refused, ", applied, changed, missed,
+                refused);
+    return finish("blur_check");
 }

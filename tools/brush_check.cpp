@@ -23,11 +23,9 @@
 #include <random>
 #include <vector>
 
-#include "vr.h"
+#include "check_common.hpp"
 
 namespace {
-
-typedef unsigned __int128 u128;
 
 // include/vr.h, literally
 void restate(const vr_brush& b, std::vector<uint8_t>& v, int nx, int ny, int nz)
@@ -74,13 +72,6 @@ long long line_centre(const vr_brush& b, const int32_t to[3], __int128 n, __int1
 {
     const __int128 d = (__int128)to[a] - b.centre[a];
     return (long long)(b.centre[a] + floor_div(2 * i * d + n, 2 * n));
-}
-
-long failures = 0;
-
-void expect(bool ok, const char* what, int it)
-{
-    if (!ok && ++failures <= 10) std::fprintf(stderr, "brush_check: %s (case %d)\n", what, it);
 }
 
 }  // namespace
@@ -251,6 +242,6 @@ int main()
         line_refused += 9;
     }
     std::printf("brush_check: %ld lines (%ld dabs, %ld long), %ld lines refused\n", lines, dabs, too_long, line_refused);
-    std::printf("brush_check: %ld applied, %ld missed, %ld refused, %ld failures\n", applied, missed, refused, failures);
-    return failures ? 1 : 0;
+    std::printf("brush_check: %ld applied, %ld missed, %ld refused, ", applied, missed, refused);
+    return finish("brush_check");
 }

@@ -21,34 +21,9 @@
 #include <random>
 #include <vector>
 
-#include "vr.h"
+#include "check_common.hpp"
 
 namespace {
-
-typedef unsigned __int128 u128;
-
-// the weight of texel (x, y, z) under b, 0 outside the ellipsoid: include/vr.h, literally
-unsigned weight(const vr_brush& b, int x, int y, int z)
-{
-    u128 D2[3];
-    for (int a = 0; a < 3; ++a) D2[a] = (u128)(2 * b.radius[a] + 1) * (u128)(2 * b.radius[a] + 1);
-    const u128 S = D2[0] * D2[1] * D2[2];
-    const long long d[3] = {(long long)x - b.centre[0], (long long)y - b.centre[1], (long long)z - b.centre[2]};
-    for (int a = 0; a < 3; ++a)
-        if (d[a] < -(long long)b.radius[a] || d[a] > (long long)b.radius[a]) return 0u;
-    const u128 Q = (u128)(4 * d[0] * d[0]) * D2[1] * D2[2] + (u128)(4 * d[1] * d[1]) * D2[0] * D2[2] +
-                   (u128)(4 * d[2] * d[2]) * D2[0] * D2[1];
-    if (Q > S) return 0u;
-    return b.falloff ? 256u - (unsigned)((256 * Q) / (S + 1)) : 256u;
-}
-
-uint8_t blend(int op, long long old, long long v, long long a)
-{
-    const long long d = (v * a + 32640) / 65280;
-    if (op == VR_BRUSH_SET) return (uint8_t)((old * (65280 - a) + v * a + 32640) / 65280);
-    if (op == VR_BRUSH_ADD) return (uint8_t)(old + d > 255 ? 255 : old + d);
-    return (uint8_t)(old - d < 0 ? 0 : old - d);
-}
 
 long long clampll(long long s, int n) { return s < 0 ? 0 : s > n - 1 ? n - 1 : s; }
 
@@ -106,22 +81,8 @@ void restate_stamp(const vr_brush& b, const std::vector<uint8_t>& stamp, const v
             }
 }
 
-long failures = 0;
-
-void expect(bool ok, const char* what, int it)
-{
-    if (!ok && ++failures <= 10) std::fprintf(stderr, "clone_check: %s (case %d)\n", what, it);
-}
-
 std::mt19937_64 rng(20240903);
 int pick(int a, int b) { return std::uniform_int_distribution<int>(a, b)(rng); }
-
-std::vector<uint8_t> random_bytes(size_t n)
-{
-    std::vector<uint8_t> v(n);
-    for (size_t i = 0; i < n; ++i) v[i] = (uint8_t)pick(0, 255);
-    return v;
-}
 
 long cloned = 0, stamped = 0, refused = 0, changed = 0, empty_boxes = 0;
 
@@ -139,7 +100,7 @@ void check_clone(const vr_brush& b, const vr_clone_map& m, const std::vector<uin
 
 void check_stamp(const vr_brush& b, const vr_box& pl, const std::vector<uint8_t>& base, int nx, int ny, int nz, int it)
 {
-    const std::vector<uint8_t> stamp = random_bytes((size_t)pl.bx * pl.by * pl.bz * 4);
+    const std::vector<uint8_t> stamp = random_bytes(rng, (size_t)pl.bx * pl.by * pl.bz * 4);
     std::vector<uint8_t> vol = base, want = base;
     int lo[3], hi[3], o[3], e[3];
     restate_stamp(b, stamp, pl, want, nx, ny, nz, lo, hi);
@@ -164,7 +125,7 @@ int main()
     // ---- the suite's brushes and maps on its volume's dimensions
     {
         const int nx = 37, ny = 22, nz = 45;
-        const std::vector<uint8_t> base = random_bytes((size_t)nx * ny * nz * 4);
+        const std::vector<uint8_t> base = random_bytes(rng, (size_t)nx * ny * nz * 4);
         const int brushes[][6] = {{17, 11, 23, 3, 2, 4},   {17, 11, 23, 0, 0, 0},  {0, 0, 0, 5, 5, 5},       {36, 21, 44, 5, 3, 6},
                                   {-2, 10, 47, 4, 4, 4},   {19, 10, 31, 16, 4, 2}, {18, 11, 22, 40, 40, 40}, {18, 11, 22, 255, 255, 255},
                                   {-10, -10, -10, 4, 4, 4}};
@@ -235,7 +196,7 @@ int main()
             m.mirror[a] = pick(0, 1);
             m.offset[a] = pick(0, 4) == 0 ? far[pick(0, 5)] : m.mirror[a] ? pick(-2, 2 * n[a] + 1) : pick(-n[a] - 1, n[a] + 1);
         }
-        const std::vector<uint8_t> base = random_bytes((size_t)nx * ny * nz * 4);
+        const std::vector<uint8_t> base = random_bytes(rng, (size_t)nx * ny * nz * 4);
         check_clone(b, m, base, nx, ny, nz, it);
         vr_box pl{};
         pl.bx = pick(1, 9); pl.by = pick(1, 9); pl.bz = pick(1, 9);
@@ -253,7 +214,7 @@ int main()
 
         // refusals: nothing written
         std::vector<uint8_t> vol = base;
-        const std::vector<uint8_t> stamp = random_bytes((size_t)pl.bx * pl.by * pl.bz * 4);
+        const std::vector<uint8_t> stamp = random_bytes(rng, (size_t)pl.bx * pl.by * pl.bz * 4);
         vr_brush bad = b;
         vr_clone_map badm = m;
         vr_box badp = pl;
@@ -286,7 +247,7 @@ int main()
     }
     expect(changed > 1500, "too few cases changed a byte", (int)changed);
     expect(empty_boxes > 100 && empty_boxes < stamped - 500, "the placements do not cover both an empty and a full edited box", (int)empty_boxes);
-    std::printf("clone_check: %ld cloned, %ld stamped (%ld empty boxes; %ld cases changed bytes), %ld refused, %ld failures\n", cloned,
-                stamped, empty_boxes, changed, refused, failures);
-    return failures ? 1 : 0;
+    std::printf("clone_check: %ld cloned, %ld stamped (%ld empty boxes; %ld cases changed bytes), %ld refused, ", cloned,
+                stamped, empty_boxes, changed, refused);
+    return finish("clone_check");
 }

@@ -31,12 +31,10 @@
 #include <random>
 #include <vector>
 
-#include "vr.h"
+#include "check_common.hpp"
 #include "../volumetricrenderer_amd/csrc/vr_fill.h"
 
 namespace {
-
-typedef unsigned __int128 u128;
 
 struct Vol {
     int nx, ny, nz;
@@ -247,13 +245,6 @@ vr_fill_report tiled(const vr_brush& b, const vr_fill_rule& r, Vol& vol, int ord
     return rep;
 }
 
-long failures = 0;
-
-void expect(bool ok, const char* what, int it)
-{
-    if (!ok && ++failures <= 10) std::fprintf(stderr, "fill_check: %s (case %d)\n", what, it);
-}
-
 }  // namespace
 
 int main()
@@ -367,7 +358,7 @@ int main()
     }
     expect(invariant_ok, "a label above its own index", 0);
     expect(filled > 300 && partial > 100 && empty > 100, "too few cases filled, filled a part, or filled nothing", (int)filled);
-    std::printf("fill_check: %ld applied (%ld filled, %ld a part of what passes, %ld nothing), %ld refused, %ld failures\n", applied,
-                filled, partial, empty, refused, failures);
-    return failures ? 1 : 0;
+    std::printf("fill_check: %ld applied (%ld filled, %ld a part of what passes, %ld nothing), %ld refused, ", applied,
+                filled, partial, empty, refused);
+    return finish("fill_check");
 }

@@ -23,35 +23,9 @@
 #include <random>
 #include <vector>
 
-#include "vr.h"
+#include "check_common.hpp"
 
 namespace {
-
-typedef unsigned __int128 u128;
-typedef __int128 i128;
-
-// the weight of texel (x, y, z) under b, 0 outside the ellipsoid: include/vr.h, literally
-unsigned weight(const vr_brush& b, int x, int y, int z)
-{
-    u128 D2[3];
-    for (int a = 0; a < 3; ++a) D2[a] = (u128)(2 * b.radius[a] + 1) * (u128)(2 * b.radius[a] + 1);
-    const u128 S = D2[0] * D2[1] * D2[2];
-    const long long d[3] = {(long long)x - b.centre[0], (long long)y - b.centre[1], (long long)z - b.centre[2]};
-    for (int a = 0; a < 3; ++a)
-        if (d[a] < -(long long)b.radius[a] || d[a] > (long long)b.radius[a]) return 0u;
-    const u128 Q = (u128)(4 * d[0] * d[0]) * D2[1] * D2[2] + (u128)(4 * d[1] * d[1]) * D2[0] * D2[2] +
-                   (u128)(4 * d[2] * d[2]) * D2[0] * D2[1];
-    if (Q > S) return 0u;
-    return b.falloff ? 256u - (unsigned)((256 * Q) / (S + 1)) : 256u;
-}
-
-uint8_t blend(int op, long long old, long long v, long long a)
-{
-    const long long d = (v * a + 32640) / 65280;
-    if (op == VR_BRUSH_SET) return (uint8_t)((old * (65280 - a) + v * a + 32640) / 65280);
-    if (op == VR_BRUSH_ADD) return (uint8_t)(old + d > 255 ? 255 : old + d);
-    return (uint8_t)(old - d < 0 ? 0 : old - d);
-}
 
 void restate_remap(const vr_brush& b, const vr_lut& lut, std::vector<uint8_t>& v, int nx, int ny, int nz)
 {
@@ -112,22 +86,8 @@ void restate_stats_lut(const vr_volume_stats& s, int kind, int mask, vr_lut& t)
     }
 }
 
-long failures = 0;
-
-void expect(bool ok, const char* what, int it)
-{
-    if (!ok && ++failures <= 10) std::fprintf(stderr, "remap_check: %s (case %d)\n", what, it);
-}
-
 std::mt19937_64 rng(20241020);
 int pick(int a, int b) { return std::uniform_int_distribution<int>(a, b)(rng); }
-
-std::vector<uint8_t> random_bytes(size_t n)
-{
-    std::vector<uint8_t> v(n);
-    for (size_t i = 0; i < n; ++i) v[i] = (uint8_t)pick(0, 255);
-    return v;
-}
 
 bool same(const vr_lut& a, const vr_lut& b) { return std::memcmp(&a, &b, sizeof(vr_lut)) == 0; }
 
@@ -187,7 +147,7 @@ int main()
     // ---- the suite's brushes on its volume's dimensions, tables of four kinds
     {
         const int nx = 37, ny = 22, nz = 45;
-        const std::vector<uint8_t> base = random_bytes((size_t)nx * ny * nz * 4);
+        const std::vector<uint8_t> base = random_bytes(rng, (size_t)nx * ny * nz * 4);
         const int brushes[][6] = {{17, 11, 23, 3, 2, 4},   {17, 11, 23, 0, 0, 0},  {0, 0, 0, 5, 5, 5},       {36, 21, 44, 5, 3, 6},
                                   {-2, 10, 47, 4, 4, 4},   {19, 10, 31, 16, 4, 2}, {18, 11, 22, 40, 40, 40}, {18, 11, 22, 255, 255, 255},
                                   {-10, -10, -10, 4, 4, 4}};
@@ -237,7 +197,7 @@ int main()
         b.op = it / 6 % 3;
         b.falloff = it / 18 % 2;
         for (int c = 0; c < 4; ++c) { b.value[c] = (uint8_t)pick(0, 255); b.strength[c] = (uint8_t)(pick(0, 3) ? pick(0, 255) : pick(0, 1) * 255); }
-        const std::vector<uint8_t> base = random_bytes((size_t)nx * ny * nz * 4);
+        const std::vector<uint8_t> base = random_bytes(rng, (size_t)nx * ny * nz * 4);
         const int tkind = pick(0, 3);
         const std::unique_ptr<vr_lut> lut = random_lut(tkind);
         check_remap(b, *lut, base, nx, ny, nz, it, tkind == 1);
@@ -319,7 +279,7 @@ int main()
     // brushes that miss (a far centre, a tiny volume), zero strengths and identity tables under SET change nothing:
     // the rest, at least a quarter of the cases, must
     expect(changed * 4 > remapped, "too few cases changed a byte", (int)changed);
-    std::printf("remap_check: %ld remapped (%ld changed bytes), %ld levels, %ld composed, %ld tables from stats, %ld refused, %ld failures\n",
-                remapped, changed, levels, composed, from_stats, refused, failures);
-    return failures ? 1 : 0;
+    std::printf("remap_check: %ld remapped (%ld changed bytes), %ld levels, %ld composed, %ld tables from stats, %ld refused, ",
+                remapped, changed, levels, composed, from_stats, refused);
+    return finish("remap_check");
 }

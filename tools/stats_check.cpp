@@ -18,11 +18,9 @@
 #include <random>
 #include <vector>
 
-#include "vr.h"
+#include "check_common.hpp"
 
 namespace {
-
-typedef unsigned __int128 u128;
 
 // include/vr.h, literally; box = nullptr: under the brush, else inside the box {x0, y0, z0, bx, by, bz}
 vr_volume_stats restate(const vr_brush* b, const int* box, unsigned mask, const std::vector<uint8_t>& v, int nx, int ny, int nz)
@@ -82,13 +80,6 @@ vr_volume_summary restate_summary(const vr_volume_stats& s)
         o.median[c] = bytes[(n + 1) / 2 - 1];
     }
     return o;
-}
-
-long failures = 0;
-
-void expect(bool ok, const char* what, int it)
-{
-    if (!ok && ++failures <= 10) std::fprintf(stderr, "stats_check: %s (case %d)\n", what, it);
 }
 
 bool same(const vr_volume_stats& a, const vr_volume_stats& b) { return std::memcmp(&a, &b, sizeof a) == 0; }
@@ -215,7 +206,7 @@ int main()
                "a hand-made struct with weight 0", -4);
     }
     expect(brushes > 300 && missed > 10 && smooth_lighter > 30, "too few cases of a kind", (int)brushes);
-    std::printf("stats_check: %ld brushes (%ld smooth ones lighter than hard), %ld missed, %ld boxes, %ld refused, %ld failures\n",
-                brushes, smooth_lighter, missed, boxes, refused, failures);
-    return failures ? 1 : 0;
+    std::printf("stats_check: %ld brushes (%ld smooth ones lighter than hard), %ld missed, %ld boxes, %ld refused, ",
+                brushes, smooth_lighter, missed, boxes, refused);
+    return finish("stats_check");
 }

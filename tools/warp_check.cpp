@@ -22,34 +22,17 @@
 #include <random>
 #include <vector>
 
-#include "vr.h"
+#include "check_common.hpp"
 
 namespace {
 
-typedef unsigned __int128 u128;
-typedef __int128 i128;
-
-int failures = 0;
+// the shared failure counter, with the failed condition and its line on stdout
 #define EXPECT(cond)                                                        \
     do {                                                                    \
         if (!(cond)) {                                                      \
             if (++failures <= 20) std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
         }                                                                   \
     } while (0)
-
-unsigned weight(const vr_brush& b, int x, int y, int z)
-{
-    u128 D2[3];
-    for (int a = 0; a < 3; ++a) D2[a] = (u128)(2 * b.radius[a] + 1) * (u128)(2 * b.radius[a] + 1);
-    const u128 S = D2[0] * D2[1] * D2[2];
-    const long long d[3] = {(long long)x - b.centre[0], (long long)y - b.centre[1], (long long)z - b.centre[2]};
-    for (int a = 0; a < 3; ++a)
-        if (d[a] < -(long long)b.radius[a] || d[a] > (long long)b.radius[a]) return 0u;
-    const u128 Q = (u128)(4 * d[0] * d[0]) * D2[1] * D2[2] + (u128)(4 * d[1] * d[1]) * D2[0] * D2[2] +
-                   (u128)(4 * d[2] * d[2]) * D2[0] * D2[1];
-    if (Q > S) return 0u;
-    return b.falloff ? 256u - (unsigned)((256 * Q) / (S + 1)) : 256u;
-}
 
 i128 floor_div(i128 a, i128 b)   // b > 0
 {
@@ -290,7 +273,7 @@ int main()
     check_reach();
     check_push();
     if (failures) {
-        std::printf("warp_check: %d FAILURES\n", failures);
+        std::printf("warp_check: %ld FAILURES\n", failures);
         return 1;
     }
     std::printf("warp_check: ok\n");
